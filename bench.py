@@ -6,12 +6,18 @@ k-mer generation + K2 COBS query + K3 (hit list grouped by read, -T, per-query o
 expansion to finalized matches in host memory (kmcpg_finalize_grouped); the host half of step i overlaps the kernels of step i+1.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload gtdb|config1|gtdb_unchunked_k31|config2_genome_search|config4_hifi|...]
+                  [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step`, what the timed steps measured on their
+own); everything else described below (sanity batch, roofline passes, host-boundary legs, CPU baseline and oracle parity,
+secondaries) runs only with --full.  --dump-outputs DIR writes the finalized matches of the last timed step as .npy files
+(dump_outputs); the inputs are a function of the arguments alone, so two builds can be compared output for output.
 
 N>1 is launched by the driver as `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`; a plain
 `python bench.py --gpus N` re-executes itself under that launcher on a free local port.  One rank per GPU; the index's independent blocks are partitioned over the ranks (libkmcpgpu shards by
 bytes), every rank searches the whole batch against its blocks, the per-read hit lists are gathered on
 rank 0 over RCCL and K3 runs there over the concatenation.  Total work is fixed as N grows => "scaling": "strong".
-Every line carries `sanity_batch.hits_checksum` (the same at every N by construction), `ranks` (who ran, per-rank kernel times) and,
+With --full every line carries `sanity_batch.hits_checksum` (the same at every N by construction), `ranks` (who ran, per-rank kernel times) and,
 at N > 1, `parity_at_n` (the merged hit list of a sample against the CPU oracle over rows fetched from every rank).
 
 The synthetic index is generated directly in HBM: 32 blocks x 14 976 columns
@@ -19,7 +25,7 @@ The synthetic index is generated directly in HBM: 32 b
 90 % of the reads are 1 %-mutated, randomly reverse-complemented copies of 150-bp fragments whose k-mers
 were planted into a random column, 10 % are uniform random.
 
-The JSON line reports the GTDB-scale workload (the configuration BASELINE.json's metric is quoted on).  At N=1 the
+The JSON line reports the GTDB-scale workload (the configuration BASELINE.json's metric is quoted on).  With --full at N=1 the
 same line carries, under "secondary", BASELINE.json configs[1] (10 k chunks, 39-byte rows; grouped and ungrouped), the
 configuration the reference's own published short-read numbers are quoted on (unchunked GTDB, k = 31, -b 1024, -t 0.8),
 configs[2] (genome search: FracMinHash scale 1000, 3 hashes, 50 k references, queries with ~9 relatives each in the index) and
@@ -296,12 +302,52 @@ def host_memory_available():
     return avail
 
 
-def run_workload(name, ctx, steps, warmup, batch_reads=0, cpu_baseline=True, cpu_target_s=8.0, cpu_sample_reads=0, extras=True):
+DUMP_LIMIT = 64_000_000  # bytes of .npy files --dump-outputs may write
+DUMP_SEED = 1729  # the sample of queries a dump larger than that keeps
+
+
+def dump_outputs(out_dir, res, limit=DUMP_LIMIT, seed=DUMP_SEED):
+    """Writes a batch's finalized result (kmcp_amd.lib.BatchResult) under `out_dir` as float64 .npy files: per query query_index,
+    query_len, query_kmers; per match (queries in order, each query's matches in the order the library returns them) match_query
+    (its query_index) and the Match fields match_col, match_target_idx, match_gsize, match_mkmers, match_qcov, match_tcov,
+    match_jacc, match_fpr.  Past `limit` bytes only a sample of the queries is written: a prefix of a permutation seeded by
+    `seed`, as long as fits - the same queries in every run whose per-query match counts are the same.  Returns the paths."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = len(res.qlen)
+    offs = np.asarray(res.offs, dtype=np.int64)
+    cnt = np.diff(offs)
+    fields = ("col", "target_idx", "gsize", "mkmers", "qcov", "tcov", "jacc", "fpr")
+    per_q, per_m = 3 * 8, (1 + len(fields)) * 8
+    budget = limit - (3 + 1 + len(fields)) * 128  # (an .npy header is 128 bytes)
+    if n * per_q + int(offs[-1]) * per_m <= budget:
+        sel = np.arange(n, dtype=np.int64)
+    else:
+        perm = np.random.default_rng(seed).permutation(n)
+        k = int(np.searchsorted(np.cumsum(per_q + per_m * cnt[perm]), budget, side="right"))
+        sel = np.sort(perm[:k])
+    keep = np.zeros(n, dtype=bool)
+    keep[sel] = True
+    m = res.matches[np.repeat(keep, cnt)]
+    arrays = {"query_index": sel, "query_len": res.qlen[sel], "query_kmers": res.qkmers[sel], "match_query": np.repeat(sel, cnt[sel])}
+    for f in fields:
+        arrays["match_" + f] = m[f]
+    paths = []
+    for nm, a in arrays.items():
+        p = os.path.join(out_dir, nm + ".npy")
+        np.save(p, np.ascontiguousarray(a, dtype=np.float64))
+        paths.append(p)
+    return paths
+
+
+def run_workload(name, ctx, steps, warmup, batch_reads=0, cpu_baseline=True, cpu_target_s=8.0, cpu_sample_reads=0, extras=True, full=True, dump_dir=None):
     """Builds the synthetic index of workload `name` in HBM, times `steps` steps, returns the result dict (rank 0).
 
     One step = reads resident in HBM -> K1 + K2 on this rank's blocks -> hit lists to rank 0 (RCCL when N > 1) -> D2H ->
     kmcpg_finalize on the host (float64 thresholds, FPR, sort): finalized matches in host memory.  The host half of step i runs
-    while the GPU works on step i+1 (it is inside the timed region for every one of the K steps)."""
+    while the GPU works on step i+1 (it is inside the timed region for every one of the K steps).
+
+    full=False stops after the timed steps (the headline figure only); dump_dir: the finalized matches of the last timed step
+    are written there as .npy files (dump_outputs)."""
     from kmcp_amd import Database, default_params, lib
     from kmcp_amd.dist import gather_hits, hits_checksum
 
@@ -498,6 +544,8 @@ def run_workload(name, ctx, steps, warmup, batch_reads=0, cpu_baseline=True, cpu
             dist.barrier()
         torch.cuda.synchronize()
 
+    last_n = [0]  # hits of the last step run_steps took through exchange()
+
     def run_steps(first, count, with_host=True, times=None):
         """`count` steps starting at batch `first`, two in flight: the kernels of step i+1 are enqueued before step i's hits are
         exchanged (N > 1: RCCL on the side stream), fetched and finalized.  Returns (#hits, #matches) on rank 0."""
@@ -513,6 +561,7 @@ def run_workload(name, ctx, steps, warmup, batch_reads=0, cpu_baseline=True, cpu
             ta = time.perf_counter()
             n = exchange(bf)
             tb = time.perf_counter()
+            last_n[0] = n
             hits += n
             if with_host:
                 matches += host_half(bf, n)
@@ -536,6 +585,17 @@ def run_workload(name, ctx, steps, warmup, batch_reads=0, cpu_baseline=True, cpu
         t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if ctx.same_gpu else dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if dump_dir and rank == 0:
+        # what a caller of the timed path receives for its last step: that step's host half once more, keeping the Match records
+        # its count_only form frees (the buffers still hold the step: nothing was enqueued on them after it)
+        bf = bufs[(steps - 1) % len(bufs)]
+        if bf.grouped:
+            kept = int(bf.h_roffs[B])
+            res = db.finalize_grouped(bf.h_pairs[:kept].numpy(), bf.h_roffs.numpy(), bf.h_qk.numpy(), bf.h_ql.numpy(), params=params)
+        else:
+            res = db.finalize(bf.h_hits[:last_n[0]].numpy().view(lib.HIT_DTYPE).reshape(-1), bf.h_qk.numpy(), bf.h_ql.numpy(), params=params)
+        dump_outputs(dump_dir, res)
+        del res
 
     # ---- roofline of the dominant kernel (k2_cobs) on this rank.
     #  algorithmic bytes per launch: sum over reads of kept k-mers x sum over local blocks of numHashes x NumRowBytes,
@@ -612,6 +672,12 @@ def run_workload(name, ctx, steps, warmup, batch_reads=0, cpu_baseline=True, cpu
         "matches_per_step": n_matches_total / max(1, steps),
         "setup_s": setup_s,
     }
+    if not full:
+        # a plain run ends here: the headline figure and what the timed steps measured on their own; every leg below is --full's
+        db.close()
+        del bufs, batches
+        torch.cuda.empty_cache()
+        return out
 
     # ---- sanity on the last batch: planted reads must come back with their column (the step holds collectives: every
     #      rank takes part, rank 0 evaluates the merged hit list)
@@ -1444,7 +1510,14 @@ def main():
     ap.add_argument("--no-secondary", action="store_true", help="skip the configs[1] numbers that ride along at N=1")
     ap.add_argument("--cli-only", type=int, default=0, metavar="READS", help="run only the kmcp-search end-to-end leg on this many reads and print its record (negative: the -g leg on that many genomes)")
     ap.add_argument("--no-extras", action="store_true", help="timed steps only (profiling runs: no pruning-off / host-boundary launches in the trace)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, every other leg too: sanity batch, roofline passes, extras, CPU baseline and oracle parity, and at "
+                         "N=1 on the headline workload the secondary workloads and the kmcp-search legs (the --no-* options trim this)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the finalized matches of the last timed step to DIR/<name>.npy (float64, at most 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     ctx = Ctx()
     ctx.world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -1489,8 +1562,8 @@ def main():
         os.write(1, (json.dumps(_finite(rec)) + "\n").encode())
         sys.exit(3 if rec.get("parity_failure") or rec.get("error") else 0)
     out = run_workload(args.workload, ctx, args.steps, args.warmup, args.batch_reads, cpu_baseline=not args.no_cpu_baseline,
-                       cpu_sample_reads=args.cpu_sample_reads, extras=not args.no_extras)
-    if ctx.world == 1 and args.workload == "gtdb" and not args.no_secondary and not args.batch_reads:
+                       cpu_sample_reads=args.cpu_sample_reads, extras=not args.no_extras, full=args.full, dump_dir=args.dump_outputs)
+    if args.full and ctx.world == 1 and args.workload == "gtdb" and not args.no_secondary and not args.batch_reads:
         sec = run_workload("config1", ctx, min(max(args.steps, 5), 20), 2, cpu_baseline=not args.no_cpu_baseline, cpu_target_s=3.0)
         keys = ("value", "value_host_to_host", "value_host_to_host_packed", "unit", "ms_per_step", "config", "roofline", "planted_recall", "sanity_batch", "device_only", "host_boundary",
                 "cpu_baseline", "hits_per_step", "matches_per_step", "setup_s", "parity_failure", "whole_genome_query")

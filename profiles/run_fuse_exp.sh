@@ -1,7 +1,7 @@
 #!/bin/bash
 out=gpurun_out/r02_fuse_exp.txt
 : > $out
-run() { echo "== $*" >> $out; env "$@" timeout 300 python bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-secondary --workload $WL 2>&1 | python -c "
+run() { echo "== $*" >> $out; env "$@" timeout 300 python bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-secondary --workload $WL 2>&1 | python -c "
 import sys,json
 for l in sys.stdin:
     l=l.strip()

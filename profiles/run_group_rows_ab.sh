@@ -4,7 +4,7 @@
 #   - builds of libkmcpgpu.so that differ in k2_cobs only (e.g. -DK2_WAVES=N for the occupancy sweep, or an older commit) are
 #     compared by swapping kmcp_amd/libkmcpgpu.so between runs: put them under scratch/ as lib_<tag>.so and list the tags.
 #   usage: profiles/run_group_rows_ab.sh [tag ...]
-run() { timeout 300 python bench.py --workload $1 --steps 6 --warmup 2 --no-cpu-baseline --no-secondary --no-extras 2>&1 | python -c "
+run() { timeout 300 python bench.py --full --workload $1 --steps 6 --warmup 2 --no-cpu-baseline --no-secondary --no-extras 2>&1 | python -c "
 import sys,json
 for l in sys.stdin:
     l=l.strip()

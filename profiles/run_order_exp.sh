@@ -5,7 +5,7 @@ out=gpurun_out/r02_order_exp.txt
 for wl in gtdb config1; do
 for sm in 0 1; do for nt in 1 0; do
   echo "== $wl slot_major=$sm nt=$nt" >> $out
-  KMCPG_SLOT_MAJOR=$sm KMCPG_NT_LOADS=$nt timeout 300 python bench.py --workload $wl --steps 4 --warmup 1 --no-cpu-baseline --no-secondary 2>&1 | python -c "
+  KMCPG_SLOT_MAJOR=$sm KMCPG_NT_LOADS=$nt timeout 300 python bench.py --full --workload $wl --steps 4 --warmup 1 --no-cpu-baseline --no-secondary 2>&1 | python -c "
 import sys,json
 for l in sys.stdin:
     l=l.strip()

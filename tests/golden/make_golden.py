@@ -7,6 +7,7 @@ Outputs: demo_searching_sketches.npz  sorted-unique sketch hashes of the 9 genom
                                       by the oracle's restatement of `kmcp compute` (data, not source)
          demo_searching_tables.json   the published tables (verbatim values) + accession mapping + intermediate KATs
          NC_018658.1.fasta.gz         the query genome of the demo (data file of the reference's worked example)
+         NC_010655.1.fasta.gz         the demo's smallest genome (data file)
 """
 import glob
 import gzip
@@ -76,7 +77,8 @@ def main():
     }
     np.savez_compressed(os.path.join(HERE, "demo_searching_sketches.npz"), **arrays)
     json.dump(meta, open(os.path.join(HERE, "demo_searching_tables.json"), "w"), indent=1)
-    shutil.copyfile(os.path.join(REF, "refs", "NC_018658.1.fasta.gz"), os.path.join(HERE, "NC_018658.1.fasta.gz"))
+    for acc in ("NC_018658.1", "NC_010655.1"):  # the query, and the smallest genome (tests/test_oracle_golden.py re-sketches both)
+        shutil.copyfile(os.path.join(REF, "refs", f"{acc}.fasta.gz"), os.path.join(HERE, f"{acc}.fasta.gz"))
     print("wrote", sorted(os.listdir(HERE)))
 
 

@@ -63,7 +63,7 @@ def test_bench_two_ranks_equal_one_rank():
     if free_b < 140e9:
         pytest.skip("needs 140 GB of free HBM (58 GB index once for the one-rank run, once split over the two ranks)")
     env, multi = _env("KMCP_BENCH_SAME_GPU")
-    args = ["--steps", "2", "--warmup", "1", "--batch-reads", "16384", "--no-cpu-baseline", "--no-secondary"]
+    args = ["--full", "--steps", "2", "--warmup", "1", "--batch-reads", "16384", "--no-cpu-baseline", "--no-secondary"]
     one = subprocess.run([sys.executable, "bench.py", "--gpus", "1"] + args, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert one.returncode == 0, one.stderr[-3000:]
     j1 = _bench_line(one.stdout)
@@ -103,7 +103,7 @@ def test_bench_two_ranks_hit_list_equals_the_cpu_oracle():
     on a sample of the batch and compares the MERGED multi-GPU hit list with it (bench.py `parity_at_n`): the first run on real
     multi-GPU hardware checks itself.  Here: BASELINE configs[1] (32 blocks, 1.4 GB) on two ranks."""
     env, multi = _env("KMCP_BENCH_SAME_GPU")
-    args = ["--steps", "2", "--warmup", "1", "--workload", "config1", "--batch-reads", "32768", "--no-secondary", "--no-extras"]
+    args = ["--full", "--steps", "2", "--warmup", "1", "--workload", "config1", "--batch-reads", "32768", "--no-secondary", "--no-extras"]
     one = subprocess.run([sys.executable, "bench.py", "--gpus", "1"] + args, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert one.returncode == 0, one.stderr[-3000:]
     j1 = _bench_line(one.stdout)
@@ -127,7 +127,7 @@ def test_bench_eight_ranks_dry_run():
     multi = n_dev >= 8
     if not multi:
         env["KMCP_BENCH_SAME_GPU"] = "1"
-    args = ["--batch-reads", "65536", "--steps", "2", "--warmup", "1"]
+    args = ["--full", "--batch-reads", "65536", "--steps", "2", "--warmup", "1"]
     eight = subprocess.run([sys.executable, "bench.py", "--gpus", "8"] + args, capture_output=True, text=True, timeout=1500, env=env, cwd=ROOT)
     if eight.returncode != 0:
         os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
@@ -155,7 +155,7 @@ def test_bench_reports_a_parity_failure_on_the_line_and_in_the_exit_status():
     one GPU hit of the sample before the comparison)."""
     env, _ = _env("KMCP_BENCH_SAME_GPU")
     env["KMCP_BENCH_FAULT"] = "parity"
-    args = ["--steps", "2", "--warmup", "1", "--workload", "config1", "--batch-reads", "32768", "--no-secondary", "--no-extras"]
+    args = ["--full", "--steps", "2", "--warmup", "1", "--workload", "config1", "--batch-reads", "32768", "--no-secondary", "--no-extras"]
     two = subprocess.run([sys.executable, "bench.py", "--gpus", "2"] + args, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert two.returncode != 0, two.stdout[-2000:]
     j2 = _bench_line(two.stdout)

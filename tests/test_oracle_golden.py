@@ -75,13 +75,13 @@ def test_demo_searching_table(oracle_lib, meta, sketches, tmp_path, mode):
     assert r["qkmers"] == meta["genomes"]["NC_018658.1"][f"{mode}_kmers"]
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/demo-searching/refs"), reason="reference tree not present")
 def test_fixture_sketches_match_reference_genomes(oracle_lib, meta, sketches):
-    """The committed sketches are what the oracle's `compute` restatement yields on the reference's genomes."""
+    """The committed sketches are what the oracle's `compute` restatement yields on the reference's genomes (two of the demo's
+    genomes are committed beside them: the smallest and the query)."""
     O = oracle_lib
     from tests.golden.make_golden import read_fasta_gz
     for acc in ("NC_010655.1", "NC_018658.1"):
-        recs = read_fasta_gz(f"/root/reference/demo-searching/refs/{acc}.fasta.gz")
+        recs = read_fasta_gz(os.path.join(GOLD, f"{acc}.fasta.gz"))
         for mode, t in meta["tables"].items():
             cfg = O.sketch_cfg(k=t["k"], scale=t["scale"], syncmer_s=t["syncmer_s"])
             h = O.sort_unique(np.concatenate([O.generate_kmers(s, cfg) for n, s in recs if "plasmid" not in n]))
