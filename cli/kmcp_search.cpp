@@ -82,6 +82,9 @@ struct Options {
   std::vector<std::string> name_maps, files;
   int min_qlen = 30, min_kmers = 10, dedup = 256, top_scores = 0, threads = 0, device = 0, batch = 131072, gpus = 1, gpu_passes = -1;
   bool batch_given = false;
+  // --sliding-step / --sliding-window / --sliding-greedy: every record searched as the windows `seqkit sliding -s S -W W [-g]` would cut
+  long long sliding_step = 0, sliding_window = 0;
+  bool sliding_step_given = false, sliding_window_given = false, sliding_greedy = false;
   std::vector<int32_t> gpu_ids;
   double min_qcov = 0.55, min_tcov = 0, max_fpr = 0.01;
   bool load_whole = false, low_mem = false, whole_file = false, use_filename = false, keep_unmatched = false, no_header = false,
@@ -108,7 +111,13 @@ static void usage() {
       "           --gpu-ids a,b,c (explicit device list)  --gpu-batch int (queries per GPU call, default 131072)\n"
       "           --gpu-passes int (an index larger than the GPU's memory is searched in this many passes per batch, one part\n"
       "                             resident at a time; 0 = as few as fit; default: only when the index does not fit)\n"
-      "           --parse-only (read the inputs and print records / bases / checksum per file; no database, no GPU)\n",
+      "           --parse-only (read the inputs and print records / bases / checksum per file; no database, no GPU)\n"
+      "Long reads and contigs (the reference's advice: split them with `seqkit sliding -s 100 -W 300`, search the pieces):\n"
+      "           --sliding-step int --sliding-window int [--sliding-greedy]\n"
+      "                             search every window of every record, as `seqkit sliding -s S -W W [-g] | kmcp search` would,\n"
+      "                             without the window text: queries are named <id>_sliding:<start>-<end> (1-based, inclusive),\n"
+      "                             queryIdx and \"# input queries\" count windows.  Both values are needed (>= 1); single-end input\n"
+      "                             only, not with -g/-G or --query-id.  --sliding-greedy keeps the last windows, cut at the end.\n",
       stderr);
 }
 
@@ -134,7 +143,8 @@ static Options parse_args(int argc, char** argv) {
       {"min-kmers", 'c', 1}, {"min-query-len", 'm', 1}, {"min-query-cov", 't', 1}, {"min-target-cov", 'T', 1}, {"max-fpr", 'f', 1},
       {"name-map", 'N', 1}, {"default-name-map", 'D', 0}, {"keep-unmatched", 'K', 0}, {"keep-top-scores", 'n', 1}, {"no-header-row", 'H', 0},
       {"sort-by", 's', 1}, {"do-not-sort", 'S', 0}, {"threads", 'j', 1}, {"quiet", 'q', 0}, {"infile-list", 'i', 1}, {"log", 0, 1},
-      {"gpu", 0, 1}, {"gpu-batch", 0, 1}, {"gpus", 0, 1}, {"gpu-ids", 0, 1}, {"gpu-passes", 0, 1}, {"parse-only", 0, 0}, {"help", 'h', 0}, {"version", 'V', 0}};
+      {"gpu", 0, 1}, {"gpu-batch", 0, 1}, {"gpus", 0, 1}, {"gpu-ids", 0, 1}, {"gpu-passes", 0, 1}, {"parse-only", 0, 0}, {"help", 'h', 0}, {"version", 'V', 0},
+      {"sliding-step", 0, 1}, {"sliding-window", 0, 1}, {"sliding-greedy", 0, 0}};
   auto apply = [&](const std::string& name, const std::string& v) {
     if (name == "db-dir") o.db_dir = v;
     else if (name == "out-file") o.out_file = v;
@@ -174,6 +184,9 @@ static Options parse_args(int argc, char** argv) {
     else if (name == "gpu-batch") { o.batch = to_i(name, v); o.batch_given = true; }
     else if (name == "gpu-passes") o.gpu_passes = to_i(name, v);
     else if (name == "parse-only") o.parse_only = true;
+    else if (name == "sliding-step") { o.sliding_step = to_i(name, v); o.sliding_step_given = true; }
+    else if (name == "sliding-window") { o.sliding_window = to_i(name, v); o.sliding_window_given = true; }
+    else if (name == "sliding-greedy") o.sliding_greedy = true;
     else if (name == "gpus") o.gpus = to_i(name, v);
     else if (name == "gpu-ids") {
       size_t b = 0;
@@ -357,6 +370,9 @@ struct Batch {
     n_exc += n_runs;
     n_bases += nb;
   }
+  // sliding windows: the records' windows are the batch's queries — wpre[r] = windows of records 0 .. r-1, res has one row per window
+  bool windows = false;
+  std::vector<uint64_t> wpre{0};
   uint64_t bases() const { return packed ? n_bases : (uint64_t)(seqs.size() + seqs2.size()); }
   size_t size() const { return id_offs.size() - 1; }
   std::string_view id(size_t i) const { return std::string_view(id_buf.data() + id_offs[i], (size_t)(id_offs[i + 1] - id_offs[i])); }
@@ -900,6 +916,16 @@ int main(int argc, char** argv) {
     }
     return 0;
   }
+  // sliding windows: seqkit sliding has no meaning for pairs, whole files as queries or one ID for everything
+  const bool sliding = o.sliding_step_given || o.sliding_window_given || o.sliding_greedy;
+  if (sliding) {
+    if (!o.sliding_step_given || !o.sliding_window_given) die("flags --sliding-step and --sliding-window are needed together");
+    if (o.sliding_step < 1 || o.sliding_window < 1) die("values of flags --sliding-step and --sliding-window should be positive");
+    if (!o.read1.empty() && !o.read2.empty()) die("flags --sliding-step/--sliding-window are not supported for paired-end input (-1/-2)");
+    if (o.whole_file || o.use_filename) die("flags --sliding-step/--sliding-window cannot be combined with -g/--query-whole-file or -G/--use-filename");
+    if (!o.query_id.empty()) die("flags --sliding-step/--sliding-window cannot be combined with --query-id");
+  }
+  kmcpg_window_spec wspec{(uint64_t)std::max(0ll, o.sliding_step), (uint64_t)std::max(0ll, o.sliding_window), o.sliding_greedy ? 1 : 0, 0};
   if (o.db_dir.empty()) die("flag -d/--db-dir needed");
   if (o.min_kmers < 1) die("value of flag --min-kmers should be positive: %d", o.min_kmers);
   if (o.dedup < 1) die("value of flag --kmer-dedup-threshold should be positive: %d", o.dedup);
@@ -1130,7 +1156,32 @@ int main(int argc, char** argv) {
         }
         for (auto& t : workers) t.join();
       }
-      for (const auto& file : o.whole_file ? std::vector<std::string>() : files) {
+      if (sliding) {
+        // records as they are (one upload of their bases); the library cuts the windows.  A batch closes at `batch_reads` windows or
+        // `max_bases` bases of records; a record with more windows than that is a batch of its own (the library cuts it into pieces).
+        for (const auto& file : files) {
+          if (verbose) info("reading sequence file: %s", file.c_str());
+          FastxReader r(file);
+          std::string rid, rs;
+          uint64_t got = 0;
+          while (r.next(&rid, &rs)) {
+            got++;
+            const uint64_t L = rs.size(), S = wspec.step, W = wspec.window;
+            const uint64_t nw = L == 0 ? 0 : (wspec.greedy ? (L + S - 1) / S : (L >= W ? (L - W) / S + 1 : 0));
+            if (nw == 0) continue;  // (seqkit sliding emits nothing for it: no query)
+            if (b->size() && (b->wpre.back() + nw > batch_reads.load() || b->seqs.size() + L > max_bases.load())) flush();
+            b->windows = true;
+            b->id_buf.insert(b->id_buf.end(), rid.begin(), rid.end());
+            b->id_offs.push_back(b->id_buf.size());
+            b->seqs.insert(b->seqs.end(), (const uint8_t*)rs.data(), (const uint8_t*)rs.data() + L);
+            b->offs.push_back(b->seqs.size());
+            b->wpre.push_back(b->wpre.back() + nw);
+            id += nw;
+          }
+          if (got == 0) warn("no valid sequences in file: %s", file.c_str());
+        }
+      }
+      for (const auto& file : o.whole_file || sliding ? std::vector<std::string>() : files) {
         if (verbose) info("reading sequence file: %s", file.c_str());
         flush();  // batches do not span input files on this path
         const uint64_t got = read_single_end(file, batch_reads.load(), max_bases.load(), [&](std::unique_ptr<Batch> nb) {
@@ -1289,6 +1340,20 @@ int main(int argc, char** argv) {
       const size_t depth = paged_passes > 1 ? 1 : 2;
       std::deque<std::pair<kmcpg_ticket*, std::unique_ptr<Batch>>> fl;
       auto search_sync = [&](Batch& bb) {  // the one-call form: it also halves a batch whose workspace does not fit (kmcp_gpu.h kmcpg_batch_hint)
+        if (bb.windows) {  // (the window route failed for memory: its windows as text, what `seqkit sliding | kmcp search` would hand over)
+          std::vector<uint8_t> wt;
+          std::vector<uint64_t> wo{0};
+          for (size_t r = 0; r + 1 < bb.offs.size(); r++) {
+            const uint64_t L = bb.offs[r + 1] - bb.offs[r];
+            for (uint64_t j = 0; j < bb.wpre[r + 1] - bb.wpre[r]; j++) {
+              const uint64_t st = j * wspec.step, en = std::min<uint64_t>(st + wspec.window, L);
+              wt.insert(wt.end(), bb.seqs.begin() + (ptrdiff_t)(bb.offs[r] + st), bb.seqs.begin() + (ptrdiff_t)(bb.offs[r] + en));
+              wo.push_back(wt.size());
+            }
+          }
+          if (kmcpg_search_batch_pairs(db, wt.data(), wo.data(), nullptr, nullptr, (uint32_t)(wo.size() - 1), &params, &bb.res) != 0) die("%s", kmcpg_last_error());
+          return;
+        }
         if (bb.packed) {  // (a rare path: the text again, the one-call form reads text)
           bb.seqs.resize((size_t)bb.n_bases + 16);
           if (kmcpg_unpack2(bb.codes.data(), bb.n_bases, bb.exc.data(), bb.n_exc, bb.seqs.data()) != 0) die("%s", kmcpg_last_error());
@@ -1326,7 +1391,7 @@ int main(int argc, char** argv) {
           finish_oldest();
           continue;
         }
-        if (paged_passes > 1 && !b->packed) {
+        if (paged_passes > 1 && !b->packed && !b->windows) {
           std::unique_ptr<Batch> nb;
           while (b->size() < batch_reads.load() && b->seqs.size() + b->seqs2.size() < max_bases.load() && q_in.try_pop(&nb)) b->append(*nb);
         }
@@ -1334,6 +1399,23 @@ int main(int argc, char** argv) {
         my_wait += std::chrono::duration<double>(t0 - tw).count();
         kmcpg_ticket* t = nullptr;
         int rc;
+        if (b->windows) {  // the records' windows (kmcp_gpu.h kmcpg_submit_windows): no one-call form, a lane the other searcher holds comes back
+          while ((rc = kmcpg_submit_windows(db, b->seqs.data(), b->offs.data(), (uint32_t)(b->offs.size() - 1), &wspec, &params, &t)) == KMCPG_EBUSY) {
+            if (!fl.empty()) finish_oldest();
+            else std::this_thread::sleep_for(std::chrono::microseconds(200));
+          }
+          if (rc == KMCPG_ENOMEM) {  // as a batch of reads does: the one-call form, which halves what does not fit
+            search_sync(*b);
+            my_gpu += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+            publish(std::move(b));
+            continue;
+          }
+          if (rc != 0) die("%s", kmcpg_last_error());
+          my_gpu += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+          fl.emplace_back(t, std::move(b));
+          if (fl.size() >= depth) finish_oldest();
+          continue;
+        }
         while ((rc = b->packed ? kmcpg_submit_packed(db, b->codes.data(), b->offs.data(), b->exc.data(), b->n_exc, (uint32_t)b->size(), &params, &t)
                                : kmcpg_submit(db, b->seqs.data(), b->offs.data(), b->paired ? b->seqs2.data() : nullptr, b->paired ? b->offs2.data() : nullptr,
                                               (uint32_t)b->size(), &params, &t)) == KMCPG_EBUSY && !fl.empty())
@@ -1439,11 +1521,25 @@ int main(int argc, char** argv) {
         chunk_owner[(size_t)pi] = &F;
         const uint32_t lo = cut[(size_t)pi], hi = cut[(size_t)pi + 1];
         buf.reserve((size_t)(r.match_offs[hi] - r.match_offs[lo]) * 112 + (size_t)(hi - lo) * (o.keep_unmatched ? 64 : 8) + 256);
+        // sliding windows: query i is window j of record wr, named as `seqkit sliding` names it: <id>_sliding:<start>-<end> (1-based)
+        size_t wr = b->windows ? (size_t)(std::upper_bound(b->wpre.begin(), b->wpre.end(), (uint64_t)lo) - b->wpre.begin()) - 1 : 0;
+        std::string wname;
+        auto qname = [&](uint32_t i) -> std::string_view {
+          if (!b->windows) return b->id(i);
+          while (b->wpre[wr + 1] <= i) wr++;
+          const uint64_t L = b->offs[wr + 1] - b->offs[wr], st = (i - b->wpre[wr]) * wspec.step, en = std::min<uint64_t>(st + wspec.window, L);
+          const std::string_view rid = b->id(wr);
+          char tail[64];
+          const int tn = snprintf(tail, sizeof tail, "_sliding:%llu-%llu", (unsigned long long)(st + 1), (unsigned long long)en);
+          wname.assign(rid.data(), rid.size());
+          wname.append(tail, (size_t)tn);
+          return wname;
+        };
         for (uint32_t i = lo; i < hi; i++) {
           const uint64_t qidx = b->first_idx + i;
           const uint64_t m0 = r.match_offs[i], m1 = r.match_offs[i + 1];
           if (m0 == m1) {
-            if (o.keep_unmatched) F.unmatched(buf, b->id(i), r.qlen[i], r.qkmers[i], r.ksize[i], qidx);
+            if (o.keep_unmatched) F.unmatched(buf, qname(i), r.qlen[i], r.qkmers[i], r.ksize[i], qidx);
             continue;
           }
           part_matched[(size_t)pi]++;
@@ -1451,7 +1547,7 @@ int main(int argc, char** argv) {
           // stays in this thread's cache: the batch's records never exist as a whole (1.5 GB per 131 072 reads of a family database)
           if (F.scratch.size() < m1 - m0) F.scratch.resize((size_t)(m1 - m0));
           if (kmcpg_expand_pairs(db, r.qkmers[i], r.pairs + m0, m1 - m0, F.scratch.data()) != 0) die("%s", kmcpg_last_error());
-          F.rows(buf, b->id(i), r.qlen[i], r.qkmers[i], F.scratch.data(), m1 - m0, target, r.ksize[i], qidx);
+          F.rows(buf, qname(i), r.qlen[i], r.qkmers[i], F.scratch.data(), m1 - m0, target, r.ksize[i], qidx);
         }
         if (out.gz()) buf = gzip_member(buf);
         part_busy[(size_t)pi] = std::chrono::duration<double>(std::chrono::steady_clock::now() - tb0).count();

@@ -276,6 +276,32 @@ int kmcpg_unpack2(const uint8_t* codes, uint64_t n_bases, const kmcpg_exc_run* e
 int kmcpg_submit_packed(kmcpg_db* db, const uint8_t* codes, const uint64_t* offs, const kmcpg_exc_run* exc, uint64_t n_exc, uint32_t n_reads,
                         const kmcpg_params* params, kmcpg_ticket** out);
 
+/* -- sliding windows of long reads and contigs: what `seqkit sliding -s step -W window [-g] | kmcp search` computes (the reference's
+ *    advice for long queries, search.go:59-61), without the window text.  Every read (single-end) yields windows i = 0, step, 2 step, ...
+ *    ending at e = i + window; with greedy a window that runs over the end is cut there (e = L) and windows go on while i < L, without it
+ *    they stop at the first such window (a read shorter than `window` has none).  Each window is an ordinary query (qlen e - i, -m, -u,
+ *    multi-k retries, -K, -n, -s / -S, -f apply per window); the result has ONE ROW PER WINDOW, read by read, start ascending, and is
+ *    consumed by kmcpg_wait / kmcpg_wait_pairs as any other ticket.  The bases of each read are uploaded once and the k-mer kernels read a
+ *    window's bases in place (windows.hip, k1_kmers.hip) on single-device handles; paged (kmcpg_open_paged) and multi-device
+ *    (kmcpg_open_devices) handles, and databases with several k-mer sizes searched without an explicit k, cut the windows into text on
+ *    the host and search that (same results).  Windows that do not fit one batch of the handle (kmcpg_batch_hint, in window bases) are
+ *    cut into pieces by the library — a read's windows may span several — and the ticket answers for all of them. */
+typedef struct {
+  uint64_t step;   /* -s, >= 1 */
+  uint64_t window; /* -W, >= 1 */
+  int32_t greedy;  /* -g */
+  int32_t reserved;
+} kmcpg_window_spec;
+int kmcpg_submit_windows(kmcpg_db* db, const uint8_t* seqs, const uint64_t* offs, uint32_t n_reads, const kmcpg_window_spec* spec,
+                         const kmcpg_params* params, kmcpg_ticket** out);
+int kmcpg_submit_packed_windows(kmcpg_db* db, const uint8_t* codes, const uint64_t* offs, const kmcpg_exc_run* exc, uint64_t n_exc,
+                                uint32_t n_reads, const kmcpg_window_spec* spec, const kmcpg_params* params, kmcpg_ticket** out);
+/* how many windows the reads of offs[0 .. n_reads] yield and how many bases they hold together (the `bases` kmcpg_batch_hint speaks of) */
+int kmcpg_window_count(const uint64_t* offs, uint32_t n_reads, const kmcpg_window_spec* spec, uint64_t* n_windows, uint64_t* window_bases);
+/* result rows first .. first + n - 1 of such a batch -> the read (index into offs) and the 0-based first base of each window */
+int kmcpg_window_locate(const uint64_t* offs, uint32_t n_reads, const kmcpg_window_spec* spec, uint64_t first, uint64_t n, uint32_t* read,
+                        uint64_t* start);
+
 int kmcpg_search_batch_pairs(kmcpg_db* db, const uint8_t* seqs, const uint64_t* offs, const uint8_t* seqs2, const uint64_t* offs2,
                              uint32_t n_reads, const kmcpg_params* params, kmcpg_result_pairs* out);
 int kmcpg_wait_pairs(kmcpg_ticket* ticket, kmcpg_result_pairs* out);

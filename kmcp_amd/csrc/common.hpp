@@ -82,7 +82,11 @@ struct K1Args {
   uint32_t n_exc;
   uint8_t* seqs_w;
   uint32_t* seg_exc;     // per (read, segment): != 0 when a foreign byte lies among the bases the segment's k-mers cover (k_mark_exc)
+  // sliding windows (kmcpg_submit_windows): query r is a view of src[r] .. src[r] + offs[r+1] - offs[r] of `seqs` — the bases of the reads are
+  // on the device once, offs numbers the windows' bases (hash output, lengths).  nullptr: query r is seqs[offs[r] ...] itself.
+  const uint64_t* src;
 };
+
 
 // the packed source of the batch the calling thread is about to enqueue (host.cpp -> run_kmers): codes + runs on the device, and the
 // text buffer the expansion goes to when the k-mer kernels of this batch read text
@@ -94,6 +98,18 @@ struct PackedSrc {
   uint64_t n_bases = 0;
 };
 extern thread_local PackedSrc tl_packed_src;
+// the windows of the batch the calling thread is about to enqueue (host.cpp -> run_kmers): src = each window's first base in the staged
+// text (K1Args::src), and the staged slices of reads with their prefix sums (windows.hip) for the hash-once form of plain / FracMinHash k-mers
+constexpr int K1_WIN_CHUNK = 1024;  // k-mer positions of a slice one wave hashes (hash-once form)
+struct WindowSrc {
+  const uint64_t* src = nullptr;   // [n windows]
+  const uint64_t* soffs = nullptr; // [ns + 1] the slices' bases in the staged text
+  const uint64_t* wpre = nullptr;  // [ns + 1] windows of slices 0 .. q-1
+  const uint64_t* cpre = nullptr;  // [ns + 1] chunks of K1_WIN_CHUNK k-mer positions of slices 0 .. q-1 (for the database's k)
+  uint32_t ns = 0;
+  uint64_t n_chunks = 0, sb = 0, step = 0, window = 0;
+};
+extern thread_local WindowSrc tl_window;
 
 struct DedupArgs {
   const uint64_t* offs;

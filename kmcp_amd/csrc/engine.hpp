@@ -140,12 +140,16 @@ struct kmcpg_db {
     kmcpg::DevBuf<uint64_t> w_huge_info;                             // whole-genome queries: (read, n, offset)
     kmcpg::DevBuf<uint8_t> w_huge_temp;                              // histogram table of the device-wide radix sort
     kmcpg::DevBuf<uint64_t> w_gathered;                              // profiling level 2: the row loads k2_cobs issued
+    // sliding windows, hash-once form: per-position hashes, kept hashes in order, ranks, per-chunk counts and their prefix
+    kmcpg::DevBuf<uint64_t> w_win_h, w_win_kept, w_win_cbase;
+    kmcpg::DevBuf<uint32_t> w_win_rank, w_win_cnt;
     hipEvent_t ev = nullptr;  // recorded at the end of every call that used the slot: the slot's next user waits for it
     bool ev_valid = false;
     hipEvent_t in_ev = nullptr, k1_ev = nullptr;  // KMCPG_K1_STREAM: inputs ready on the caller's stream / k-mers ready on k1_stream
     void release() {
       w_hashes.release(); w_scratch.release(); w_nk_raw.release(); w_nk1.release(); w_seg_cnt.release(); w_long_list.release();
       w_long_meta.release(); w_long_counts.release(); w_huge_info.release(); w_huge_temp.release(); w_gathered.release();
+      w_win_h.release(); w_win_kept.release(); w_win_cbase.release(); w_win_rank.release(); w_win_cnt.release();
       if (ev) (void)hipEventDestroy(ev);
       if (in_ev) (void)hipEventDestroy(in_ev);
       if (k1_ev) (void)hipEventDestroy(k1_ev);

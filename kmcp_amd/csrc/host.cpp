@@ -87,6 +87,15 @@ struct Lane {
   bool packed = false;
   uint32_t n_exc = 0;
   const uint8_t* ext_pack = nullptr;  // codes that live in the CALLER's pinned memory (kmcpg_host_alloc): uploaded from there, no staging copy
+  // sliding windows (kmcpg_submit_windows): the lane staged ns slices of reads (sb bases, h_offs = their offsets) and searches n windows over
+  // them (tb1 = the windows' bases, maxlen = the longest window); h_wmeta = the slices' window prefix and window-base prefix (2 x (ns + 1)).
+  // The device builds d_offs (the windows' numbering) and d_wsrc (each window's first base in d_seqs) from d_soffs + d_wmeta (windows.hip).
+  // A third array in h_wmeta: the slices' chunks of K1_WIN_CHUNK k-mer positions (wchunks in all), for the hash-once form of K1.
+  bool win = false;
+  uint32_t ns = 0;
+  uint64_t sb = 0, wstep = 0, wwin = 0, wchunks = 0;
+  PinBuf<uint64_t> h_wmeta;
+  DevBuf<uint64_t> d_soffs, d_wmeta, d_wsrc;
   int32_t bound_n = 0;   // the -f bound of the LAST kmcpg_query_device call for this batch covered queries of up to this many k-mers
   bool grouped = false;  // this batch went through K3: h_pairs / h_roffs hold its result, h_hits is not filled
   hipEvent_t k3_ev = nullptr, eager_ev = nullptr;  // K3 done on the kernel stream -> the eager copy of the pairs on the copy stream
@@ -104,6 +113,7 @@ struct Lane {
     d_seqs.release(); d_seqs2.release(); d_offs.release(); d_offs2.release(); d_cnt.release(); d_qk.release(); d_ql.release(); d_hits.release();
     d_pairs.release(); d_roffs.release(); h_pairs.release(); h_roffs.release();
     h_pack.release(); h_exc.release(); d_pack.release(); d_exc.release();
+    h_wmeta.release(); d_soffs.release(); d_wmeta.release(); d_wsrc.release();
     if (done) (void)hipEventDestroy(done);
     if (uploaded) (void)hipEventDestroy(uploaded);
     if (k3_ev) (void)hipEventDestroy(k3_ev);
@@ -185,6 +195,10 @@ struct kmcpg_ticket {
   std::vector<uint64_t> offs, offs2;
   std::vector<kmcpg_hit, NoInitAlloc<kmcpg_hit>> hits;
   std::vector<int32_t> qk, ql;
+  // sliding windows cut into pieces (kmcpg_submit_windows): the pieces' tickets in window order; a piece that was finished early to free a
+  // lane for a later one has its result in piece_res[i] instead (pieces[i] == nullptr).  Such a ticket holds no lane itself.
+  std::vector<kmcpg_ticket*> pieces;
+  std::vector<kmcpg_result> piece_res;
 };
 
 namespace {
@@ -286,8 +300,10 @@ bool pack_wanted(uint64_t total_bases, uint32_t n) {
 
 int stage(Lane* L, const uint8_t* seqs, const uint64_t* offs, const uint8_t* seqs2, const uint64_t* offs2, uint32_t n, bool allow_pack = false) {
   L->n = n;
+  L->win = false;
   L->packed = false;
   L->n_exc = 0;
+  L->ext_pack = nullptr;  // (a lane that served kmcpg_submit_packed from the caller's pinned codes last time uploads from its own buffer now)
   L->paired = seqs2 != nullptr;
   L->tb1 = L->tb2 = 0;
   L->maxlen = 0;
@@ -343,6 +359,7 @@ struct PackedIn {
 int stage_packed(Lane* L, const PackedIn& in, const uint64_t* offs, uint32_t n) {
   static_assert(sizeof(kmcpg_exc_run) == sizeof(ExcRun), "one layout");
   L->n = n;
+  L->win = false;
   L->packed = false;
   L->n_exc = 0;
   L->ext_pack = nullptr;
@@ -398,11 +415,30 @@ int enqueue_query(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p, c
       s.exc = L->n_exc ? L->d_exc.p : nullptr;
       s.n_exc = L->n_exc;
       s.text = L->d_seqs.p;
-      s.n_bases = L->tb1;
+      s.n_bases = L->win ? L->sb : L->tb1;
       tl_packed_src = s;
     }
     ~PackedScope() { tl_packed_src = PackedSrc{}; }
   } packed_scope(L);
+  // sliding windows: the k-mer kernels read each window's bases in place (d_wsrc, built by the prologue of the first attempt)
+  struct WindowScope {
+    explicit WindowScope(Lane* L) {
+      tl_window = WindowSrc{};
+      if (!L->win) return;
+      WindowSrc w;
+      w.src = L->d_wsrc.p;
+      w.soffs = L->d_soffs.p;
+      w.wpre = L->d_wmeta.p;
+      w.cpre = L->d_wmeta.p + 2 * ((size_t)L->ns + 1);
+      w.ns = L->ns;
+      w.n_chunks = L->wchunks;
+      w.sb = L->sb;
+      w.step = L->wstep;
+      w.window = L->wwin;
+      tl_window = w;
+    }
+    ~WindowScope() { tl_window = WindowSrc{}; }
+  } window_scope(L);
   int rc = query_device_after(db, L->d_seqs.p, L->d_offs.p, L->paired ? L->d_seqs2.p : nullptr, L->paired ? L->d_offs2.p : nullptr, L->n, L->tb1 + L->tb2,
                               L->maxlen, &p, L->d_hits.p, L->d_hits.cap, L->d_cnt.p, L->d_qk.p, L->d_ql.p, st, prologue);
   if (rc) return rc;
@@ -454,8 +490,12 @@ int enqueue(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p, bool ge
     L->d_pairs.release();
   }
   uint64_t cap = std::max<uint64_t>(L->d_hits.cap, want);
-  if (L->d_seqs.ensure(L->tb1 + 16) || L->d_offs.ensure((size_t)n + 1) || L->d_cnt.ensure(2) || L->d_qk.ensure(n) || L->d_ql.ensure(n) ||
-      (L->paired && (L->d_seqs2.ensure(L->tb2 + 16) || L->d_offs2.ensure((size_t)n + 1))))
+  // the bases and reads that go up: the batch itself, or — sliding windows — the slices of reads its windows view
+  const uint64_t up_bases = L->win ? L->sb : L->tb1;
+  const size_t up_reads = L->win ? L->ns : n;
+  if (L->d_seqs.ensure(up_bases + 16) || L->d_offs.ensure((size_t)n + 1) || L->d_cnt.ensure(2) || L->d_qk.ensure(n) || L->d_ql.ensure(n) ||
+      (L->paired && (L->d_seqs2.ensure(L->tb2 + 16) || L->d_offs2.ensure((size_t)n + 1))) ||
+      (L->win && (L->d_soffs.ensure(up_reads + 1) || L->d_wmeta.ensure(3 * (up_reads + 1)) || L->d_wsrc.ensure(n))))
     return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
   if (L->d_hits.ensure(cap)) {  // no room for the generous size next to the index: the plain one, and a rerun if it overflows
     (void)hipGetLastError();
@@ -471,13 +511,18 @@ int enqueue(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p, bool ge
   // kernels of consecutive batches); the lane's device buffers are idle, its previous batch was waited for
   hipStream_t up = A->up_stream;
   if (L->packed) {
-    if (L->d_pack.ensure(L->tb1 / 4 + 16) || (L->n_exc && L->d_exc.ensure(L->n_exc))) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
-    HIPCHK(hipMemcpyAsync(L->d_pack.p, L->ext_pack ? L->ext_pack : L->h_pack.p, (L->tb1 + 3) / 4, hipMemcpyHostToDevice, up));
+    if (L->d_pack.ensure(up_bases / 4 + 16) || (L->n_exc && L->d_exc.ensure(L->n_exc))) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
+    HIPCHK(hipMemcpyAsync(L->d_pack.p, L->ext_pack ? L->ext_pack : L->h_pack.p, (up_bases + 3) / 4, hipMemcpyHostToDevice, up));
     if (L->n_exc) HIPCHK(hipMemcpyAsync(L->d_exc.p, L->h_exc.p, (size_t)L->n_exc * sizeof(ExcRun), hipMemcpyHostToDevice, up));
-  } else if (L->tb1) {
-    HIPCHK(hipMemcpyAsync(L->d_seqs.p, L->h_seqs.p, L->tb1, hipMemcpyHostToDevice, up));
+  } else if (up_bases) {
+    HIPCHK(hipMemcpyAsync(L->d_seqs.p, L->h_seqs.p, up_bases, hipMemcpyHostToDevice, up));
   }
-  HIPCHK(hipMemcpyAsync(L->d_offs.p, L->h_offs.p, ((size_t)n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, up));
+  if (L->win) {
+    HIPCHK(hipMemcpyAsync(L->d_soffs.p, L->h_offs.p, (up_reads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, up));
+    HIPCHK(hipMemcpyAsync(L->d_wmeta.p, L->h_wmeta.p, 3 * (up_reads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, up));
+  } else {
+    HIPCHK(hipMemcpyAsync(L->d_offs.p, L->h_offs.p, ((size_t)n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, up));
+  }
   if (L->paired) {
     if (L->tb2) HIPCHK(hipMemcpyAsync(L->d_seqs2.p, L->h_seqs2.p, L->tb2, hipMemcpyHostToDevice, up));
     HIPCHK(hipMemcpyAsync(L->d_offs2.p, L->h_offs2.p, ((size_t)n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, up));
@@ -487,6 +532,10 @@ int enqueue(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p, bool ge
   // lock: see query.cpp query_device_after
   const std::function<int()> after_upload = [&]() -> int {
     HIPCHK(hipStreamWaitEvent(st, L->uploaded, 0));
+    if (L->win) {  // the windows' descriptors, in front of the k-mer kernels that read through them
+      launch_window_desc(L->d_soffs.p, L->d_wmeta.p, L->d_wmeta.p + up_reads + 1, (uint32_t)up_reads, n, L->wstep, L->wwin, L->d_wsrc.p, L->d_offs.p, st);
+      HIPCHK(hipGetLastError());
+    }
     return 0;
   };
   int rc = enqueue_query(db, A, L, p, &after_upload);
@@ -589,6 +638,9 @@ int collect(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p, uint64_
 }
 
 void drop_ticket(kmcpg_ticket* t, bool failed = false) {
+  for (kmcpg_ticket* pc : t->pieces)
+    if (pc) drop_ticket(pc, failed);
+  for (kmcpg_result& r : t->piece_res) kmcpg_result_free(&r);
   for (auto& pt : t->parts) {
     if (pt.shard->opts.device >= 0) (void)hipSetDevice(pt.shard->opts.device);
     // the lane must be idle before someone else stages into it
@@ -933,6 +985,268 @@ int retry_unmatched(kmcpg_ticket* t, kmcpg_result* out) {
   return rc;
 }
 
+
+// ---- sliding windows (kmcpg_submit_windows): seqkit sliding's enumeration, pieces, and the two ways a piece is searched
+uint64_t win_count(uint64_t L, const kmcpg_window_spec& s) {
+  if (L == 0) return 0;
+  if (s.greedy) return (L + s.step - 1) / s.step;
+  return L >= s.window ? (L - s.window) / s.step + 1 : 0;
+}
+
+// bases of windows 0 .. j-1 of a read of L bases: the full ones (W each), then — greedy — the ones cut at the read's end (windows.hip does
+// the same sum on the device)
+uint64_t win_bases_before(uint64_t L, uint64_t j, const kmcpg_window_spec& s) {
+  const uint64_t S = s.step, W = s.window;
+  const uint64_t full = L >= W ? (L - W) / S + 1 : 0;
+  if (j <= full) return j * W;
+  return full * W + (j - full) * L - S * ((j * (j - 1)) / 2 - (full * (full - (full > 0 ? 1 : 0))) / 2);
+}
+
+struct WinSlice {
+  uint32_t r;
+  uint64_t j0, j1;  // windows [j0, j1) of read r
+};
+struct WinPiece {
+  std::vector<WinSlice> sl;
+  uint64_t n_win = 0, bases = 0;
+};
+
+// the batch's windows in order, cut where a piece would exceed `budget` window bases or `max_win` windows (one window always goes)
+std::vector<WinPiece> plan_windows(const uint64_t* offs, uint32_t n, const kmcpg_window_spec& s, uint64_t budget, uint64_t max_win) {
+  std::vector<WinPiece> out;
+  WinPiece cur;
+  for (uint32_t r = 0; r < n; r++) {
+    const uint64_t L = offs[r + 1] - offs[r], c = win_count(L, s);
+    uint64_t j = 0;
+    while (j < c) {
+      const uint64_t room = budget > cur.bases ? budget - cur.bases : 0, vj = win_bases_before(L, j, s);
+      const uint64_t lim = std::min<uint64_t>(c, j + (max_win - cur.n_win));
+      uint64_t j1 = lim;
+      if (win_bases_before(L, lim, s) - vj > room) {  // the last j1 in [j, lim) whose windows fit
+        uint64_t lo = j, hi = lim;
+        while (hi - lo > 1) {
+          const uint64_t mid = lo + (hi - lo) / 2;
+          if (win_bases_before(L, mid, s) - vj <= room) lo = mid;
+          else hi = mid;
+        }
+        j1 = lo;
+      }
+      if (j1 == j) {
+        if (cur.n_win) {
+          out.push_back(std::move(cur));
+          cur = WinPiece();
+          continue;
+        }
+        j1 = j + 1;
+      }
+      cur.sl.push_back({r, j, j1});
+      cur.n_win += j1 - j;
+      cur.bases += win_bases_before(L, j1, s) - vj;
+      j = j1;
+      if (cur.n_win >= max_win || cur.bases >= budget) {
+        out.push_back(std::move(cur));
+        cur = WinPiece();
+      }
+    }
+  }
+  if (cur.n_win) out.push_back(std::move(cur));
+  return out;
+}
+
+// window bases one piece may hold: what kmcpg_batch_hint says fits beside the index, at most 256 M (6 GB of k-mer workspace)
+uint64_t window_budget(const kmcpg_db* db) {
+  uint64_t b = 1ull << 28, hint = 0;
+  if (kmcpg_batch_hint(db, &hint) == 0 && hint > 0) b = std::min(b, hint);
+  static const bool test_hooks = getenv("KMCPG_TEST_HOOKS") && atoi(getenv("KMCPG_TEST_HOOKS")) == 1;
+  if (test_hooks)  // the fake ENOMEM of query.cpp: tests cut a read's windows over several pieces this way
+    if (const char* e = getenv("KMCPG_TEST_MAX_BASES")) b = std::min<uint64_t>(b, (uint64_t)std::max(1ll, atoll(e)));
+  return std::max<uint64_t>(b, 1);
+}
+
+// device path: the slices of reads the piece's windows cover go up as they are (a batch of reads, packed by stage() where that pays); the
+// windows are descriptors built on the device (windows.hip) and read in place by the k-mer kernels
+int submit_window_piece_device(kmcpg_db* db, const uint8_t* seqs, const uint64_t* offs, const kmcpg_window_spec& s, const WinPiece& pc,
+                               const kmcpg_params& p, kmcpg_ticket** out) {
+  static thread_local std::vector<uint8_t> text;
+  static thread_local std::vector<uint64_t> soffs, wpre, vpre, cpre;
+  text.clear();
+  soffs.assign(1, 0);
+  wpre.assign(1, 0);
+  vpre.assign(1, 0);
+  cpre.assign(1, 0);
+  const uint64_t k = (uint64_t)(p.k > 0 ? p.k : db->info.k);
+  uint64_t wmax = 0;
+  auto slice = [&](uint32_t r, uint64_t rlen, uint64_t j0, uint64_t j1) {
+    const uint64_t a0 = j0 * s.step, a1 = std::min<uint64_t>((j1 - 1) * s.step + s.window, rlen);
+    text.insert(text.end(), seqs + offs[r] + a0, seqs + offs[r] + a1);
+    soffs.push_back(text.size());
+    wpre.push_back(wpre.back() + (j1 - j0));
+    vpre.push_back(vpre.back() + win_bases_before(rlen, j1, s) - win_bases_before(rlen, j0, s));
+    cpre.push_back(cpre.back() + (a1 - a0 >= k ? (a1 - a0 - k + 1 + K1_WIN_CHUNK - 1) / K1_WIN_CHUNK : 0));
+    wmax = std::max<uint64_t>(wmax, std::min<uint64_t>(s.window, a1 - a0));
+  };
+  for (const WinSlice& x : pc.sl) {
+    const uint64_t rlen = offs[x.r + 1] - offs[x.r];
+    if (s.step >= s.window)  // windows that do not overlap (-s 1000 -W 212): the bases between them stay home, each window is a slice of its own
+      for (uint64_t j = x.j0; j < x.j1; j++) slice(x.r, rlen, j, j + 1);
+    else
+      slice(x.r, rlen, x.j0, x.j1);
+  }
+  const uint32_t ns = (uint32_t)(soffs.size() - 1);
+  std::unique_ptr<kmcpg_ticket> t(new kmcpg_ticket());
+  t->db = db;
+  t->n = (uint32_t)pc.n_win;
+  t->p = p;
+  AsyncState* A = nullptr;
+  if (int rc = async_state(db, &A)) return rc;
+  Lane* L = acquire_lane(A, false, false);
+  if (!L) return kmcpg_fail(KMCPG_EBUSY, "all %zu lanes of this handle are in flight: kmcpg_wait for a ticket first (KMCPG_INFLIGHT)", A->max_lanes);
+  t->parts.push_back({db, L, false});
+  int rc = stage(L, text.data(), soffs.data(), nullptr, nullptr, ns, true);
+  if (rc == 0 && L->h_wmeta.ensure(3 * ((size_t)ns + 1))) rc = kmcpg_fail(KMCPG_ENOMEM, "hipHostMalloc failed");
+  if (rc == 0) {
+    memcpy(L->h_wmeta.p, wpre.data(), ((size_t)ns + 1) * sizeof(uint64_t));
+    memcpy(L->h_wmeta.p + ns + 1, vpre.data(), ((size_t)ns + 1) * sizeof(uint64_t));
+    memcpy(L->h_wmeta.p + 2 * ((size_t)ns + 1), cpre.data(), ((size_t)ns + 1) * sizeof(uint64_t));
+    L->wchunks = cpre.back();
+    L->win = true;
+    L->ns = ns;
+    L->sb = L->tb1;
+    L->wstep = s.step;
+    L->wwin = s.window;
+    L->n = (uint32_t)pc.n_win;
+    L->tb1 = pc.bases;
+    L->maxlen = (uint32_t)wmax;
+    rc = enqueue(db, A, L, p);
+  }
+  if (rc) {
+    const std::string keep = kmcpg_err_ref();
+    drop_ticket(t.release(), true);
+    return kmcpg_fail(rc, "%s", keep.c_str());
+  }
+  t->S[0] = L->h_seqs.p;
+  t->O[0] = L->h_offs.p;
+  *out = t.release();
+  return 0;
+}
+
+// host path (paged and multi-device handles, multi-k databases without an explicit k): the windows cut into text, searched as reads
+int submit_window_piece_text(kmcpg_db* db, const uint8_t* seqs, const uint64_t* offs, const kmcpg_window_spec& s, const WinPiece& pc,
+                             const kmcpg_params& p, kmcpg_ticket** out) {
+  static thread_local std::vector<uint8_t> text;
+  static thread_local std::vector<uint64_t> woffs;
+  text.clear();
+  woffs.assign(1, 0);
+  for (const WinSlice& x : pc.sl) {
+    const uint64_t L = offs[x.r + 1] - offs[x.r];
+    for (uint64_t j = x.j0; j < x.j1; j++) {
+      const uint64_t i = j * s.step, e = std::min<uint64_t>(i + s.window, L);
+      text.insert(text.end(), seqs + offs[x.r] + i, seqs + offs[x.r] + e);
+      woffs.push_back(text.size());
+    }
+  }
+  return submit_impl(db, text.data(), woffs.data(), nullptr, nullptr, (uint32_t)pc.n_win, p, false, false, out);
+}
+
+int submit_windows_impl(kmcpg_db* db, const uint8_t* seqs, const uint64_t* offs, uint32_t n, const kmcpg_window_spec& s, const kmcpg_params& p,
+                        kmcpg_ticket** out) {
+  // which handles read the windows in place: one GPU holding the whole index, and no search of the window text again (the smaller k of a
+  // multi-k database re-reads the staged text, retry_unmatched).  KMCPG_WINDOWS_HOST=1 cuts text everywhere (A/B runs).
+  static const bool host_env = getenv("KMCPG_WINDOWS_HOST") && atoi(getenv("KMCPG_WINDOWS_HOST")) == 1;
+  const bool device = !host_env && db->paged_passes == 0 && db->shards.empty() && (p.k > 0 || db->ks_desc.size() < 2);
+  const std::vector<WinPiece> pieces = plan_windows(offs, n, s, window_budget(db), 1ull << 22);
+  auto one = [&](const WinPiece& pc, kmcpg_ticket** o) {
+    return device ? submit_window_piece_device(db, seqs, offs, s, pc, p, o) : submit_window_piece_text(db, seqs, offs, s, pc, p, o);
+  };
+  if (pieces.empty()) {  // no read yields a window: an empty batch
+    static const uint64_t zero = 0;
+    return submit_impl(db, nullptr, &zero, nullptr, nullptr, 0, p, false, false, out);
+  }
+  if (pieces.size() == 1) return one(pieces[0], out);
+  uint64_t total = 0;
+  for (const WinPiece& pc : pieces) total += pc.n_win;
+  if (total > 0xffffffffULL) return kmcpg_fail(KMCPG_EUNSUPPORTED, "%llu windows in one batch: at most 2^32 - 1", (unsigned long long)total);
+  std::unique_ptr<kmcpg_ticket> t(new kmcpg_ticket());
+  t->db = db;
+  t->n = (uint32_t)total;
+  t->p = p;
+  t->pieces.assign(pieces.size(), nullptr);
+  t->piece_res.assign(pieces.size(), kmcpg_result{});
+  size_t oldest = 0;  // pieces before this one are finished or waited for
+  for (size_t i = 0; i < pieces.size(); i++) {
+    for (;;) {
+      const int rc = one(pieces[i], &t->pieces[i]);
+      if (rc == 0) break;
+      // every lane in flight: finish this ticket's own oldest piece into its slot and take its lane (a caller whose other tickets hold every
+      // lane gets KMCPG_EBUSY, as from kmcpg_submit)
+      while (oldest < i && !t->pieces[oldest]) oldest++;
+      if (rc != KMCPG_EBUSY || oldest == i) {
+        const std::string keep = kmcpg_err_ref();
+        drop_ticket(t.release(), true);
+        return kmcpg_fail(rc, "%s", keep.c_str());
+      }
+      kmcpg_ticket* w = t->pieces[oldest];
+      t->pieces[oldest] = nullptr;
+      if (const int rc2 = kmcpg_wait(w, &t->piece_res[oldest])) {
+        const std::string keep = kmcpg_err_ref();
+        drop_ticket(t.release(), true);
+        return kmcpg_fail(rc2, "%s", keep.c_str());
+      }
+    }
+  }
+  *out = t.release();
+  return 0;
+}
+
+// a ticket of several window pieces: their results one behind the other, as one result (the record or the compact form the caller asked for)
+int wait_pieces(kmcpg_ticket* t, kmcpg_result* out) {
+  const size_t np = t->pieces.size();
+  std::vector<kmcpg_result> rs(np);
+  int rc = 0;
+  for (size_t i = 0; i < np && rc == 0; i++) {
+    if (t->pieces[i]) {
+      kmcpg_ticket* w = t->pieces[i];
+      t->pieces[i] = nullptr;
+      rc = kmcpg_wait(w, &rs[i]);
+    } else {
+      rs[i] = t->piece_res[i];
+      t->piece_res[i] = kmcpg_result{};
+    }
+  }
+  if (rc) {
+    for (kmcpg_result& r : rs) kmcpg_result_free(&r);
+    return rc;
+  }
+  ResultOwner* o = result_owner_take();
+  result_owner_shape(o, t->n);
+  uint32_t base = 0;
+  std::vector<kmcpg_match> ex;
+  for (kmcpg_result& r : rs) {
+    ResultOwner* oi = (ResultOwner*)r.owner;
+    const uint32_t m = r.n_reads;
+    if (oi && m) {
+      if (o->pairs_mode) result_records_to_pairs(oi);
+      for (uint32_t q = 0; q < m; q++) {
+        o->qlen[base + q] = r.qlen[q];
+        o->qkmers[base + q] = r.qkmers[q];
+        o->ksize[base + q] = r.ksize[q];
+        const uint64_t a = oi->offs[q], b = oi->offs[q + 1];
+        o->offs[(size_t)base + q + 1] = b - a;
+        if (o->pairs_mode) o->pairs.insert(o->pairs.end(), oi->pairs.begin() + (ptrdiff_t)a, oi->pairs.begin() + (ptrdiff_t)b);
+        else if (!oi->pairs_mode) o->matches.insert(o->matches.end(), oi->matches.begin() + (ptrdiff_t)a, oi->matches.begin() + (ptrdiff_t)b);
+        else {  // (a piece finished in the compact form, the caller wants records)
+          ex.resize(b - a);
+          if (b > a) (void)kmcpg_expand_pairs(t->db, r.qkmers[q], oi->pairs.data() + a, b - a, ex.data());
+          o->matches.insert(o->matches.end(), ex.begin(), ex.end());
+        }
+      }
+    }
+    base += m;
+    kmcpg_result_free(&r);
+  }
+  result_publish(o, t->n, t->p.k > 0 ? t->p.k : t->db->info.k, out);
+  return 0;
+}
 }  // namespace
 
 extern "C" int kmcpg_open_devices(const char* db_dir, const int32_t* devices, int32_t n_devices, kmcpg_db** out) {
@@ -1128,14 +1442,100 @@ extern "C" int kmcpg_submit_packed(kmcpg_db* db, const uint8_t* codes, const uin
   return submit_impl(db, nullptr, offs, nullptr, nullptr, n_reads, p, false, false, out, &in);
 }
 
+
+static int window_args(const uint64_t* offs, uint32_t n_reads, const kmcpg_window_spec* spec) {
+  if (!spec || (n_reads && !offs)) return kmcpg_fail(KMCPG_EINVAL, "null argument");
+  if (spec->step < 1 || spec->window < 1) return kmcpg_fail(KMCPG_EINVAL, "window spec: step and window must be >= 1");
+  // (a negative value from a caller that meant a signed type arrives as ~2^64: refused, as is anything in the fields the ABI keeps for later)
+  if (spec->step > (1ull << 40) || spec->window > (1ull << 40)) return kmcpg_fail(KMCPG_EINVAL, "window spec: step and window must be <= 2^40");
+  if (spec->greedy != 0 && spec->greedy != 1) return kmcpg_fail(KMCPG_EINVAL, "window spec: greedy must be 0 or 1");
+  if (spec->reserved != 0) return kmcpg_fail(KMCPG_EINVAL, "window spec: reserved must be 0 (zero the struct)");
+  if (n_reads && offs[0] != 0) return kmcpg_fail(KMCPG_EINVAL, "offs[0] must be 0");
+  for (uint32_t i = 0; i < n_reads; i++) {
+    if (offs[i + 1] < offs[i]) return kmcpg_fail(KMCPG_EINVAL, "offsets must not decrease (read %u)", i);
+    if (offs[i + 1] - offs[i] > 0x7fffffffULL) return kmcpg_fail(KMCPG_EUNSUPPORTED, "query longer than 2^31-1 bases");
+  }
+  return 0;
+}
+
+static int window_handle(kmcpg_db* db, const kmcpg_params* params, kmcpg_params* p) {
+  if (db->opts.shard_count != 1)
+    return kmcpg_fail(KMCPG_EINVAL, "kmcpg_submit/kmcpg_search_batch need the whole database: open it on one GPU or with kmcpg_open_devices; use kmcpg_query_device + kmcpg_finalize per shard");
+  if (db->shards.empty() && db->opts.device < 0 && db->paged_passes == 0) return kmcpg_fail(KMCPG_EDEVICE, "metadata-only handle (device -1): no GPU work possible");
+  *p = params ? *params : default_params();
+  if (p->min_matched < 1) return kmcpg_fail(KMCPG_EINVAL, "min_matched must be >= 1");
+  return 0;
+}
+
+extern "C" int kmcpg_window_count(const uint64_t* offs, uint32_t n_reads, const kmcpg_window_spec* spec, uint64_t* n_windows, uint64_t* window_bases) {
+  if (int rc = window_args(offs, n_reads, spec)) return rc;
+  uint64_t nw = 0, nb = 0;
+  for (uint32_t r = 0; r < n_reads; r++) {
+    const uint64_t L = offs[r + 1] - offs[r], c = win_count(L, *spec);
+    nw += c;
+    nb += win_bases_before(L, c, *spec);
+  }
+  if (n_windows) *n_windows = nw;
+  if (window_bases) *window_bases = nb;
+  return 0;
+}
+
+extern "C" int kmcpg_window_locate(const uint64_t* offs, uint32_t n_reads, const kmcpg_window_spec* spec, uint64_t first, uint64_t n, uint32_t* read,
+                                   uint64_t* start) {
+  if (int rc = window_args(offs, n_reads, spec)) return rc;
+  if (n && (!read || !start)) return kmcpg_fail(KMCPG_EINVAL, "null argument");
+  uint64_t w = 0, done = 0;
+  for (uint32_t r = 0; r < n_reads && done < n; r++) {
+    const uint64_t c = win_count(offs[r + 1] - offs[r], *spec);
+    for (uint64_t j = first > w ? first - w : 0; j < c && done < n; j++) {
+      read[done] = r;
+      start[done] = j * spec->step;
+      done++;
+    }
+    w += c;
+  }
+  if (done < n) return kmcpg_fail(KMCPG_EINVAL, "rows %llu .. %llu: the batch has %llu windows", (unsigned long long)first, (unsigned long long)(first + n - 1), (unsigned long long)w);
+  return 0;
+}
+
+extern "C" int kmcpg_submit_windows(kmcpg_db* db, const uint8_t* seqs, const uint64_t* offs, uint32_t n_reads, const kmcpg_window_spec* spec,
+                                    const kmcpg_params* params, kmcpg_ticket** out) {
+  if (!db || !out || (n_reads && (!seqs || !offs))) return kmcpg_fail(KMCPG_EINVAL, "null argument");
+  *out = nullptr;
+  kmcpg_params p;
+  if (int rc = window_handle(db, params, &p)) return rc;
+  if (int rc = window_args(offs, n_reads, spec)) return rc;
+  return submit_windows_impl(db, seqs, offs, n_reads, *spec, p, out);
+}
+
+extern "C" int kmcpg_submit_packed_windows(kmcpg_db* db, const uint8_t* codes, const uint64_t* offs, const kmcpg_exc_run* exc, uint64_t n_exc,
+                                           uint32_t n_reads, const kmcpg_window_spec* spec, const kmcpg_params* params, kmcpg_ticket** out) {
+  if (!db || !out || (n_reads && (!codes || !offs)) || (n_exc && !exc)) return kmcpg_fail(KMCPG_EINVAL, "null argument");
+  *out = nullptr;
+  kmcpg_params p;
+  if (int rc = window_handle(db, params, &p)) return rc;
+  if (int rc = window_args(offs, n_reads, spec)) return rc;
+  // the reads' bases once as text on the host (not the windows'): the slices a piece needs are cut from it and go up packed again where that
+  // pays (stage)
+  std::vector<uint8_t> text;  // (released on return: the pieces have been staged by then)
+  const uint64_t tb = n_reads ? offs[n_reads] : 0;
+  text.resize(tb + 1);
+  if (int rc = kmcpg_unpack2(codes, tb, exc, n_exc, text.data())) return rc;
+  return submit_windows_impl(db, text.data(), offs, n_reads, *spec, p, out);
+}
+
 extern "C" int kmcpg_wait(kmcpg_ticket* t, kmcpg_result* out) {
   if (!t || !out) {
     if (t) drop_ticket(t);
     return kmcpg_fail(KMCPG_EINVAL, "null argument");
   }
   memset(out, 0, sizeof *out);
-  int rc = finish_raw(t, out);
-  if (rc == 0) rc = retry_unmatched(t, out);
+  int rc;
+  if (!t->pieces.empty()) rc = wait_pieces(t, out);
+  else {
+    rc = finish_raw(t, out);
+    if (rc == 0) rc = retry_unmatched(t, out);
+  }
   const std::string keep = rc ? kmcpg_err_ref() : std::string();
   if (rc) kmcpg_result_free(out);
   drop_ticket(t, rc != 0);

@@ -239,6 +239,9 @@ __device__ __forceinline__ int sketch_mate(const K1Args& a, int mode, const uint
   return hash_mate(s, len, a.k, tab, a.scaled != 0, a.max_hash, out, cnt, lane);
 }
 
+// the first base of query r as the k-mer kernels read it (o1 = offs[r]): in place, or a window's view into its read (K1Args::src)
+__device__ __forceinline__ const uint8_t* k1_bases(const K1Args& a, uint32_t r, uint64_t o1) { return a.seqs + (a.src ? a.src[r] : o1); }
+
 // one kernel per sketch mode: the plain/FracMinHash form (every short-read search) does not carry the window sketches' registers
 template <int MODE>
 __global__ void __launch_bounds__(256) k1_kmers(const K1Args a) {
@@ -265,7 +268,7 @@ __global__ void __launch_bounds__(256) k1_kmers(const K1Args a) {
     if (!skip) {
       uint64_t* tk = a.scratch ? a.scratch + o1 + o2 : nullptr;   // k-mer hashes of the mate being sketched
       uint64_t* ts = a.scratch2 ? a.scratch2 + o1 + o2 : nullptr;  // its s-mer hashes (syncmer mode)
-      cnt = sketch_mate(a, MODE, a.seqs + o1, len1, tab, tk, ts, out, 0, lane);
+      cnt = sketch_mate(a, MODE, k1_bases(a, r, o1), len1, tab, tk, ts, out, 0, lane);
       cnt1 = cnt;
       if (pe) {
         __threadfence_block();
@@ -669,13 +672,13 @@ __device__ __forceinline__ void wg_reads(const K1Args& a, int mode, const uint64
     int cnt = 0, cnt1 = 0;
     if (!skip) {
       if (LDS) {
-        cnt = wg_sketch_mate_lds(a, mode, a.seqs + o1, len1, tab, *lds, out, 0, s_wave, tid);
+        cnt = wg_sketch_mate_lds(a, mode, k1_bases(a, r, o1), len1, tab, *lds, out, 0, s_wave, tid);
         cnt1 = cnt;
         if (pe) cnt = wg_sketch_mate_lds(a, mode, a.seqs2 + o2, len2, tab, *lds, out, cnt, s_wave, tid);
       } else {
         uint64_t* tk = a.scratch ? a.scratch + o1 + o2 : nullptr;
         uint64_t* ts = a.scratch2 ? a.scratch2 + o1 + o2 : nullptr;
-        cnt = wg_sketch_mate(a, mode, a.seqs + o1, len1, tab, tk, ts, out, 0, s_wave, tid);
+        cnt = wg_sketch_mate(a, mode, k1_bases(a, r, o1), len1, tab, tk, ts, out, 0, s_wave, tid);
         cnt1 = cnt;
         if (pe) cnt = wg_sketch_mate(a, mode, a.seqs2 + o2, len2, tab, tk, ts, out, cnt, s_wave, tid);
       }
@@ -715,7 +718,7 @@ __device__ __forceinline__ void wg_reads_windows(const K1Args& a, const uint64_t
       if ((a.flags & 2) && a.nk_adj && a.scratch && len1 + len2 > raw_bound) {  // (a mate emits at most one value per base)
         AdjCarry c;
         uint64_t* adj = a.scratch + o1 + o2;
-        int m = wg_window_mate_lds<true>(a, MODE, a.seqs + o1, len1, tab, L, adj, 0, c, s_wave, s_wave2, s_last, tid);
+        int m = wg_window_mate_lds<true>(a, MODE, k1_bases(a, r, o1), len1, tab, L, adj, 0, c, s_wave, s_wave2, s_last, tid);
         raw1 = c.raw;
         if (pe) m = wg_window_mate_lds<true>(a, MODE, a.seqs2 + o2, len2, tab, L, adj, m, c, s_wave, s_wave2, s_last, tid);
         raw = c.raw;
@@ -725,7 +728,7 @@ __device__ __forceinline__ void wg_reads_windows(const K1Args& a, const uint64_t
       if (need_raw) {
         AdjCarry c;
         uint64_t* out = a.hashes + o1 + o2;
-        raw = wg_window_mate_lds<false>(a, MODE, a.seqs + o1, len1, tab, L, out, 0, c, s_wave, s_wave2, s_last, tid);
+        raw = wg_window_mate_lds<false>(a, MODE, k1_bases(a, r, o1), len1, tab, L, out, 0, c, s_wave, s_wave2, s_last, tid);
         raw1 = raw;
         if (pe) raw = wg_window_mate_lds<false>(a, MODE, a.seqs2 + o2, len2, tab, L, out, raw, c, s_wave, s_wave2, s_last, tid);
       }
@@ -1039,7 +1042,7 @@ __global__ void __launch_bounds__(K1W_THREADS) k1_windows_wave(const K1Args a) {
       bool need_raw = true;
       if (a.nk_adj && len1 + len2 > raw_bound) {  // (a mate emits at most one value per base)
         SeqCarry c;
-        wgw_mate<MODE, true>(a, a.seqs + o1, len1, tab, ring, sh, hs_out, sc_out, c, tid);
+        wgw_mate<MODE, true>(a, k1_bases(a, r, o1), len1, tab, ring, sh, hs_out, sc_out, c, tid);
         raw1 = c.raw;
         if (pe) wgw_mate<MODE, true>(a, a.seqs2 + o2, len2, tab, ring, sh, hs_out + len1, sc_out, c, tid);
         raw = c.raw;
@@ -1048,7 +1051,7 @@ __global__ void __launch_bounds__(K1W_THREADS) k1_windows_wave(const K1Args a) {
       }
       if (need_raw) {
         SeqCarry c;
-        wgw_mate<MODE, false>(a, a.seqs + o1, len1, tab, ring, sh, sc_out, hs_out, c, tid);
+        wgw_mate<MODE, false>(a, k1_bases(a, r, o1), len1, tab, ring, sh, sc_out, hs_out, c, tid);
         raw1 = c.raw;
         if (pe) wgw_mate<MODE, false>(a, a.seqs2 + o2, len2, tab, ring, sh, sc_out + len1, hs_out, c, tid);
         raw = c.raw;
@@ -1130,7 +1133,7 @@ __global__ void __launch_bounds__(64 * WR_WAVES) k1_windows_roll(const K1Args a,
   }
   // ---- the read as 2-bit codes (zeros behind its end)
   {
-    const uint8_t* __restrict__ s = a.seqs + o1;
+    const uint8_t* __restrict__ s = k1_bases(a, r, o1);
     typedef uint32_t u32x4_any __attribute__((ext_vector_type(4), aligned(1)));
     bool bad = false;
     for (int gi = lane; gi < words; gi += 64) {
@@ -1357,7 +1360,7 @@ __global__ void __launch_bounds__(K1WG) k1_seg_hash(const K1Args a) {
   const int p_lo = (int)seg * K1SEG;
   int cnt = 0;
   if (len >= a.min_qlen && p_lo < npos) {  // (:778-786 gate; ErrShortSeq => no k-mers)
-    const uint8_t* __restrict__ s = a.seqs + o1;
+    const uint8_t* __restrict__ s = k1_bases(a, r, o1);
     uint64_t* __restrict__ out = a.scratch + o1 + p_lo;
     const int p_hi = min(npos, p_lo + K1SEG);
     const bool scaled = a.scaled != 0;
@@ -1415,7 +1418,7 @@ __global__ void __launch_bounds__(64 * ROLL_WAVES) k1_seg_roll(const K1Args a) {
   uint8_t* __restrict__ B = bases[w];
   auto at = [&](int q) -> int { return (q / ROLL_L) * ROLL_PITCH + (q % ROLL_L); };
   if (wpos > 0) {
-    const uint8_t* __restrict__ s = a.seqs + o1 + P0;
+    const uint8_t* __restrict__ s = k1_bases(a, r, o1) + P0;
     const int nb = wpos + k - 1;  // bases this wave needs (k <= 128, the launcher checks: they end inside the 65th run slot)
     // 16 bases per lane and turn (a 16-byte piece at a multiple of 16 never crosses the end of a 128-byte run, so it stays in one
     // piece in LDS too; the source is wherever the read starts: unaligned loads), then what is left byte by byte
@@ -1575,7 +1578,7 @@ __global__ void __launch_bounds__(64 * R2_WAVES) k1_seg_roll2(const K1Args a) {
     }
     if (tid == 0 && a.seg_exc && a.seg_exc[blockIdx.x]) s_bad = 1;
   } else {
-    const uint8_t* __restrict__ s = a.seqs + o1 + P0;
+    const uint8_t* __restrict__ s = k1_bases(a, r, o1) + P0;
     const int nb = wpos > 0 ? wpos + k - 1 : 0;  // bases this wave needs
     typedef uint32_t u32x4_any __attribute__((ext_vector_type(4), aligned(1)));
     bool bad = false;
@@ -1803,6 +1806,142 @@ __global__ void k_nk_simple(const int32_t* nk_raw, int32_t* nk_search, uint32_t 
 }
 
 
+
+// ---- sliding windows of plain / FracMinHash k-mers, hash-once form (host.cpp kmcpg_submit_windows; launch_k1_windows_once) ----------------------
+// A k-mer's hash and whether it is kept do not depend on the window it is read in, so the staged slices of reads are hashed once — one wave per
+// K1_WIN_CHUNK positions of a slice, the wave form of the short-read kernel (hash_mate_scan) over the chunk's bases — and every window's list is
+// the run of its slice's kept hashes between the ranks of its first and one-past-last k-mer position.  Positions are numbered by the slice's
+// first base in the staged text (soffs[q] + p, p < npos_q = ls_q - k + 1), so h[] / rank[] need one entry per staged base.
+__device__ __forceinline__ uint32_t win_slice_of(const uint64_t* __restrict__ pre, uint32_t n, uint64_t x) {  // the last q with pre[q] <= x
+  uint32_t lo = 0, hi = n;
+  while (hi - lo > 1) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (pre[mid] <= x) lo = mid;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// pass 1: hashes of a chunk's positions -> h[], how many of them are kept -> cnt[chunk]
+__global__ void __launch_bounds__(256) k1_win_hash(const K1Args a, const WindowSrc w, uint64_t* __restrict__ h, uint32_t* __restrict__ cnt) {
+  __shared__ uint64_t tab[256];
+  tab[threadIdx.x] = seed_of(threadIdx.x);
+  __syncthreads();
+  const int lane = threadIdx.x & 63;
+  const int k = a.k;
+  const bool scaled = a.scaled != 0;
+  for (uint64_t c = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); c < w.n_chunks; c += (uint64_t)gridDim.x * 4) {
+    const uint32_t q = win_slice_of(w.cpre, w.ns, c);
+    const uint64_t g0 = w.soffs[q], ls = w.soffs[q + 1] - g0;
+    const uint64_t p0 = (c - w.cpre[q]) * K1_WIN_CHUNK;
+    const int pn = (int)min((uint64_t)K1_WIN_CHUNK, ls - (uint64_t)k + 1 - p0);  // (a slice with chunks holds >= k bases)
+    const uint8_t* __restrict__ s = a.seqs + g0 + p0;
+    const int len = pn + k - 1;
+    uint64_t* __restrict__ out = h + g0 + p0;
+    uint64_t cp = 0, cq = 0;
+    int kept = 0;
+    WTile cur = wave_tile(s, len, 0, tab, cp, cq, lane);
+    for (int base = 0; base < pn; base += 64) {
+      const WTile nxt = wave_tile(s, len, base + 64, tab, cp, cq, lane);
+      const uint64_t hv = wave_hash(cur, nxt, k, lane);
+      const bool v = base + lane < pn;
+      if (v) out[base + lane] = hv;
+      kept += __popcll(__ballot(v && hv != 0 && (!scaled || hv <= a.max_hash)));  // :1097-1103, as hash_mate_scan
+      cur = nxt;
+    }
+    if (lane == 0) cnt[c] = (uint32_t)kept;
+  }
+}
+
+// the chunks' kept counts -> exclusive prefix cbase[0 .. n] (one workgroup; a batch has at most 2^16 chunks at the default piece size)
+__global__ void __launch_bounds__(1024) k1_win_scan(const uint32_t* __restrict__ cnt, uint64_t n, uint64_t* __restrict__ cbase) {
+  __shared__ uint64_t sm[1024];
+  const uint32_t t = threadIdx.x;
+  const uint64_t per = (n + 1023) / 1024, lo = min(n, (uint64_t)t * per), hi = min(n, lo + per);
+  uint64_t sum = 0;
+  for (uint64_t i = lo; i < hi; i++) sum += cnt[i];
+  sm[t] = sum;
+  __syncthreads();
+  for (uint32_t off = 1; off < 1024; off <<= 1) {
+    const uint64_t v = t >= off ? sm[t - off] : 0;
+    __syncthreads();
+    sm[t] += v;
+    __syncthreads();
+  }
+  uint64_t run = sm[t] - sum;
+  for (uint64_t i = lo; i < hi; i++) {
+    cbase[i] = run;
+    run += cnt[i];
+  }
+  if (t == 1023) cbase[n] = sm[1023];
+}
+
+// pass 2: the kept hashes of a chunk in order -> kept[cbase[chunk] ...], every position's rank (kept positions before it) -> rank[]
+__global__ void __launch_bounds__(256) k1_win_rank(const K1Args a, const WindowSrc w, const uint64_t* __restrict__ h, const uint64_t* __restrict__ cbase,
+                                                   uint64_t* __restrict__ kept, uint32_t* __restrict__ rank) {
+  const int lane = threadIdx.x & 63;
+  const int k = a.k;
+  const bool scaled = a.scaled != 0;
+  for (uint64_t c = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); c < w.n_chunks; c += (uint64_t)gridDim.x * 4) {
+    const uint32_t q = win_slice_of(w.cpre, w.ns, c);
+    const uint64_t g0 = w.soffs[q], ls = w.soffs[q + 1] - g0;
+    const uint64_t p0 = (c - w.cpre[q]) * K1_WIN_CHUNK;
+    const int pn = (int)min((uint64_t)K1_WIN_CHUNK, ls - (uint64_t)k + 1 - p0);
+    uint64_t r = cbase[c];
+    for (int base = 0; base < pn; base += 64) {
+      const bool v = base + lane < pn;
+      const uint64_t hv = v ? h[g0 + p0 + base + lane] : 0;
+      const bool keep = v && hv != 0 && (!scaled || hv <= a.max_hash);
+      const uint64_t m = __ballot(keep);
+      const uint64_t mine = r + __popcll(m & ((1ULL << lane) - 1ULL));
+      if (v) rank[g0 + p0 + base + lane] = (uint32_t)mine;
+      if (keep) kept[mine] = hv;
+      r += __popcll(m);
+    }
+  }
+}
+
+// pass 3: one wave per window: qlen, and the run of kept hashes between its first and one-past-last k-mer position (nk_raw = nk1 = its
+// length; a window shorter than -m has none, handleQuery :778-786)
+__global__ void __launch_bounds__(256) k1_win_gather(const K1Args a, const WindowSrc w, const uint64_t* __restrict__ kept, const uint32_t* __restrict__ rank,
+                                                     const uint64_t* __restrict__ cbase) {
+  const uint32_t lane = threadIdx.x & 63;
+  for (uint32_t r = blockIdx.x * 4 + (threadIdx.x >> 6); r < a.n_reads; r += gridDim.x * 4) {
+    const uint32_t q = win_slice_of(w.wpre, w.ns, r);
+    const uint64_t g0 = w.soffs[q], ls = w.soffs[q + 1] - g0;
+    const uint64_t i = (r - w.wpre[q]) * w.step, e = min(i + w.window, ls);
+    const int len = (int)(e - i);
+    const int np = len - a.k + 1;
+    uint64_t lo = 0, n = 0;
+    if (len >= a.min_qlen && np > 0) {
+      const uint64_t npos = ls - (uint64_t)a.k + 1;
+      lo = rank[g0 + i];
+      const uint64_t hi = i + (uint64_t)np == npos ? cbase[w.cpre[q + 1]] : rank[g0 + i + (uint64_t)np];
+      n = hi - lo;
+    }
+    uint64_t* __restrict__ out = a.hashes + a.offs[r];
+    for (uint64_t t = lane; t < n; t += 64) out[t] = kept[lo + t];
+    if (lane == 0) {
+      a.nk_raw[r] = (int32_t)n;
+      a.nk1[r] = (int32_t)n;
+      a.qlen[r] = len;
+    }
+  }
+}
+
+void launch_k1_windows_once(const K1Args& a, const WindowSrc& w, uint64_t* h, uint64_t* kept, uint32_t* rank, uint32_t* cnt, uint64_t* cbase,
+                            hipStream_t st) {
+  if (a.n_reads == 0) return;
+  if (w.n_chunks) {
+    const unsigned blocks = (unsigned)std::min<uint64_t>((w.n_chunks + 3) / 4, 65536);
+    hipLaunchKernelGGL(k1_win_hash, dim3(blocks), dim3(256), 0, st, a, w, h, cnt);
+    hipLaunchKernelGGL(k1_win_scan, dim3(1), dim3(1024), 0, st, cnt, w.n_chunks, cbase);
+    hipLaunchKernelGGL(k1_win_rank, dim3(blocks), dim3(256), 0, st, a, w, h, cbase, kept, rank);
+  } else {
+    (void)hipMemsetAsync(cbase, 0, sizeof(uint64_t), st);
+  }
+  hipLaunchKernelGGL(k1_win_gather, dim3(std::min((a.n_reads + 3) / 4, 65536u)), dim3(256), 0, st, a, w, kept, rank, cbase);
+}
 
 int k1_segment_len() { return K1SEG; }
 

@@ -39,6 +39,17 @@ void launch_build_scatter(uint8_t* sigs, uint64_t num_sigs, uint64_t mh, uint32_
 void launch_unpack2(const uint8_t* packed, uint8_t* out, uint64_t n_bases, const ExcRun* runs, uint32_t n_runs, hipStream_t st);
 void launch_apply_exc(const ExcRun* runs, uint32_t n_runs, uint8_t* out, hipStream_t st);  // the runs alone, over text that is there
 
+// sliding windows (windows.hip): descriptors of n_win windows over n_slices staged slices of reads (soffs: the slices' bases in the staged
+// text, wpre / vpre: prefix sums of their windows and of those windows' bases) -> src[w] (first base in the text), offs[0 .. n_win]
+void launch_window_desc(const uint64_t* soffs, const uint64_t* wpre, const uint64_t* vpre, uint32_t n_slices, uint64_t n_win, uint64_t step,
+                        uint64_t window, uint64_t* src, uint64_t* offs, hipStream_t st);
+// hash-once form of plain / FracMinHash windows (k1_kmers.hip, k <= 65, single-end): every k-mer position of the staged slices hashed once
+// (h[], one wave per K1_WIN_CHUNK positions), the kept ones compacted in order (kept[]) with each position's rank (rank[]), then every
+// window's list is the run kept[rank[i] .. rank[e - k + 1]) copied to a.hashes[a.offs[w] ...]; nk_raw / nk1 / qlen as k1_kmers<0> writes
+// them.  cnt: n_chunks words, cbase: n_chunks + 1
+void launch_k1_windows_once(const K1Args& a, const WindowSrc& w, uint64_t* h, uint64_t* kept, uint32_t* rank, uint32_t* cnt, uint64_t* cbase,
+                            hipStream_t st);
+
 // experiment only (KMCPG_DEBUG_ROWSORT): every query's hashes re-ordered by h % num_sigs of one block; mode 2 = rotated
 void launch_debug_rowsort(uint64_t* hashes, const uint64_t* offs, const int32_t* nk, uint32_t n_reads, uint64_t num_sigs, uint64_t mh, int mode, hipStream_t st);
 

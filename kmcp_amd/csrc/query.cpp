@@ -41,6 +41,7 @@ void release_fpr_bounds(kmcpg_db* db) {
 // GPU half
 // ------------------------------------------------------------------------------------------------
 thread_local kmcpg::PackedSrc kmcpg::tl_packed_src;
+thread_local kmcpg::WindowSrc kmcpg::tl_window;
 
 // a batch the k-mer stage hashes segment by segment (run_kmers: plain or FracMinHash k-mers, single-end, some query above one segment)
 bool kmcpg::whole_genome_batch(const kmcpg_db* db, uint32_t max_read_len, bool paired) {
@@ -93,9 +94,14 @@ int run_kmers(kmcpg_db* db, kmcpg_db::Workspace& W, const uint8_t* d_seqs, const
   // here.  (A batch with a run per 4 kb or more is not what the direct form is for: expanded whole.)  KMCPG_K1_CODES=0: always expand.
   const PackedSrc src = tl_packed_src;
   tl_packed_src = PackedSrc{};
+  // sliding windows (host.cpp kmcpg_submit_windows): every kernel reads a window's bases in place through its view; the codes of such a batch
+  // are expanded first (the direct 2-bit form addresses the codes by the batch's own offsets)
+  const WindowSrc win = tl_window;
+  tl_window = WindowSrc{};
+  a.src = win.src;
   if (src.codes) {
     static const int codes_mode = getenv("KMCPG_K1_CODES") ? atoi(getenv("KMCPG_K1_CODES")) : 1;  // 2 (tests): however many runs there are
-    const bool direct = codes_mode != 0 && a.seg_cnt && a.segs_max > 1 && a.k <= 128 && !(a.flags & 24) && src.text == d_seqs &&
+    const bool direct = codes_mode != 0 && !a.src && a.seg_cnt && a.segs_max > 1 && a.k <= 128 && !(a.flags & 24) && src.text == d_seqs &&
                         (codes_mode == 2 || (uint64_t)src.n_exc <= src.n_bases / 4096 + 64);
     if (direct) {
       a.codes = src.codes;
@@ -114,7 +120,19 @@ int run_kmers(kmcpg_db* db, kmcpg_db::Workspace& W, const uint8_t* d_seqs, const
   }
   a.nk_adj = d_nk_search;
   a.dedup_threshold = p.dedup_threshold;
-  const bool adj_done = launch_k1(a, max_read_len, st);
+  // sliding windows of plain / FracMinHash k-mers: each staged base hashed once, each window's list a run of the slice's kept hashes
+  // (KMCPG_WIN_ONCE=0: every window hashed in place, as window sketches always are — their emission at a window's edges is the window's own)
+  static const bool win_once = !getenv("KMCPG_WIN_ONCE") || atoi(getenv("KMCPG_WIN_ONCE")) != 0;
+  bool adj_done = false;
+  // (windows that do not overlap, S >= W, share no k-mer: nothing to hash once, they are read in place)
+  if (win.src && win_once && a.mode == 0 && !d_seqs2 && a.k <= 65 && win.step < win.window) {
+    if (W.w_win_h.ensure(win.sb + 1) || W.w_win_kept.ensure(win.sb + 1) || W.w_win_rank.ensure(win.sb + 1) || W.w_win_cnt.ensure(win.n_chunks + 1) ||
+        W.w_win_cbase.ensure(win.n_chunks + 1))
+      return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
+    launch_k1_windows_once(a, win, W.w_win_h.p, W.w_win_kept.p, W.w_win_rank.p, W.w_win_cnt.p, W.w_win_cbase.p, st);
+  } else {
+    adj_done = launch_k1(a, max_read_len, st);
+  }
   uint64_t ub = max_read_len >= (uint32_t)a.k ? (uint64_t)(max_read_len - a.k + 1) : 0;
   if (d_seqs2) ub *= 2;
   *max_n_out = ub;

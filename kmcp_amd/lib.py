@@ -20,6 +20,7 @@ EXPORTS = [
     "kmcpg_search_batch_pairs", "kmcpg_wait_pairs", "kmcpg_result_pairs_free", "kmcpg_expand_pairs", "kmcpg_save_db",
     "kmcpg_pack2", "kmcpg_unpack2", "kmcpg_submit_packed", "kmcpg_host_alloc", "kmcpg_host_free",
     "kmcpg_kmers_device_packed", "kmcpg_k1_codes_batches",
+    "kmcpg_submit_windows", "kmcpg_submit_packed_windows", "kmcpg_window_count", "kmcpg_window_locate",
 ]
 
 
@@ -117,6 +118,11 @@ class Match(C.Structure):
 class Result(C.Structure):
     _fields_ = [("n_reads", C.c_uint32), ("k", C.c_int32), ("qlen", C.POINTER(C.c_int32)), ("qkmers", C.POINTER(C.c_int32)),
                 ("ksize", C.POINTER(C.c_int32)), ("match_offs", C.POINTER(C.c_uint64)), ("matches", C.POINTER(Match)), ("owner", C.c_void_p)]
+
+
+class WindowSpec(C.Structure):
+    """kmcpg_window_spec: seqkit sliding -s step -W window [-g]"""
+    _fields_ = [("step", C.c_uint64), ("window", C.c_uint64), ("greedy", C.c_int32), ("reserved", C.c_int32)]
 
 
 class SynthSpec(C.Structure):
@@ -230,6 +236,10 @@ def load():
     L.kmcpg_host_alloc.argtypes = [C.c_uint64, C.POINTER(vp)]
     L.kmcpg_host_free.argtypes = [vp]
     L.kmcpg_submit_packed.argtypes = [vp, vp, vp, vp, C.c_uint64, C.c_uint32, C.POINTER(Params), C.POINTER(vp)]
+    L.kmcpg_submit_windows.argtypes = [vp, vp, vp, C.c_uint32, C.POINTER(WindowSpec), C.POINTER(Params), C.POINTER(vp)]
+    L.kmcpg_submit_packed_windows.argtypes = [vp, vp, vp, vp, C.c_uint64, C.c_uint32, C.POINTER(WindowSpec), C.POINTER(Params), C.POINTER(vp)]
+    L.kmcpg_window_count.argtypes = [vp, C.c_uint32, C.POINTER(WindowSpec), u64p, u64p]
+    L.kmcpg_window_locate.argtypes = [vp, C.c_uint32, C.POINTER(WindowSpec), C.c_uint64, C.c_uint64, vp, vp]
     _lib = L
     return L
 
@@ -246,6 +256,27 @@ class Pair(C.Structure):
 class ResultPairs(C.Structure):
     _fields_ = [("n_reads", C.c_uint32), ("k", C.c_int32), ("qlen", C.POINTER(C.c_int32)), ("qkmers", C.POINTER(C.c_int32)),
                 ("ksize", C.POINTER(C.c_int32)), ("match_offs", C.POINTER(C.c_uint64)), ("pairs", C.POINTER(Pair)), ("owner", C.c_void_p)]
+
+
+def window_count(offs, step, window, greedy=False):
+    """kmcpg_window_count: (windows, their bases) of the reads of offs[0..n]"""
+    offs = np.ascontiguousarray(offs, dtype=np.uint64)
+    spec = WindowSpec(step, window, 1 if greedy else 0, 0)
+    nw, nb = C.c_uint64(), C.c_uint64()
+    _check(load().kmcpg_window_count(offs.ctypes.data, len(offs) - 1, C.byref(spec), C.byref(nw), C.byref(nb)))
+    return nw.value, nb.value
+
+
+def window_locate(offs, step, window, greedy=False):
+    """kmcpg_window_locate: for every result row of a window batch, the read it came from and the window's 0-based first base"""
+    offs = np.ascontiguousarray(offs, dtype=np.uint64)
+    n, _ = window_count(offs, step, window, greedy)
+    spec = WindowSpec(step, window, 1 if greedy else 0, 0)
+    read = np.zeros(n, dtype=np.uint32)
+    start = np.zeros(n, dtype=np.uint64)
+    if n:
+        _check(load().kmcpg_window_locate(offs.ctypes.data, len(offs) - 1, C.byref(spec), 0, n, read.ctypes.data, start.ctypes.data))
+    return read, start
 
 
 def pack_reads(reads):
@@ -450,6 +481,39 @@ class Database:
         n = len(offs) - 1
         _check(load().kmcpg_submit_packed(self._h, codes.ctypes.data, offs.ctypes.data, exc.ctypes.data if len(exc) else None, len(exc), n, C.byref(p), C.byref(t)))
         return t
+
+    # ---- sliding windows of long queries (seqkit sliding -s step -W window [-g] | kmcp search) -----------------
+    def submit_windows(self, seqs, offs, step, window, greedy=False, params=None):
+        """kmcpg_submit_windows: one result row per window (wait / wait_pairs); single-end reads as text + offsets"""
+        p = params or default_params()
+        spec = WindowSpec(step, window, 1 if greedy else 0, 0)
+        t = C.c_void_p()
+        n = len(offs) - 1
+        _check(load().kmcpg_submit_windows(self._h, seqs.ctypes.data, offs.ctypes.data, n, C.byref(spec), C.byref(p), C.byref(t)))
+        return t
+
+    def submit_packed_windows(self, codes, offs, exc, step, window, greedy=False, params=None):
+        """kmcpg_submit_packed_windows: the same on reads as 2-bit codes (pack2) + exception runs"""
+        p = params or default_params()
+        spec = WindowSpec(step, window, 1 if greedy else 0, 0)
+        t = C.c_void_p()
+        n = len(offs) - 1
+        _check(load().kmcpg_submit_packed_windows(self._h, codes.ctypes.data, offs.ctypes.data, exc.ctypes.data if len(exc) else None, len(exc), n,
+                                                  C.byref(spec), C.byref(p), C.byref(t)))
+        return t
+
+    def search_windows(self, reads, step, window, greedy=False, params=None, pairs=False):
+        """windows of `reads` (list of bytes) searched as queries -> (BatchResult or PairsResult, read of each row, start of each row)"""
+        seqs, offs = pack_reads(reads)
+        t = self.submit_windows(seqs, offs, step, window, greedy, params)
+        res = self.wait_pairs(t) if pairs else self.wait(t)
+        return (res,) + window_locate(offs, step, window, greedy)
+
+    def search_packed_windows(self, codes, offs, exc, step, window, greedy=False, params=None, pairs=False):
+        """the same on a batch as 2-bit codes + exception runs (pack2); offs in bases"""
+        t = self.submit_packed_windows(codes, offs, exc, step, window, greedy, params)
+        res = self.wait_pairs(t) if pairs else self.wait(t)
+        return (res,) + window_locate(offs, step, window, greedy)
 
     def wait(self, ticket, count_only=False):
         """kmcpg_wait: the finalized matches of a submitted batch (or just their number)."""

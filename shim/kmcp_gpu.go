@@ -12,6 +12,11 @@
 // kmcpg_wait_pairs from other threads, kmcpg_expand_pairs per matched query into a malloc'd scratch array,
 // kmcpg_result_pairs_free, the error fetch on the failing thread — is replayed from several threads by tests/shim_replay.c
 // (tests/test_gpu_shim_replay.py), which is compiled and run with every GPU test run.
+//
+// Long reads and contigs: kmcpg_submit_windows / kmcpg_submit_packed_windows (include/kmcp_gpu.h, a kmcpg_window_spec beside the usual
+// single-end batch) search every window `seqkit sliding -s S -W W [-g]` would cut, one result row per window, through the same
+// kmcpg_wait_pairs; kmcpg_window_locate maps rows to (read, start).  This binding does not call them (kmcp search has no such flag);
+// kmcp-search --sliding-* does (INTEGRATION.md, "Sliding windows").
 package cmd
 
 // Tree layout the #cgo lines assume (shim/build.sh puts the files there): this file and kmcp_gpu_test.go in
