@@ -88,8 +88,8 @@ struct K1Args {
 };
 
 
-// the packed source of the batch the calling thread is about to enqueue (host.cpp -> run_kmers): codes + runs on the device, and the
-// text buffer the expansion goes to when the k-mer kernels of this batch read text
+// the packed source of a batch (DeviceBatch::packed, engine.hpp): codes + runs on the device, and the text buffer the expansion goes to
+// when the k-mer kernels of this batch read text.  codes == nullptr: the batch is text already.
 struct PackedSrc {
   const uint8_t* codes = nullptr;
   const ExcRun* exc = nullptr;
@@ -97,9 +97,8 @@ struct PackedSrc {
   uint8_t* text = nullptr;
   uint64_t n_bases = 0;
 };
-extern thread_local PackedSrc tl_packed_src;
-// the windows of the batch the calling thread is about to enqueue (host.cpp -> run_kmers): src = each window's first base in the staged
-// text (K1Args::src), and the staged slices of reads with their prefix sums (windows.hip) for the hash-once form of plain / FracMinHash k-mers
+// the windows of a batch (DeviceBatch::windows): src = each window's first base in the staged text (K1Args::src), and the staged slices of
+// reads with their prefix sums (windows.hip) for the hash-once form of plain / FracMinHash k-mers.  src == nullptr: no window view.
 constexpr int K1_WIN_CHUNK = 1024;  // k-mer positions of a slice one wave hashes (hash-once form)
 struct WindowSrc {
   const uint64_t* src = nullptr;   // [n windows]
@@ -109,7 +108,6 @@ struct WindowSrc {
   uint32_t ns = 0;
   uint64_t n_chunks = 0, sb = 0, step = 0, window = 0;
 };
-extern thread_local WindowSrc tl_window;
 
 struct DedupArgs {
   const uint64_t* offs;

@@ -245,24 +245,21 @@ struct ResultOwner {
   std::vector<kmcpg_pair, NoInitAlloc<kmcpg_pair>> pairs;
   bool pairs_mode = false;
 };
-// set for the duration of a kmcpg_*_pairs call on the calling thread: results shaped meanwhile (result_owner_shape) collect pairs
-extern thread_local bool tl_pairs_mode;
 // finalize.cpp: a result assembled piece by piece (kmcpg_search_batch cuts large batches into pieces, host.cpp)
 ResultOwner* result_owner_take();
 void result_owner_give(ResultOwner* o);
-void result_owner_shape(ResultOwner* o, uint32_t n_reads);
+void result_owner_shape(ResultOwner* o, uint32_t n_reads, bool as_pairs);  // as_pairs: the result collects compact pairs, not Match records
 // trusted: the list is what K2 + K3 made of this very batch with these very params (the library's own pipelines) — thresholds, -T, the
 // -f bound of short queries and the order of segments up to K3_WG_CAP hold by construction
 int finalize_grouped_into(const kmcpg_db* db, const kmcpg_pair* pairs, const uint64_t* read_offs, const int32_t* qkmers, const int32_t* qlen, uint32_t n_reads,
                           const kmcpg_params& p, ResultOwner* o, uint32_t read_base, uint64_t match_base, uint64_t* kept_out, bool trusted = false,
                           int32_t bound_n = 0);
 int finalize_grouped_trusted(const kmcpg_db* db, const kmcpg_pair* pairs, const uint64_t* read_offs, const int32_t* qkmers, const int32_t* qlen, uint32_t n_reads,
-                             const kmcpg_params& p, kmcpg_result* out, int32_t bound_n);
+                             const kmcpg_params& p, kmcpg_result* out, int32_t bound_n, bool as_pairs);
 // bound_n: what the kmcpg_query_device call(s) that produced the list actually did — every query of up to bound_n k-mers had the -f bound
-// applied on the device, whichever kernel form served it (0: no bound table in that call).  kmcpg_query_device leaves the value of its
-// call in tl_query_bound_n on the calling thread; host.cpp keeps it with the batch (Lane::bound_n) and hands it to the finalizer, which
-// takes a compact segment as final only for n <= bound_n — it does not look at the environment again.
-extern thread_local int32_t tl_query_bound_n;
+// applied on the device, whichever kernel form served it (0: no bound table in that call).  query_device_after reports the value of its
+// call; host.cpp keeps it with the batch (Lane::bound_n) and hands it to the finalizer, which takes a compact segment as final only for
+// n <= bound_n — it does not look at the environment again.
 // batches of whole genomes (segment path of the k-mer stage): the ones whose k-mer kernels run beside the previous batch's COBS kernel by
 // default — second workspace slot (query.cpp pick_slot) and second kernel stream (host.cpp enqueue; bench.py does the same with its streams)
 bool whole_genome_batch(const kmcpg_db* db, uint32_t max_read_len, bool paired);
@@ -273,10 +270,30 @@ inline bool fpr_bound_enabled() {
 }
 constexpr int kFprBoundAlways = 512;  // queries of up to this many k-mers are covered by the bound table whatever the batch holds
 void result_publish(ResultOwner* o, uint32_t n_reads, int k_used, kmcpg_result* out);
-// query.cpp: kmcpg_query_device with a prologue run under the handle's enqueue lock, in front of the batch's first kernel
-int query_device_after(kmcpg_db* db, const uint8_t* d_seqs, const uint64_t* d_offs, const uint8_t* d_seqs2, const uint64_t* d_offs2, uint32_t n_reads,
-                       uint64_t total_bases, uint32_t max_read_len, const kmcpg_params* params, kmcpg_hit* d_hits, uint64_t hit_cap, uint64_t* d_counters,
-                       int32_t* d_qkmers, int32_t* d_qlen, void* stream, const std::function<int()>* prologue);
+// A batch on the device, as the GPU half is told about it (query.cpp run_kmers, query_device_after): text, or — `packed` — 2-bit codes
+// that the k-mer stage reads as they are or expands into d_seqs; its queries are the reads themselves, or — `windows` — views into them.
+struct DeviceBatch {
+  const uint8_t* d_seqs = nullptr;
+  const uint64_t* d_offs = nullptr;
+  const uint8_t* d_seqs2 = nullptr;  // mates or nullptr
+  const uint64_t* d_offs2 = nullptr;
+  uint32_t n_reads = 0;
+  uint64_t total_bases = 0;  // of the queries, both mates
+  uint32_t max_read_len = 0;
+  PackedSrc packed;
+  WindowSrc windows;
+};
+// where the outputs of kmcpg_query_device go
+struct QueryOut {
+  kmcpg_hit* d_hits;
+  uint64_t hit_cap;
+  uint64_t* d_counters;
+  int32_t *d_qkmers, *d_qlen;
+};
+// query.cpp: kmcpg_query_device with a prologue run under the handle's enqueue lock, in front of the batch's first kernel.
+// *bound_n (optional): see finalize_grouped_trusted
+int query_device_after(kmcpg_db* db, const DeviceBatch& b, const kmcpg_params* params, const QueryOut& out, void* stream, const std::function<int()>* prologue,
+                       int32_t* bound_n);
 void result_records_to_pairs(ResultOwner* o);  // finalize.cpp: a result that holds records -> the pairs of a compact result
 
 }  // namespace kmcpg

@@ -528,8 +528,6 @@ extern "C" int kmcpg_finalize(const kmcpg_db* db, const kmcpg_hit* hits, uint64_
 // while it streams: a list from elsewhere is finalized correctly too — segments longer than K3 orders (K3_WG_CAP) and segments
 // found out of order are sorted here.
 namespace kmcpg {
-thread_local bool tl_pairs_mode = false;
-thread_local int32_t tl_query_bound_n = 0;
 ResultOwner* result_owner_take() { return take_owner(); }
 void result_owner_give(ResultOwner* o) { give_owner(o); }
 
@@ -752,8 +750,8 @@ void result_publish(ResultOwner* o, uint32_t n_reads, int k_used, kmcpg_result* 
   out->owner = o;
 }
 
-void result_owner_shape(ResultOwner* o, uint32_t n_reads) {
-  o->pairs_mode = tl_pairs_mode;
+void result_owner_shape(ResultOwner* o, uint32_t n_reads, bool as_pairs) {
+  o->pairs_mode = as_pairs;
   o->pairs.clear();
   o->qlen.resize(n_reads);
   o->qkmers.resize(n_reads);
@@ -765,9 +763,9 @@ void result_owner_shape(ResultOwner* o, uint32_t n_reads) {
 
 namespace kmcpg {
 int finalize_grouped_trusted(const kmcpg_db* db, const kmcpg_pair* pairs, const uint64_t* read_offs, const int32_t* qkmers, const int32_t* qlen, uint32_t n_reads,
-                             const kmcpg_params& p, kmcpg_result* out, int32_t bound_n) {
+                             const kmcpg_params& p, kmcpg_result* out, int32_t bound_n, bool as_pairs) {
   std::unique_ptr<ResultOwner, OwnerReturn> o(take_owner());
-  result_owner_shape(o.get(), n_reads);
+  result_owner_shape(o.get(), n_reads, as_pairs);
   uint64_t kept = 0;
   if (int rc = finalize_grouped_into(db, pairs, read_offs, qkmers, qlen, n_reads, p, o.get(), 0, 0, &kept, true, bound_n)) return rc;
   result_publish(o.release(), n_reads, p.k > 0 ? p.k : db->info.k, out);
@@ -780,7 +778,7 @@ extern "C" int kmcpg_finalize_grouped(const kmcpg_db* db, const kmcpg_pair* pair
   if (!db || !out || !read_offs || (n_reads && (!qkmers || !qlen))) return kmcpg_fail(KMCPG_EINVAL, "null argument");
   const kmcpg_params p = params ? *params : default_params();
   std::unique_ptr<ResultOwner, OwnerReturn> o(take_owner());
-  result_owner_shape(o.get(), n_reads);
+  result_owner_shape(o.get(), n_reads, false);  // the public entry produces Match records
   uint64_t kept = 0;
   if (int rc = finalize_grouped_into(db, pairs, read_offs, qkmers, qlen, n_reads, p, o.get(), 0, 0, &kept)) return rc;
   result_publish(o.release(), n_reads, p.k > 0 ? p.k : db->info.k, out);

@@ -84,16 +84,23 @@ struct Lane {
   PinBuf<ExcRun> h_exc;
   DevBuf<uint8_t> d_pack;
   DevBuf<ExcRun> d_exc;
+  // what goes up (stage / stage_packed): up_reads reads of up_bases bases with h_offs = their offsets, as text in h_seqs or — packed — as codes
+  // + n_exc runs; single reads, or — paired — their mates beside them (tb2 bases)
+  uint32_t up_reads = 0;
+  uint64_t up_bases = 0;
   bool packed = false;
   uint32_t n_exc = 0;
   const uint8_t* ext_pack = nullptr;  // codes that live in the CALLER's pinned memory (kmcpg_host_alloc): uploaded from there, no staging copy
-  // sliding windows (kmcpg_submit_windows): the lane staged ns slices of reads (sb bases, h_offs = their offsets) and searches n windows over
-  // them (tb1 = the windows' bases, maxlen = the longest window); h_wmeta = the slices' window prefix and window-base prefix (2 x (ns + 1)).
-  // The device builds d_offs (the windows' numbering) and d_wsrc (each window's first base in d_seqs) from d_soffs + d_wmeta (windows.hip).
+  // what is searched: n queries of tb1 (+ tb2) bases, the longest of maxlen.  They are the staged reads themselves (as stage leaves it), or —
+  // win, kmcpg_submit_windows — windows over them: h_wmeta = the staged slices' window prefix and window-base prefix (2 x (up_reads + 1)); the
+  // device builds d_offs (the windows' numbering) and d_wsrc (each window's first base in d_seqs) from d_soffs + d_wmeta (windows.hip).
   // A third array in h_wmeta: the slices' chunks of K1_WIN_CHUNK k-mer positions (wchunks in all), for the hash-once form of K1.
+  uint32_t n = 0;
+  bool paired = false;
+  uint64_t tb1 = 0, tb2 = 0;
+  uint32_t maxlen = 0;
   bool win = false;
-  uint32_t ns = 0;
-  uint64_t sb = 0, wstep = 0, wwin = 0, wchunks = 0;
+  uint64_t wstep = 0, wwin = 0, wchunks = 0;
   PinBuf<uint64_t> h_wmeta;
   DevBuf<uint64_t> d_soffs, d_wmeta, d_wsrc;
   int32_t bound_n = 0;   // the -f bound of the LAST kmcpg_query_device call for this batch covered queries of up to this many k-mers
@@ -102,10 +109,6 @@ struct Lane {
   bool eager_aside = false;                        // ... when it was put there (pieces of a large kmcpg_search_batch call)
   hipEvent_t done = nullptr, uploaded = nullptr;
   hipStream_t st = nullptr;  // the kernel stream this batch was enqueued on (AsyncState::stream or stream2, taken in turn)
-  uint32_t n = 0;
-  bool paired = false;
-  uint64_t tb1 = 0, tb2 = 0;
-  uint32_t maxlen = 0;
   uint64_t copied = 0;  // hits already on their way to h_hits when `done` fires
   bool busy = false;
   void release() {
@@ -298,38 +301,63 @@ bool pack_wanted(uint64_t total_bases, uint32_t n) {
   return total_bases >= (8ull << 20) && total_bases / std::max<uint32_t>(1, n) >= 1000;
 }
 
-int stage(Lane* L, const uint8_t* seqs, const uint64_t* offs, const uint8_t* seqs2, const uint64_t* offs2, uint32_t n, bool allow_pack = false) {
-  L->n = n;
-  L->win = false;
-  L->packed = false;
+// a batch in the caller's memory, as the entry points take it: n reads, seqs2 / offs2 = their mates or nullptr
+struct HostBatch {
+  const uint8_t* seqs;
+  const uint64_t* offs;
+  const uint8_t* seqs2;
+  const uint64_t* offs2;
+  uint32_t n;
+};
+
+// offsets start at 0 and never decrease; *maxlen = the longest read (either mate)
+int check_offsets(const HostBatch& b, uint64_t* maxlen) {
+  *maxlen = 0;
+  if (b.n == 0) return 0;
+  if (b.offs[0] != 0 || (b.seqs2 && b.offs2[0] != 0)) return kmcpg_fail(KMCPG_EINVAL, "offs[0] must be 0");
+  for (uint32_t i = 0; i < b.n; i++) {
+    if (b.offs[i + 1] < b.offs[i] || (b.seqs2 && b.offs2[i + 1] < b.offs2[i])) return kmcpg_fail(KMCPG_EINVAL, "offsets must not decrease (read %u)", i);
+    *maxlen = std::max(*maxlen, b.offs[i + 1] - b.offs[i]);
+    if (b.seqs2) *maxlen = std::max(*maxlen, b.offs2[i + 1] - b.offs2[i]);
+  }
+  return 0;
+}
+
+// a lane takes a new batch: nothing of its previous one is left (a lane that served kmcpg_submit_packed from the caller's pinned codes, or
+// windows, last time does not now), the offsets are checked, and what is searched are the reads as they go up
+int lane_begin(Lane* L, const HostBatch& b) {
+  L->up_reads = L->n = b.n;
+  L->up_bases = L->tb1 = L->tb2 = 0;
+  L->packed = L->win = false;
   L->n_exc = 0;
-  L->ext_pack = nullptr;  // (a lane that served kmcpg_submit_packed from the caller's pinned codes last time uploads from its own buffer now)
-  L->paired = seqs2 != nullptr;
-  L->tb1 = L->tb2 = 0;
+  L->ext_pack = nullptr;
+  L->paired = b.seqs2 != nullptr;
   L->maxlen = 0;
   L->copied = 0;
-  if (n == 0) return 0;
-  if (offs[0] != 0 || (seqs2 && offs2[0] != 0)) return kmcpg_fail(KMCPG_EINVAL, "offs[0] must be 0");
   uint64_t maxlen = 0;
-  for (uint32_t i = 0; i < n; i++) {
-    if (offs[i + 1] < offs[i] || (seqs2 && offs2[i + 1] < offs2[i])) return kmcpg_fail(KMCPG_EINVAL, "offsets must not decrease (read %u)", i);
-    maxlen = std::max(maxlen, offs[i + 1] - offs[i]);
-    if (seqs2) maxlen = std::max(maxlen, offs2[i + 1] - offs2[i]);
-  }
+  if (int rc = check_offsets(b, &maxlen)) return rc;
   if (maxlen > 0x7fffffffULL) return kmcpg_fail(KMCPG_EUNSUPPORTED, "query longer than 2^31-1 bases");
+  if (b.n == 0) return 0;
   L->maxlen = (uint32_t)maxlen;
-  L->tb1 = offs[n];
-  L->tb2 = seqs2 ? offs2[n] : 0;
-  if (L->h_offs.ensure((size_t)n + 1) || (seqs2 && (L->h_seqs2.ensure(L->tb2 + 16) || L->h_offs2.ensure((size_t)n + 1))))
+  L->up_bases = L->tb1 = b.offs[b.n];
+  L->tb2 = b.seqs2 ? b.offs2[b.n] : 0;
+  return 0;
+}
+
+int stage(Lane* L, const HostBatch& b, bool allow_pack = false) {
+  if (int rc = lane_begin(L, b)) return rc;
+  const uint32_t n = b.n;
+  if (n == 0) return 0;
+  if (L->h_offs.ensure((size_t)n + 1) || (b.seqs2 && (L->h_seqs2.ensure(L->tb2 + 16) || L->h_offs2.ensure((size_t)n + 1))))
     return kmcpg_fail(KMCPG_ENOMEM, "hipHostMalloc failed");
-  if (allow_pack && !seqs2 && pack_wanted(L->tb1, n)) {
+  if (allow_pack && !b.seqs2 && pack_wanted(L->tb1, n)) {
     static thread_local std::vector<PackRun> exc;
     static_assert(sizeof(PackRun) == sizeof(ExcRun), "one layout");
     if (L->h_pack.ensure(L->tb1 / 4 + 16)) return kmcpg_fail(KMCPG_ENOMEM, "hipHostMalloc failed");
     static const unsigned pack_threads = getenv("KMCPG_PACK_THREADS") ? (unsigned)std::max(1, std::min(atoi(getenv("KMCPG_PACK_THREADS")), 64))
                                                                       : std::max(1u, std::min(8u, std::thread::hardware_concurrency()));
     // more than one foreign run per 256 bases: not nucleotide text, sent as it is
-    if (pack2_parallel(seqs, L->tb1, L->h_pack.p, exc, std::max<size_t>(1024, L->tb1 / 256), pack_threads)) {
+    if (pack2_parallel(b.seqs, L->tb1, L->h_pack.p, exc, std::max<size_t>(1024, L->tb1 / 256), pack_threads)) {
       if (L->h_exc.ensure(exc.size() + 1)) return kmcpg_fail(KMCPG_ENOMEM, "hipHostMalloc failed");
       if (!exc.empty()) memcpy(L->h_exc.p, exc.data(), exc.size() * sizeof(ExcRun));
       L->n_exc = (uint32_t)exc.size();
@@ -338,12 +366,12 @@ int stage(Lane* L, const uint8_t* seqs, const uint64_t* offs, const uint8_t* seq
   }
   if (!L->packed) {
     if (L->h_seqs.ensure(L->tb1 + 16)) return kmcpg_fail(KMCPG_ENOMEM, "hipHostMalloc failed");
-    par_memcpy(L->h_seqs.p, seqs, L->tb1);
+    par_memcpy(L->h_seqs.p, b.seqs, L->tb1);
   }
-  par_memcpy(L->h_offs.p, offs, ((size_t)n + 1) * sizeof(uint64_t));
-  if (seqs2) {
-    par_memcpy(L->h_seqs2.p, seqs2, L->tb2);
-    par_memcpy(L->h_offs2.p, offs2, ((size_t)n + 1) * sizeof(uint64_t));
+  par_memcpy(L->h_offs.p, b.offs, ((size_t)n + 1) * sizeof(uint64_t));
+  if (b.seqs2) {
+    par_memcpy(L->h_seqs2.p, b.seqs2, L->tb2);
+    par_memcpy(L->h_offs2.p, b.offs2, ((size_t)n + 1) * sizeof(uint64_t));
   }
   return 0;
 }
@@ -356,33 +384,17 @@ struct PackedIn {
   uint64_t n_exc;
 };
 
-int stage_packed(Lane* L, const PackedIn& in, const uint64_t* offs, uint32_t n) {
+int stage_packed(Lane* L, const PackedIn& in, const HostBatch& b) {  // b: offsets and count (single reads; the bases are in.codes)
   static_assert(sizeof(kmcpg_exc_run) == sizeof(ExcRun), "one layout");
-  L->n = n;
-  L->win = false;
-  L->packed = false;
-  L->n_exc = 0;
-  L->ext_pack = nullptr;
-  L->paired = false;
-  L->tb1 = L->tb2 = 0;
-  L->maxlen = 0;
-  L->copied = 0;
+  if (int rc = lane_begin(L, b)) return rc;
+  const uint32_t n = b.n;
   if (n == 0) return 0;
-  if (offs[0] != 0) return kmcpg_fail(KMCPG_EINVAL, "offs[0] must be 0");
-  uint64_t maxlen = 0;
-  for (uint32_t i = 0; i < n; i++) {
-    if (offs[i + 1] < offs[i]) return kmcpg_fail(KMCPG_EINVAL, "offsets must not decrease (read %u)", i);
-    maxlen = std::max(maxlen, offs[i + 1] - offs[i]);
-  }
-  if (maxlen > 0x7fffffffULL) return kmcpg_fail(KMCPG_EUNSUPPORTED, "query longer than 2^31-1 bases");
-  const uint64_t tb = offs[n];
+  const uint64_t tb = L->tb1;
   if (in.n_exc > 0xffffffffULL) return kmcpg_fail(KMCPG_EINVAL, "too many exception runs");
   for (uint64_t i = 0; i < in.n_exc; i++) {  // the device writes these runs into the batch's text: they must lie inside it
     const kmcpg_exc_run& e = in.exc[i];
     if (e.pos > tb || e.len > tb - e.pos || e.byte > 255) return kmcpg_fail(KMCPG_EINVAL, "exception run %llu lies outside the batch", (unsigned long long)i);
   }
-  L->maxlen = (uint32_t)maxlen;
-  L->tb1 = tb;
   // Codes in memory from kmcpg_host_alloc are page-locked already: the DMA engine reads them where they are (the caller keeps them untouched
   // until kmcpg_wait has returned).  Staging 256 MB — a batch of 256 assemblies — took the submitting thread 15-25 ms, longer than the GPU
   // needs for the batch (profiles/r06_h2h.txt); anything else is copied to the lane's pinned buffer as before.
@@ -397,52 +409,44 @@ int stage_packed(Lane* L, const PackedIn& in, const uint64_t* offs, uint32_t n) 
   if (pinned) L->ext_pack = in.codes;
   else par_memcpy(L->h_pack.p, in.codes, (tb + 3) / 4);
   if (in.n_exc) memcpy(L->h_exc.p, in.exc, in.n_exc * sizeof(ExcRun));
-  par_memcpy(L->h_offs.p, offs, ((size_t)n + 1) * sizeof(uint64_t));
+  par_memcpy(L->h_offs.p, b.offs, ((size_t)n + 1) * sizeof(uint64_t));
   L->n_exc = (uint32_t)in.n_exc;
   L->packed = true;
   return 0;
 }
 
+// the lane's batch as the GPU half is told about it.  Packed input: the k-mer stage (query.cpp run_kmers) reads the codes where it can — whole
+// genomes — and expands them to the text in d_seqs where it cannot.  Sliding windows: the k-mer kernels read each window's bases in place
+// (d_wsrc, built by the prologue of the first attempt)
+DeviceBatch lane_batch(const Lane* L) {
+  DeviceBatch b{L->d_seqs.p, L->d_offs.p, L->paired ? L->d_seqs2.p : nullptr, L->paired ? L->d_offs2.p : nullptr, L->n, L->tb1 + L->tb2, L->maxlen};
+  if (L->packed) {
+    b.packed.codes = L->d_pack.p;
+    b.packed.exc = L->n_exc ? L->d_exc.p : nullptr;
+    b.packed.n_exc = L->n_exc;
+    b.packed.text = L->d_seqs.p;
+    b.packed.n_bases = L->up_bases;
+  }
+  if (L->win) {
+    WindowSrc& w = b.windows;
+    w.src = L->d_wsrc.p;
+    w.soffs = L->d_soffs.p;
+    w.wpre = L->d_wmeta.p;
+    w.cpre = L->d_wmeta.p + 2 * ((size_t)L->up_reads + 1);
+    w.ns = L->up_reads;
+    w.n_chunks = L->wchunks;
+    w.sb = L->up_bases;
+    w.step = L->wstep;
+    w.window = L->wwin;
+  }
+  return b;
+}
+
+// K1 + K2 (+ K3) of a staged and uploaded lane; a rerun of the batch (ENOMEM, hit-buffer overflow) does all of it again
 int enqueue_query(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p, const std::function<int()>* prologue = nullptr) {
   hipStream_t st = L->st;
-  // packed input: the k-mer stage of this call (query.cpp run_kmers, on this thread) reads the codes where it can — whole genomes — and
-  // expands them to the text in d_seqs where it cannot; a rerun of the batch (ENOMEM, hit-buffer overflow) does the same again
-  struct PackedScope {
-    explicit PackedScope(Lane* L) {
-      if (!L->packed) return;
-      PackedSrc s;
-      s.codes = L->d_pack.p;
-      s.exc = L->n_exc ? L->d_exc.p : nullptr;
-      s.n_exc = L->n_exc;
-      s.text = L->d_seqs.p;
-      s.n_bases = L->win ? L->sb : L->tb1;
-      tl_packed_src = s;
-    }
-    ~PackedScope() { tl_packed_src = PackedSrc{}; }
-  } packed_scope(L);
-  // sliding windows: the k-mer kernels read each window's bases in place (d_wsrc, built by the prologue of the first attempt)
-  struct WindowScope {
-    explicit WindowScope(Lane* L) {
-      tl_window = WindowSrc{};
-      if (!L->win) return;
-      WindowSrc w;
-      w.src = L->d_wsrc.p;
-      w.soffs = L->d_soffs.p;
-      w.wpre = L->d_wmeta.p;
-      w.cpre = L->d_wmeta.p + 2 * ((size_t)L->ns + 1);
-      w.ns = L->ns;
-      w.n_chunks = L->wchunks;
-      w.sb = L->sb;
-      w.step = L->wstep;
-      w.window = L->wwin;
-      tl_window = w;
-    }
-    ~WindowScope() { tl_window = WindowSrc{}; }
-  } window_scope(L);
-  int rc = query_device_after(db, L->d_seqs.p, L->d_offs.p, L->paired ? L->d_seqs2.p : nullptr, L->paired ? L->d_offs2.p : nullptr, L->n, L->tb1 + L->tb2,
-                              L->maxlen, &p, L->d_hits.p, L->d_hits.cap, L->d_cnt.p, L->d_qk.p, L->d_ql.p, st, prologue);
+  int rc = query_device_after(db, lane_batch(L), &p, QueryOut{L->d_hits.p, L->d_hits.cap, L->d_cnt.p, L->d_qk.p, L->d_ql.p}, st, prologue, &L->bound_n);
   if (rc) return rc;
-  L->bound_n = tl_query_bound_n;
   HIPCHK(hipMemcpyAsync(L->h_cnt.p, L->d_cnt.p, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
   if (L->grouped) {  // K3 right behind K2 (an overflowing hit buffer makes both run again, collect())
     if (L->d_pairs.ensure(L->d_hits.cap) || L->d_roffs.ensure((size_t)L->n + 2) || L->h_roffs.ensure((size_t)L->n + 2)) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
@@ -490,9 +494,8 @@ int enqueue(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p, bool ge
     L->d_pairs.release();
   }
   uint64_t cap = std::max<uint64_t>(L->d_hits.cap, want);
-  // the bases and reads that go up: the batch itself, or — sliding windows — the slices of reads its windows view
-  const uint64_t up_bases = L->win ? L->sb : L->tb1;
-  const size_t up_reads = L->win ? L->ns : n;
+  const uint64_t up_bases = L->up_bases;  // (the batch itself, or — sliding windows — the slices of reads its windows view)
+  const size_t up_reads = L->up_reads;
   if (L->d_seqs.ensure(up_bases + 16) || L->d_offs.ensure((size_t)n + 1) || L->d_cnt.ensure(2) || L->d_qk.ensure(n) || L->d_ql.ensure(n) ||
       (L->paired && (L->d_seqs2.ensure(L->tb2 + 16) || L->d_offs2.ensure((size_t)n + 1))) ||
       (L->win && (L->d_soffs.ensure(up_reads + 1) || L->d_wmeta.ensure(3 * (up_reads + 1)) || L->d_wsrc.ensure(n))))
@@ -664,28 +667,27 @@ void drop_ticket(kmcpg_ticket* t, bool failed = false) {
 // (kmcpg_open with shard r of S), K1 + K2, keep the hit tuples, drop it, next shard — and the concatenated hit lists are
 // finalized once, exactly as the lists of S GPUs would be.  The shard searched last stays resident and is the first one of
 // the next batch, so a batch costs S - 1 uploads: the larger the batch, the smaller their share.
-int search_paged(kmcpg_db* front, const uint8_t* seqs, const uint64_t* offs, const uint8_t* seqs2, const uint64_t* offs2, uint32_t n, const kmcpg_params& p,
-                 kmcpg_ticket* t) {
+int search_paged(kmcpg_db* front, const HostBatch& b, const kmcpg_params& p, kmcpg_ticket* t) {
+  const uint32_t n = b.n;
   std::lock_guard<std::mutex> g(front->paged_mu);
   t->paged = true;
   t->hits.clear();
   t->qk.assign(n, 0);
   t->ql.assign(n, 0);
   if (n == 0) return 0;
-  if (offs[0] != 0 || (seqs2 && offs2[0] != 0)) return kmcpg_fail(KMCPG_EINVAL, "offs[0] must be 0");
-  for (uint32_t i = 0; i < n; i++)
-    if (offs[i + 1] < offs[i] || (seqs2 && offs2[i + 1] < offs2[i])) return kmcpg_fail(KMCPG_EINVAL, "offsets must not decrease (read %u)", i);
+  uint64_t maxlen = 0;  // (stage() below refuses a read that is too long)
+  if (int rc = check_offsets(b, &maxlen)) return rc;
   // retries (--try-se, smaller k) read the batch again after kmcpg_submit has returned the caller's buffers
-  t->seqs.assign(seqs, seqs + offs[n]);
-  t->offs.assign(offs, offs + n + 1);
-  if (seqs2) {
-    t->seqs2.assign(seqs2, seqs2 + offs2[n]);
-    t->offs2.assign(offs2, offs2 + n + 1);
+  t->seqs.assign(b.seqs, b.seqs + b.offs[n]);
+  t->offs.assign(b.offs, b.offs + n + 1);
+  if (b.seqs2) {
+    t->seqs2.assign(b.seqs2, b.seqs2 + b.offs2[n]);
+    t->offs2.assign(b.offs2, b.offs2 + n + 1);
   }
   t->S[0] = t->seqs.data();
   t->O[0] = t->offs.data();
-  t->S[1] = seqs2 ? t->seqs2.data() : nullptr;
-  t->O[1] = seqs2 ? t->offs2.data() : nullptr;
+  t->S[1] = b.seqs2 ? t->seqs2.data() : nullptr;
+  t->O[1] = b.seqs2 ? t->offs2.data() : nullptr;
   const int S = front->paged_passes;
   const int first = front->paged_rank >= 0 ? front->paged_rank : 0;
   for (int i = 0; i < S; i++) {
@@ -712,7 +714,7 @@ int search_paged(kmcpg_db* front, const uint8_t* seqs, const uint64_t* offs, con
     if (rc) return rc;
     Lane* L = acquire_lane(A, false, true);
     uint64_t cnt = 0;
-    rc = stage(L, seqs, offs, seqs2, offs2, n);
+    rc = stage(L, b);
     if (rc == 0) rc = enqueue(sh, A, L, p);
     if (rc == 0) rc = collect(sh, A, L, p, &cnt);
     if (rc == 0) {
@@ -731,15 +733,14 @@ int search_paged(kmcpg_db* front, const uint8_t* seqs, const uint64_t* offs, con
   return 0;
 }
 
-int submit_impl(kmcpg_db* db, const uint8_t* seqs, const uint64_t* offs, const uint8_t* seqs2, const uint64_t* offs2, uint32_t n, const kmcpg_params& p, bool retry,
-                bool block, kmcpg_ticket** out, const PackedIn* packed = nullptr) {
+int submit_impl(kmcpg_db* db, const HostBatch& b, const kmcpg_params& p, bool retry, bool block, kmcpg_ticket** out, const PackedIn* packed = nullptr) {
   std::unique_ptr<kmcpg_ticket> t(new kmcpg_ticket());
   t->db = db;
-  t->n = n;
-  t->paired = seqs2 != nullptr;
+  t->n = b.n;
+  t->paired = b.seqs2 != nullptr;
   t->p = p;
   if (db->paged_passes > 0) {
-    int rc = search_paged(db, seqs, offs, seqs2, offs2, n, p, t.get());
+    int rc = search_paged(db, b, p, t.get());
     if (rc) return rc;
     *out = t.release();
     return 0;
@@ -763,10 +764,10 @@ int submit_impl(kmcpg_db* db, const uint8_t* seqs, const uint64_t* offs, const u
   std::vector<int> rcs(t->parts.size(), 0);
   std::vector<std::string> errs(t->parts.size());
   // the staged ASCII is read again only by the retries of retry_unmatched (--try-se on pairs, the smaller k of a multi-k database)
-  const bool can_pack = !seqs2 && !retry && (p.k > 0 || db->ks_desc.size() < 2);
+  const bool can_pack = !b.seqs2 && !retry && (p.k > 0 || db->ks_desc.size() < 2);
   auto one = [&](size_t i) {
     auto& pt = t->parts[i];
-    rcs[i] = packed ? stage_packed(pt.lane, *packed, offs, n) : stage(pt.lane, seqs, offs, seqs2, offs2, n, can_pack);
+    rcs[i] = packed ? stage_packed(pt.lane, *packed, b) : stage(pt.lane, b, can_pack);
     if (rcs[i] == 0) rcs[i] = enqueue(pt.shard, pt.shard->async, pt.lane, p);
     if (rcs[i]) errs[i] = kmcpg_err_ref();
   };
@@ -794,7 +795,7 @@ int submit_impl(kmcpg_db* db, const uint8_t* seqs, const uint64_t* offs, const u
 
 // raw results of a ticket -> finalized matches (host half).  The hit lists of the parts are concatenated exactly as the
 // reference concatenates the replies of its per-block workers (:946-964).
-int finish_raw(kmcpg_ticket* t, kmcpg_result* out) {
+int finish_raw(kmcpg_ticket* t, kmcpg_result* out, bool as_pairs) {
   const kmcpg_hit* hits = nullptr;
   uint64_t n_hits = 0;
   static thread_local std::vector<kmcpg_hit, NoInitAlloc<kmcpg_hit>> merged;
@@ -805,7 +806,7 @@ int finish_raw(kmcpg_ticket* t, kmcpg_result* out) {
     int rc = collect(pt.shard, pt.shard->async, pt.lane, t->p, &n_hits);
     if (rc) return rc;
     if (pt.lane->grouped && t->n)
-      return finalize_grouped_trusted(t->db, pt.lane->h_pairs.p, pt.lane->h_roffs.p, pt.lane->h_qk.p, pt.lane->h_ql.p, t->n, t->p, out, pt.lane->bound_n);
+      return finalize_grouped_trusted(t->db, pt.lane->h_pairs.p, pt.lane->h_roffs.p, pt.lane->h_qk.p, pt.lane->h_ql.p, t->n, t->p, out, pt.lane->bound_n, as_pairs);
     hits = pt.lane->h_hits.p;
   } else if (Exchange* x = t->db->exchange) {
     // the shards' lists meet on the first GPU (RCCL send/recv over xGMI, exactly the bytes each shard produced) and come to
@@ -849,7 +850,7 @@ int finish_raw(kmcpg_ticket* t, kmcpg_result* out) {
       if (rc) return rc;
       int32_t bound_n = INT32_MAX;  // every shard ran the same params on the same batch; the smallest cover is what holds for the merged list
       for (auto& pt : t->parts) bound_n = std::min(bound_n, pt.lane->bound_n);
-      return finalize_grouped_trusted(t->db, L0->h_pairs.p, L0->h_roffs.p, L0->h_qk.p, L0->h_ql.p, t->n, t->p, out, bound_n);
+      return finalize_grouped_trusted(t->db, L0->h_pairs.p, L0->h_roffs.p, L0->h_qk.p, L0->h_ql.p, t->n, t->p, out, bound_n, as_pairs);
     }
     if (L0->h_hits.ensure(n_hits + 1)) return kmcpg_fail(KMCPG_ENOMEM, "hipHostMalloc failed");
     int rc = exchange_gather(x, src, bytes, (uint8_t*)L0->h_hits.p);
@@ -871,12 +872,12 @@ int finish_raw(kmcpg_ticket* t, kmcpg_result* out) {
 }
 
 // a small synchronous search on the retry lane(s): the sub-batches of --try-se and of the smaller k of multi-k databases
-int search_sync(kmcpg_db* db, const uint8_t* seqs, const uint64_t* offs, const uint8_t* seqs2, const uint64_t* offs2, uint32_t n, const kmcpg_params& p,
-                kmcpg_result* out) {
+// (always Match records: retry_unmatched splices them into the batch's result record by record)
+int search_sync(kmcpg_db* db, const HostBatch& b, const kmcpg_params& p, kmcpg_result* out) {
   kmcpg_ticket* t = nullptr;
-  int rc = submit_impl(db, seqs, offs, seqs2, offs2, n, p, true, true, &t);
+  int rc = submit_impl(db, b, p, true, true, &t);
   if (rc) return rc;
-  rc = finish_raw(t, out);
+  rc = finish_raw(t, out, false);
   const std::string keep = rc ? kmcpg_err_ref() : std::string();
   drop_ticket(t, rc != 0);
   if (rc) kmcpg_err_ref() = keep;
@@ -949,7 +950,7 @@ int retry_unmatched(kmcpg_ticket* t, kmcpg_result* out) {
       q.k = ks[ik];
       q.try_se = 0;
       kmcpg_result r2;
-      rc = search_sync(db, sub[0].data(), so[0].data(), S[1] ? sub[1].data() : nullptr, S[1] ? so[1].data() : nullptr, (uint32_t)todo.size(), q, &r2);
+      rc = search_sync(db, HostBatch{sub[0].data(), so[0].data(), S[1] ? sub[1].data() : nullptr, S[1] ? so[1].data() : nullptr, (uint32_t)todo.size()}, q, &r2);
       if (rc) break;
       splice(r2, true, ks[ik]);
       kmcpg_result_free(&r2);
@@ -971,7 +972,7 @@ int retry_unmatched(kmcpg_ticket* t, kmcpg_result* out) {
       q.min_qlen = 0;  // the length gate was applied once, before k-mer generation
       q.try_se = 0;
       kmcpg_result r2;
-      rc = search_sync(db, sub[0].data(), so[0].data(), nullptr, nullptr, (uint32_t)todo.size(), q, &r2);
+      rc = search_sync(db, HostBatch{sub[0].data(), so[0].data(), nullptr, nullptr, (uint32_t)todo.size()}, q, &r2);
       if (rc) break;
       splice(r2, false, ks[ik]);
       kmcpg_result_free(&r2);
@@ -1102,21 +1103,19 @@ int submit_window_piece_device(kmcpg_db* db, const uint8_t* seqs, const uint64_t
   Lane* L = acquire_lane(A, false, false);
   if (!L) return kmcpg_fail(KMCPG_EBUSY, "all %zu lanes of this handle are in flight: kmcpg_wait for a ticket first (KMCPG_INFLIGHT)", A->max_lanes);
   t->parts.push_back({db, L, false});
-  int rc = stage(L, text.data(), soffs.data(), nullptr, nullptr, ns, true);
+  int rc = stage(L, HostBatch{text.data(), soffs.data(), nullptr, nullptr, ns}, true);  // the slices go up ...
   if (rc == 0 && L->h_wmeta.ensure(3 * ((size_t)ns + 1))) rc = kmcpg_fail(KMCPG_ENOMEM, "hipHostMalloc failed");
   if (rc == 0) {
     memcpy(L->h_wmeta.p, wpre.data(), ((size_t)ns + 1) * sizeof(uint64_t));
     memcpy(L->h_wmeta.p + ns + 1, vpre.data(), ((size_t)ns + 1) * sizeof(uint64_t));
     memcpy(L->h_wmeta.p + 2 * ((size_t)ns + 1), cpre.data(), ((size_t)ns + 1) * sizeof(uint64_t));
-    L->wchunks = cpre.back();
-    L->win = true;
-    L->ns = ns;
-    L->sb = L->tb1;
-    L->wstep = s.step;
-    L->wwin = s.window;
+    L->win = true;  // ... and the windows over them are what is searched
     L->n = (uint32_t)pc.n_win;
     L->tb1 = pc.bases;
     L->maxlen = (uint32_t)wmax;
+    L->wstep = s.step;
+    L->wwin = s.window;
+    L->wchunks = cpre.back();
     rc = enqueue(db, A, L, p);
   }
   if (rc) {
@@ -1145,8 +1144,10 @@ int submit_window_piece_text(kmcpg_db* db, const uint8_t* seqs, const uint64_t* 
       woffs.push_back(text.size());
     }
   }
-  return submit_impl(db, text.data(), woffs.data(), nullptr, nullptr, (uint32_t)pc.n_win, p, false, false, out);
+  return submit_impl(db, HostBatch{text.data(), woffs.data(), nullptr, nullptr, (uint32_t)pc.n_win}, p, false, false, out);
 }
+
+int wait_impl(kmcpg_ticket* t, kmcpg_result* out, bool as_pairs);
 
 int submit_windows_impl(kmcpg_db* db, const uint8_t* seqs, const uint64_t* offs, uint32_t n, const kmcpg_window_spec& s, const kmcpg_params& p,
                         kmcpg_ticket** out) {
@@ -1160,7 +1161,7 @@ int submit_windows_impl(kmcpg_db* db, const uint8_t* seqs, const uint64_t* offs,
   };
   if (pieces.empty()) {  // no read yields a window: an empty batch
     static const uint64_t zero = 0;
-    return submit_impl(db, nullptr, &zero, nullptr, nullptr, 0, p, false, false, out);
+    return submit_impl(db, HostBatch{nullptr, &zero, nullptr, nullptr, 0}, p, false, false, out);
   }
   if (pieces.size() == 1) return one(pieces[0], out);
   uint64_t total = 0;
@@ -1187,7 +1188,7 @@ int submit_windows_impl(kmcpg_db* db, const uint8_t* seqs, const uint64_t* offs,
       }
       kmcpg_ticket* w = t->pieces[oldest];
       t->pieces[oldest] = nullptr;
-      if (const int rc2 = kmcpg_wait(w, &t->piece_res[oldest])) {
+      if (const int rc2 = wait_impl(w, &t->piece_res[oldest], false)) {
         const std::string keep = kmcpg_err_ref();
         drop_ticket(t.release(), true);
         return kmcpg_fail(rc2, "%s", keep.c_str());
@@ -1199,7 +1200,7 @@ int submit_windows_impl(kmcpg_db* db, const uint8_t* seqs, const uint64_t* offs,
 }
 
 // a ticket of several window pieces: their results one behind the other, as one result (the record or the compact form the caller asked for)
-int wait_pieces(kmcpg_ticket* t, kmcpg_result* out) {
+int wait_pieces(kmcpg_ticket* t, kmcpg_result* out, bool as_pairs) {
   const size_t np = t->pieces.size();
   std::vector<kmcpg_result> rs(np);
   int rc = 0;
@@ -1207,7 +1208,7 @@ int wait_pieces(kmcpg_ticket* t, kmcpg_result* out) {
     if (t->pieces[i]) {
       kmcpg_ticket* w = t->pieces[i];
       t->pieces[i] = nullptr;
-      rc = kmcpg_wait(w, &rs[i]);
+      rc = wait_impl(w, &rs[i], as_pairs);
     } else {
       rs[i] = t->piece_res[i];
       t->piece_res[i] = kmcpg_result{};
@@ -1218,7 +1219,7 @@ int wait_pieces(kmcpg_ticket* t, kmcpg_result* out) {
     return rc;
   }
   ResultOwner* o = result_owner_take();
-  result_owner_shape(o, t->n);
+  result_owner_shape(o, t->n, as_pairs);
   uint32_t base = 0;
   std::vector<kmcpg_match> ex;
   for (kmcpg_result& r : rs) {
@@ -1245,6 +1246,33 @@ int wait_pieces(kmcpg_ticket* t, kmcpg_result* out) {
     kmcpg_result_free(&r);
   }
   result_publish(o, t->n, t->p.k > 0 ? t->p.k : t->db->info.k, out);
+  return 0;
+}
+
+// kmcpg_wait / kmcpg_wait_pairs: the ticket's result in the form asked for where the path it took collects that form natively (as_pairs only
+// ever comes with a batch nothing searches again, kmcpg_wait_pairs), as Match records everywhere else; gives the ticket back
+int wait_impl(kmcpg_ticket* t, kmcpg_result* out, bool as_pairs) {
+  memset(out, 0, sizeof *out);
+  int rc;
+  if (!t->pieces.empty()) rc = wait_pieces(t, out, as_pairs);
+  else {
+    rc = finish_raw(t, out, as_pairs);
+    if (rc == 0) rc = retry_unmatched(t, out);
+  }
+  const std::string keep = rc ? kmcpg_err_ref() : std::string();
+  if (rc) kmcpg_result_free(out);
+  drop_ticket(t, rc != 0);
+  if (rc) kmcpg_err_ref() = keep;
+  return rc;
+}
+
+// the submit family works on a handle that holds the whole database and can reach a GPU; *p = the caller's params or the defaults
+int submit_handle(kmcpg_db* db, const kmcpg_params* params, kmcpg_params* p) {
+  if (db->opts.shard_count != 1)
+    return kmcpg_fail(KMCPG_EINVAL, "kmcpg_submit/kmcpg_search_batch need the whole database: open it on one GPU or with kmcpg_open_devices; use kmcpg_query_device + kmcpg_finalize per shard");
+  if (db->shards.empty() && db->opts.device < 0 && db->paged_passes == 0) return kmcpg_fail(KMCPG_EDEVICE, "metadata-only handle (device -1): no GPU work possible");
+  *p = params ? *params : default_params();
+  if (p->min_matched < 1) return kmcpg_fail(KMCPG_EINVAL, "min_matched must be >= 1");
   return 0;
 }
 }  // namespace
@@ -1344,22 +1372,18 @@ extern "C" int kmcpg_paged_info(const kmcpg_db* db, int32_t* passes, uint64_t* u
   return 0;
 }
 
-static int submit_checked(kmcpg_db* db, const uint8_t* seqs, const uint64_t* offs, const uint8_t* seqs2, const uint64_t* offs2, uint32_t n_reads,
-                          const kmcpg_params* params, bool block, kmcpg_ticket** out) {
-  if (!db || !out || (n_reads && (!seqs || !offs))) return kmcpg_fail(KMCPG_EINVAL, "null argument");
+static int submit_checked(kmcpg_db* db, const HostBatch& b, const kmcpg_params* params, bool block, kmcpg_ticket** out) {
+  if (!db || !out || (b.n && (!b.seqs || !b.offs))) return kmcpg_fail(KMCPG_EINVAL, "null argument");
   *out = nullptr;
-  if ((seqs2 == nullptr) != (offs2 == nullptr)) return kmcpg_fail(KMCPG_EINVAL, "seqs2 and offs2 must be given together");
-  if (db->opts.shard_count != 1)
-    return kmcpg_fail(KMCPG_EINVAL, "kmcpg_submit/kmcpg_search_batch need the whole database: open it on one GPU or with kmcpg_open_devices; use kmcpg_query_device + kmcpg_finalize per shard");
-  if (db->shards.empty() && db->opts.device < 0 && db->paged_passes == 0) return kmcpg_fail(KMCPG_EDEVICE, "metadata-only handle (device -1): no GPU work possible");
-  const kmcpg_params p = params ? *params : default_params();
-  if (p.min_matched < 1) return kmcpg_fail(KMCPG_EINVAL, "min_matched must be >= 1");
-  return submit_impl(db, seqs, offs, seqs2, offs2, n_reads, p, false, block, out);
+  if ((b.seqs2 == nullptr) != (b.offs2 == nullptr)) return kmcpg_fail(KMCPG_EINVAL, "seqs2 and offs2 must be given together");
+  kmcpg_params p;
+  if (int rc = submit_handle(db, params, &p)) return rc;
+  return submit_impl(db, b, p, false, block, out);
 }
 
 extern "C" int kmcpg_submit(kmcpg_db* db, const uint8_t* seqs, const uint64_t* offs, const uint8_t* seqs2, const uint64_t* offs2, uint32_t n_reads,
                             const kmcpg_params* params, kmcpg_ticket** out) {
-  return submit_checked(db, seqs, offs, seqs2, offs2, n_reads, params, false, out);
+  return submit_checked(db, HostBatch{seqs, offs, seqs2, offs2, n_reads}, params, false, out);
 }
 
 // ---- packed queries (kmcp_gpu.h): the packer and its inverse for hosts, and the entry that takes codes
@@ -1426,20 +1450,17 @@ extern "C" int kmcpg_submit_packed(kmcpg_db* db, const uint8_t* codes, const uin
                                    const kmcpg_params* params, kmcpg_ticket** out) {
   if (!db || !out || (n_reads && (!codes || !offs)) || (n_exc && !exc)) return kmcpg_fail(KMCPG_EINVAL, "null argument");
   *out = nullptr;
-  if (db->opts.shard_count != 1)
-    return kmcpg_fail(KMCPG_EINVAL, "kmcpg_submit/kmcpg_search_batch need the whole database: open it on one GPU or with kmcpg_open_devices; use kmcpg_query_device + kmcpg_finalize per shard");
-  if (db->shards.empty() && db->opts.device < 0 && db->paged_passes == 0) return kmcpg_fail(KMCPG_EDEVICE, "metadata-only handle (device -1): no GPU work possible");
-  const kmcpg_params p = params ? *params : default_params();
-  if (p.min_matched < 1) return kmcpg_fail(KMCPG_EINVAL, "min_matched must be >= 1");
+  kmcpg_params p;
+  if (int rc = submit_handle(db, params, &p)) return rc;
   // handles that read the batch's text again — the smaller k of a multi-k database (retry_unmatched), the passes of a paged index — get text
   if (db->paged_passes > 0 || (p.k <= 0 && db->ks_desc.size() > 1)) {
     const uint64_t tb = n_reads ? offs[n_reads] : 0;
     std::vector<uint8_t, NoInitAlloc<uint8_t>> text((size_t)tb + 16);
     if (int rc = kmcpg_unpack2(codes, tb, exc, n_exc, text.data())) return rc;
-    return submit_impl(db, text.data(), offs, nullptr, nullptr, n_reads, p, false, false, out);
+    return submit_impl(db, HostBatch{text.data(), offs, nullptr, nullptr, n_reads}, p, false, false, out);
   }
   const PackedIn in{codes, exc, n_exc};
-  return submit_impl(db, nullptr, offs, nullptr, nullptr, n_reads, p, false, false, out, &in);
+  return submit_impl(db, HostBatch{nullptr, offs, nullptr, nullptr, n_reads}, p, false, false, out, &in);
 }
 
 
@@ -1455,15 +1476,6 @@ static int window_args(const uint64_t* offs, uint32_t n_reads, const kmcpg_windo
     if (offs[i + 1] < offs[i]) return kmcpg_fail(KMCPG_EINVAL, "offsets must not decrease (read %u)", i);
     if (offs[i + 1] - offs[i] > 0x7fffffffULL) return kmcpg_fail(KMCPG_EUNSUPPORTED, "query longer than 2^31-1 bases");
   }
-  return 0;
-}
-
-static int window_handle(kmcpg_db* db, const kmcpg_params* params, kmcpg_params* p) {
-  if (db->opts.shard_count != 1)
-    return kmcpg_fail(KMCPG_EINVAL, "kmcpg_submit/kmcpg_search_batch need the whole database: open it on one GPU or with kmcpg_open_devices; use kmcpg_query_device + kmcpg_finalize per shard");
-  if (db->shards.empty() && db->opts.device < 0 && db->paged_passes == 0) return kmcpg_fail(KMCPG_EDEVICE, "metadata-only handle (device -1): no GPU work possible");
-  *p = params ? *params : default_params();
-  if (p->min_matched < 1) return kmcpg_fail(KMCPG_EINVAL, "min_matched must be >= 1");
   return 0;
 }
 
@@ -1503,7 +1515,7 @@ extern "C" int kmcpg_submit_windows(kmcpg_db* db, const uint8_t* seqs, const uin
   if (!db || !out || (n_reads && (!seqs || !offs))) return kmcpg_fail(KMCPG_EINVAL, "null argument");
   *out = nullptr;
   kmcpg_params p;
-  if (int rc = window_handle(db, params, &p)) return rc;
+  if (int rc = submit_handle(db, params, &p)) return rc;
   if (int rc = window_args(offs, n_reads, spec)) return rc;
   return submit_windows_impl(db, seqs, offs, n_reads, *spec, p, out);
 }
@@ -1513,7 +1525,7 @@ extern "C" int kmcpg_submit_packed_windows(kmcpg_db* db, const uint8_t* codes, c
   if (!db || !out || (n_reads && (!codes || !offs)) || (n_exc && !exc)) return kmcpg_fail(KMCPG_EINVAL, "null argument");
   *out = nullptr;
   kmcpg_params p;
-  if (int rc = window_handle(db, params, &p)) return rc;
+  if (int rc = submit_handle(db, params, &p)) return rc;
   if (int rc = window_args(offs, n_reads, spec)) return rc;
   // the reads' bases once as text on the host (not the windows'): the slices a piece needs are cut from it and go up packed again where that
   // pays (stage)
@@ -1529,18 +1541,19 @@ extern "C" int kmcpg_wait(kmcpg_ticket* t, kmcpg_result* out) {
     if (t) drop_ticket(t);
     return kmcpg_fail(KMCPG_EINVAL, "null argument");
   }
-  memset(out, 0, sizeof *out);
-  int rc;
-  if (!t->pieces.empty()) rc = wait_pieces(t, out);
-  else {
-    rc = finish_raw(t, out);
-    if (rc == 0) rc = retry_unmatched(t, out);
+  return wait_impl(t, out, false);
+}
+
+// reads [lo, lo + cnt) of a batch as a batch of their own: offsets of a part start at its first read — a rebased copy in o1 / o2 (the
+// sequences themselves are addressed in place)
+static HostBatch sub_batch(const HostBatch& b, uint32_t lo, uint32_t cnt, std::vector<uint64_t>& o1, std::vector<uint64_t>& o2) {
+  o1.resize((size_t)cnt + 1);
+  for (uint32_t r = 0; r <= cnt; r++) o1[r] = b.offs[lo + r] - b.offs[lo];
+  if (b.offs2) {
+    o2.resize((size_t)cnt + 1);
+    for (uint32_t r = 0; r <= cnt; r++) o2[r] = b.offs2[lo + r] - b.offs2[lo];
   }
-  const std::string keep = rc ? kmcpg_err_ref() : std::string();
-  if (rc) kmcpg_result_free(out);
-  drop_ticket(t, rc != 0);
-  if (rc) kmcpg_err_ref() = keep;
-  return rc;
+  return HostBatch{b.seqs + b.offs[lo], o1.data(), b.seqs2 ? b.seqs2 + b.offs2[lo] : nullptr, b.offs2 ? o2.data() : nullptr, cnt};
 }
 
 // One large batch, several pieces in flight.  kmcpg_search_batch is a synchronous call: upload, K1 + K2 + K3, the copy of the ordered
@@ -1552,8 +1565,8 @@ extern "C" int kmcpg_wait(kmcpg_ticket* t, kmcpg_result* out) {
 // need a second search (--try-se on pairs, several k-mer sizes: those splice sub-results and keep the plain path).
 // A thread only ever BLOCKS for a lane while it holds none (two threads in here at once share the lanes instead of waiting for each
 // other's).  *took = false: not applicable, nothing done.
-static int search_batch_pieces(kmcpg_db* db, const uint8_t* seqs, const uint64_t* offs, const uint8_t* seqs2, const uint64_t* offs2, uint32_t n,
-                               const kmcpg_params& p, kmcpg_result* out, bool* took) {
+static int search_batch_pieces(kmcpg_db* db, const HostBatch& b, const kmcpg_params& p, bool as_pairs, kmcpg_result* out, bool* took) {
+  const uint32_t n = b.n;
   *took = false;
   uint32_t kMinPiece = 16384;
   if (const char* e = getenv("KMCPG_PIECE_MIN")) kMinPiece = (uint32_t)std::max(1, atoi(e));  // tests and tools/stress_async.py: pieces of small batches
@@ -1561,7 +1574,7 @@ static int search_batch_pieces(kmcpg_db* db, const uint8_t* seqs, const uint64_t
   if (const char* e = getenv("KMCPG_PIECES")) want = atoi(e);
   if (want < 2 || (uint64_t)n < 2 * (uint64_t)kMinPiece) return 0;
   if (!db->shards.empty() || db->paged_passes > 0 || db->opts.device < 0 || db->opts.shard_count != 1) return 0;
-  if ((p.try_se && seqs2) || (p.k <= 0 && db->ks_desc.size() > 1)) return 0;
+  if ((p.try_se && b.seqs2) || (p.k <= 0 && db->ks_desc.size() > 1)) return 0;
   AsyncState* A = nullptr;
   if (int rc = async_state(db, &A)) return rc;
   if (!A->device_finalize || A->hits_stay_on_device) return 0;
@@ -1583,7 +1596,7 @@ static int search_batch_pieces(kmcpg_db* db, const uint8_t* seqs, const uint64_t
     pc[j].cnt = (uint32_t)((uint64_t)n * (j + 1) / S) - pc[j].lo;
   }
   ResultOwner* o = result_owner_take();
-  result_owner_shape(o, n);
+  result_owner_shape(o, n, as_pairs);
   uint64_t match_base = 0;
   uint32_t next_finish = 0, next_submit = 0;
   int rc = 0;
@@ -1623,13 +1636,7 @@ static int search_batch_pieces(kmcpg_db* db, const uint8_t* seqs, const uint64_t
     }
     Piece& q = pc[next_submit];
     q.lane = L;
-    o1.resize((size_t)q.cnt + 1);
-    for (uint32_t r = 0; r <= q.cnt; r++) o1[r] = offs[q.lo + r] - offs[q.lo];
-    if (offs2) {
-      o2.resize((size_t)q.cnt + 1);
-      for (uint32_t r = 0; r <= q.cnt; r++) o2[r] = offs2[q.lo + r] - offs2[q.lo];
-    }
-    rc = stage(L, seqs + offs[q.lo], o1.data(), seqs2 ? seqs2 + offs2[q.lo] : nullptr, offs2 ? o2.data() : nullptr, q.cnt, !seqs2);
+    rc = stage(L, sub_batch(b, q.lo, q.cnt, o1, o2), !b.seqs2);
     if (rc == 0) rc = enqueue(db, A, L, p, true);
     if (timing) fprintf(stderr, "piece %u: enqueued at %.2f ms\n", next_submit, now() - t_begin);
     next_submit++;
@@ -1662,40 +1669,33 @@ static int search_batch_pieces(kmcpg_db* db, const uint8_t* seqs, const uint64_t
   return 0;
 }
 
-extern "C" int kmcpg_search_batch(kmcpg_db* db, const uint8_t* seqs, const uint64_t* offs, const uint8_t* seqs2, const uint64_t* offs2, uint32_t n_reads,
-                                  const kmcpg_params* params, kmcpg_result* out) {
-  if (!out) return kmcpg_fail(KMCPG_EINVAL, "null argument");
+// kmcpg_search_batch / kmcpg_search_batch_pairs: as_pairs = the paths that can collect compact pairs natively do so (the caller converts
+// whatever comes back as records)
+static int search_batch_impl(kmcpg_db* db, const HostBatch& in, const kmcpg_params* params, bool as_pairs, kmcpg_result* out) {
   memset(out, 0, sizeof *out);
   kmcpg_ticket* t = nullptr;
   int rc = 0;
   bool took = false;
-  if (db && n_reads && seqs && offs && (seqs2 == nullptr) == (offs2 == nullptr)) {
+  if (db && in.n && in.seqs && in.offs && (in.seqs2 == nullptr) == (in.offs2 == nullptr)) {
     const kmcpg_params pp = params ? *params : default_params();
-    if (pp.min_matched >= 1 && offs[0] == 0 && (!offs2 || offs2[0] == 0)) rc = search_batch_pieces(db, seqs, offs, seqs2, offs2, n_reads, pp, out, &took);
+    if (pp.min_matched >= 1 && in.offs[0] == 0 && (!in.offs2 || in.offs2[0] == 0)) rc = search_batch_pieces(db, in, pp, as_pairs, out, &took);
   }
   if (took && rc == 0) return 0;
   if (took) memset(out, 0, sizeof *out);
   if (!took || rc == KMCPG_ENOMEM) {
-    rc = submit_checked(db, seqs, offs, seqs2, offs2, n_reads, params, true, &t);
-    if (rc == 0) rc = kmcpg_wait(t, out);
+    rc = submit_checked(db, in, params, true, &t);
+    if (rc == 0) rc = wait_impl(t, out, as_pairs);
   }
-  if (rc != KMCPG_ENOMEM || n_reads < 2) return rc;
+  if (rc != KMCPG_ENOMEM || in.n < 2) return rc;
   // The batch's workspace (8-24 B per base next to the resident index) or its hit buffers did not fit: the two halves of the
   // batch one after the other, their results joined — a caller that sized its batches for an emptier GPU gets its answer
   // instead of an error (the reference has no such limit: it searches query by query).  The halves split again if they must.
   const std::string why = kmcpg_err_ref();
-  const uint32_t h = n_reads / 2;
+  const uint32_t h = in.n / 2;
   kmcpg_result part[2];
   for (int i = 0; i < 2; i++) {
-    const uint32_t lo = i ? h : 0, cnt = i ? n_reads - h : h;
-    // offsets of a half start at its first read: a rebased copy (the sequences themselves are addressed in place)
-    std::vector<uint64_t> o1((size_t)cnt + 1), o2;
-    for (uint32_t r = 0; r <= cnt; r++) o1[r] = offs[lo + r] - offs[lo];
-    if (offs2) {
-      o2.resize((size_t)cnt + 1);
-      for (uint32_t r = 0; r <= cnt; r++) o2[r] = offs2[lo + r] - offs2[lo];
-    }
-    rc = kmcpg_search_batch(db, seqs + offs[lo], o1.data(), seqs2 ? seqs2 + offs2[lo] : nullptr, offs2 ? o2.data() : nullptr, cnt, params, &part[i]);
+    std::vector<uint64_t> o1, o2;
+    rc = search_batch_impl(db, sub_batch(in, i ? h : 0, i ? in.n - h : h, o1, o2), params, as_pairs, &part[i]);
     if (rc) {
       if (i) kmcpg_result_free(&part[0]);
       return rc;
@@ -1715,30 +1715,26 @@ extern "C" int kmcpg_search_batch(kmcpg_db* db, const uint8_t* seqs, const uint6
   if (a->pairs_mode) a->pairs.insert(a->pairs.end(), b->pairs.begin(), b->pairs.end());
   else a->matches.insert(a->matches.end(), b->matches.begin(), b->matches.end());
   *out = part[0];
-  out->n_reads = n_reads;
+  out->n_reads = in.n;
   out->qlen = a->qlen.data();
   out->qkmers = a->qkmers.data();
   out->ksize = a->ksize.data();
   out->match_offs = a->offs.data();
   out->matches = a->matches.data();
   kmcpg_result_free(&part[1]);
-  if (getenv("KMCPG_VERBOSE")) fprintf(stderr, "kmcpg_search_batch: %u queries searched as two halves (%s)\n", n_reads, why.c_str());
+  if (getenv("KMCPG_VERBOSE")) fprintf(stderr, "kmcpg_search_batch: %u queries searched as two halves (%s)\n", in.n, why.c_str());
   return 0;
 }
 
-// ---- compact results: the record forms under tl_pairs_mode (results shaped meanwhile collect pairs, finalize.cpp), then whatever a
-//      path without native pairs produced (retries, host-merged lists, paged passes) is converted
-namespace {
-struct PairsScope {
-  bool on;
-  explicit PairsScope(bool want) : on(want) {
-    if (on) tl_pairs_mode = true;
-  }
-  ~PairsScope() {
-    if (on) tl_pairs_mode = false;
-  }
-};
+extern "C" int kmcpg_search_batch(kmcpg_db* db, const uint8_t* seqs, const uint64_t* offs, const uint8_t* seqs2, const uint64_t* offs2, uint32_t n_reads,
+                                  const kmcpg_params* params, kmcpg_result* out) {
+  if (!out) return kmcpg_fail(KMCPG_EINVAL, "null argument");
+  return search_batch_impl(db, HostBatch{seqs, offs, seqs2, offs2, n_reads}, params, false, out);
+}
 
+// ---- compact results: the internal forms of search and wait are asked for pairs (results shaped on the way collect pairs, finalize.cpp), then
+//      whatever a path without native pairs produced (retries, host-merged lists, paged passes) is converted
+namespace {
 int publish_pairs(kmcpg_result* r, kmcpg_result_pairs* out) {
   ResultOwner* o = (ResultOwner*)r->owner;
   memset(out, 0, sizeof *out);
@@ -1765,12 +1761,7 @@ extern "C" int kmcpg_search_batch_pairs(kmcpg_db* db, const uint8_t* seqs, const
   // record by record (retry_unmatched): those batches collect records and are converted at the end
   const bool native = db && !((params && params->try_se && seqs2) || ((!params || params->k <= 0) && db->ks_desc.size() > 1));
   kmcpg_result r{};
-  int rc;
-  {
-    PairsScope scope(native);
-    rc = kmcpg_search_batch(db, seqs, offs, seqs2, offs2, n_reads, params, &r);
-  }
-  if (rc) return rc;
+  if (int rc = search_batch_impl(db, HostBatch{seqs, offs, seqs2, offs2, n_reads}, params, native, &r)) return rc;
   return publish_pairs(&r, out);
 }
 
@@ -1782,12 +1773,7 @@ extern "C" int kmcpg_wait_pairs(kmcpg_ticket* t, kmcpg_result_pairs* out) {
   memset(out, 0, sizeof *out);
   const bool native = !((t->p.try_se && t->paired) || (t->p.k <= 0 && t->db->ks_desc.size() > 1));
   kmcpg_result r{};
-  int rc;
-  {
-    PairsScope scope(native);
-    rc = kmcpg_wait(t, &r);
-  }
-  if (rc) return rc;
+  if (int rc = wait_impl(t, &r, native)) return rc;
   return publish_pairs(&r, out);
 }
 

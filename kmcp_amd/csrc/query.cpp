@@ -40,9 +40,6 @@ void release_fpr_bounds(kmcpg_db* db) {
 // ------------------------------------------------------------------------------------------------
 // GPU half
 // ------------------------------------------------------------------------------------------------
-thread_local kmcpg::PackedSrc kmcpg::tl_packed_src;
-thread_local kmcpg::WindowSrc kmcpg::tl_window;
-
 // a batch the k-mer stage hashes segment by segment (run_kmers: plain or FracMinHash k-mers, single-end, some query above one segment)
 bool kmcpg::whole_genome_batch(const kmcpg_db* db, uint32_t max_read_len, bool paired) {
   return !paired && !db->info.syncmer && !db->info.minimizer && max_read_len > (uint32_t)k1_segment_len();
@@ -57,51 +54,54 @@ uint64_t max_hash_for(uint32_t scale) {
   return (uint64_t)d;
 }
 
+// where the k-mer stage writes: d_scratch (optional) is two halves of scratch_half words, the counters are per read
+struct KmerOut {
+  uint64_t *d_hashes, *d_scratch;
+  uint64_t scratch_half;
+  int32_t *d_nk_raw, *d_nk1, *d_nk_search, *d_qlen;
+};
+
 // K1 (+K1d): hashes of read i end up at d_hashes[offs[i] + offs2[i] ...], NumKmers in d_nk_search
-int run_kmers(kmcpg_db* db, kmcpg_db::Workspace& W, const uint8_t* d_seqs, const uint64_t* d_offs, const uint8_t* d_seqs2, const uint64_t* d_offs2, uint32_t n_reads,
-              uint32_t max_read_len, const kmcpg_params& p, uint64_t* d_hashes, uint64_t* d_scratch, uint64_t scratch_half, int32_t* d_nk_raw, int32_t* d_nk1,
-              int32_t* d_nk_search, int32_t* d_qlen, hipStream_t st, uint64_t* max_n_out) {
+int run_kmers(kmcpg_db* db, kmcpg_db::Workspace& W, const DeviceBatch& b, const kmcpg_params& p, const KmerOut& o, hipStream_t st, uint64_t* max_n_out) {
   const kmcpg_info& I = db->info;
   if (!I.canonical) return kmcpg_fail(KMCPG_EUNSUPPORTED, "non-canonical index");
   K1Args a{};
-  a.seqs = d_seqs;
-  a.offs = d_offs;
-  a.seqs2 = d_seqs2;
-  a.offs2 = d_offs2;
-  a.n_reads = n_reads;
+  a.seqs = b.d_seqs;
+  a.offs = b.d_offs;
+  a.seqs2 = b.d_seqs2;
+  a.offs2 = b.d_offs2;
+  a.n_reads = b.n_reads;
   a.k = p.k > 0 ? p.k : I.k;
   a.min_qlen = p.min_qlen;
   a.scaled = I.scaled;
   a.max_hash = I.scaled ? max_hash_for(I.scale) : ~0ULL;
   a.mode = I.syncmer ? 2 : (I.minimizer ? 1 : 0);  // syncmer > minimizer > plain (:1052-1058)
   a.w_or_s = I.syncmer ? I.syncmer_s : I.minimizer_w;
-  a.hashes = d_hashes;
-  a.scratch = d_scratch;
-  a.scratch2 = d_scratch ? d_scratch + scratch_half : nullptr;
-  a.nk_raw = d_nk_raw;
-  a.nk1 = d_nk1;
-  a.qlen = d_qlen;
+  a.hashes = o.d_hashes;
+  a.scratch = o.d_scratch;
+  a.scratch2 = o.d_scratch ? o.d_scratch + o.scratch_half : nullptr;
+  a.nk_raw = o.d_nk_raw;
+  a.nk1 = o.d_nk1;
+  a.qlen = o.d_qlen;
   a.flags = getenv("KMCPG_K1_FLAGS") ? atoi(getenv("KMCPG_K1_FLAGS")) : 3;
   // whole genomes (single-end, plain or FracMinHash k-mers): segments of a read on their own workgroups
-  const uint32_t segs = (max_read_len + (uint32_t)k1_segment_len() - 1) / (uint32_t)k1_segment_len();
-  if (a.mode == 0 && !d_seqs2 && segs > 1 && d_scratch && (uint64_t)n_reads * segs <= (1ull << 21)) {  // one workgroup of 1024 threads per segment, < 2^32 threads per launch
-    if (W.w_seg_cnt.ensure(3 * (size_t)n_reads * segs + 2)) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");  // counts + launch_k1's fallback list + its marks
+  const uint32_t segs = (b.max_read_len + (uint32_t)k1_segment_len() - 1) / (uint32_t)k1_segment_len();
+  if (a.mode == 0 && !b.d_seqs2 && segs > 1 && o.d_scratch && (uint64_t)b.n_reads * segs <= (1ull << 21)) {  // one workgroup of 1024 threads per segment, < 2^32 threads per launch
+    if (W.w_seg_cnt.ensure(3 * (size_t)b.n_reads * segs + 2)) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");  // counts + launch_k1's fallback list + its marks
     a.seg_cnt = W.w_seg_cnt.p;
     a.segs_max = segs;
   }
   // A batch that came as 2-bit codes (host.cpp: kmcpg_submit_packed, or text stage() packed): the whole-genome kernel reads the codes as
   // they are, and text exists only for the segments a foreign byte reaches (launch_k1); every other k-mer kernel reads text, expanded
   // here.  (A batch with a run per 4 kb or more is not what the direct form is for: expanded whole.)  KMCPG_K1_CODES=0: always expand.
-  const PackedSrc src = tl_packed_src;
-  tl_packed_src = PackedSrc{};
+  const PackedSrc& src = b.packed;
   // sliding windows (host.cpp kmcpg_submit_windows): every kernel reads a window's bases in place through its view; the codes of such a batch
   // are expanded first (the direct 2-bit form addresses the codes by the batch's own offsets)
-  const WindowSrc win = tl_window;
-  tl_window = WindowSrc{};
+  const WindowSrc& win = b.windows;
   a.src = win.src;
   if (src.codes) {
     static const int codes_mode = getenv("KMCPG_K1_CODES") ? atoi(getenv("KMCPG_K1_CODES")) : 1;  // 2 (tests): however many runs there are
-    const bool direct = codes_mode != 0 && !a.src && a.seg_cnt && a.segs_max > 1 && a.k <= 128 && !(a.flags & 24) && src.text == d_seqs &&
+    const bool direct = codes_mode != 0 && !a.src && a.seg_cnt && a.segs_max > 1 && a.k <= 128 && !(a.flags & 24) && src.text == b.d_seqs &&
                         (codes_mode == 2 || (uint64_t)src.n_exc <= src.n_bases / 4096 + 64);
     if (direct) {
       a.codes = src.codes;
@@ -113,40 +113,40 @@ int run_kmers(kmcpg_db* db, kmcpg_db::Workspace& W, const uint8_t* d_seqs, const
     }
     (direct ? db->k1_codes_direct : db->k1_codes_expanded)++;
   }
-  if (a.mode != 0 && !d_seqs2 && d_scratch) {  // the list the rolling window-sketch kernel leaves to k1_windows_wave (launch_k1): count + read indices
-    if (W.w_seg_cnt.ensure((size_t)n_reads + 2)) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
+  if (a.mode != 0 && !b.d_seqs2 && o.d_scratch) {  // the list the rolling window-sketch kernel leaves to k1_windows_wave (launch_k1): count + read indices
+    if (W.w_seg_cnt.ensure((size_t)b.n_reads + 2)) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
     a.seg_nflag = (uint32_t*)W.w_seg_cnt.p;
     a.seg_list = a.seg_nflag + 1;
   }
-  a.nk_adj = d_nk_search;
+  a.nk_adj = o.d_nk_search;
   a.dedup_threshold = p.dedup_threshold;
   // sliding windows of plain / FracMinHash k-mers: each staged base hashed once, each window's list a run of the slice's kept hashes
   // (KMCPG_WIN_ONCE=0: every window hashed in place, as window sketches always are — their emission at a window's edges is the window's own)
   static const bool win_once = !getenv("KMCPG_WIN_ONCE") || atoi(getenv("KMCPG_WIN_ONCE")) != 0;
   bool adj_done = false;
   // (windows that do not overlap, S >= W, share no k-mer: nothing to hash once, they are read in place)
-  if (win.src && win_once && a.mode == 0 && !d_seqs2 && a.k <= 65 && win.step < win.window) {
+  if (win.src && win_once && a.mode == 0 && !b.d_seqs2 && a.k <= 65 && win.step < win.window) {
     if (W.w_win_h.ensure(win.sb + 1) || W.w_win_kept.ensure(win.sb + 1) || W.w_win_rank.ensure(win.sb + 1) || W.w_win_cnt.ensure(win.n_chunks + 1) ||
         W.w_win_cbase.ensure(win.n_chunks + 1))
       return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
     launch_k1_windows_once(a, win, W.w_win_h.p, W.w_win_kept.p, W.w_win_rank.p, W.w_win_cnt.p, W.w_win_cbase.p, st);
   } else {
-    adj_done = launch_k1(a, max_read_len, st);
+    adj_done = launch_k1(a, b.max_read_len, st);
   }
-  uint64_t ub = max_read_len >= (uint32_t)a.k ? (uint64_t)(max_read_len - a.k + 1) : 0;
-  if (d_seqs2) ub *= 2;
+  uint64_t ub = b.max_read_len >= (uint32_t)a.k ? (uint64_t)(b.max_read_len - a.k + 1) : 0;
+  if (b.d_seqs2) ub *= 2;
   *max_n_out = ub;
   if (ub > (uint64_t)p.dedup_threshold) {
     DedupArgs d{};
-    d.offs = d_offs;
-    d.offs2 = d_offs2;
-    d.n_reads = n_reads;
+    d.offs = b.d_offs;
+    d.offs2 = b.d_offs2;
+    d.n_reads = b.n_reads;
     d.dedup_threshold = p.dedup_threshold;
     d.min_matched = p.min_matched;
-    d.hashes = d_hashes;
-    d.scratch = d_scratch;
-    d.nk_raw = d_nk_raw;
-    d.nk_search = d_nk_search;
+    d.hashes = o.d_hashes;
+    d.scratch = o.d_scratch;
+    d.nk_raw = o.d_nk_raw;
+    d.nk_search = o.d_nk_search;
     d.pre = a.mode != 0;
     d.pre_done = adj_done;
     d.key_shift = (I.scaled && a.max_hash) ? __builtin_clzll(a.max_hash) : 0;
@@ -156,15 +156,15 @@ int run_kmers(kmcpg_db* db, kmcpg_db::Workspace& W, const uint8_t* d_seqs, const
       // sort + unique per such query
       const int32_t thr = std::max<int32_t>((int32_t)HUGE_MIN, p.dedup_threshold);
       uint32_t meta[2] = {0, 0};
-      if (W.w_long_list.ensure(n_reads + 1) || W.w_long_meta.ensure(2)) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
+      if (W.w_long_list.ensure(b.n_reads + 1) || W.w_long_meta.ensure(2)) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
       HIPCHK(hipMemsetAsync(W.w_long_meta.p, 0, 2 * sizeof(uint32_t), st));
-      launch_list_long(d_nk_raw, n_reads, thr, W.w_long_list.p, W.w_long_meta.p, st);
+      launch_list_long(o.d_nk_raw, b.n_reads, thr, W.w_long_list.p, W.w_long_meta.p, st);
       HIPCHK(hipMemcpyAsync(meta, W.w_long_meta.p, sizeof meta, hipMemcpyDeviceToHost, st));
       HIPCHK(hipStreamSynchronize(st));
       if (meta[0]) {
         const size_t tb = huge_dedup_temp_bytes(meta[1]);
         if (W.w_huge_info.ensure(3 * (size_t)meta[0] + 1) || W.w_huge_temp.ensure(tb + 64)) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
-        launch_gather_huge(W.w_long_list.p, meta[0], d_nk_raw, d_offs, d_offs2, W.w_huge_info.p, st);
+        launch_gather_huge(W.w_long_list.p, meta[0], o.d_nk_raw, b.d_offs, b.d_offs2, W.w_huge_info.p, st);
         std::vector<uint64_t> hinfo(3 * (size_t)meta[0]);
         HIPCHK(hipMemcpyAsync(hinfo.data(), W.w_huge_info.p, hinfo.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
@@ -172,13 +172,13 @@ int run_kmers(kmcpg_db* db, kmcpg_db::Workspace& W, const uint8_t* d_seqs, const
         for (uint32_t i = 0; i < meta[0]; i++) {
           const uint32_t r = (uint32_t)hinfo[3 * i], n = (uint32_t)hinfo[3 * i + 1];
           const uint64_t koff = hinfo[3 * i + 2];
-          if (huge_dedup(d_hashes + koff, d_scratch + koff, n, d_num, W.w_huge_temp.p + 64, tb, d_nk_search, r, p.min_matched, st) != 0)
+          if (huge_dedup(o.d_hashes + koff, o.d_scratch + koff, n, d_num, W.w_huge_temp.p + 64, tb, o.d_nk_search, r, p.min_matched, st) != 0)
             return kmcpg_fail(KMCPG_EDEVICE, "device-wide sort of a %u-k-mer query failed", n);
         }
       }
     }
   } else {
-    launch_nk_simple(d_nk_raw, d_nk_search, n_reads, p.min_matched, st);
+    launch_nk_simple(o.d_nk_raw, o.d_nk_search, b.n_reads, p.min_matched, st);
   }
   return 0;
 }
@@ -308,11 +308,11 @@ int fpr_bound(kmcpg_db* db, double max_fpr, uint64_t max_kmers, hipStream_t st, 
 
 }  // namespace
 
-extern "C" int kmcpg_kmers_device(kmcpg_db* db, const uint8_t* d_seqs, const uint64_t* d_offs, uint32_t n_reads, uint64_t total_bases,
-                                  uint32_t max_read_len, const kmcpg_params* params, uint64_t* d_hashes, uint64_t hashes_cap, uint64_t* d_koff,
-                                  int32_t* d_nk, void* stream) {
-  if (!db || !d_seqs || !d_offs || !d_hashes || !d_nk) return kmcpg_fail(KMCPG_EINVAL, "null argument");
-  if (hashes_cap < total_bases) return kmcpg_fail(KMCPG_EINVAL, "hashes_cap must be >= total_bases");
+// the k-mer stage alone on a batch of single reads, text or packed (b.d_seqs = the text, or where its expansion goes)
+static int kmers_device(kmcpg_db* db, const DeviceBatch& b, const kmcpg_params* params, uint64_t* d_hashes, uint64_t hashes_cap, uint64_t* d_koff, int32_t* d_nk,
+                        void* stream) {
+  if (!db || !b.d_seqs || !b.d_offs || !d_hashes || !d_nk) return kmcpg_fail(KMCPG_EINVAL, "null argument");
+  if (hashes_cap < b.total_bases) return kmcpg_fail(KMCPG_EINVAL, "hashes_cap must be >= total_bases");
   std::lock_guard<std::mutex> g(db->mu);
   KMCPG_USE_DEVICE(db);
   const kmcpg_params p = params ? *params : default_params();
@@ -320,18 +320,23 @@ extern "C" int kmcpg_kmers_device(kmcpg_db* db, const uint8_t* d_seqs, const uin
   kmcpg_db::Workspace& W = db->ws[0];
   if (int rc0 = ws_begin(W, st)) return rc0;
   WsGuard wsg{W, st, st};
-  if (W.w_scratch.ensure(2 * total_bases + 2) || W.w_nk_raw.ensure(n_reads + 1) || W.w_nk1.ensure(n_reads + 1)) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
+  if (W.w_scratch.ensure(2 * b.total_bases + 2) || W.w_nk_raw.ensure(b.n_reads + 1) || W.w_nk1.ensure(b.n_reads + 1)) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
   DevBuf<int32_t> ql;
-  if (ql.ensure(n_reads + 1)) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
+  if (ql.ensure(b.n_reads + 1)) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
   uint64_t maxn = 0;
-  int rc = run_kmers(db, W, d_seqs, d_offs, nullptr, nullptr, n_reads, max_read_len, p, d_hashes, W.w_scratch.p, total_bases + 1, W.w_nk_raw.p, W.w_nk1.p,
-                     d_nk, ql.p, st, &maxn);
-  if (rc == 0 && d_koff) HIPCHK(hipMemcpyAsync(d_koff, d_offs, (size_t)n_reads * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
+  int rc = run_kmers(db, W, b, p, KmerOut{d_hashes, W.w_scratch.p, b.total_bases + 1, W.w_nk_raw.p, W.w_nk1.p, d_nk, ql.p}, st, &maxn);
+  if (rc == 0 && d_koff) HIPCHK(hipMemcpyAsync(d_koff, b.d_offs, (size_t)b.n_reads * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
   hipError_t e = hipStreamSynchronize(st);
   ql.release();
   if (rc) return rc;
   if (e != hipSuccess) return kmcpg_fail(KMCPG_EDEVICE, "k-mer kernel failed: %s", hipGetErrorString(e));
   return 0;
+}
+
+extern "C" int kmcpg_kmers_device(kmcpg_db* db, const uint8_t* d_seqs, const uint64_t* d_offs, uint32_t n_reads, uint64_t total_bases,
+                                  uint32_t max_read_len, const kmcpg_params* params, uint64_t* d_hashes, uint64_t hashes_cap, uint64_t* d_koff,
+                                  int32_t* d_nk, void* stream) {
+  return kmers_device(db, DeviceBatch{d_seqs, d_offs, nullptr, nullptr, n_reads, total_bases, max_read_len}, params, d_hashes, hashes_cap, d_koff, d_nk, stream);
 }
 
 extern "C" int kmcpg_kmers_device_packed(kmcpg_db* db, const uint8_t* d_codes, const kmcpg_exc_run* d_exc, uint32_t n_exc, uint8_t* d_text,
@@ -341,16 +346,13 @@ extern "C" int kmcpg_kmers_device_packed(kmcpg_db* db, const uint8_t* d_codes, c
   static_assert(sizeof(kmcpg_exc_run) == sizeof(ExcRun), "one layout");
   if (!d_codes || !d_text || (n_exc && !d_exc)) return kmcpg_fail(KMCPG_EINVAL, "null argument");
   if (((uintptr_t)d_codes & 3) || ((uintptr_t)d_text & 3)) return kmcpg_fail(KMCPG_EINVAL, "d_codes and d_text must be 4-byte aligned");
-  PackedSrc src;
-  src.codes = d_codes;
-  src.exc = reinterpret_cast<const ExcRun*>(d_exc);
-  src.n_exc = n_exc;
-  src.text = d_text;
-  src.n_bases = total_bases;
-  tl_packed_src = src;
-  const int rc = kmcpg_kmers_device(db, d_text, d_offs, n_reads, total_bases, max_read_len, params, d_hashes, hashes_cap, d_koff, d_nk, stream);
-  tl_packed_src = PackedSrc{};  // (a call that failed before the k-mer kernels has not taken it)
-  return rc;
+  DeviceBatch b{d_text, d_offs, nullptr, nullptr, n_reads, total_bases, max_read_len};
+  b.packed.codes = d_codes;
+  b.packed.exc = reinterpret_cast<const ExcRun*>(d_exc);
+  b.packed.n_exc = n_exc;
+  b.packed.text = d_text;
+  b.packed.n_bases = total_bases;
+  return kmers_device(db, b, params, d_hashes, hashes_cap, d_koff, d_nk, stream);
 }
 
 extern "C" int kmcpg_k1_codes_batches(kmcpg_db* db, uint64_t* direct, uint64_t* expanded) {
@@ -364,8 +366,8 @@ extern "C" int kmcpg_k1_codes_batches(kmcpg_db* db, uint64_t* direct, uint64_t* 
 extern "C" int kmcpg_query_device(kmcpg_db* db, const uint8_t* d_seqs, const uint64_t* d_offs, const uint8_t* d_seqs2, const uint64_t* d_offs2,
                                   uint32_t n_reads, uint64_t total_bases, uint32_t max_read_len, const kmcpg_params* params, kmcpg_hit* d_hits,
                                   uint64_t hit_cap, uint64_t* d_counters, int32_t* d_qkmers, int32_t* d_qlen, void* stream) {
-  return kmcpg::query_device_after(db, d_seqs, d_offs, d_seqs2, d_offs2, n_reads, total_bases, max_read_len, params, d_hits, hit_cap, d_counters, d_qkmers, d_qlen,
-                                   stream, nullptr);
+  return kmcpg::query_device_after(db, DeviceBatch{d_seqs, d_offs, d_seqs2, d_offs2, n_reads, total_bases, max_read_len}, params,
+                                   QueryOut{d_hits, hit_cap, d_counters, d_qkmers, d_qlen}, stream, nullptr, nullptr);
 }
 
 // kmcpg_query_device with a prologue that runs once the handle's enqueue lock is held, i.e. right in front of this batch's first kernel.
@@ -373,11 +375,10 @@ extern "C" int kmcpg_query_device(kmcpg_db* db, const uint8_t* d_seqs, const uin
 // land in the kernel stream between the k-mer kernels and the COBS kernel of the batch before — a call that reads a word back in the middle
 // (whole-genome queries) releases nothing until it returns — and the earlier batch's COBS kernel then sat behind the later batch's 4.5-ms
 // upload (profiles/r06_h2h.txt: 2.4 ms of idle GPU per batch of 256 assemblies).
-int kmcpg::query_device_after(kmcpg_db* db, const uint8_t* d_seqs, const uint64_t* d_offs, const uint8_t* d_seqs2, const uint64_t* d_offs2, uint32_t n_reads,
-                              uint64_t total_bases, uint32_t max_read_len, const kmcpg_params* params, kmcpg_hit* d_hits, uint64_t hit_cap, uint64_t* d_counters,
-                              int32_t* d_qkmers, int32_t* d_qlen, void* stream, const std::function<int()>* prologue) {
-  if (!db || !d_seqs || !d_offs || !d_counters || !d_qkmers || !d_qlen || (!d_hits && hit_cap)) return kmcpg_fail(KMCPG_EINVAL, "null argument");
-  if ((d_seqs2 == nullptr) != (d_offs2 == nullptr)) return kmcpg_fail(KMCPG_EINVAL, "seqs2 and offs2 must be given together");
+int kmcpg::query_device_after(kmcpg_db* db, const DeviceBatch& b, const kmcpg_params* params, const QueryOut& out, void* stream,
+                              const std::function<int()>* prologue, int32_t* bound_n) {
+  if (!db || !b.d_seqs || !b.d_offs || !out.d_counters || !out.d_qkmers || !out.d_qlen || (!out.d_hits && out.hit_cap)) return kmcpg_fail(KMCPG_EINVAL, "null argument");
+  if ((b.d_seqs2 == nullptr) != (b.d_offs2 == nullptr)) return kmcpg_fail(KMCPG_EINVAL, "seqs2 and offs2 must be given together");
   std::lock_guard<std::mutex> g(db->mu);
   KMCPG_USE_DEVICE(db);
   if (prologue)
@@ -394,8 +395,8 @@ int kmcpg::query_device_after(kmcpg_db* db, const uint8_t* d_seqs, const uint64_
   static const bool test_hooks = getenv("KMCPG_TEST_HOOKS") && atoi(getenv("KMCPG_TEST_HOOKS")) == 1;
   if (test_hooks)
     if (const char* e = getenv("KMCPG_TEST_MAX_BASES"))
-      if (total_bases > (uint64_t)atoll(e)) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed (KMCPG_TEST_MAX_BASES)");
-  const int slot = pick_slot(db, total_bases, whole_genome_batch(db, max_read_len, d_seqs2 != nullptr));
+      if (b.total_bases > (uint64_t)atoll(e)) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed (KMCPG_TEST_MAX_BASES)");
+  const int slot = pick_slot(db, b.total_bases, whole_genome_batch(db, b.max_read_len, b.d_seqs2 != nullptr));
   db->ws_calls++;
   db->ws_last = slot;
   kmcpg_db::Workspace& W = db->ws[slot];
@@ -418,11 +419,11 @@ int kmcpg::query_device_after(kmcpg_db* db, const uint8_t* d_seqs, const uint64_
   }
   if (int rc0 = ws_begin(W, kst)) return rc0;
   WsGuard wsg{W, st, kst};
-  if (W.w_hashes.ensure(total_bases + 1) || W.w_nk_raw.ensure(n_reads + 1) || W.w_nk1.ensure(n_reads + 1)) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
-  uint64_t ub = max_read_len >= (uint32_t)k_used ? (uint64_t)(max_read_len - k_used + 1) : 0;
-  if (d_seqs2) ub *= 2;
+  if (W.w_hashes.ensure(b.total_bases + 1) || W.w_nk_raw.ensure(b.n_reads + 1) || W.w_nk1.ensure(b.n_reads + 1)) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
+  uint64_t ub = b.max_read_len >= (uint32_t)k_used ? (uint64_t)(b.max_read_len - k_used + 1) : 0;
+  if (b.d_seqs2) ub *= 2;
   const bool window_sketch = db->info.syncmer || db->info.minimizer;
-  if ((ub > (uint64_t)p.dedup_threshold || window_sketch) && W.w_scratch.ensure(2 * total_bases + 2)) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
+  if ((ub > (uint64_t)p.dedup_threshold || window_sketch) && W.w_scratch.ensure(2 * b.total_bases + 2)) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
   uint64_t maxn = 0;
   hipEvent_t* pev = db->ev + 4 * (db->ev_calls % 4);
   if (db->profiling) {
@@ -430,19 +431,18 @@ int kmcpg::query_device_after(kmcpg_db* db, const uint8_t* d_seqs, const uint64_
       if (!ev) HIPCHK(hipEventCreate(&ev));
     HIPCHK(hipEventRecord(pev[0], kst));
   }
-  int rc = run_kmers(db, W, d_seqs, d_offs, d_seqs2, d_offs2, n_reads, max_read_len, p, W.w_hashes.p, W.w_scratch.p, total_bases + 1, W.w_nk_raw.p,
-                     W.w_nk1.p, d_qkmers, d_qlen, kst, &maxn);
+  int rc = run_kmers(db, W, b, p, KmerOut{W.w_hashes.p, W.w_scratch.p, b.total_bases + 1, W.w_nk_raw.p, W.w_nk1.p, out.d_qkmers, out.d_qlen}, kst, &maxn);
   if (rc) return rc;
-  HIPCHK(hipMemsetAsync(d_counters, 0, 2 * sizeof(uint64_t), kst));
-  launch_max_nk(d_qkmers, n_reads, (unsigned long long*)d_counters + 1, kst);
+  HIPCHK(hipMemsetAsync(out.d_counters, 0, 2 * sizeof(uint64_t), kst));
+  launch_max_nk(out.d_qkmers, b.n_reads, (unsigned long long*)out.d_counters + 1, kst);
   if (db->profiling) HIPCHK(hipEventRecord(pev[3], kst));  // k-mers done
   if (k1_own) {
     HIPCHK(hipEventRecord(W.k1_ev, kst));
     HIPCHK(hipStreamWaitEvent(st, W.k1_ev, 0));
   }
   static const int debug_rowsort = getenv("KMCPG_DEBUG_ROWSORT") ? atoi(getenv("KMCPG_DEBUG_ROWSORT")) : 0;
-  if (debug_rowsort && !d_offs2 && !db->h_groupdev.empty())  // experiment only: profiles/r05_rowsort_gate.txt
-    launch_debug_rowsort(W.w_hashes.p, d_offs, d_qkmers, n_reads, db->h_groupdev[0].num_sigs, db->h_groupdev[0].magic_hi, debug_rowsort, st);
+  if (debug_rowsort && !b.d_offs2 && !db->h_groupdev.empty())  // experiment only: profiles/r05_rowsort_gate.txt
+    launch_debug_rowsort(W.w_hashes.p, b.d_offs, out.d_qkmers, b.n_reads, db->h_groupdev[0].num_sigs, db->h_groupdev[0].magic_hi, debug_rowsort, st);
   // long queries (whole genomes, -g) are split into chunks of k-mers so that they spread over the chip; short ones keep
   // the one-wave-per-(query, slot) kernel.  Which queries are long is only known on the device: one small D2H read.
   const char* sm_env = getenv("KMCPG_SPLIT_MIN");
@@ -453,11 +453,11 @@ int kmcpg::query_device_after(kmcpg_db* db, const uint8_t* d_seqs, const uint64_
   // The read-back below costs a host round trip in the middle of the batch (~2.5 ms: more than the kernels of a batch of HiFi
   // reads take).  It is only worth it when splitting could pay: a batch that fills the chip with its (query, slot) pairs anyway
   // and whose queries are bounded by 32 768 k-mers (HiFi reads, contigs) runs the plain kernel on 16 planes without asking.
-  const bool ask = split_min > 0 && maxn > (uint64_t)split_min && (sm_env || maxn > 32768 || (uint64_t)n_reads * total_slots <= 16384);
+  const bool ask = split_min > 0 && maxn > (uint64_t)split_min && (sm_env || maxn > 32768 || (uint64_t)b.n_reads * total_slots <= 16384);
   if (ask) {
-    if (W.w_long_list.ensure(n_reads + 1) || W.w_long_meta.ensure(2)) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
+    if (W.w_long_list.ensure(b.n_reads + 1) || W.w_long_meta.ensure(2)) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
     HIPCHK(hipMemsetAsync(W.w_long_meta.p, 0, 2 * sizeof(uint32_t), st));
-    launch_list_long(d_qkmers, n_reads, split_min, W.w_long_list.p, W.w_long_meta.p, st);
+    launch_list_long(out.d_qkmers, b.n_reads, split_min, W.w_long_list.p, W.w_long_meta.p, st);
     HIPCHK(hipMemcpyAsync(long_meta, W.w_long_meta.p, sizeof long_meta, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
   }
@@ -482,11 +482,11 @@ int kmcpg::query_device_after(kmcpg_db* db, const uint8_t* d_seqs, const uint64_
   K2Args a{};
   a.blocks = db->d_groupdev;
   a.segs = db->d_segs;
-  a.n_reads = n_reads;
+  a.n_reads = b.n_reads;
   a.hashes = W.w_hashes.p;
-  a.offs = d_offs;
-  a.offs2 = d_offs2;
-  a.nk = d_qkmers;
+  a.offs = b.d_offs;
+  a.offs2 = b.d_offs2;
+  a.nk = out.d_qkmers;
   a.min_qcov = p.min_qcov;
   a.min_matched = p.min_matched;
   a.num_hashes = db->info.num_hashes;
@@ -521,12 +521,11 @@ int kmcpg::query_device_after(kmcpg_db* db, const uint8_t* d_seqs, const uint64_
     HIPCHK(hipMemsetAsync(W.w_gathered.p, 0, (size_t)K2_GATHER_SLOTS * 16 * sizeof(uint64_t), st));
     a.gathered = (unsigned long long*)W.w_gathered.p;
   }
-  tl_query_bound_n = 0;
   if (int rcb = fpr_bound(db, p.max_fpr, max_short, st, &a.cmin_fpr, &a.cmin_fpr_n)) return rcb;
-  tl_query_bound_n = a.cmin_fpr ? a.cmin_fpr_n : 0;  // both kernel forms apply the table to every query of up to this many k-mers
-  a.hits = d_hits;
-  a.hit_cap = hit_cap;
-  a.counter = (unsigned long long*)d_counters;
+  if (bound_n) *bound_n = a.cmin_fpr ? a.cmin_fpr_n : 0;  // both kernel forms apply the table to every query of up to this many k-mers
+  a.hits = out.d_hits;
+  a.hit_cap = out.hit_cap;
+  a.counter = (unsigned long long*)out.d_counters;
   // COBS kernels one batch at a time (the k-mer kernels above may have run beside the previous batch's)
   // (KMCPG_COBS_CHAIN=0, experiment with two kernel streams + two workspace slots: the next batch's COBS kernel may start in the previous
   // one's ragged end — nothing is shared between them but the read-only index; their HIP-event durations then overlap)
@@ -695,8 +694,8 @@ extern "C" int kmcpg_plant_reads_device(kmcpg_db* db, const uint8_t* d_seqs, con
   p.dedup_threshold = 0x7fffffff;  // plant every k-mer occurrence (idempotent)
   uint64_t maxn = 0;
   if ((db->info.syncmer || db->info.minimizer) && W.w_scratch.ensure(2 * total_bases + 2)) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
-  int rc = run_kmers(db, W, d_seqs, d_offs, nullptr, nullptr, n_reads, max_read_len, p, W.w_hashes.p, W.w_scratch.p, total_bases + 1, W.w_nk_raw.p,
-                     W.w_nk1.p, tmp.p, tmp.p + n_reads + 1, st, &maxn);
+  int rc = run_kmers(db, W, DeviceBatch{d_seqs, d_offs, nullptr, nullptr, n_reads, total_bases, max_read_len}, p,
+                     KmerOut{W.w_hashes.p, W.w_scratch.p, total_bases + 1, W.w_nk_raw.p, W.w_nk1.p, tmp.p, tmp.p + n_reads + 1}, st, &maxn);
   if (rc == 0)
     launch_plant_reads(db->d_blockdev, (uint32_t)db->h_blockdev.size(), db->info.num_hashes, W.w_hashes.p, d_offs, W.w_nk_raw.p, d_cols, n_reads, st);
   hipError_t e = hipStreamSynchronize(st);
