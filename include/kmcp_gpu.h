@@ -350,6 +350,22 @@ int kmcpg_last_hash_bytes(kmcpg_db* db, uint64_t* bytes);
 /* ... and how many waves of those launches finished in tail mode (long queries on 1-KiB row tiles whose sectors had died down
  * to at most four: the idle lanes take shares of the remaining rows, k2_cobs.hip; KMCPG_TAIL_SECTORS=0 switches it off).  Level 2 only. */
 int kmcpg_last_tail_waves(kmcpg_db* db, uint64_t* waves);
+/* Which COBS kernels the last kmcpg_query_device call launched, one record per launch in launch order (a form launched several
+ * times in one call appears as often), written where the kernel is launched from the template parameters of that kernel.  Tests
+ * use it to assert which instantiation served a batch.  kind: 0 = k2_cobs, 1 = its chunked long-query form, 2 = k2_cobs_pair
+ * (two lane forms in one grid: lpr lanes + lprb lanes).  Profiling level >= 1; the log is cleared at the start of every call. */
+typedef struct {
+  int32_t kind;
+  int32_t lpr;        /* lanes per row tile: 4, 8, 16, 32, 64 */
+  int32_t lprb;       /* kind 2: lanes of the second form; otherwise 0 */
+  int32_t npl;        /* counter planes: 8, 10, 16, 24 */
+  int32_t multi;      /* 1 = the several-hash-functions form */
+  int32_t group_rows; /* rows between two pruning tests: 8 or 4 */
+  uint32_t workgroups;
+  uint32_t reserved;
+} kmcpg_k2_launch;
+/* Copies up to `cap` records to out (may be NULL when cap is 0); *n = how many launches the call made. */
+int kmcpg_last_k2_launches(kmcpg_db* db, kmcpg_k2_launch* out, uint32_t cap, uint32_t* n);
 int kmcpg_last_timing(kmcpg_db* db, float* kmers_ms, float* cobs_ms);
 /* The same for an earlier call: age 0 = the last one, 1 = the one before ... (the last 4 are kept), so that a caller with
  * several batches in flight can read the times of a finished one without waiting for the newest. */

@@ -182,6 +182,7 @@ struct kmcpg_db {
   uint64_t paged_reserve = 0;  // HBM plan_passes() kept free beside the largest shard: what a batch's workspace may take
   // optional HIP-event timing of the last kmcpg_query_device call
   int profiling = 0;  // 1: HIP-event timing of the kernels; 2: + count the row loads k2_cobs issues
+  std::vector<kmcpg_k2_launch> k2_log;  // the COBS kernels the last kmcpg_query_device call launched (profiling >= 1; kmcpg_last_k2_launches)
   // K3 (device half of finalize): Header.Sizes of every global column on the device, per-read counters and scan scratch
   uint64_t* d_col_size = nullptr;
   kmcpg::DevBuf<uint32_t> w_fin_cnt;

@@ -108,8 +108,35 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((NPL =
 
 constexpr uint64_t K2_MAX_BLOCKS = 1ull << 23;  // x 256 threads = 2^31
 
+// Every K2 kernel is launched by launch_k2_form or launch_k2_pair_form and nowhere else: the kernel's template arguments are the
+// function's own, so the record a launch leaves in the log (kmcpg_last_k2_launches) cannot name another form than the one that ran.
+static void note_k2(K2Log* log, int kind, int lpr, int lprb, int npl, bool multi, int gr, unsigned nb) {
+  if (!log) return;
+  kmcpg_k2_launch r{};
+  r.kind = kind;
+  r.lpr = lpr;
+  r.lprb = lprb;
+  r.npl = npl;
+  r.multi = multi ? 1 : 0;
+  r.group_rows = gr;
+  r.workgroups = nb;
+  log->push_back(r);
+}
+
+template <int LPR, int NPL, bool MULTI, bool SPLIT, int GR>
+static void launch_k2_form(const K2Args& b, unsigned nb, hipStream_t st, K2Log* log) {
+  hipLaunchKernelGGL((k2_cobs<LPR, NPL, MULTI, SPLIT, GR>), dim3(nb), dim3(256), 0, st, b);
+  note_k2(log, SPLIT ? 1 : 0, LPR, 0, NPL, MULTI, GR, nb);
+}
+
+template <int LPRA, int LPRB, int NPL, bool MULTI>
+static void launch_k2_pair_form(const K2Args& a, const K2Args& b, unsigned nba, unsigned nbb, hipStream_t st, K2Log* log) {
+  hipLaunchKernelGGL((k2_cobs_pair<LPRA, LPRB, NPL, MULTI>), dim3(nba + nbb), dim3(256), 0, st, a, b, nba);
+  note_k2(log, 2, LPRA, LPRB, NPL, MULTI, 8, nba + nbb);  // both halves are k2_body<..., 8>
+}
+
 template <int LPR, int NPL>
-static void launch_k2_t(const K2Args& a, bool multi, hipStream_t st) {
+static void launch_k2_t(const K2Args& a, bool multi, hipStream_t st, K2Log* log) {
   constexpr int G = 64 / LPR;
   const uint64_t units = (G > 1 && a.slot_major == 2) ? (uint64_t)a.n_reads * (((uint64_t)a.nslots + G - 1) / G) * G : (uint64_t)a.n_reads * a.nslots;
   const uint64_t waves = (units + G - 1) / G;
@@ -120,35 +147,35 @@ static void launch_k2_t(const K2Args& a, bool multi, hipStream_t st) {
     b.unit_base = b0 * 4 * G;
     if (NPL <= 10 && a.group_rows == 4) {
       if (multi)
-        hipLaunchKernelGGL((k2_cobs<LPR, NPL <= 10 ? NPL : 8, true, false, 4>), dim3(nb), dim3(256), 0, st, b);
+        launch_k2_form<LPR, NPL <= 10 ? NPL : 8, true, false, 4>(b, nb, st, log);
       else
-        hipLaunchKernelGGL((k2_cobs<LPR, NPL <= 10 ? NPL : 8, false, false, 4>), dim3(nb), dim3(256), 0, st, b);
+        launch_k2_form<LPR, NPL <= 10 ? NPL : 8, false, false, 4>(b, nb, st, log);
     } else if (multi)
-      hipLaunchKernelGGL((k2_cobs<LPR, NPL, true, false>), dim3(nb), dim3(256), 0, st, b);
+      launch_k2_form<LPR, NPL, true, false, 8>(b, nb, st, log);
     else
-      hipLaunchKernelGGL((k2_cobs<LPR, NPL, false, false>), dim3(nb), dim3(256), 0, st, b);
+      launch_k2_form<LPR, NPL, false, false, 8>(b, nb, st, log);
   }
 }
 
 template <int LPR>
-static int launch_k2_l(const K2Args& a, int npl, bool multi, hipStream_t st) {
+static int launch_k2_l(const K2Args& a, int npl, bool multi, hipStream_t st, K2Log* log) {
   switch (npl) {
-    case 8: launch_k2_t<LPR, 8>(a, multi, st); return 0;
-    case 10: launch_k2_t<LPR, 10>(a, multi, st); return 0;
-    case 16: launch_k2_t<LPR, 16>(a, multi, st); return 0;
-    case 24: launch_k2_t<LPR, 24>(a, multi, st); return 0;
+    case 8: launch_k2_t<LPR, 8>(a, multi, st, log); return 0;
+    case 10: launch_k2_t<LPR, 10>(a, multi, st, log); return 0;
+    case 16: launch_k2_t<LPR, 16>(a, multi, st, log); return 0;
+    case 24: launch_k2_t<LPR, 24>(a, multi, st, log); return 0;
     default: return -1;
   }
 }
 
-int launch_k2(const K2Args& a, int lpr, int npl, hipStream_t st) {
+int launch_k2(const K2Args& a, int lpr, int npl, hipStream_t st, K2Log* log) {
   const bool multi = a.num_hashes > 1;
   switch (lpr) {
-    case 4: return launch_k2_l<4>(a, npl, multi, st);
-    case 8: return launch_k2_l<8>(a, npl, multi, st);
-    case 16: return launch_k2_l<16>(a, npl, multi, st);
-    case 32: return launch_k2_l<32>(a, npl, multi, st);
-    case 64: return launch_k2_l<64>(a, npl, multi, st);
+    case 4: return launch_k2_l<4>(a, npl, multi, st, log);
+    case 8: return launch_k2_l<8>(a, npl, multi, st, log);
+    case 16: return launch_k2_l<16>(a, npl, multi, st, log);
+    case 32: return launch_k2_l<32>(a, npl, multi, st, log);
+    case 64: return launch_k2_l<64>(a, npl, multi, st, log);
     default: return -1;
   }
 }
@@ -161,33 +188,33 @@ static uint64_t k2_blocks(const K2Args& a, int lpr) {
 }
 
 template <int LPRB, int NPL>
-static int launch_k2_pair_t(const K2Args& a, const K2Args& b, bool multi, hipStream_t st) {
+static int launch_k2_pair_t(const K2Args& a, const K2Args& b, bool multi, hipStream_t st, K2Log* log) {
   const uint64_t nba = k2_blocks(a, 64), nbb = k2_blocks(b, LPRB);
   if (nba == 0 || nbb == 0 || nba + nbb > K2_MAX_BLOCKS) return -1;
   K2Args a0 = a, b0 = b;
   a0.unit_base = b0.unit_base = 0;
   if (multi)
-    hipLaunchKernelGGL((k2_cobs_pair<64, LPRB, NPL, true>), dim3((unsigned)(nba + nbb)), dim3(256), 0, st, a0, b0, (unsigned)nba);
+    launch_k2_pair_form<64, LPRB, NPL, true>(a0, b0, (unsigned)nba, (unsigned)nbb, st, log);
   else
-    hipLaunchKernelGGL((k2_cobs_pair<64, LPRB, NPL, false>), dim3((unsigned)(nba + nbb)), dim3(256), 0, st, a0, b0, (unsigned)nba);
+    launch_k2_pair_form<64, LPRB, NPL, false>(a0, b0, (unsigned)nba, (unsigned)nbb, st, log);
   return 0;
 }
 
 // the 64-lane form (args a) and a narrower one (args b, lane form lprb) of the same batch in one grid; -1: not a pair this file has a kernel for
-int launch_k2_pair(const K2Args& a, const K2Args& b, int lprb, int npl, hipStream_t st) {
+int launch_k2_pair(const K2Args& a, const K2Args& b, int lprb, int npl, hipStream_t st, K2Log* log) {
   const bool multi = a.num_hashes > 1;
   if (npl != 16 || (a.group_rows == 4)) return -1;
   switch (lprb) {
-    case 32: return launch_k2_pair_t<32, 16>(a, b, multi, st);
-    case 16: return launch_k2_pair_t<16, 16>(a, b, multi, st);
-    case 8: return launch_k2_pair_t<8, 16>(a, b, multi, st);
-    case 4: return launch_k2_pair_t<4, 16>(a, b, multi, st);
+    case 32: return launch_k2_pair_t<32, 16>(a, b, multi, st, log);
+    case 16: return launch_k2_pair_t<16, 16>(a, b, multi, st, log);
+    case 8: return launch_k2_pair_t<8, 16>(a, b, multi, st, log);
+    case 4: return launch_k2_pair_t<4, 16>(a, b, multi, st, log);
     default: return -1;
   }
 }
 
 template <int LPR>
-static void launch_k2_split_t(const K2Args& a, bool multi, hipStream_t st) {
+static void launch_k2_split_t(const K2Args& a, bool multi, hipStream_t st, K2Log* log) {
   constexpr int G = 64 / LPR;
   const uint64_t units = (uint64_t)a.n_long * a.nslots * a.split_chunks;
   const uint64_t blocks = ((units + G - 1) / G + 3) / 4;
@@ -196,20 +223,20 @@ static void launch_k2_split_t(const K2Args& a, bool multi, hipStream_t st) {
     const unsigned nb = (unsigned)std::min<uint64_t>(K2_MAX_BLOCKS, blocks - b0);
     b.unit_base = b0 * 4 * G;
     if (multi)
-      hipLaunchKernelGGL((k2_cobs<LPR, 16, true, true>), dim3(nb), dim3(256), 0, st, b);
+      launch_k2_form<LPR, 16, true, true, 8>(b, nb, st, log);
     else
-      hipLaunchKernelGGL((k2_cobs<LPR, 16, false, true>), dim3(nb), dim3(256), 0, st, b);
+      launch_k2_form<LPR, 16, false, true, 8>(b, nb, st, log);
   }
 }
 
-int launch_k2_split(const K2Args& a, int lpr, hipStream_t st) {
+int launch_k2_split(const K2Args& a, int lpr, hipStream_t st, K2Log* log) {
   const bool multi = a.num_hashes > 1;
   switch (lpr) {
-    case 4: launch_k2_split_t<4>(a, multi, st); return 0;
-    case 8: launch_k2_split_t<8>(a, multi, st); return 0;
-    case 16: launch_k2_split_t<16>(a, multi, st); return 0;
-    case 32: launch_k2_split_t<32>(a, multi, st); return 0;
-    case 64: launch_k2_split_t<64>(a, multi, st); return 0;
+    case 4: launch_k2_split_t<4>(a, multi, st, log); return 0;
+    case 8: launch_k2_split_t<8>(a, multi, st, log); return 0;
+    case 16: launch_k2_split_t<16>(a, multi, st, log); return 0;
+    case 32: launch_k2_split_t<32>(a, multi, st, log); return 0;
+    case 64: launch_k2_split_t<64>(a, multi, st, log); return 0;
     default: return -1;
   }
 }

@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <vector>
+
 #include "common.hpp"
 
 namespace kmcpg {
@@ -10,12 +12,15 @@ bool launch_k1(const K1Args& a, uint32_t max_read_len, hipStream_t st);  // true
 int k1_segment_len();  // positions per workgroup on the whole-genome path
 void launch_nk_simple(const int32_t* nk_raw, int32_t* nk_search, uint32_t n, int32_t min_matched, hipStream_t st);
 void launch_dedup(DedupArgs a, uint64_t max_n, hipStream_t st);  // queries above HUGE_MIN are left to huge_dedup
+// what the K2 launchers note about every kernel they launch (kmcpg_last_k2_launches): written at the launch site from the template
+// parameters of the kernel launched.  nullptr = no log
+typedef std::vector<kmcpg_k2_launch> K2Log;
 // lpr in {4,8,16,32,64}: lanes per row tile; npl in {8,10,16,24}: counter planes.  <0 on bad arguments.
-int launch_k2(const K2Args& a, int lpr, int npl, hipStream_t st);
+int launch_k2(const K2Args& a, int lpr, int npl, hipStream_t st, K2Log* log);
 // two lane forms in one grid (long queries: the 64-lane tiles + the remainder's form); -1 when there is no such kernel: launch them one by one
-int launch_k2_pair(const K2Args& a64, const K2Args& b, int lprb, int npl, hipStream_t st);
+int launch_k2_pair(const K2Args& a64, const K2Args& b, int lprb, int npl, hipStream_t st, K2Log* log);
 // long queries: chunked counting into a.long_counts, then one thresholding pass
-int launch_k2_split(const K2Args& a, int lpr, hipStream_t st);
+int launch_k2_split(const K2Args& a, int lpr, hipStream_t st, K2Log* log);
 void launch_list_long(const int32_t* nk, uint32_t n_reads, int32_t split_min, uint32_t* list, uint32_t* meta, hipStream_t st);
 void launch_threshold_long(const K2Args& a, hipStream_t st);
 // K3: group + filter + order the hit list on the device (k3_finalize.hip); hits_hint = expected number of hits (grid sizing), 0 = hit_cap

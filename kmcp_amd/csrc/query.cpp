@@ -399,6 +399,8 @@ int kmcpg::query_device_after(kmcpg_db* db, const DeviceBatch& b, const kmcpg_pa
   const int slot = pick_slot(db, b.total_bases, whole_genome_batch(db, b.max_read_len, b.d_seqs2 != nullptr));
   db->ws_calls++;
   db->ws_last = slot;
+  db->k2_log.clear();
+  K2Log* const k2_log = db->profiling >= 1 ? &db->k2_log : nullptr;  // the launchers write it (k2_cobs.hip), kmcpg_last_k2_launches reads it
   kmcpg_db::Workspace& W = db->ws[slot];
   // experiment (KMCPG_K1_STREAM=1): the k-mer kernels on a high-priority stream of the handle's own, so that their workgroups are
   // dispatched AHEAD of the previous batch's COBS workgroups whenever a slot frees up (on equal terms the dispatcher keeps feeding the
@@ -541,13 +543,13 @@ int kmcpg::query_device_after(kmcpg_db* db, const DeviceBatch& b, const kmcpg_pa
     a1.nslots = (uint32_t)db->classes[0].slots.size();
     b1.slots = db->classes[1].d_slots;
     b1.nslots = (uint32_t)db->classes[1].slots.size();
-    paired = launch_k2_pair(a1, b1, db->classes[1].lpr, npl, st) == 0;
+    paired = launch_k2_pair(a1, b1, db->classes[1].lpr, npl, st, k2_log) == 0;
   }
   for (const auto& c : db->classes) {
     if (paired) break;
     a.slots = c.d_slots;
     a.nslots = (uint32_t)c.slots.size();
-    if (launch_k2(a, c.lpr, npl, st) != 0) return kmcpg_fail(KMCPG_EINVAL, "batch too large for one launch: split it");
+    if (launch_k2(a, c.lpr, npl, st, k2_log) != 0) return kmcpg_fail(KMCPG_EINVAL, "batch too large for one launch: split it");
   }
   if (n_long) {
     a.ncols_total = (uint32_t)db->info.n_cols;
@@ -568,7 +570,7 @@ int kmcpg::query_device_after(kmcpg_db* db, const DeviceBatch& b, const kmcpg_pa
       for (const auto& c : db->classes) {
         a.slots = c.d_slots;
         a.nslots = (uint32_t)c.slots.size();
-        if (launch_k2_split(a, c.lpr, st) != 0) return kmcpg_fail(KMCPG_EINVAL, "batch too large for one launch: split it");
+        if (launch_k2_split(a, c.lpr, st, k2_log) != 0) return kmcpg_fail(KMCPG_EINVAL, "batch too large for one launch: split it");
       }
       launch_threshold_long(a, st);
     }
@@ -658,6 +660,18 @@ static int read_gather_slots(kmcpg_db* db, int word, uint64_t unit, uint64_t* by
 extern "C" int kmcpg_last_gathered_bytes(kmcpg_db* db, uint64_t* bytes) { return read_gather_slots(db, 0, 16, bytes); }
 extern "C" int kmcpg_last_hash_bytes(kmcpg_db* db, uint64_t* bytes) { return read_gather_slots(db, 1, 8, bytes); }
 extern "C" int kmcpg_last_tail_waves(kmcpg_db* db, uint64_t* waves) { return read_gather_slots(db, 2, 1, waves); }
+
+extern "C" int kmcpg_last_k2_launches(kmcpg_db* db, kmcpg_k2_launch* out, uint32_t cap, uint32_t* n) {
+  static_assert(sizeof(kmcpg_k2_launch) == 32, "eight 4-byte words");
+  if (!db || !n || (cap && !out)) return kmcpg_fail(KMCPG_EINVAL, "null argument");
+  std::lock_guard<std::mutex> g(db->mu);
+  if (db->profiling < 1) return kmcpg_fail(KMCPG_EINVAL, "no kmcpg_query_device call at profiling level >= 1 yet");
+  // the records are written while the call enqueues its kernels: nothing to wait for
+  const size_t m = std::min<size_t>(cap, db->k2_log.size());
+  if (m) memcpy(out, db->k2_log.data(), m * sizeof(kmcpg_k2_launch));
+  *n = (uint32_t)db->k2_log.size();
+  return 0;
+}
 
 extern "C" int kmcpg_timing_at(kmcpg_db* db, uint32_t age, float* kmers_ms, float* cobs_ms) {
   if (!db) return kmcpg_fail(KMCPG_EINVAL, "null argument");

@@ -15,7 +15,7 @@ EXPORTS = [
     "kmcpg_open", "kmcpg_close", "kmcpg_last_error", "kmcpg_db_info", "kmcpg_col_info", "kmcpg_search_batch",
     "kmcpg_result_free", "kmcpg_query_device", "kmcpg_finalize", "kmcpg_open_synthetic", "kmcpg_plant",
     "kmcpg_read_rows", "kmcpg_block_info", "kmcpg_kmers_device", "kmcpg_plant_reads_device", "kmcpg_set_profiling",
-    "kmcpg_last_timing", "kmcpg_open_devices", "kmcpg_build_db", "kmcpg_submit", "kmcpg_wait", "kmcpg_read_row_range", "kmcpg_timing_at", "kmcpg_last_gathered_bytes", "kmcpg_last_hash_bytes", "kmcpg_last_tail_waves",
+    "kmcpg_last_timing", "kmcpg_open_devices", "kmcpg_build_db", "kmcpg_submit", "kmcpg_wait", "kmcpg_read_row_range", "kmcpg_timing_at", "kmcpg_last_gathered_bytes", "kmcpg_last_hash_bytes", "kmcpg_last_tail_waves", "kmcpg_last_k2_launches",
     "kmcpg_db_ks", "kmcpg_open_paged", "kmcpg_paged_info", "kmcpg_exchange_info", "kmcpg_batch_hint", "kmcpg_group_device", "kmcpg_finalize_grouped",
     "kmcpg_search_batch_pairs", "kmcpg_wait_pairs", "kmcpg_result_pairs_free", "kmcpg_expand_pairs", "kmcpg_save_db",
     "kmcpg_pack2", "kmcpg_unpack2", "kmcpg_submit_packed", "kmcpg_host_alloc", "kmcpg_host_free",
@@ -125,6 +125,15 @@ class WindowSpec(C.Structure):
     _fields_ = [("step", C.c_uint64), ("window", C.c_uint64), ("greedy", C.c_int32), ("reserved", C.c_int32)]
 
 
+class K2Launch(C.Structure):
+    """kmcpg_k2_launch: one COBS kernel launch of a query_device call"""
+    _fields_ = [("kind", C.c_int32), ("lpr", C.c_int32), ("lprb", C.c_int32), ("npl", C.c_int32), ("multi", C.c_int32),
+                ("group_rows", C.c_int32), ("workgroups", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+K2_KINDS = ("plain", "split", "pair")
+
+
 class SynthSpec(C.Structure):
     _fields_ = [("k", C.c_int32), ("num_hashes", C.c_int32), ("fpr", C.c_double), ("n_blocks", C.c_uint32),
                 ("cols_per_block", C.c_uint32), ("num_sigs", C.c_uint64), ("kmers_per_col", C.c_uint64), ("seed", C.c_uint64),
@@ -228,6 +237,7 @@ def load():
     L.kmcpg_last_gathered_bytes.argtypes = [vp, u64p]
     L.kmcpg_last_tail_waves.argtypes = [vp, u64p]
     L.kmcpg_last_hash_bytes.argtypes = [vp, u64p]
+    L.kmcpg_last_k2_launches.argtypes = [vp, C.POINTER(K2Launch), C.c_uint32, C.POINTER(C.c_uint32)]
     L.kmcpg_timing_at.argtypes = [vp, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.kmcpg_build_db.argtypes = [C.c_char_p, C.POINTER(BuildCfg), C.POINTER(BuildCol), C.c_uint32, C.c_int32]
     L.kmcpg_save_db.argtypes = [vp, C.c_char_p]
@@ -670,6 +680,15 @@ class Database:
         n = C.c_uint64()
         _check(load().kmcpg_last_tail_waves(self._h, C.byref(n)))
         return n.value
+
+    def last_k2_launches(self):
+        """The COBS kernels the last query_device call launched, in launch order (profiling level >= 1): tuples
+        (kind, lpr, lprb, npl, multi, group_rows, workgroups) with kind in K2_KINDS; lprb is 0 unless kind == "pair"."""
+        n = C.c_uint32(0)
+        _check(load().kmcpg_last_k2_launches(self._h, None, 0, C.byref(n)))
+        buf = (K2Launch * max(1, n.value))()
+        _check(load().kmcpg_last_k2_launches(self._h, buf, n.value, C.byref(n)))
+        return [(K2_KINDS[r.kind], r.lpr, r.lprb, r.npl, bool(r.multi), r.group_rows, r.workgroups) for r in buf[:n.value]]
 
     def last_hash_bytes(self):
         """Bytes of k-mer hashes the COBS kernel(s) of the last query_device call read (profiling level 2)."""

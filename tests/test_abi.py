@@ -33,6 +33,7 @@ def test_struct_layouts_match_header(L):
     assert C.sizeof(L.Opts) == 16
     assert C.sizeof(L.Params) == 64
     assert C.sizeof(L.SynthSpec) == 64
+    assert C.sizeof(L.K2Launch) == 32
 
 
 def test_no_cpu_fallback(L, tmp_path):
