@@ -64,16 +64,19 @@ struct K1Args {
   int32_t* nk_raw;       // k-mers emitted for read i (both mates)
   int32_t* nk1;          // k-mers emitted for mate 1 (for --try-se)
   int32_t* qlen;
-  int32_t* seg_cnt;      // whole-genome path: kept hashes per (read, segment), n_reads * segs_max entries; else nullptr
+  // K1's side buffer (K1Plan's regions; query.cpp run_kmers places all four, nullptr where the plan has none)
+  int32_t* seg_cnt;      // whole genomes: kept hashes per (read, segment), n_reads * segs_max entries
   uint32_t segs_max;
   // window sketches of long reads (k1_kmers_wg<1|2>): emissions without adjacent repeats go to scratch[], their number here
   // (queries above max(dedup_threshold, 512) emissions; the others keep their raw emissions in hashes[]); nullptr = raw only
   int32_t* nk_adj;
   int32_t dedup_threshold;
-  int32_t flags;         // experiments (KMCPG_K1_FLAGS): bit 0 = two-level window arg-min, bit 1 = fused adjacent-repeat filter
-  uint32_t* seg_list;    // ... the segments k1_seg_roll2 left to the byte kernel, and how many (launch_k1 places both behind seg_cnt[])
+  int32_t flags;         // experiments (KMCPG_K1_FLAGS, the K1F_ bits of k1_plan.hpp)
+  // the list a kernel leaves to the one launched behind it, and its length: whole genomes — the (read, segment) numbers k1_seg_roll2 could
+  // not take (seg_cnt == -1), for k1_seg_roll; closed syncmers of long reads — the reads k1_windows_roll could not take, for k1_windows_wave
+  uint32_t* seg_list;
   uint32_t* seg_nflag;
-  int32_t seg_only_flagged;  // k1_seg_roll as the fallback of k1_seg_roll2: only the segments that kernel marked (seg_cnt == -1)
+  int32_t seg_only_flagged;  // k1_seg_roll / k1_windows_wave as that second kernel: a small grid walks the list (0: the whole batch, no list)
   // whole genomes that arrived as 2-bit codes (kmcpg_submit_packed / a batch stage() packed): k1_seg_roll2 takes its codes from the packed
   // stream as it is — base j of the batch in bits 2 (j % 4) of byte j / 4 — and only the segments a run of foreign bytes reaches are expanded
   // to text (seqs_w = the buffer `seqs` points at) for the byte kernel.  nullptr: `seqs` holds the text already.

@@ -15,6 +15,7 @@
 #include "../../include/kmcp_gpu.h"
 #include "common.hpp"
 #include "dbformat.hpp"
+#include "k1_plan.hpp"
 #include "fpr.hpp"
 
 // error sink: sets the thread-local message behind kmcpg_last_error() and returns `code`
@@ -261,9 +262,10 @@ int finalize_grouped_trusted(const kmcpg_db* db, const kmcpg_pair* pairs, const 
 // applied on the device, whichever kernel form served it (0: no bound table in that call).  query_device_after reports the value of its
 // call; host.cpp keeps it with the batch (Lane::bound_n) and hands it to the finalizer, which takes a compact segment as final only for
 // n <= bound_n — it does not look at the environment again.
-// batches of whole genomes (segment path of the k-mer stage): the ones whose k-mer kernels run beside the previous batch's COBS kernel by
-// default — second workspace slot (query.cpp pick_slot) and second kernel stream (host.cpp enqueue; bench.py does the same with its streams)
-bool whole_genome_batch(const kmcpg_db* db, uint32_t max_read_len, bool paired);
+inline int k1_mode(const kmcpg_info& I) { return I.syncmer ? 2 : (I.minimizer ? 1 : 0); }  // syncmer > minimizer > plain (util-db-search.go:1052-1058)
+// batches of whole genomes (segment forms of the k-mer stage, k1_plan.hpp): the ones whose k-mer kernels run beside the previous batch's COBS
+// kernel by default — second workspace slot (query.cpp pick_slot) and second kernel stream (host.cpp enqueue; bench.py does the same with its streams)
+bool whole_genome_batch(const kmcpg_db* db, uint32_t max_read_len, bool paired);  // k1_whole_genomes (k1_plan.hpp) of the handle's database
 // KMCPG_FPR_BOUND (default on): K2 leaves out counts that cannot pass -f for queries of up to 512 (1024) k-mers (query.cpp fpr_bound)
 inline bool fpr_bound_enabled() {
   const char* e = getenv("KMCPG_FPR_BOUND");

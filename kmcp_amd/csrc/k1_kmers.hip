@@ -10,6 +10,7 @@
 
 #include "common.hpp"
 #include "device_utils.hpp"
+#include "k1_plan.hpp"
 #include "kernels.hpp"
 
 namespace kmcpg {
@@ -48,7 +49,6 @@ struct WTile {
   uint64_t ip, iq;  // inclusive prefixes P(e+1), Q(e+1) at this lane's base e
   uint64_t xp, xq;  // this base's own terms
 };
-constexpr int K1_SCAN_MAX_K = 65;  // a k-mer may reach into the next tile only
 
 __device__ __forceinline__ WTile wave_tile(const uint8_t* __restrict__ s, int len, int e0, const uint64_t* tab, uint64_t& cp, uint64_t& cq, int lane) {
   const int e = e0 + lane;
@@ -285,7 +285,7 @@ __global__ void __launch_bounds__(256) k1_kmers(const K1Args a) {
 
 // ---- long queries (HiFi reads, -g whole genomes): one 1024-thread workgroup per read -------------------------
 constexpr int K1WG = 1024;
-constexpr int K1_WAVE_SORT_CAP = DEDUP_WAVE_CAP;  // (kernels.hpp)
+static_assert(K1_WAVE_SORT_CAP == DEDUP_WAVE_CAP, "k1_plan.hpp restates kernels.hpp");
 
 // ordered compaction of one tile of K1WG candidates into out[cnt...]; returns the new (uniform) count
 __device__ __forceinline__ int wg_compact(bool keep, uint64_t h, uint64_t* __restrict__ out, int cnt, int* s_wave, int tid) {
@@ -381,7 +381,6 @@ __device__ __forceinline__ int wg_sketch_mate(const K1Args& a, int mode, const u
 // built in LDS by wave scans + a scan of the 64-base group totals, after which any k-mer or s-mer hash of the tile costs
 // four LDS reads; the window scans never go to global memory.  Usable while the halo fits (L = 2k-s-1 <= 512 for syncmers,
 // w < 512 for minimizers); otherwise the scratch-buffer version above is used.
-constexpr int K1H = 512;
 constexpr int K1CAP = 2 * K1WG;  // bases per tile: 1024 positions + a halo of at most 1024
 struct K1Lds {
   uint64_t ip[K1CAP + 1];                   // ip[n] = P(n) = XOR_{m<n} ror(F[m], m) over the tile's bases, ip[0] = 0
@@ -559,13 +558,6 @@ __device__ __forceinline__ int wg_compact_adj(bool keep, uint64_t h, uint64_t* _
 // positions per tile: with a small halo the tile shrinks so that positions + halo fit one scan round of K1WG bases
 __device__ __forceinline__ int wg_tile_step(int halo) { return halo <= K1WG / 2 ? K1WG - halo : K1WG; }
 
-__host__ __device__ __forceinline__ bool wg_lds_usable(const K1Args& a) {
-  if (a.k > 255) return false;
-  if (a.mode == 2) return 2 * a.k - (int)a.w_or_s - 1 <= K1H && (int)a.w_or_s >= 1 && (int)a.w_or_s <= a.k;
-  if (a.mode == 1) return (int)a.w_or_s >= 1 && (int)a.w_or_s + 1 < K1H;
-  return true;
-}
-
 __device__ __forceinline__ int wg_sketch_mate_lds(const K1Args& a, int mode, const uint8_t* __restrict__ s, int len, const uint64_t* tab, K1Lds& L,
                                                   uint64_t* __restrict__ out, int cnt, int* s_wave, int tid) {
   const int k = a.k;
@@ -612,7 +604,7 @@ __device__ __forceinline__ int wg_window_mate_lds(const K1Args& a, int mode, con
       const int nst = min(ns - p0, T + max(wsz - 1, 0));
       for (int i = tid; i < nst; i += K1WG) L.hw[i] = lds_hash(L, i, sm);
       __syncthreads();
-      const bool two = wsz >= 4 && (a.flags & 1);
+      const bool two = wsz >= 4 && (a.flags & K1F_TWO_LEVEL);
       if (two) wg_min4(L, nst, tid);
       const bool v = tid < T && p0 + tid < nw;
       uint64_t h = 0;
@@ -639,7 +631,7 @@ __device__ __forceinline__ int wg_window_mate_lds(const K1Args& a, int mode, con
     const int nkt = min(nk - b0, T + w);
     for (int i = tid; i < nkt; i += K1WG) L.hw[i] = lds_hash(L, i, k);
     __syncthreads();
-    const bool two = w >= 4 && (a.flags & 1);
+    const bool two = w >= 4 && (a.flags & K1F_TWO_LEVEL);
     if (two) wg_min4(L, nkt, tid);
     const int w0 = p0 + tid;
     const bool v = tid < T && w0 < nw;
@@ -715,7 +707,7 @@ __device__ __forceinline__ void wg_reads_windows(const K1Args& a, const uint64_t
     int raw = 0, raw1 = 0;
     if (!skip) {
       bool need_raw = true;
-      if ((a.flags & 2) && a.nk_adj && a.scratch && len1 + len2 > raw_bound) {  // (a mate emits at most one value per base)
+      if ((a.flags & K1F_FUSED_ADJ) && a.nk_adj && a.scratch && len1 + len2 > raw_bound) {  // (a mate emits at most one value per base)
         AdjCarry c;
         uint64_t* adj = a.scratch + o1 + o2;
         int m = wg_window_mate_lds<true>(a, MODE, k1_bases(a, r, o1), len1, tab, L, adj, 0, c, s_wave, s_wave2, s_last, tid);
@@ -790,14 +782,6 @@ struct SeqCarry {  // uniform over the workgroup
   uint64_t last = 0;
   int have = 0, raw = 0, cnt = 0;
 };
-
-__host__ __device__ __forceinline__ bool wave_windows_usable(const K1Args& a) {
-  if (a.k > K1_SCAN_MAX_K || a.k < 1) return false;
-  const int ws = (int)a.w_or_s;
-  if (a.mode == 2) return ws >= 1 && ws <= a.k && 2 * (a.k - ws) <= 60;
-  if (a.mode == 1) return ws >= 1 && ws <= 60;
-  return false;
-}
 
 __device__ __forceinline__ uint64_t readfirst64(uint64_t v) {
   return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
@@ -1087,11 +1071,7 @@ __global__ void __launch_bounds__(K1W_THREADS) k1_windows_wave(const K1Args a) {
 // Reference: sketches.NewSyncmerSketch / NextSyncmer behind generateKmers (util-db-search.go:1053,1068).
 // ------------------------------------------------------------------------------------------------
 constexpr int WR_MIN_WINDOWS = 1024;
-constexpr int WR_PAD_BASES = 1024 + 256;  // what the last lanes' (predicated-off) steps and the refills may still read: zeros
-
-__host__ __device__ __forceinline__ int wr_words_for(int max_read_len) { return (max_read_len + WR_PAD_BASES + 15) / 16 + 4; }
-__host__ __device__ __forceinline__ int wr_ring(int wsz) { return wsz <= 30 ? 16 : 32; }  // >= k - s + 1 = wsz / 2 + 1 slots
-__host__ __device__ __forceinline__ size_t wr_lds_bytes(int wsz, int words, int waves) { return 1024 + (size_t)waves * ((size_t)wr_ring(wsz) * 64 * 8 + (size_t)words * 4); }
+// (WR_PAD_BASES, wr_words_for, wr_ring, wr_lds_bytes: k1_plan.hpp)
 
 template <int WSZ, int WR_WAVES>
 __global__ void __launch_bounds__(64 * WR_WAVES) k1_windows_roll(const K1Args a, int words) {
@@ -1344,7 +1324,7 @@ __global__ void __launch_bounds__(K1WG) k1_kmers_wg_global(const K1Args a) {
 // ---- whole genomes (plain / FracMinHash k-mers): segments of K1SEG positions on their own workgroups ----------------
 // Pass 1 hashes a segment and compacts its kept hashes at scratch[offs[r] + seg*K1SEG ...]; pass 2 moves the segments of a
 // read together in order (destination = sum of the counts of the earlier segments).
-constexpr int K1SEG = 65536;
+// (K1SEG: k1_plan.hpp)
 
 __global__ void __launch_bounds__(K1WG) k1_seg_hash(const K1Args a) {
   __shared__ uint64_t tab[256];
@@ -1807,7 +1787,7 @@ __global__ void k_nk_simple(const int32_t* nk_raw, int32_t* nk_search, uint32_t 
 
 
 
-// ---- sliding windows of plain / FracMinHash k-mers, hash-once form (host.cpp kmcpg_submit_windows; launch_k1_windows_once) ----------------------
+// ---- sliding windows of plain / FracMinHash k-mers, hash-once form (host.cpp kmcpg_submit_windows; launch_k1, form WinOnce) ----------------------
 // A k-mer's hash and whether it is kept do not depend on the window it is read in, so the staged slices of reads are hashed once — one wave per
 // K1_WIN_CHUNK positions of a slice, the wave form of the short-read kernel (hash_mate_scan) over the chunk's bases — and every window's list is
 // the run of its slice's kept hashes between the ranks of its first and one-past-last k-mer position.  Positions are numbered by the slice's
@@ -1929,125 +1909,90 @@ __global__ void __launch_bounds__(256) k1_win_gather(const K1Args a, const Windo
   }
 }
 
-void launch_k1_windows_once(const K1Args& a, const WindowSrc& w, uint64_t* h, uint64_t* kept, uint32_t* rank, uint32_t* cnt, uint64_t* cbase,
-                            hipStream_t st) {
-  if (a.n_reads == 0) return;
-  if (w.n_chunks) {
-    const unsigned blocks = (unsigned)std::min<uint64_t>((w.n_chunks + 3) / 4, 65536);
-    hipLaunchKernelGGL(k1_win_hash, dim3(blocks), dim3(256), 0, st, a, w, h, cnt);
-    hipLaunchKernelGGL(k1_win_scan, dim3(1), dim3(1024), 0, st, cnt, w.n_chunks, cbase);
-    hipLaunchKernelGGL(k1_win_rank, dim3(blocks), dim3(256), 0, st, a, w, h, cbase, kept, rank);
-  } else {
-    (void)hipMemsetAsync(cbase, 0, sizeof(uint64_t), st);
-  }
-  hipLaunchKernelGGL(k1_win_gather, dim3(std::min((a.n_reads + 3) / 4, 65536u)), dim3(256), 0, st, a, w, kept, rank, cbase);
+// k1_windows_roll<WSZ, WAVES>: the 15 forms the plan can name (WSZ 12 / 16 / 20 / 24 / 32 s-mers, 4 / 2 / 1 reads per workgroup)
+template <int WSZ, int WAVES>
+static void windows_roll_launch(const K1Args& a, const K1Plan& p, hipStream_t st) {
+  hipLaunchKernelGGL((k1_windows_roll<WSZ, WAVES>), dim3(p.grid), dim3(64 * WAVES), p.lds_bytes, st, a, p.words);
+}
+template <int WSZ>
+static void windows_roll_waves(const K1Args& a, const K1Plan& p, hipStream_t st) {
+  if (p.waves == 4) windows_roll_launch<WSZ, 4>(a, p, st);
+  else if (p.waves == 2) windows_roll_launch<WSZ, 2>(a, p, st);
+  else windows_roll_launch<WSZ, 1>(a, p, st);
 }
 
-int k1_segment_len() { return K1SEG; }
-
-// true when the kernel that ran drops the adjacent repeats itself (window sketches of long reads: scratch[] + nk_adj[])
-bool launch_k1(const K1Args& a, uint32_t max_read_len, hipStream_t st) {
-  if (a.n_reads == 0) return false;
-  if (a.seg_cnt && a.segs_max > 1) {  // whole genomes: one workgroup per 65536-position segment, then an ordered pack
-    const unsigned blocks = a.n_reads * a.segs_max;
-    // rolling hashes for every k the staging halo holds (flags bit 3 = 8: the prefix-XOR form, for A/B runs)
-    // (flags bit 4 = 16: the byte kernel alone, for A/B runs)
-    if (a.k <= 128 && !(a.flags & 8) && !(a.flags & 16)) {
-      // the list of segments the 2-bit kernel leaves to the byte kernel lives behind seg_cnt[] (run_kmers sizes it: counts, the counter, the list and — packed batches — a mark per segment: 3 * blocks + 2 words)
-      K1Args b = a;
-      b.seg_nflag = (uint32_t*)(a.seg_cnt + blocks);
-      b.seg_list = b.seg_nflag + 1;
-      (void)hipMemsetAsync(b.seg_nflag, 0, sizeof(uint32_t), st);
-      if (a.codes) {  // packed batch (run_kmers sized seg_cnt[] for it: the marks live behind the list)
-        b.seg_exc = nullptr;
-        if (a.n_exc) {
-          b.seg_exc = b.seg_list + blocks;
-          (void)hipMemsetAsync(b.seg_exc, 0, (size_t)blocks * sizeof(uint32_t), st);
-          hipLaunchKernelGGL(k_mark_exc, dim3((a.n_exc + 255) / 256), dim3(256), 0, st, b);
-        }
-        hipLaunchKernelGGL(k1_seg_roll2, dim3(blocks), dim3(64 * R2_WAVES), 0, st, b);
-        if (a.n_exc) {  // (no foreign byte in the batch: nothing is on the list, nothing reads text)
-          hipLaunchKernelGGL(k_unpack2_list, dim3(std::min(blocks, 512u)), dim3(256), 0, st, b);
-          launch_apply_exc(a.exc, a.n_exc, a.seqs_w, st);
-          b.seg_only_flagged = 1;
-          hipLaunchKernelGGL(k1_seg_roll, dim3(std::min(blocks, 512u)), dim3(64 * ROLL_WAVES), 0, st, b);
-        }
-        hipLaunchKernelGGL(k1_seg_pack, dim3(blocks), dim3(256), 0, st, a);
-        return false;
+// the kernels of the plan's form, in order (k1_plan.hpp; the table: DESIGN.md §4).  Everything was decided there: `a` is complete, side
+// buffer pointers included, and nothing here looks at the batch again.
+void launch_k1(const K1Args& a, const K1Plan& p, const K1WinOnce& wo, hipStream_t st) {
+  switch (p.form) {
+    case K1Form::None: break;
+    case K1Form::WinOnce:  // sliding windows, each staged base hashed once
+      if (p.grid) {
+        hipLaunchKernelGGL(k1_win_hash, dim3(p.grid), dim3(256), 0, st, a, wo.w, wo.h, wo.cnt);
+        hipLaunchKernelGGL(k1_win_scan, dim3(1), dim3(1024), 0, st, wo.cnt, wo.w.n_chunks, wo.cbase);
+        hipLaunchKernelGGL(k1_win_rank, dim3(p.grid), dim3(256), 0, st, a, wo.w, wo.h, wo.cbase, wo.kept, wo.rank);
+      } else {
+        (void)hipMemsetAsync(wo.cbase, 0, sizeof(uint64_t), st);
       }
-      hipLaunchKernelGGL(k1_seg_roll2, dim3(blocks), dim3(64 * R2_WAVES), 0, st, b);  // 2-bit codes; lists the segments it cannot take
-      b.seg_only_flagged = 1;
-      // ... and the byte kernel does those: a grid that fills the chip once (2 workgroups of 8 waves per CU) walks the list — nothing
-      // but the read of one counter for a clean batch, where a launch over all segments was up to 2^21 workgroups exiting at once
-      hipLaunchKernelGGL(k1_seg_roll, dim3(std::min(blocks, 512u)), dim3(64 * ROLL_WAVES), 0, st, b);
-    } else if (a.k <= 128 && !(a.flags & 8)) hipLaunchKernelGGL(k1_seg_roll, dim3(blocks), dim3(64 * ROLL_WAVES), 0, st, a);
-    else hipLaunchKernelGGL(k1_seg_hash, dim3(blocks), dim3(K1WG), 0, st, a);
-    hipLaunchKernelGGL(k1_seg_pack, dim3(blocks), dim3(256), 0, st, a);
-    return false;
-  }
-  if (max_read_len > 2048) {  // long queries: a whole workgroup per read
-    unsigned blocks = a.n_reads > 65536 ? 65536 : a.n_reads;
-    if (a.mode != 0 && a.scratch && wave_windows_usable(a) && !(a.flags & 4)) {  // window sketches: the barrier-free form
-      // closed syncmers with a window of 12 / 16 / 20 / 24 / 32 s-mers (k - s = 6 .. 16), single-end, the fused adjacent-repeat path wanted:
-      // the rolling kernel first, k1_windows_wave behind it for the reads it leaves on its list (flags bit 5 = 32: the old kernel alone)
-      const int wsz = a.mode == 2 ? 2 * (a.k - (int)a.w_or_s) : 0;
-      const int words = wr_words_for((int)max_read_len);
-      // reads (= waves) per workgroup: LDS per wave (k-mer ring 8 KB + 2-bit codes of the longest read) decides how many waves a CU holds —
-      // two per SIMD for 20-kb reads whatever the grouping (tools/ubench_lds_occ.cpp); 2 measured 0.7 % ahead of 4 and 1
-      int waves = getenv("KMCPG_WR_WAVES") ? atoi(getenv("KMCPG_WR_WAVES")) : 2;
-      if (waves != 1 && waves != 4) waves = 2;
-      while (waves > 1 && wr_lds_bytes(wsz, words, waves) > 65536) waves >>= 1;
-      // (no read of the batch can exceed the -u / wave-sort bound — planting, a huge -u —: the fused path is nobody's, the old kernel alone)
-      const bool any_fused = (long long)max_read_len > (long long)std::max(a.dedup_threshold, K1_WAVE_SORT_CAP);
-      const bool wsz_ok = wsz == 12 || wsz == 16 || wsz == 20 || wsz == 24 || wsz == 32;  // k - s = 6, 8, 10, 12, 16 (21/11, 31/15, 21/13, 31/19 ...)
-      if (a.mode == 2 && wsz_ok && a.k <= 64 && !a.offs2 && a.nk_adj && a.seg_list && !(a.flags & 32) && any_fused &&
-          wr_lds_bytes(wsz, words, waves) <= 65536) {
-        K1Args b = a;
-        (void)hipMemsetAsync(b.seg_nflag, 0, sizeof(uint32_t), st);
-        const unsigned wg = (a.n_reads + waves - 1) / waves;
-        const size_t lds = wr_lds_bytes(wsz, words, waves);
-#define KMCPG_WR_LAUNCH(WSZ_, WV_) hipLaunchKernelGGL((k1_windows_roll<WSZ_, WV_>), dim3(wg), dim3(64 * WV_), lds, st, b, words)
-#define KMCPG_WR_WAVES_OF(WSZ_)                \
-  do {                                         \
-    if (waves == 4) KMCPG_WR_LAUNCH(WSZ_, 4);  \
-    else if (waves == 2) KMCPG_WR_LAUNCH(WSZ_, 2); \
-    else KMCPG_WR_LAUNCH(WSZ_, 1);             \
-  } while (0)
-        switch (wsz) {
-          case 12: KMCPG_WR_WAVES_OF(12); break;
-          case 16: KMCPG_WR_WAVES_OF(16); break;
-          case 20: KMCPG_WR_WAVES_OF(20); break;
-          case 24: KMCPG_WR_WAVES_OF(24); break;
-          default: KMCPG_WR_WAVES_OF(32); break;
-        }
-#undef KMCPG_WR_WAVES_OF
-#undef KMCPG_WR_LAUNCH
-        b.seg_only_flagged = 1;
-        hipLaunchKernelGGL(k1_windows_wave<2>, dim3(std::min(blocks, 1024u)), dim3(K1W_THREADS), 0, st, b);
-        if (getenv("KMCPG_K1_DEBUG")) {  // how many reads the rolling kernel left to k1_windows_wave
-          uint32_t nf = 0;
-          (void)hipStreamSynchronize(st);
-          (void)hipMemcpy(&nf, b.seg_nflag, sizeof nf, hipMemcpyDeviceToHost);
-          fprintf(stderr, "k1_windows_roll<%d>: %u of %u reads left to k1_windows_wave (max_read_len %u, %d words)\n", wsz, nf, a.n_reads, max_read_len, words);
-        }
-        return true;
+      hipLaunchKernelGGL(k1_win_gather, dim3(p.grid2), dim3(256), 0, st, a, wo.w, wo.kept, wo.rank, wo.cbase);
+      break;
+    case K1Form::SegRoll2:  // whole genomes: one workgroup per 65536-position segment, then an ordered pack
+      (void)hipMemsetAsync(a.seg_nflag, 0, sizeof(uint32_t), st);
+      if (p.marks.len) {  // codes with runs of foreign bytes: the segments they reach are marked for the list ...
+        (void)hipMemsetAsync(a.seg_exc, 0, p.marks.len * sizeof(uint32_t), st);
+        hipLaunchKernelGGL(k_mark_exc, dim3((a.n_exc + 255) / 256), dim3(256), 0, st, a);
       }
-      if (a.mode == 2) hipLaunchKernelGGL(k1_windows_wave<2>, dim3(blocks), dim3(K1W_THREADS), 0, st, a);
-      else hipLaunchKernelGGL(k1_windows_wave<1>, dim3(blocks), dim3(K1W_THREADS), 0, st, a);
-      return a.nk_adj != nullptr;
-    }
-    if (!wg_lds_usable(a)) hipLaunchKernelGGL(k1_kmers_wg_global, dim3(blocks), dim3(K1WG), 0, st, a);
-    else if (a.mode == 2) hipLaunchKernelGGL(k1_kmers_wg<2>, dim3(blocks), dim3(K1WG), 0, st, a);
-    else if (a.mode == 1) hipLaunchKernelGGL(k1_kmers_wg<1>, dim3(blocks), dim3(K1WG), 0, st, a);
-    else hipLaunchKernelGGL(k1_kmers_wg<0>, dim3(blocks), dim3(K1WG), 0, st, a);
-    return wg_lds_usable(a) && a.mode != 0 && a.nk_adj && a.scratch && (a.flags & 2);
+      hipLaunchKernelGGL(k1_seg_roll2, dim3(p.grid), dim3(64 * R2_WAVES), 0, st, a);  // 2-bit codes; lists the segments it cannot take
+      if (p.marks.len) {  // ... and only those become text
+        hipLaunchKernelGGL(k_unpack2_list, dim3(p.grid2), dim3(256), 0, st, a);
+        launch_apply_exc(a.exc, a.n_exc, a.seqs_w, st);
+      }
+      // the byte kernel does the listed segments: nothing but the read of one counter for a clean batch, where a launch over all segments
+      // was up to 2^21 workgroups exiting at once
+      if (p.list_fallback) hipLaunchKernelGGL(k1_seg_roll, dim3(p.grid2), dim3(64 * ROLL_WAVES), 0, st, a);
+      hipLaunchKernelGGL(k1_seg_pack, dim3(p.grid), dim3(256), 0, st, a);
+      break;
+    case K1Form::SegRoll:
+      hipLaunchKernelGGL(k1_seg_roll, dim3(p.grid), dim3(64 * ROLL_WAVES), 0, st, a);
+      hipLaunchKernelGGL(k1_seg_pack, dim3(p.grid), dim3(256), 0, st, a);
+      break;
+    case K1Form::SegHash:
+      hipLaunchKernelGGL(k1_seg_hash, dim3(p.grid), dim3(K1WG), 0, st, a);
+      hipLaunchKernelGGL(k1_seg_pack, dim3(p.grid), dim3(256), 0, st, a);
+      break;
+    case K1Form::WindowsRoll:  // closed syncmers of long reads: the rolling kernel, k1_windows_wave behind it for the reads on its list
+      (void)hipMemsetAsync(a.seg_nflag, 0, sizeof(uint32_t), st);
+      switch (p.wsz) {
+        case 12: windows_roll_waves<12>(a, p, st); break;
+        case 16: windows_roll_waves<16>(a, p, st); break;
+        case 20: windows_roll_waves<20>(a, p, st); break;
+        case 24: windows_roll_waves<24>(a, p, st); break;
+        default: windows_roll_waves<32>(a, p, st); break;
+      }
+      hipLaunchKernelGGL(k1_windows_wave<2>, dim3(p.grid2), dim3(K1W_THREADS), 0, st, a);
+      if (p.debug) {  // how many reads the rolling kernel left to k1_windows_wave
+        uint32_t nf = 0;
+        (void)hipStreamSynchronize(st);
+        (void)hipMemcpy(&nf, a.seg_nflag, sizeof nf, hipMemcpyDeviceToHost);
+        fprintf(stderr, "k1_windows_roll<%d>: %u of %u reads left to k1_windows_wave (max_read_len %u, %d words)\n", p.wsz, nf, a.n_reads, p.max_read_len, p.words);
+      }
+      break;
+    case K1Form::WindowsWave:  // window sketches of long reads, a wave per read
+      if (a.mode == 2) hipLaunchKernelGGL(k1_windows_wave<2>, dim3(p.grid), dim3(K1W_THREADS), 0, st, a);
+      else hipLaunchKernelGGL(k1_windows_wave<1>, dim3(p.grid), dim3(K1W_THREADS), 0, st, a);
+      break;
+    case K1Form::WgGlobal: hipLaunchKernelGGL(k1_kmers_wg_global, dim3(p.grid), dim3(K1WG), 0, st, a); break;
+    case K1Form::Wg:  // long queries: a whole workgroup per read
+      if (a.mode == 2) hipLaunchKernelGGL(k1_kmers_wg<2>, dim3(p.grid), dim3(K1WG), 0, st, a);
+      else if (a.mode == 1) hipLaunchKernelGGL(k1_kmers_wg<1>, dim3(p.grid), dim3(K1WG), 0, st, a);
+      else hipLaunchKernelGGL(k1_kmers_wg<0>, dim3(p.grid), dim3(K1WG), 0, st, a);
+      break;
+    case K1Form::Short:  // four reads per workgroup, a wave each
+      if (a.mode == 2) hipLaunchKernelGGL(k1_kmers<2>, dim3(p.grid), dim3(256), 0, st, a);
+      else if (a.mode == 1) hipLaunchKernelGGL(k1_kmers<1>, dim3(p.grid), dim3(256), 0, st, a);
+      else hipLaunchKernelGGL(k1_kmers<0>, dim3(p.grid), dim3(256), 0, st, a);
+      break;
   }
-  unsigned blocks = (a.n_reads + 3) / 4;
-  if (blocks > 32768) blocks = 32768;
-  if (a.mode == 2) hipLaunchKernelGGL(k1_kmers<2>, dim3(blocks), dim3(256), 0, st, a);
-  else if (a.mode == 1) hipLaunchKernelGGL(k1_kmers<1>, dim3(blocks), dim3(256), 0, st, a);
-  else hipLaunchKernelGGL(k1_kmers<0>, dim3(blocks), dim3(256), 0, st, a);
-  return false;
 }
 
 void launch_nk_simple(const int32_t* nk_raw, int32_t* nk_search, uint32_t n, int32_t min_matched, hipStream_t st) {

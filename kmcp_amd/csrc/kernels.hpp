@@ -5,11 +5,24 @@
 #include <vector>
 
 #include "common.hpp"
+#include "k1_plan.hpp"
 
 namespace kmcpg {
 
-bool launch_k1(const K1Args& a, uint32_t max_read_len, hipStream_t st);  // true: adjacent repeats already dropped (scratch[], nk_adj[])
-int k1_segment_len();  // positions per workgroup on the whole-genome path
+// What form WinOnce of launch_k1 works on besides K1Args (no other form reads it) — the hash-once form of plain / FracMinHash windows
+// (k <= 65, single-end): every k-mer position of the staged slices `w` is hashed once (h[], one wave per K1_WIN_CHUNK positions), the kept
+// ones are compacted in order (kept[]) with each position's rank (rank[]), then every window's list is the run
+// kept[rank[i] .. rank[e - k + 1]) copied to a.hashes[a.offs[w] ...]; nk_raw / nk1 / qlen as k1_kmers<0> writes them.
+// h / kept / rank: K1Plan::win_words (one per staged base), cnt / cbase: K1Plan::win_chunk_words
+struct K1WinOnce {
+  WindowSrc w;
+  uint64_t *h, *kept;
+  uint32_t *rank, *cnt;
+  uint64_t* cbase;
+};
+// K1: the kernels of the plan's form (k1_plan.hpp); `a` complete, side buffer pointers included.  Whether adjacent repeats are already
+// dropped afterwards is the plan's adj_done
+void launch_k1(const K1Args& a, const K1Plan& p, const K1WinOnce& wo, hipStream_t st);
 void launch_nk_simple(const int32_t* nk_raw, int32_t* nk_search, uint32_t n, int32_t min_matched, hipStream_t st);
 void launch_dedup(DedupArgs a, uint64_t max_n, hipStream_t st);  // queries above HUGE_MIN are left to huge_dedup
 // what the K2 launchers note about every kernel they launch (kmcpg_last_k2_launches): written at the launch site from the template
@@ -48,12 +61,6 @@ void launch_apply_exc(const ExcRun* runs, uint32_t n_runs, uint8_t* out, hipStre
 // text, wpre / vpre: prefix sums of their windows and of those windows' bases) -> src[w] (first base in the text), offs[0 .. n_win]
 void launch_window_desc(const uint64_t* soffs, const uint64_t* wpre, const uint64_t* vpre, uint32_t n_slices, uint64_t n_win, uint64_t step,
                         uint64_t window, uint64_t* src, uint64_t* offs, hipStream_t st);
-// hash-once form of plain / FracMinHash windows (k1_kmers.hip, k <= 65, single-end): every k-mer position of the staged slices hashed once
-// (h[], one wave per K1_WIN_CHUNK positions), the kept ones compacted in order (kept[]) with each position's rank (rank[]), then every
-// window's list is the run kept[rank[i] .. rank[e - k + 1]) copied to a.hashes[a.offs[w] ...]; nk_raw / nk1 / qlen as k1_kmers<0> writes
-// them.  cnt: n_chunks words, cbase: n_chunks + 1
-void launch_k1_windows_once(const K1Args& a, const WindowSrc& w, uint64_t* h, uint64_t* kept, uint32_t* rank, uint32_t* cnt, uint64_t* cbase,
-                            hipStream_t st);
 
 // experiment only (KMCPG_DEBUG_ROWSORT): every query's hashes re-ordered by h % num_sigs of one block; mode 2 = rotated
 void launch_debug_rowsort(uint64_t* hashes, const uint64_t* offs, const int32_t* nk, uint32_t n_reads, uint64_t num_sigs, uint64_t mh, int mode, hipStream_t st);

@@ -40,10 +40,7 @@ void release_fpr_bounds(kmcpg_db* db) {
 // ------------------------------------------------------------------------------------------------
 // GPU half
 // ------------------------------------------------------------------------------------------------
-// a batch the k-mer stage hashes segment by segment (run_kmers: plain or FracMinHash k-mers, single-end, some query above one segment)
-bool kmcpg::whole_genome_batch(const kmcpg_db* db, uint32_t max_read_len, bool paired) {
-  return !paired && !db->info.syncmer && !db->info.minimizer && max_read_len > (uint32_t)k1_segment_len();
-}
+bool kmcpg::whole_genome_batch(const kmcpg_db* db, uint32_t max_read_len, bool paired) { return k1_whole_genomes(k1_mode(db->info), paired, max_read_len); }
 
 namespace {
 
@@ -61,78 +58,87 @@ struct KmerOut {
   int32_t *d_nk_raw, *d_nk1, *d_nk_search, *d_qlen;
 };
 
+// The K1 knobs.  KMCPG_K1_FLAGS, KMCPG_WR_WAVES and KMCPG_K1_DEBUG are read at every call (tests flip them inside one
+// process), KMCPG_K1_CODES and KMCPG_WIN_ONCE once per process.
+K1Knobs k1_knobs() {
+  static const int codes_mode = getenv("KMCPG_K1_CODES") ? atoi(getenv("KMCPG_K1_CODES")) : 1;
+  static const bool win_once = !getenv("KMCPG_WIN_ONCE") || atoi(getenv("KMCPG_WIN_ONCE")) != 0;
+  K1Knobs kn;
+  if (const char* e = getenv("KMCPG_K1_FLAGS")) kn.flags = atoi(e);
+  if (const char* e = getenv("KMCPG_WR_WAVES")) kn.wr_waves = atoi(e);
+  kn.codes_mode = codes_mode;
+  kn.win_once = win_once;
+  kn.debug = getenv("KMCPG_K1_DEBUG") != nullptr;
+  return kn;
+}
+
 // K1 (+K1d): hashes of read i end up at d_hashes[offs[i] + offs2[i] ...], NumKmers in d_nk_search
 int run_kmers(kmcpg_db* db, kmcpg_db::Workspace& W, const DeviceBatch& b, const kmcpg_params& p, const KmerOut& o, hipStream_t st, uint64_t* max_n_out) {
   const kmcpg_info& I = db->info;
   if (!I.canonical) return kmcpg_fail(KMCPG_EUNSUPPORTED, "non-canonical index");
+  const PackedSrc& src = b.packed;   // a batch that came as 2-bit codes (host.cpp: kmcpg_submit_packed, or text stage() packed)
+  const WindowSrc& win = b.windows;  // sliding windows (host.cpp kmcpg_submit_windows): every kernel reads a window's bases in place through its view
+  // which kernels, on what side buffer (k1_plan.hpp)
+  K1Shape s;
+  s.mode = k1_mode(I);
+  s.k = p.k > 0 ? p.k : I.k;
+  s.w_or_s = I.syncmer ? I.syncmer_s : I.minimizer_w;
+  s.paired = b.d_seqs2 != nullptr;
+  s.n_reads = b.n_reads;
+  s.max_read_len = b.max_read_len;
+  s.have_scratch = o.d_scratch != nullptr;
+  s.dedup_threshold = p.dedup_threshold;
+  s.win = {win.src != nullptr, win.step, win.window, win.sb, win.n_chunks};
+  s.packed = {src.codes != nullptr, src.n_exc, src.n_bases, src.text == b.d_seqs};
+  s.knobs = k1_knobs();
+  const K1Plan plan = k1_plan(s);
+  if (W.w_seg_cnt.ensure(plan.side_words) || W.w_win_h.ensure(plan.win_words) || W.w_win_kept.ensure(plan.win_words) || W.w_win_rank.ensure(plan.win_words) ||
+      W.w_win_cnt.ensure(plan.win_chunk_words) || W.w_win_cbase.ensure(plan.win_chunk_words))
+    return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
+  uint32_t* const side = (uint32_t*)W.w_seg_cnt.p;
+  auto side_at = [side](const K1Region& r) { return r.len ? side + r.off : nullptr; };
   K1Args a{};
   a.seqs = b.d_seqs;
   a.offs = b.d_offs;
   a.seqs2 = b.d_seqs2;
   a.offs2 = b.d_offs2;
   a.n_reads = b.n_reads;
-  a.k = p.k > 0 ? p.k : I.k;
+  a.k = s.k;
   a.min_qlen = p.min_qlen;
   a.scaled = I.scaled;
   a.max_hash = I.scaled ? max_hash_for(I.scale) : ~0ULL;
-  a.mode = I.syncmer ? 2 : (I.minimizer ? 1 : 0);  // syncmer > minimizer > plain (:1052-1058)
-  a.w_or_s = I.syncmer ? I.syncmer_s : I.minimizer_w;
+  a.mode = s.mode;
+  a.w_or_s = s.w_or_s;
   a.hashes = o.d_hashes;
   a.scratch = o.d_scratch;
   a.scratch2 = o.d_scratch ? o.d_scratch + o.scratch_half : nullptr;
   a.nk_raw = o.d_nk_raw;
   a.nk1 = o.d_nk1;
   a.qlen = o.d_qlen;
-  a.flags = getenv("KMCPG_K1_FLAGS") ? atoi(getenv("KMCPG_K1_FLAGS")) : 3;
-  // whole genomes (single-end, plain or FracMinHash k-mers): segments of a read on their own workgroups
-  const uint32_t segs = (b.max_read_len + (uint32_t)k1_segment_len() - 1) / (uint32_t)k1_segment_len();
-  if (a.mode == 0 && !b.d_seqs2 && segs > 1 && o.d_scratch && (uint64_t)b.n_reads * segs <= (1ull << 21)) {  // one workgroup of 1024 threads per segment, < 2^32 threads per launch
-    if (W.w_seg_cnt.ensure(3 * (size_t)b.n_reads * segs + 2)) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");  // counts + launch_k1's fallback list + its marks
-    a.seg_cnt = W.w_seg_cnt.p;
-    a.segs_max = segs;
-  }
-  // A batch that came as 2-bit codes (host.cpp: kmcpg_submit_packed, or text stage() packed): the whole-genome kernel reads the codes as
-  // they are, and text exists only for the segments a foreign byte reaches (launch_k1); every other k-mer kernel reads text, expanded
-  // here.  (A batch with a run per 4 kb or more is not what the direct form is for: expanded whole.)  KMCPG_K1_CODES=0: always expand.
-  const PackedSrc& src = b.packed;
-  // sliding windows (host.cpp kmcpg_submit_windows): every kernel reads a window's bases in place through its view; the codes of such a batch
-  // are expanded first (the direct 2-bit form addresses the codes by the batch's own offsets)
-  const WindowSrc& win = b.windows;
+  a.flags = s.knobs.flags;
+  a.seg_cnt = (int32_t*)side_at(plan.counts);
+  a.segs_max = plan.segs;
+  a.seg_nflag = side_at(plan.counter);
+  a.seg_list = side_at(plan.list);
+  a.seg_exc = side_at(plan.marks);
+  a.seg_only_flagged = plan.list_fallback;
+  a.nk_adj = o.d_nk_search;
+  a.dedup_threshold = p.dedup_threshold;
   a.src = win.src;
+  // packed input: k1_seg_roll2 reads the codes as they are, and text exists only for the segments a foreign byte reaches; every other form
+  // reads text, expanded here
   if (src.codes) {
-    static const int codes_mode = getenv("KMCPG_K1_CODES") ? atoi(getenv("KMCPG_K1_CODES")) : 1;  // 2 (tests): however many runs there are
-    const bool direct = codes_mode != 0 && !a.src && a.seg_cnt && a.segs_max > 1 && a.k <= 128 && !(a.flags & 24) && src.text == b.d_seqs &&
-                        (codes_mode == 2 || (uint64_t)src.n_exc <= src.n_bases / 4096 + 64);
-    if (direct) {
+    if (plan.codes_direct) {
       a.codes = src.codes;
       a.exc = src.exc;
       a.n_exc = src.n_exc;
       a.seqs_w = src.text;
     } else {
-      launch_unpack2(src.codes, src.text, src.n_bases, src.n_exc ? src.exc : nullptr, src.n_exc, st);  // codes -> the text the kernels read
+      launch_unpack2(src.codes, src.text, src.n_bases, src.n_exc ? src.exc : nullptr, src.n_exc, st);
     }
-    (direct ? db->k1_codes_direct : db->k1_codes_expanded)++;
+    (plan.codes_direct ? db->k1_codes_direct : db->k1_codes_expanded)++;
   }
-  if (a.mode != 0 && !b.d_seqs2 && o.d_scratch) {  // the list the rolling window-sketch kernel leaves to k1_windows_wave (launch_k1): count + read indices
-    if (W.w_seg_cnt.ensure((size_t)b.n_reads + 2)) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
-    a.seg_nflag = (uint32_t*)W.w_seg_cnt.p;
-    a.seg_list = a.seg_nflag + 1;
-  }
-  a.nk_adj = o.d_nk_search;
-  a.dedup_threshold = p.dedup_threshold;
-  // sliding windows of plain / FracMinHash k-mers: each staged base hashed once, each window's list a run of the slice's kept hashes
-  // (KMCPG_WIN_ONCE=0: every window hashed in place, as window sketches always are — their emission at a window's edges is the window's own)
-  static const bool win_once = !getenv("KMCPG_WIN_ONCE") || atoi(getenv("KMCPG_WIN_ONCE")) != 0;
-  bool adj_done = false;
-  // (windows that do not overlap, S >= W, share no k-mer: nothing to hash once, they are read in place)
-  if (win.src && win_once && a.mode == 0 && !b.d_seqs2 && a.k <= 65 && win.step < win.window) {
-    if (W.w_win_h.ensure(win.sb + 1) || W.w_win_kept.ensure(win.sb + 1) || W.w_win_rank.ensure(win.sb + 1) || W.w_win_cnt.ensure(win.n_chunks + 1) ||
-        W.w_win_cbase.ensure(win.n_chunks + 1))
-      return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
-    launch_k1_windows_once(a, win, W.w_win_h.p, W.w_win_kept.p, W.w_win_rank.p, W.w_win_cnt.p, W.w_win_cbase.p, st);
-  } else {
-    adj_done = launch_k1(a, b.max_read_len, st);
-  }
+  launch_k1(a, plan, K1WinOnce{win, W.w_win_h.p, W.w_win_kept.p, W.w_win_rank.p, W.w_win_cnt.p, W.w_win_cbase.p}, st);
   uint64_t ub = b.max_read_len >= (uint32_t)a.k ? (uint64_t)(b.max_read_len - a.k + 1) : 0;
   if (b.d_seqs2) ub *= 2;
   *max_n_out = ub;
@@ -148,7 +154,7 @@ int run_kmers(kmcpg_db* db, kmcpg_db::Workspace& W, const DeviceBatch& b, const 
     d.nk_raw = o.d_nk_raw;
     d.nk_search = o.d_nk_search;
     d.pre = a.mode != 0;
-    d.pre_done = adj_done;
+    d.pre_done = plan.adj_done;
     d.key_shift = (I.scaled && a.max_hash) ? __builtin_clzll(a.max_hash) : 0;
     launch_dedup(d, ub, st);
     if (ub > HUGE_MIN) {
