@@ -3,8 +3,10 @@
 //
 //   kmcp [persistent flags] search ...  -> kmcp-search (the MI355X search path; flags of kmcp/cmd/search.go:1031-1107)
 //   kmcp [persistent flags] merge  ...  -> kmcp-merge  (kmcp/cmd/merge.go)
+//   kmcp [persistent flags] utils index-density | ref-info ...
+//                                       -> kmcp-inspect (index inspection on the GPU; kmcp/cmd/index-density.go, ref-info.go)
 //   kmcp <any other command> ...        -> the reference binary named by $KMCP_REFERENCE_BIN, or the next `kmcp` on PATH that
-//                                          is not this file (compute / index / profile / utils are out of scope of this build,
+//                                          is not this file (compute / index / profile / the other utils are out of scope of this build,
 //                                          SURVEY.md §2); without one: an error that says so, exit status 255 like checkError.
 //
 // cobra accepts the root command's persistent flags (-j/--threads, -q/--quiet, -i/--infile-list, --log; root.go:62-82) before
@@ -86,6 +88,11 @@ int main(int argc, char** argv) {
     args.insert(args.end(), before.begin(), before.end());
     run(dir + (cmd == "search" ? "/kmcp-search" : "/kmcp-merge"), args);
   }
+  if (cmd == "utils" && !after.empty() && (after[0] == "index-density" || after[0] == "ref-info")) {
+    std::vector<std::string> args = after;
+    args.insert(args.end(), before.begin(), before.end());
+    run(dir + "/kmcp-inspect", args);
+  }
   if (cmd.empty()) {
     bool help = false, version = false;
     for (const auto& b : before) {
@@ -94,15 +101,18 @@ int main(int argc, char** argv) {
     }
     if (version) run(dir + "/kmcp-search", {"--version"});
     fputs("kmcp (MI355X build of the `kmcp search` hot path)\n\nUsage:\n  kmcp search [flags]   search sequences against a database on the GPU (kmcp-search)\n"
-          "  kmcp merge  [flags]   merge search results from several databases (kmcp-merge)\n\n"
-          "Every other kmcp command (compute, index, profile, utils, ...) is handed to the reference binary:\n"
+          "  kmcp merge  [flags]   merge search results from several databases (kmcp-merge)\n"
+          "  kmcp utils index-density [flags] <file.uniki>   bit density of an index file per column and bin of rows (kmcp-inspect)\n"
+          "  kmcp utils ref-info -d <db> [flags]             k-mers and false-positive rate of every reference chunk (kmcp-inspect)\n\n"
+          "Every other kmcp command (compute, index, profile, the other utils, ...) is handed to the reference binary:\n"
           "$KMCP_REFERENCE_BIN, or the next `kmcp` on PATH.\n", help ? stdout : stderr);
     return help ? 0 : 255;
   }
   const std::string ref = find_reference();
   if (ref.empty()) {
-    fprintf(stderr, "[ERRO] kmcp %s is not part of this build (only `search` and `merge` are); no reference kmcp binary found "
-                    "(set KMCP_REFERENCE_BIN or put it on PATH)\n", cmd.c_str());
+    const std::string what = cmd == "utils" && !after.empty() ? cmd + " " + after[0] : cmd;
+    fprintf(stderr, "[ERRO] kmcp %s is not part of this build (only `search`, `merge`, `utils index-density` and `utils ref-info` are); no reference kmcp binary found "
+                    "(set KMCP_REFERENCE_BIN or put it on PATH)\n", what.c_str());
     return 255;
   }
   std::vector<std::string> args = before;

@@ -394,6 +394,46 @@ int kmcpg_kmers_device_packed(kmcpg_db* db, const uint8_t* d_codes, const kmcpg_
  * were expanded to text first. */
 int kmcpg_k1_codes_batches(kmcpg_db* db, uint64_t* direct, uint64_t* expanded);
 
+/* -- index inspection: what `kmcp utils index-density` counts (kmcp/cmd/index-density.go:139-213) and the measured side of
+ *    `kmcp utils ref-info` (ref-info.go:128-150), from resident rows.  Read-only; every number is an integer a caller can recount from
+ *    the file.  The rows of block `block` from first_row on (n_rows of them, 0 = to the block's last row) are cut into bins of bin_rows
+ *    rows — the last bin may be short — and kmcpg_block_density counts the set bits of every column in every bin.  The calls take the
+ *    handle's enqueue lock as the GPU half of a search does, allocate their device scratch per call and free it before they return
+ *    (KMCPG_ENOMEM names the bytes asked for); they may be used beside kmcpg_submit / kmcpg_wait on a kmcpg_open handle.
+ *    KMCPG_EINVAL: non-local block, bin_rows == 0, rows outside the block, cap too small, reserved != 0.  KMCPG_EUNSUPPORTED: paged
+ *    (kmcpg_open_paged) and multi-device (kmcpg_open_devices) front handles.  KMCPG_EDEVICE: metadata-only handles. */
+typedef struct {
+  uint64_t bin_rows;   /* >= 1 */
+  uint64_t first_row;  /* 0 */
+  uint64_t n_rows;     /* 0 = to the block's last row */
+  uint64_t reserved;   /* must be 0 */
+} kmcpg_density_spec;
+/* n_bins = ceil(rows / bin_rows): the last bin may be short */
+int kmcpg_density_bins(const kmcpg_db* db, uint32_t block, const kmcpg_density_spec* spec, uint64_t* n_bins);
+/* counts[c * n_bins + b], c = column of the block (host memory, cap in elements) */
+int kmcpg_block_density(kmcpg_db* db, uint32_t block, const kmcpg_density_spec* spec, uint32_t* counts, uint64_t cap);
+/* set bits of every global column over all its rows; 0 for columns of non-local blocks.  One pass over every resident group. */
+int kmcpg_col_ones(kmcpg_db* db, uint64_t* ones, uint64_t cap);
+/* what the last density call launched: form (0 carry-save planes, 1 small-bin bit extracts), lanes per row tile and planes (form 0; of the
+ * last launch), workgroups of the form-0 launches together, launches */
+typedef struct {
+  int32_t form, lpr, npl, reserved;
+  uint32_t workgroups, launches;
+} kmcpg_density_launch;
+int kmcpg_last_density_launch(kmcpg_db* db, kmcpg_density_launch* out);
+/* A handle over the given .uniki files alone, no __db.yml needed: headers parsed and checked for mutual compatibility as kmcpg_open
+ * checks them (serialization.go:90-99), rows resident when device >= 0 (-1: metadata only), blocks numbered in argument order, every
+ * block local.  Inspecting one block of a large database uploads only that block.  Work: the inspection calls above, kmcpg_db_info,
+ * kmcpg_block_info, kmcpg_col_info, kmcpg_read_rows, kmcpg_read_row_range.  Every search entry point refuses with KMCPG_EUNSUPPORTED
+ * (the handle knows neither the database's fpr nor how its k-mers were sketched). */
+int kmcpg_open_files(const char* const* uniki_paths, uint32_t n, int32_t device, kmcpg_db** out);
+
+/* bench support (tools/bench_density.py): HIP-event milliseconds of the device work of the last kmcpg_block_density / kmcpg_col_ones call
+ * (memsets and kernels, before the copy to the host), and a yardstick for it — kmcpg_stream_probe reads the rows of every resident
+ * group once with 16 B per lane and one XOR per load (one launch per group, as kmcpg_col_ones) and reports its HIP-event time and bytes. */
+int kmcpg_last_density_ms(kmcpg_db* db, float* ms);
+int kmcpg_stream_probe(kmcpg_db* db, float* ms, uint64_t* bytes);
+
 /* -- index building on the GPU ("next" row of SURVEY.md §8f): the Bloom-column scatter of `kmcp index`
  *    (kmcp/cmd/index.go:657-682 block layout, :1023 signature size, :1107-1309 scatter, index/serialization.go:159-300 file,
  *    util-db-info.go:46-79 __db.yml) from lists of k-mer hashes — what the .unik files of `kmcp compute` hold.  Writes

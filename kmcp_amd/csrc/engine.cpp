@@ -593,6 +593,59 @@ extern "C" int kmcpg_open(const char* db_dir, const kmcpg_opts* opts, kmcpg_db**
   return 0;
 }
 
+// kmcpg_open without the yml half: the handle's info comes from the first header
+extern "C" int kmcpg_open_files(const char* const* uniki_paths, uint32_t n, int32_t device, kmcpg_db** out) {
+  if (!uniki_paths || !out || n == 0) return kmcpg_fail(KMCPG_EINVAL, "null argument");
+  *out = nullptr;
+  for (uint32_t i = 0; i < n; i++)
+    if (!uniki_paths[i]) return kmcpg_fail(KMCPG_EINVAL, "null path");
+  DbPtr db(new kmcpg_db());
+  const kmcpg_opts o{device, 0, 1, 0};
+  int rc = check_opts(&o, &db->opts);
+  if (rc) return rc;
+  const bool meta_only = db->opts.device < 0;
+  if (!meta_only) HIPCHK(hipSetDevice(db->opts.device));
+  db->files_only = true;
+  kmcpg_info& I = db->info;
+  uint32_t base = 0;
+  for (uint32_t i = 0; i < n; i++) {
+    BlockMeta b;
+    b.path = uniki_paths[i];
+    const std::string e = read_uniki_header(b.path, &b.h);
+    if (!e.empty()) return kmcpg_fail(e.find("missing") != std::string::npos ? KMCPG_EIO : KMCPG_EFORMAT, "%s", e.c_str());
+    if (i == 0) {
+      I.k = b.h.k;
+      I.canonical = b.h.canonical;
+      I.num_hashes = b.h.num_hashes;
+      I.scale = 1;
+    } else {
+      const UnikiHeader& f = db->blocks[0].h;  // Header.Compatible (serialization.go:90-99)
+      if (b.h.version != f.version || b.h.k != f.k || b.h.canonical != f.canonical || b.h.num_hashes != f.num_hashes)
+        return kmcpg_fail(KMCPG_EFORMAT, "index files not compatible");
+    }
+    b.col_base = base;
+    b.local = true;
+    base += (uint32_t)b.h.names.size();
+    I.matrix_bytes += b.h.num_sigs * (uint64_t)b.h.row_bytes;
+    db->blocks.push_back(std::move(b));
+  }
+  I.n_blocks = (int32_t)db->blocks.size();
+  I.n_cols = base;
+  if (I.num_hashes < 1 || I.num_hashes > 4) return kmcpg_fail(KMCPG_EUNSUPPORTED, "hashes=%d (kmcp index allows 1..4)", I.num_hashes);
+  db->ks_desc.assign(1, I.k);
+  form_groups(db.get());
+  if (!meta_only) {
+    rc = alloc_groups(db.get());
+    if (rc) return rc;
+    rc = upload_blocks(db.get());
+    if (rc) return rc;
+  }
+  rc = finish_open(db.get());
+  if (rc) return rc;
+  *out = db.release();
+  return 0;
+}
+
 extern "C" int kmcpg_open_synthetic(const kmcpg_synth_spec* s, const kmcpg_opts* opts, kmcpg_db** out) {
   if (!s || !out) return kmcpg_fail(KMCPG_EINVAL, "null argument");
   *out = nullptr;

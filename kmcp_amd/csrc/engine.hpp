@@ -28,6 +28,12 @@ std::string& kmcpg_err_ref();  // the calling thread's message (workers hand the
     if (e_ != hipSuccess) return kmcpg_fail(KMCPG_EDEVICE, "%s: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
   } while (0)
 
+// search entry points: refused on a handle over bare .uniki files (kmcpg_open_files knows no __db.yml: no fpr, no k-mer sketching parameters)
+#define KMCPG_NO_FILES_ONLY(db)                                                                                   \
+  do {                                                                                                            \
+    if ((db)->files_only) return kmcpg_fail(KMCPG_EUNSUPPORTED, "handle of kmcpg_open_files: index inspection only, open the database directory with kmcpg_open to search it"); \
+  } while (0)
+
 // GPU work on a handle: refused for metadata-only handles (opts.device == -1)
 #define KMCPG_USE_DEVICE(db)                                                                                      \
   do {                                                                                                            \
@@ -168,6 +174,9 @@ struct kmcpg_db {
   hipEvent_t fin_ev = nullptr;   // K3's scratch (w_fin_cnt, w_fin_sums) has one user at a time, whatever the k-mer slots do
   bool fin_ev_valid = false;
   bool synthetic = false;
+  bool files_only = false;  // kmcpg_open_files: .uniki files without a __db.yml — inspection and read-back only, every search entry point refuses
+  float last_density_ms = -1;  // HIP-event time of that call's device work (memsets, kernels), before the copy to the host
+  kmcpg_density_launch last_density{};  // what the last kmcpg_block_density / kmcpg_col_ones call launched (density_host.cpp)
   // in-process multi-GPU front handle (kmcpg_open_devices): metadata only itself, one resident shard handle per device
   std::vector<kmcpg_db*> shards;
   kmcpg::Exchange* exchange = nullptr;  // RCCL gather of the shards' hit lists (exchange.cpp); nullptr = host merge

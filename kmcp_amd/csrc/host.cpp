@@ -1268,6 +1268,7 @@ int wait_impl(kmcpg_ticket* t, kmcpg_result* out, bool as_pairs) {
 
 // the submit family works on a handle that holds the whole database and can reach a GPU; *p = the caller's params or the defaults
 int submit_handle(kmcpg_db* db, const kmcpg_params* params, kmcpg_params* p) {
+  KMCPG_NO_FILES_ONLY(db);
   if (db->opts.shard_count != 1)
     return kmcpg_fail(KMCPG_EINVAL, "kmcpg_submit/kmcpg_search_batch need the whole database: open it on one GPU or with kmcpg_open_devices; use kmcpg_query_device + kmcpg_finalize per shard");
   if (db->shards.empty() && db->opts.device < 0 && db->paged_passes == 0) return kmcpg_fail(KMCPG_EDEVICE, "metadata-only handle (device -1): no GPU work possible");

@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "density_core.hpp"
 #include "k1_plan.hpp"
 
 namespace kmcpg {
@@ -61,6 +62,18 @@ void launch_apply_exc(const ExcRun* runs, uint32_t n_runs, uint8_t* out, hipStre
 // text, wpre / vpre: prefix sums of their windows and of those windows' bases) -> src[w] (first base in the text), offs[0 .. n_win]
 void launch_window_desc(const uint64_t* soffs, const uint64_t* wpre, const uint64_t* vpre, uint32_t n_slices, uint64_t n_win, uint64_t step,
                         uint64_t window, uint64_t* src, uint64_t* offs, hipStream_t st);
+
+// index inspection (density.hip): set bits per (column, row bin) of 16-byte lanes lane0 .. lane0 + nlanes - 1 of resident rows,
+// rows first_row .. last_row - 1, bins of bin_rows rows from first_row.  out[bin * width + 128 * (lane - lane0) + column of the lane],
+// zero on entry (bins shared by several waves are added to).  plan_density (density_core.hpp) decides the form and the grid; the host sizes `out` from it.
+int launch_density(const DensityPlan& p, DensityArgs a, hipStream_t st);  // <0 on bad arguments
+// in[b * width + col0 + c] -> out[c * nb + b] for c < ncols, b < nb
+void launch_density_transpose(const uint32_t* in, uint64_t width, uint32_t col0, uint32_t ncols, uint64_t nb, uint32_t* out, hipStream_t st);
+// one bin over a whole group's row (lane0 = 0) -> ones[global column] of the group's members
+void launch_density_cols(const uint32_t* in, const Seg* segs, uint32_t nsegs, uint32_t max_ncols, uint64_t* ones, hipStream_t st);
+
+// bench support: `bytes` of device memory read once, 16 B per lane, one XOR per load (out: one word, never written in practice)
+void launch_stream_probe(const uint8_t* buf, uint64_t bytes, uint32_t* out, hipStream_t st);
 
 // experiment only (KMCPG_DEBUG_ROWSORT): every query's hashes re-ordered by h % num_sigs of one block; mode 2 = rotated
 void launch_debug_rowsort(uint64_t* hashes, const uint64_t* offs, const int32_t* nk, uint32_t n_reads, uint64_t num_sigs, uint64_t mh, int mode, hipStream_t st);

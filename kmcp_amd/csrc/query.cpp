@@ -319,6 +319,7 @@ static int kmers_device(kmcpg_db* db, const DeviceBatch& b, const kmcpg_params* 
                         void* stream) {
   if (!db || !b.d_seqs || !b.d_offs || !d_hashes || !d_nk) return kmcpg_fail(KMCPG_EINVAL, "null argument");
   if (hashes_cap < b.total_bases) return kmcpg_fail(KMCPG_EINVAL, "hashes_cap must be >= total_bases");
+  KMCPG_NO_FILES_ONLY(db);
   std::lock_guard<std::mutex> g(db->mu);
   KMCPG_USE_DEVICE(db);
   const kmcpg_params p = params ? *params : default_params();
@@ -385,6 +386,7 @@ int kmcpg::query_device_after(kmcpg_db* db, const DeviceBatch& b, const kmcpg_pa
                               const std::function<int()>* prologue, int32_t* bound_n) {
   if (!db || !b.d_seqs || !b.d_offs || !out.d_counters || !out.d_qkmers || !out.d_qlen || (!out.d_hits && out.hit_cap)) return kmcpg_fail(KMCPG_EINVAL, "null argument");
   if ((b.d_seqs2 == nullptr) != (b.d_offs2 == nullptr)) return kmcpg_fail(KMCPG_EINVAL, "seqs2 and offs2 must be given together");
+  KMCPG_NO_FILES_ONLY(db);
   std::lock_guard<std::mutex> g(db->mu);
   KMCPG_USE_DEVICE(db);
   if (prologue)

@@ -21,6 +21,8 @@ EXPORTS = [
     "kmcpg_pack2", "kmcpg_unpack2", "kmcpg_submit_packed", "kmcpg_host_alloc", "kmcpg_host_free",
     "kmcpg_kmers_device_packed", "kmcpg_k1_codes_batches",
     "kmcpg_submit_windows", "kmcpg_submit_packed_windows", "kmcpg_window_count", "kmcpg_window_locate",
+    "kmcpg_density_bins", "kmcpg_block_density", "kmcpg_col_ones", "kmcpg_last_density_launch", "kmcpg_open_files",
+    "kmcpg_last_density_ms", "kmcpg_stream_probe",
 ]
 
 
@@ -132,6 +134,20 @@ class K2Launch(C.Structure):
 
 
 K2_KINDS = ("plain", "split", "pair")
+
+
+class DensitySpec(C.Structure):
+    """kmcpg_density_spec: rows first_row .. (n_rows of them, 0 = to the end) in bins of bin_rows rows"""
+    _fields_ = [("bin_rows", C.c_uint64), ("first_row", C.c_uint64), ("n_rows", C.c_uint64), ("reserved", C.c_uint64)]
+
+
+class DensityLaunch(C.Structure):
+    """kmcpg_density_launch: what the last density call launched"""
+    _fields_ = [("form", C.c_int32), ("lpr", C.c_int32), ("npl", C.c_int32), ("reserved", C.c_int32), ("workgroups", C.c_uint32),
+                ("launches", C.c_uint32)]
+
+
+DENSITY_FORMS = ("csa", "small")
 
 
 class SynthSpec(C.Structure):
@@ -250,6 +266,13 @@ def load():
     L.kmcpg_submit_packed_windows.argtypes = [vp, vp, vp, vp, C.c_uint64, C.c_uint32, C.POINTER(WindowSpec), C.POINTER(Params), C.POINTER(vp)]
     L.kmcpg_window_count.argtypes = [vp, C.c_uint32, C.POINTER(WindowSpec), u64p, u64p]
     L.kmcpg_window_locate.argtypes = [vp, C.c_uint32, C.POINTER(WindowSpec), C.c_uint64, C.c_uint64, vp, vp]
+    L.kmcpg_density_bins.argtypes = [vp, C.c_uint32, C.POINTER(DensitySpec), u64p]
+    L.kmcpg_block_density.argtypes = [vp, C.c_uint32, C.POINTER(DensitySpec), vp, C.c_uint64]
+    L.kmcpg_col_ones.argtypes = [vp, vp, C.c_uint64]
+    L.kmcpg_last_density_launch.argtypes = [vp, C.POINTER(DensityLaunch)]
+    L.kmcpg_last_density_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    L.kmcpg_stream_probe.argtypes = [vp, C.POINTER(C.c_float), u64p]
+    L.kmcpg_open_files.argtypes = [C.POINTER(C.c_char_p), C.c_uint32, C.c_int32, C.POINTER(vp)]
     _lib = L
     return L
 
@@ -407,6 +430,56 @@ class Database:
         h = C.c_void_p()
         _check(load().kmcpg_open_paged(os.fsencode(db_dir), device, passes, C.byref(h)))
         return cls(h)
+
+    @classmethod
+    def open_files(cls, paths, device=0):
+        """kmcpg_open_files: a handle over the given .uniki files alone (no __db.yml), blocks numbered in argument order; index
+        inspection and row read-back only, every search entry point refuses.  device=-1: headers only."""
+        h = C.c_void_p()
+        arr = (C.c_char_p * len(paths))(*[os.fsencode(p) for p in paths])
+        _check(load().kmcpg_open_files(arr, len(paths), device, C.byref(h)))
+        return cls(h)
+
+    # ---- index inspection (kmcp utils index-density / ref-info) -------------------------------------------------
+    def density_bins(self, block, bin_rows, first_row=0, n_rows=0, reserved=0):
+        """kmcpg_density_bins: bins of a request (the last one may be short)"""
+        spec = DensitySpec(bin_rows, first_row, n_rows, reserved)
+        n = C.c_uint64(0)
+        _check(load().kmcpg_density_bins(self._h, block, C.byref(spec), C.byref(n)))
+        return int(n.value)
+
+    def block_density(self, block, bin_rows, first_row=0, n_rows=0):
+        """kmcpg_block_density: set bits per (column of the block, bin of bin_rows rows) -> uint32 [n_cols, n_bins]"""
+        n_bins = self.density_bins(block, bin_rows, first_row, n_rows)
+        n_cols = self.block_info(block)["n_cols"]
+        out = np.zeros((n_cols, n_bins), dtype=np.uint32)
+        spec = DensitySpec(bin_rows, first_row, n_rows, 0)
+        _check(load().kmcpg_block_density(self._h, block, C.byref(spec), out.ctypes.data, out.size))
+        return out
+
+    def col_ones(self):
+        """kmcpg_col_ones: set bits of every global column over all its rows (0 for columns of non-local blocks) -> uint64 [n_cols]"""
+        out = np.zeros(int(self.info.n_cols), dtype=np.uint64)
+        _check(load().kmcpg_col_ones(self._h, out.ctypes.data, out.size))
+        return out
+
+    def last_density_launch(self):
+        """what the last block_density / col_ones call launched: dict(form "csa" | "small", lpr, npl, workgroups, launches)"""
+        r = DensityLaunch()
+        _check(load().kmcpg_last_density_launch(self._h, C.byref(r)))
+        return dict(form=DENSITY_FORMS[r.form], lpr=r.lpr, npl=r.npl, workgroups=r.workgroups, launches=r.launches)
+
+    def last_density_ms(self):
+        """HIP-event milliseconds of the device work of the last block_density / col_ones call"""
+        ms = C.c_float()
+        _check(load().kmcpg_last_density_ms(self._h, C.byref(ms)))
+        return float(ms.value)
+
+    def stream_probe(self):
+        """kmcpg_stream_probe: (ms, bytes) of one read-only pass over every resident group's rows, 16 B per lane and one XOR per load"""
+        ms, n = C.c_float(), C.c_uint64()
+        _check(load().kmcpg_stream_probe(self._h, C.byref(ms), C.byref(n)))
+        return float(ms.value), int(n.value)
 
     def save(self, out_dir):
         """kmcpg_save_db: the resident database as <out_dir>/R001 in the reference's on-disk format; returns that directory."""
