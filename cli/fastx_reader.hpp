@@ -33,6 +33,7 @@
 struct FastxRec {
   const char* id = nullptr;
   size_t id_len = 0;
+  size_t name_len = 0;  // the whole header line from `id` on (fastx: record.Name), id_len <= name_len
   const char* seq = nullptr;
   size_t seq_len = 0;
 };
@@ -351,6 +352,7 @@ class FastxReader {
     }
     r->id = buf_.data() + hdr_off_ + 1;
     r->id_len = id_len;
+    r->name_len = hdr_len_ - 1;
     r->seq = joined ? tmp_.data() : buf_.data() + seq_off_;
     r->seq_len = joined ? tmp_.size() : seq_len_;
     return true;

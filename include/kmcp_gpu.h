@@ -476,6 +476,62 @@ int kmcpg_build_db(const char* out_dir, const kmcpg_build_cfg* cfg, const kmcpg_
  * /dev/shm this way and searches it with kmcp-search, FASTQ in, TSV out.  Every block must be resident on the handle. */
 int kmcpg_save_db(kmcpg_db* db, const char* out_dir);
 
+/* -- sketching reference genomes: `kmcp compute` in --split-number mode (kmcp/cmd/compute.go:569-826) without a database handle —
+ *    the records of a file joined, cut into chunks, the k-mers of every chunk hashed (the K1 kernels of the search path, chosen
+ *    through k1_plan.hpp), sorted and de-duplicated (sort_segments.hip: all chunk lists of a batch in one set of launches).  The
+ *    lists slot straight into kmcpg_build_col.  Structs are zeroed, then filled, then validated (as kmcpg_window_spec). */
+typedef struct {
+  int32_t ks[8];        /* k-mer sizes, 1 <= k <= 64 (compute.go:176-181), the first n_k entries; a chunk's list holds the k-mers of all */
+  int32_t n_k;          /* 1 .. 8 */
+  uint32_t scale;       /* -D: 0 / 1 = every k-mer, > 1 = FracMinHash (hash <= maxHash) */
+  uint32_t minimizer_w; /* -W, 0 = off; not together with syncmer_s */
+  uint32_t syncmer_s;   /* -S, 0 = off */
+  uint32_t reserved[4]; /* must be 0 */
+} kmcpg_sketch_cfg;     /* always canonical (compute.go:752) */
+typedef struct {
+  uint32_t split_number;  /* -n: 0 / 1 = one chunk per genome */
+  uint32_t split_overlap; /* -l */
+  uint64_t split_min_ref; /* -m: a shorter genome is one chunk */
+  int32_t k_min, k_max;   /* smallest / largest k of the cfg (k_max is what the joiner pads records with, k_min drops short windows) */
+  uint64_t reserved;      /* must be 0 */
+} kmcpg_split_spec;
+typedef struct kmcpg_sketcher kmcpg_sketcher;
+typedef struct {
+  uint32_t n_chunks;
+  uint32_t reserved;
+  uint32_t* genome;    /* [n_chunks] index of the genome in the batch */
+  uint32_t* chunk_idx; /* [n_chunks] index of the chunk among the genome's surviving chunks */
+  uint32_t* chunks;    /* [n_chunks] the genome's number of chunks */
+  uint64_t* koff;      /* [n_chunks + 1] list i is hashes[koff[i] .. koff[i + 1]) */
+  uint64_t* hashes;    /* ascending, unique; page-locked host memory (as kmcpg_host_alloc gives) */
+  void* owner;         /* internal */
+} kmcpg_sketch_result;
+/* what the segmented sort of the last kmcpg_sketch_genomes call launched, one record per piece of the batch */
+typedef struct {
+  int32_t kind;        /* 0 = segmented LSD radix sort + unique */
+  int32_t passes;      /* 8-bit radix passes: ceil(key_bits / 8) */
+  int32_t key_bits;    /* 64, or the bits of maxHash for FracMinHash sketches */
+  uint32_t segments;   /* chunk lists */
+  uint32_t workgroups; /* of the histogram / scatter launches */
+  uint32_t launches;   /* kernels launched: a function of passes alone */
+  uint64_t keys;       /* raw k-mer hashes sorted */
+} kmcpg_sketch_launch;
+int kmcpg_sketcher_open(const kmcpg_sketch_cfg* cfg, int32_t device, kmcpg_sketcher** out);
+int kmcpg_sketcher_close(kmcpg_sketcher* s);
+/* host only: the chunks [first[i], end[i]) of a joined sequence of `len` bases, in order; *n = how many survive (the genome's
+ * `chunks`), the first min(*n, cap) are written (split_plan.hpp restates compute.go:675-744) */
+int kmcpg_split_bounds(uint64_t len, const kmcpg_split_spec* spec, uint64_t* first, uint64_t* end, uint64_t cap, uint64_t* n);
+/* genome g is seqs[offs[g] .. offs[g + 1]) (host text, the records already joined).  Every genome's bases are uploaded once and the
+ * k-mer kernels read each chunk in place.  A batch whose chunks do not fit the workspace (KMCPG_SKETCH_PIECE_BASES bases of chunks,
+ * default 2^28) is sketched in pieces and answered as one result. */
+int kmcpg_sketch_genomes(kmcpg_sketcher* s, const uint8_t* seqs, const uint64_t* offs, uint32_t n_genomes, const kmcpg_split_spec* spec,
+                         kmcpg_sketch_result* out);
+void kmcpg_sketch_result_free(kmcpg_sketch_result* r);
+/* copies up to `cap` records to out (may be NULL when cap is 0); *n = pieces of the last call */
+int kmcpg_last_sketch_launches(kmcpg_sketcher* s, kmcpg_sketch_launch* out, uint32_t cap, uint32_t* n);
+/* HIP-event milliseconds of the last call's device work: the k-mer kernels, and the segmented sort + unique (bench support) */
+int kmcpg_last_sketch_ms(kmcpg_sketcher* s, float* kmers_ms, float* sort_ms);
+
 #ifdef __cplusplus
 }
 #endif

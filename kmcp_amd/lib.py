@@ -23,6 +23,8 @@ EXPORTS = [
     "kmcpg_submit_windows", "kmcpg_submit_packed_windows", "kmcpg_window_count", "kmcpg_window_locate",
     "kmcpg_density_bins", "kmcpg_block_density", "kmcpg_col_ones", "kmcpg_last_density_launch", "kmcpg_open_files",
     "kmcpg_last_density_ms", "kmcpg_stream_probe",
+    "kmcpg_sketcher_open", "kmcpg_sketcher_close", "kmcpg_split_bounds", "kmcpg_sketch_genomes", "kmcpg_sketch_result_free",
+    "kmcpg_last_sketch_launches", "kmcpg_last_sketch_ms",
 ]
 
 
@@ -150,6 +152,29 @@ class DensityLaunch(C.Structure):
 DENSITY_FORMS = ("csa", "small")
 
 
+class SketchCfg(C.Structure):
+    """kmcpg_sketch_cfg: the sketch of `kmcp compute` (always canonical)"""
+    _fields_ = [("ks", C.c_int32 * 8), ("n_k", C.c_int32), ("scale", C.c_uint32), ("minimizer_w", C.c_uint32), ("syncmer_s", C.c_uint32),
+                ("reserved", C.c_uint32 * 4)]
+
+
+class SplitSpec(C.Structure):
+    """kmcpg_split_spec: -n / -l / -m of `kmcp compute`, and the smallest / largest k of the sketch"""
+    _fields_ = [("split_number", C.c_uint32), ("split_overlap", C.c_uint32), ("split_min_ref", C.c_uint64), ("k_min", C.c_int32),
+                ("k_max", C.c_int32), ("reserved", C.c_uint64)]
+
+
+class SketchResult(C.Structure):
+    _fields_ = [("n_chunks", C.c_uint32), ("reserved", C.c_uint32), ("genome", C.POINTER(C.c_uint32)), ("chunk_idx", C.POINTER(C.c_uint32)),
+                ("chunks", C.POINTER(C.c_uint32)), ("koff", C.POINTER(C.c_uint64)), ("hashes", C.POINTER(C.c_uint64)), ("owner", C.c_void_p)]
+
+
+class SketchLaunch(C.Structure):
+    """kmcpg_sketch_launch: the segmented sort of one piece of a sketch_genomes call"""
+    _fields_ = [("kind", C.c_int32), ("passes", C.c_int32), ("key_bits", C.c_int32), ("segments", C.c_uint32), ("workgroups", C.c_uint32),
+                ("launches", C.c_uint32), ("keys", C.c_uint64)]
+
+
 class SynthSpec(C.Structure):
     _fields_ = [("k", C.c_int32), ("num_hashes", C.c_int32), ("fpr", C.c_double), ("n_blocks", C.c_uint32),
                 ("cols_per_block", C.c_uint32), ("num_sigs", C.c_uint64), ("kmers_per_col", C.c_uint64), ("seed", C.c_uint64),
@@ -273,6 +298,14 @@ def load():
     L.kmcpg_last_density_ms.argtypes = [vp, C.POINTER(C.c_float)]
     L.kmcpg_stream_probe.argtypes = [vp, C.POINTER(C.c_float), u64p]
     L.kmcpg_open_files.argtypes = [C.POINTER(C.c_char_p), C.c_uint32, C.c_int32, C.POINTER(vp)]
+    L.kmcpg_sketcher_open.argtypes = [C.POINTER(SketchCfg), C.c_int32, C.POINTER(vp)]
+    L.kmcpg_sketcher_close.argtypes = [vp]
+    L.kmcpg_split_bounds.argtypes = [C.c_uint64, C.POINTER(SplitSpec), vp, vp, C.c_uint64, u64p]
+    L.kmcpg_sketch_genomes.argtypes = [vp, vp, vp, C.c_uint32, C.POINTER(SplitSpec), C.POINTER(SketchResult)]
+    L.kmcpg_sketch_result_free.argtypes = [C.POINTER(SketchResult)]
+    L.kmcpg_sketch_result_free.restype = None
+    L.kmcpg_last_sketch_launches.argtypes = [vp, C.POINTER(SketchLaunch), C.c_uint32, C.POINTER(C.c_uint32)]
+    L.kmcpg_last_sketch_ms.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     _lib = L
     return L
 
@@ -336,6 +369,104 @@ def build_db(out_dir, columns, k=21, num_hashes=1, fpr=0.3, threads=32, block_si
         arr[i] = BuildCol(name.encode(), gsize, ci, nch, h.ctypes.data, len(h))
     _check(load().kmcpg_build_db(os.fsencode(out_dir), C.byref(cfg), arr, len(columns), device))
     return os.path.join(out_dir, "R001")
+
+
+def split_bounds(length, split_number=1, split_overlap=0, split_min_ref=0, k_min=21, k_max=None):
+    """kmcpg_split_bounds: [(first, end), ...] of the chunks `kmcp compute --split-number` cuts a joined sequence of `length` bases into"""
+    spec = SplitSpec(split_number, split_overlap, split_min_ref, k_min, k_min if k_max is None else k_max, 0)
+    n = C.c_uint64(0)
+    _check(load().kmcpg_split_bounds(length, C.byref(spec), None, None, 0, C.byref(n)))
+    first = np.zeros(n.value, dtype=np.uint64)
+    end = np.zeros(n.value, dtype=np.uint64)
+    if n.value:
+        _check(load().kmcpg_split_bounds(length, C.byref(spec), first.ctypes.data, end.ctypes.data, n.value, C.byref(n)))
+    return [(int(a), int(b)) for a, b in zip(first, end)]
+
+
+class Sketch:
+    """The chunk lists of one Sketcher.sketch call: genome / chunk_idx / chunks per list, and list i = hashes[koff[i]:koff[i + 1]]
+    (sorted, unique).  The arrays are views of library memory until close() (or the end of the `with` block)."""
+
+    def __init__(self, res):
+        self._res = res
+        n = res.n_chunks
+        as_np = lambda p, m, dt: np.ctypeslib.as_array(p, shape=(m,)) if m else np.zeros(0, dtype=dt)  # noqa: E731
+        self.genome = as_np(res.genome, n, np.uint32)
+        self.chunk_idx = as_np(res.chunk_idx, n, np.uint32)
+        self.chunks = as_np(res.chunks, n, np.uint32)
+        self.koff = np.ctypeslib.as_array(res.koff, shape=(n + 1,))
+        self.hashes = as_np(res.hashes, int(self.koff[n]), np.uint64)
+
+    def __len__(self):
+        return len(self.genome)
+
+    def list(self, i):
+        return self.hashes[int(self.koff[i]):int(self.koff[i + 1])]
+
+    def close(self):
+        if self._res is not None:
+            self.genome = self.chunk_idx = self.chunks = self.koff = self.hashes = None
+            load().kmcpg_sketch_result_free(C.byref(self._res))
+            self._res = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class Sketcher:
+    """kmcpg_sketcher: `kmcp compute` for batches of joined genomes on the GPU."""
+
+    def __init__(self, k=21, scale=1, minimizer_w=0, syncmer_s=0, device=0):
+        ks = [k] if isinstance(k, int) else list(k)
+        cfg = SketchCfg(n_k=len(ks), scale=scale, minimizer_w=minimizer_w, syncmer_s=syncmer_s)
+        for i, v in enumerate(ks[:8]):
+            cfg.ks[i] = v
+        if len(ks) > 8:
+            cfg.n_k = 9  # refused by the library
+        self.ks = ks
+        h = C.c_void_p()
+        _check(load().kmcpg_sketcher_open(C.byref(cfg), device, C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if self._h:
+            load().kmcpg_sketcher_close(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def sketch(self, genomes, split_number=1, split_overlap=0, split_min_ref=0):
+        """genomes: list of joined sequences (bytes).  Returns a Sketch."""
+        seqs, offs = pack_reads(list(genomes))
+        spec = SplitSpec(split_number, split_overlap, split_min_ref, min(self.ks), max(self.ks), 0)
+        res = SketchResult()
+        _check(load().kmcpg_sketch_genomes(self._h, seqs.ctypes.data, offs.ctypes.data, len(genomes), C.byref(spec), C.byref(res)))
+        return Sketch(res)
+
+    def last_sketch_launches(self):
+        n = C.c_uint32(0)
+        _check(load().kmcpg_last_sketch_launches(self._h, None, 0, C.byref(n)))
+        arr = (SketchLaunch * max(1, n.value))()
+        _check(load().kmcpg_last_sketch_launches(self._h, arr, n.value, C.byref(n)))
+        return [dict(kind=a.kind, passes=a.passes, key_bits=a.key_bits, segments=a.segments, workgroups=a.workgroups, launches=a.launches,
+                     keys=a.keys) for a in arr[:n.value]]
+
+    def last_sketch_ms(self):
+        a, b = C.c_float(0), C.c_float(0)
+        _check(load().kmcpg_last_sketch_ms(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+
+def last_sketch_launches(sketcher):
+    """kmcpg_last_sketch_launches of a Sketcher"""
+    return sketcher.last_sketch_launches()
 
 
 class BatchResult:
