@@ -40,6 +40,14 @@ namespace kmcpg {
   }
 #endif
 
+// majority of three words alone (one v_bitop3_b32): with c = all ones it is a | b, with c = 0 it is a & b — a bit-sliced compare
+// against a threshold that differs from lane to lane takes its per-plane choice between the two from a mask word (k2_cobs_body.inc)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define MAJ3(a_, b_, c_) __builtin_amdgcn_bitop3_b32((a_), (b_), (c_), 0xE8)
+#else
+#define MAJ3(a_, b_, c_) ((((a_) & (b_)) | (((a_) ^ (b_)) & (c_))))
+#endif
+
 // a carry of plane FROM's weight rippling through the planes above
 template <int NPL, int FROM>
 KMCPG_CSA_HD void ripple(uint32_t (&pl)[NPL], uint32_t e) {

@@ -286,10 +286,27 @@ int finish_open(kmcpg_db* db) {
     HIPCHK(hipMalloc((void**)&db->d_segs, db->h_segs.size() * sizeof(Seg)));
     HIPCHK(hipMemcpy(db->d_segs, db->h_segs.data(), db->h_segs.size() * sizeof(Seg), hipMemcpyHostToDevice));
   }
+  // Block units of the 64-lane class (short reads, k2_cobs_body.inc): the slots of a class are in group order, so the tiles of a group
+  // are a run; the run becomes one slot when the whole row is in this class (no narrower remainder tile) and the count fits the field.
+  for (auto& c : db->classes) {
+    if (c.lpr != 64) continue;
+    for (size_t i = 0; i < c.slots.size();) {
+      size_t j = i;
+      while (j < c.slots.size() && c.slots[j].block == c.slots[i].block) j++;
+      const Group& G = db->groups[c.slots[i].block];
+      const bool whole = (uint64_t)(j - i) * 1024u >= G.stride && j - i <= SLOT_MAX_TILES && c.slots[j - 1].tile < (1u << SLOT_TILE_BITS);
+      if (whole) c.bslots.push_back(Slot{c.slots[i].block, c.slots[i].tile | (uint32_t)(j - i) << SLOT_TILE_BITS});
+      for (size_t t = i; !whole && t < j; t++) c.bslots.push_back(Slot{c.slots[t].block, c.slots[t].tile | 1u << SLOT_TILE_BITS});
+      i = j;
+    }
+  }
   for (auto& c : db->classes) {
     if (db->opts.device < 0) break;
     HIPCHK(hipMalloc((void**)&c.d_slots, c.slots.size() * sizeof(Slot)));
     HIPCHK(hipMemcpy(c.d_slots, c.slots.data(), c.slots.size() * sizeof(Slot), hipMemcpyHostToDevice));
+    if (c.bslots.empty()) continue;
+    HIPCHK(hipMalloc((void**)&c.d_bslots, c.bslots.size() * sizeof(Slot)));
+    HIPCHK(hipMemcpy(c.d_bslots, c.bslots.data(), c.bslots.size() * sizeof(Slot), hipMemcpyHostToDevice));
   }
   db->col_block.clear();
   db->col_meta.clear();
@@ -733,6 +750,8 @@ extern "C" int kmcpg_close(kmcpg_db* db) {
   if (db->d_segs) (void)hipFree(db->d_segs);
   for (auto& c : db->classes)
     if (c.d_slots) (void)hipFree(c.d_slots);
+  for (auto& c : db->classes)
+    if (c.d_bslots) (void)hipFree(c.d_bslots);
   for (auto& w : db->ws) w.release();
   db->w_fin_cnt.release();
   db->w_fin_sums.release();

@@ -67,6 +67,10 @@ struct SlotClass {
   int lpr = 0;
   std::vector<Slot> slots;
   Slot* d_slots = nullptr;
+  // the same tiles as block units (64-lane class only): a group whose tiles all fall into this class is ONE slot, the tiles of any
+  // other group stay one slot each (finish_open)
+  std::vector<Slot> bslots;
+  Slot* d_bslots = nullptr;
 };
 
 template <typename T>

@@ -77,6 +77,72 @@ struct alignas(16) UnitConst {  // one (read, slot) unit as the index phase sees
   int32_t n;        // k-mers of the read handled by this unit
 };
 
+// Hit emission of one tile as a function, for the short-read path of the body, which takes several tiles per wave and emits after each
+// (the body's own epilogue stays where it is: the other forms keep their token stream).  Wave-aggregated as there: bit-sliced compare with
+// cmin, ONE atomic on the global counter for the wave's hits, the tuples side by side; the segment of the previous hit stays in registers.
+template <int NPL>
+__device__ __forceinline__ void k2_emit_tile(const K2Args& a, const BlockDev* __restrict__ bd, uint32_t r, uint32_t boff, uint32_t cmin, bool live,
+                                             const uint32_t (&pl)[4][NPL], int lane) {
+  const bool emit = live && (cmin >> NPL) == 0;  // else: nothing left alive (cmin always fits the planes: query.cpp)
+  uint32_t ge[4];
+  uint32_t mine = 0;
+#pragma unroll
+  for (int d = 0; d < 4; d++) {
+    uint32_t v = emit ? 0xffffffffu : 0u;  // bit-sliced (count >= cmin), LSB to MSB
+#pragma unroll
+    for (int p = 0; p < NPL; p++) v = ((cmin >> p) & 1u) ? (v & pl[d][p]) : (v | pl[d][p]);
+    ge[d] = v;
+    mine += (uint32_t)__popc(v);
+  }
+  if (__ballot(mine != 0) == 0) return;  // wave-uniform: the common case
+  uint32_t incl = mine;  // inclusive prefix sum over the wave
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const uint32_t t = __shfl_up(incl, off);
+    if (lane >= off) incl += t;
+  }
+  const uint32_t total = __shfl(incl, 63);
+  unsigned long long base_idx = 0;
+  if (lane == 63) base_idx = atomicAdd(a.counter, (unsigned long long)total);
+  base_idx = __shfl(base_idx, 63);
+  unsigned long long idx = base_idx + (incl - mine);
+  uint32_t sg_lo = 1, sg_hi = 0, sg_col = 0;  // the segment of the previous hit: bytes [sg_lo, sg_hi), column of its first bit
+  const Seg* __restrict__ segs = a.segs + bd->seg0;
+  const uint32_t nsegs = bd->nsegs;
+#pragma unroll
+  for (int d = 0; d < 4; d++) {
+    uint32_t w = ge[d];
+    while (w) {
+      const int q = __ffs(w) - 1;
+      w &= w - 1;
+      uint32_t count = 0;
+#pragma unroll
+      for (int p = 0; p < NPL; p++) count |= ((pl[d][p] >> q) & 1u) << p;
+      const uint32_t byte = boff + (uint32_t)d * 4u + (uint32_t)(q >> 3);  // bit 7 = first column of the byte (index.go:1157)
+      if (byte < sg_lo || byte >= sg_hi) {
+        for (uint32_t i = 0; i < nsegs; i++) {
+          const Seg sg = segs[i];
+          if (byte < sg.byte_end) {
+            sg_lo = sg.byte_start;
+            sg_hi = sg.byte_end;
+            sg_col = sg.col_base;
+            break;
+          }
+        }
+      }
+      if (idx < a.hit_cap) {
+        kmcpg_hit hit;
+        hit.read = r;
+        hit.col = sg_col + (byte - sg_lo) * 8u + (7u - (uint32_t)(q & 7));
+        hit.count = count;
+        if (byte < sg_lo || byte >= sg_hi) hit = kmcpg_hit{0xffffffffu, 0xffffffffu, 0u};  // a tombstone, as in the body
+        a.hits[idx] = hit;
+      }
+      idx++;
+    }
+  }
+}
+
 // The body lives in k2_cobs_body.inc and is included twice: as the kernel k2_cobs (one launch = one lane form; the token stream the kernel
 // has always had, so the tuned instantiations compile to the ISA they had) and as the device function k2_body, which k2_cobs_pair calls
 // for each of its two lane forms.

@@ -553,12 +553,28 @@ int kmcpg::query_device_after(kmcpg_db* db, const DeviceBatch& b, const kmcpg_pa
     b1.nslots = (uint32_t)db->classes[1].slots.size();
     paired = launch_k2_pair(a1, b1, db->classes[1].lpr, npl, st, k2_log) == 0;
   }
+  // The short-read path of k2_cobs<64, 8|10, false, false, 4> (k2_cobs_body.inc): KMCPG_K2_BLOCK_UNITS=1 — one index phase per (read, block
+  // group), the tiles of the row one after the other in one wave; KMCPG_K2_EXACT_STOP=1 — every sector steps by the rows its best column
+  // proves necessary and stops at its exact row.  Defaults: DESIGN.md §4 (profiles/k2_exact_stop_ab.txt).
+  int32_t short_flags = 0;
+  if (npl <= 10 && a.group_rows == 4 && a.num_hashes == 1 && a.prune && a.prune_every == 1) {
+    if (getenv("KMCPG_K2_BLOCK_UNITS") ? atoi(getenv("KMCPG_K2_BLOCK_UNITS")) != 0 : K2_BLOCK_UNITS_DEFAULT) short_flags |= K2F_BLOCK_UNITS;
+    if (getenv("KMCPG_K2_EXACT_STOP") ? atoi(getenv("KMCPG_K2_EXACT_STOP")) != 0 : K2_EXACT_STOP_DEFAULT) short_flags |= K2F_EXACT_STOP;
+  }
   for (const auto& c : db->classes) {
     if (paired) break;
     a.slots = c.d_slots;
     a.nslots = (uint32_t)c.slots.size();
+    a.k2_flags = c.lpr == 64 ? short_flags : 0;
+    if ((a.k2_flags & K2F_BLOCK_UNITS) && c.d_bslots) {
+      a.slots = c.d_bslots;
+      a.nslots = (uint32_t)c.bslots.size();
+    } else {
+      a.k2_flags &= ~K2F_BLOCK_UNITS;
+    }
     if (launch_k2(a, c.lpr, npl, st, k2_log) != 0) return kmcpg_fail(KMCPG_EINVAL, "batch too large for one launch: split it");
   }
+  a.k2_flags = 0;
   if (n_long) {
     a.ncols_total = (uint32_t)db->info.n_cols;
     // ~64 chunks for the largest query, 1024..8192 k-mers each (at most 8192: the chunk's counts fit 16 planes)
