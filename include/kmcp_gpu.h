@@ -390,6 +390,21 @@ int kmcpg_kmers_device_packed(kmcpg_db* db, const uint8_t* d_codes, const kmcpg_
                               const uint64_t* d_offs, uint32_t n_reads, uint64_t total_bases, uint32_t max_read_len,
                               const kmcpg_params* params, uint64_t* d_hashes, uint64_t hashes_cap, uint64_t* d_koff, int32_t* d_nk,
                               void* stream);
+typedef struct kmcpg_sketch_launch kmcpg_sketch_launch; /* defined with kmcpg_sketch_genomes below */
+/* The segmented sort + unique of kmcpg_sketch_genomes (sort_segments.hip) on lists the caller lays out; needs no handle and runs on
+ * the current device.  Debug/tests.  All pointers but rec are device memory.  List s is the concatenation over parts p < parts of
+ * d_keys[p * part_stride + d_in_off[s] .. + d_cnt[p * cnt_stride + s]); every list lies inside its part, d_keys holds
+ * part_stride * parts words and is left intact (the sort runs on a copy, in the buffer arrangement of kmcpg_sketch_genomes).
+ * key_bits: no key has a bit set at or above it; max_waves: at least the sum over the lists of ceil(keys / 4096).  On return (the
+ * stream synchronised) list s is d_out[d_koff[s] .. d_koff[s + 1]), ascending and unique; d_koff has n_segs + 2 words, the last
+ * one holds the number of raw keys.  out_cap (words of d_out) must be at least part_stride * parts, whatever the lists hold.  rec
+ * (host, may be NULL) receives the launch record.  KMCPG_EINVAL before anything is launched: a null pointer, parts outside 1..8,
+ * key_bits outside 0..64, cnt_stride < n_segs, part_stride >= 2^32, out_cap too small; from the sizes read back: a negative count,
+ * a list outside its part, 2^32 raw keys or more, more raw keys than part_stride * parts (lists that overlap), more waves than
+ * max_waves; and what the sort's launcher itself refuses: key_bits == 0 with max_waves > 0. */
+int kmcpg_sort_segments_device(const uint64_t* d_keys, const uint64_t* d_in_off, const int32_t* d_cnt, uint64_t part_stride,
+                               uint32_t cnt_stride, int32_t parts, uint32_t n_segs, uint32_t max_waves, int32_t key_bits,
+                               uint64_t* d_out, uint64_t out_cap, uint64_t* d_koff, kmcpg_sketch_launch* rec, void* stream);
 /* Batches of this handle so far whose k-mer kernels read 2-bit codes directly (packed whole-genome batches), and packed batches that
  * were expanded to text first. */
 int kmcpg_k1_codes_batches(kmcpg_db* db, uint64_t* direct, uint64_t* expanded);
@@ -507,7 +522,7 @@ typedef struct {
   void* owner;         /* internal */
 } kmcpg_sketch_result;
 /* what the segmented sort of the last kmcpg_sketch_genomes call launched, one record per piece of the batch */
-typedef struct {
+struct kmcpg_sketch_launch {
   int32_t kind;        /* 0 = segmented LSD radix sort + unique */
   int32_t passes;      /* 8-bit radix passes: ceil(key_bits / 8) */
   int32_t key_bits;    /* 64, or the bits of maxHash for FracMinHash sketches */
@@ -515,7 +530,7 @@ typedef struct {
   uint32_t workgroups; /* of the histogram / scatter launches */
   uint32_t launches;   /* kernels launched: a function of passes alone */
   uint64_t keys;       /* raw k-mer hashes sorted */
-} kmcpg_sketch_launch;
+};
 int kmcpg_sketcher_open(const kmcpg_sketch_cfg* cfg, int32_t device, kmcpg_sketcher** out);
 int kmcpg_sketcher_close(kmcpg_sketcher* s);
 /* host only: the chunks [first[i], end[i]) of a joined sequence of `len` bases, in order; *n = how many survive (the genome's

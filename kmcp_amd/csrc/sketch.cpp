@@ -357,3 +357,84 @@ extern "C" int kmcpg_last_sketch_ms(kmcpg_sketcher* s, float* kmers_ms, float* s
   if (sort_ms) *sort_ms = s->sort_ms;
   return 0;
 }
+
+// The segmented sort + unique on lists the caller laid out (tests): the buffers are arranged as sketch_piece arranges them — the raw
+// lists in the sort's buffer a, a second buffer b of the same size — so that the radix passes alternate over the raw lists themselves.
+extern "C" int kmcpg_sort_segments_device(const uint64_t* d_keys, const uint64_t* d_in_off, const int32_t* d_cnt, uint64_t part_stride,
+                                          uint32_t cnt_stride, int32_t parts, uint32_t n_segs, uint32_t max_waves, int32_t key_bits,
+                                          uint64_t* d_out, uint64_t out_cap, uint64_t* d_koff, kmcpg_sketch_launch* rec, void* stream) {
+  if (!d_keys || !d_in_off || !d_cnt || !d_out || !d_koff) return kmcpg_fail(KMCPG_EINVAL, "null argument");
+  if (parts < 1 || parts > 8) return kmcpg_fail(KMCPG_EINVAL, "parts = %d: 1 to 8 wanted", parts);
+  if (key_bits < 0 || key_bits > 64) return kmcpg_fail(KMCPG_EINVAL, "key_bits = %d: 0 to 64 wanted", key_bits);
+  if (cnt_stride < n_segs) return kmcpg_fail(KMCPG_EINVAL, "cnt_stride %u below n_segs %u", cnt_stride, n_segs);
+  if (part_stride >= (1ull << 32) || max_waves >= (1u << 30)) return kmcpg_fail(KMCPG_EINVAL, "fewer than 2^32 raw keys and 2^30 waves wanted");
+  const uint64_t words = part_stride * (uint64_t)parts;
+  if (out_cap < words) return kmcpg_fail(KMCPG_EINVAL, "out_cap %llu below part_stride * parts = %llu", (unsigned long long)out_cap, (unsigned long long)words);
+  hipStream_t st = (hipStream_t)stream;
+  // the sizes come back to the host first: a list outside its part or more waves than max_waves would send the kernels out of bounds
+  std::vector<int32_t> cnt((size_t)parts * n_segs);  // [parts][n_segs]
+  std::vector<uint64_t> off(n_segs);
+  if (n_segs) {
+    for (int p = 0; p < parts; p++)
+      HIPCHK(hipMemcpyAsync(cnt.data() + (size_t)p * n_segs, d_cnt + (size_t)p * cnt_stride, n_segs * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(off.data(), d_in_off, off.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+  }
+  uint64_t total = 0, waves = 0;
+  for (uint32_t s = 0; s < n_segs; s++) {
+    uint64_t n = 0;
+    for (int p = 0; p < parts; p++) {
+      const int32_t c = cnt[(size_t)p * n_segs + s];
+      if (c < 0 || off[s] > part_stride || (uint64_t)c > part_stride - off[s])
+        return kmcpg_fail(KMCPG_EINVAL, "segment %u, part %d: %d keys at in_off %llu do not fit part_stride %llu", s, p, c, (unsigned long long)off[s],
+                          (unsigned long long)part_stride);
+      n += (uint64_t)c;
+    }
+    total += n;
+    waves += seg_sort_waves_for(n);
+  }
+  if (total >= (1ull << 32)) return kmcpg_fail(KMCPG_EINVAL, "%llu raw keys: fewer than 2^32 wanted", (unsigned long long)total);
+  if (total > words)  // lists that overlap: the compact buffers hold part_stride * parts keys
+    return kmcpg_fail(KMCPG_EINVAL, "%llu raw keys in part_stride * parts = %llu words: the lists overlap", (unsigned long long)total, (unsigned long long)words);
+  if (waves > max_waves) return kmcpg_fail(KMCPG_EINVAL, "max_waves %u below the %llu waves of the segments", max_waves, (unsigned long long)waves);
+  const size_t temp_words = seg_sort_temp_words(n_segs, max_waves);
+  uint64_t *a = nullptr, *b = nullptr;
+  uint32_t* temp = nullptr;
+  auto done = [&](int rc) {
+    (void)hipStreamSynchronize(st);
+    if (a) (void)hipFree(a);
+    if (b) (void)hipFree(b);
+    if (temp) (void)hipFree(temp);
+    return rc;
+  };
+  const size_t buf_bytes = (size_t)std::max<uint64_t>(words, 1) * sizeof(uint64_t);
+  if (hipMalloc((void**)&a, buf_bytes) != hipSuccess || hipMalloc((void**)&b, buf_bytes) != hipSuccess ||
+      hipMalloc((void**)&temp, temp_words * sizeof(uint32_t)) != hipSuccess)
+    return done(kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed (%zu bytes of sort buffers)", 2 * buf_bytes + temp_words * sizeof(uint32_t)));
+  if (words && hipMemcpyAsync(a, d_keys, words * sizeof(uint64_t), hipMemcpyDeviceToDevice, st) != hipSuccess)
+    return done(kmcpg_fail(KMCPG_EDEVICE, "copy of the raw lists failed"));
+  SegSortIn in{};
+  in.keys = a;
+  in.in_off = d_in_off;
+  in.cnt = d_cnt;
+  in.part_stride = part_stride;
+  in.cnt_stride = cnt_stride;
+  in.parts = parts;
+  in.n_segs = n_segs;
+  kmcpg_sketch_launch r{};
+  uint64_t* sorted = nullptr;
+  if (seg_sort_unique(in, a, b, max_waves, key_bits, temp, temp_words, d_koff, &sorted, &r, st) != 0) {
+    // of what the launcher refuses before it enqueues anything, only a key width without passes is left after the checks above
+    if (max_waves && !seg_sort_passes(key_bits)) return done(kmcpg_fail(KMCPG_EINVAL, "key_bits = %d sorts no key: max_waves must be 0", key_bits));
+    return done(kmcpg_fail(KMCPG_EDEVICE, "segmented sort of %u lists failed", n_segs));
+  }
+  uint64_t tail[2] = {0, 0};  // unique keys, raw keys
+  if (hipMemcpyAsync(tail, d_koff + n_segs, sizeof tail, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+    return done(kmcpg_fail(KMCPG_EDEVICE, "segmented sort of %u lists failed on the device: %s", n_segs, hipGetErrorString(hipGetLastError())));
+  if (tail[0] > tail[1] || tail[1] != total) return done(kmcpg_fail(KMCPG_EDEVICE, "segmented sort: inconsistent counts (internal error)"));
+  if (tail[0] && hipMemcpyAsync(d_out, sorted, tail[0] * sizeof(uint64_t), hipMemcpyDeviceToDevice, st) != hipSuccess)
+    return done(kmcpg_fail(KMCPG_EDEVICE, "copy of the sorted lists failed"));
+  r.keys = tail[1];
+  if (rec) *rec = r;
+  return done(hipStreamSynchronize(st) == hipSuccess ? 0 : kmcpg_fail(KMCPG_EDEVICE, "stream synchronisation failed"));
+}

@@ -285,6 +285,8 @@ int seg_sort_unique(const SegSortIn& in, uint64_t* a, uint64_t* b, uint32_t max_
                     uint64_t** out, kmcpg_sketch_launch* rec, hipStream_t st) {
   if (in.parts < 1 || in.parts > 8 || key_bits < 0 || key_bits > 64) return -1;
   if (temp_words < seg_sort_temp_words(in.n_segs, max_waves)) return -1;
+  const int passes = seg_sort_passes(key_bits);
+  if (max_waves && !passes) return -1;  // key_bits == 0 with room for keys: every kept hash is > 0.  Refused before anything is enqueued
   uint32_t launches = 0;
 #define SS_LAUNCH(kern, grid, block, ...)                          \
   do {                                                              \
@@ -299,7 +301,6 @@ int seg_sort_unique(const SegSortIn& in, uint64_t* a, uint64_t* b, uint32_t max_
   uint32_t* wave_cnt = hist + table;      // max_waves + 1
   uint32_t* tile_sum = wave_cnt + max_waves + 2;
   const unsigned wgrid = (max_waves + 3) / 4;
-  const int passes = seg_sort_passes(key_bits);
   auto scan = [&](uint32_t* data, uint64_t total) {  // three launches whatever the size
     const unsigned tiles = (unsigned)((total + SS_SCAN_TILE - 1) / SS_SCAN_TILE);
     SS_LAUNCH(k_ss_tile_sums, tiles, 256, data, total, tile_sum);
@@ -315,7 +316,11 @@ int seg_sort_unique(const SegSortIn& in, uint64_t* a, uint64_t* b, uint32_t max_
   const uint64_t* src = nullptr;  // pass 0 reads the raw lists
   uint64_t* dst = b;
   if (max_waves) {
-    if (passes && hipMemsetAsync(hist, 0, table * sizeof(uint32_t), st) != hipSuccess) return -1;  // entries past the last wave stay zero in every pass
+    // max_waves is an upper bound: no wave writes the entries past 256 * wbase[n_segs].  They are zero for the scan of pass 0, which
+    // leaves the number of raw keys in each of them; later passes scan those stale totals again (sums that may wrap).  Harmless: the
+    // scan is exclusive and every real entry precedes them, so no real entry's offset depends on them, and the histogram and scatter
+    // kernels read real entries only.
+    if (hipMemsetAsync(hist, 0, table * sizeof(uint32_t), st) != hipSuccess) return -1;
     for (int p = 0; p < passes; p++) {
       if (p == 0) SS_LAUNCH((k_ss_hist<true>), wgrid, 256, in, src, wbase, cbase, 0, hist);
       else SS_LAUNCH((k_ss_hist<false>), wgrid, 256, in, src, wbase, cbase, p * 8, hist);
@@ -325,7 +330,6 @@ int seg_sort_unique(const SegSortIn& in, uint64_t* a, uint64_t* b, uint32_t max_
       src = dst;
       dst = dst == b ? a : b;
     }
-    if (!src) return -1;  // key_bits == 0 with keys present: every kept hash is > 0
     SS_LAUNCH(k_ss_uq_count, (max_waves + 1 + 3) / 4, 256, in.n_segs, src, wbase, cbase, wave_cnt, max_waves);
     scan(wave_cnt, (uint64_t)max_waves + 1);
     SS_LAUNCH(k_ss_uq_scatter, wgrid, 256, in.n_segs, src, wbase, cbase, wave_cnt, dst);

@@ -24,7 +24,7 @@ EXPORTS = [
     "kmcpg_density_bins", "kmcpg_block_density", "kmcpg_col_ones", "kmcpg_last_density_launch", "kmcpg_open_files",
     "kmcpg_last_density_ms", "kmcpg_stream_probe",
     "kmcpg_sketcher_open", "kmcpg_sketcher_close", "kmcpg_split_bounds", "kmcpg_sketch_genomes", "kmcpg_sketch_result_free",
-    "kmcpg_last_sketch_launches", "kmcpg_last_sketch_ms",
+    "kmcpg_last_sketch_launches", "kmcpg_last_sketch_ms", "kmcpg_sort_segments_device",
 ]
 
 
@@ -306,6 +306,8 @@ def load():
     L.kmcpg_sketch_result_free.restype = None
     L.kmcpg_last_sketch_launches.argtypes = [vp, C.POINTER(SketchLaunch), C.c_uint32, C.POINTER(C.c_uint32)]
     L.kmcpg_last_sketch_ms.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.kmcpg_sort_segments_device.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_int32, C.c_uint32, C.c_uint32, C.c_int32, vp, C.c_uint64, vp,
+                                             C.POINTER(SketchLaunch), vp]
     _lib = L
     return L
 
@@ -467,6 +469,15 @@ class Sketcher:
 def last_sketch_launches(sketcher):
     """kmcpg_last_sketch_launches of a Sketcher"""
     return sketcher.last_sketch_launches()
+
+
+def sort_segments_device(d_keys, d_in_off, d_cnt, part_stride, cnt_stride, parts, n_segs, max_waves, key_bits, d_out, out_cap, d_koff, stream=None):
+    """kmcpg_sort_segments_device (debug/tests): the segmented sort + unique on lists laid out in device memory (pointers as integers).
+    Returns the launch record as Sketcher.last_sketch_launches gives them."""
+    a = SketchLaunch()
+    _check(load().kmcpg_sort_segments_device(d_keys, d_in_off, d_cnt, part_stride, cnt_stride, parts, n_segs, max_waves, key_bits, d_out, out_cap,
+                                             d_koff, C.byref(a), stream))
+    return dict(kind=a.kind, passes=a.passes, key_bits=a.key_bits, segments=a.segments, workgroups=a.workgroups, launches=a.launches, keys=a.keys)
 
 
 class BatchResult:

@@ -19,8 +19,9 @@ MODES = {
 
 
 def expected_lists(O, genomes, mode, n, overlap, min_ref):
-    """[(genome, chunk_idx, chunks, sorted-unique hashes)] as `kmcp compute` + sort would give them"""
-    kw = dict(MODES[mode])
+    """[(genome, chunk_idx, chunks, sorted-unique hashes)] as `kmcp compute` + sort would give them; mode = a key of MODES or the
+    Sketcher's keyword arguments themselves"""
+    kw = dict(MODES[mode] if isinstance(mode, str) else mode)
     ks = kw.pop("k")
     ks = [ks] if isinstance(ks, int) else list(ks)
     cfgs = [O.sketch_cfg(k=k, **kw) for k in ks]
@@ -37,7 +38,7 @@ def expected_lists(O, genomes, mode, n, overlap, min_ref):
 def check(O, genomes, mode, n, overlap, min_ref=0):
     from kmcp_amd import lib
     want = expected_lists(O, genomes, mode, n, overlap, min_ref)
-    with lib.Sketcher(device=0, **MODES[mode]) as sk:
+    with lib.Sketcher(device=0, **(MODES[mode] if isinstance(mode, str) else mode)) as sk:
         with sk.sketch(genomes, split_number=n, split_overlap=overlap, split_min_ref=min_ref) as got:
             assert len(got) == len(want)
             for i, (gi, ci, of, h) in enumerate(want):
@@ -157,3 +158,69 @@ def test_launches_do_not_depend_on_the_number_of_chunks(oracle_lib):
     assert a["launches"] == 2 + 5 * 8 + 5 + 1
     # the same k-mers up to the k - 1 positions lost at every cut
     assert abs(a["keys"] - b["keys"]) <= 20 * 512 and a["keys"] > 33000000
+
+
+# ---- the segmented sort at its edges, through the sketcher (tests/test_gpu_sort_segments.py has the sort alone) ----
+@pytest.mark.parametrize("scale,key_bits,passes,length", [
+    (256, 57, 8, 300000),     # maxHash == 2**56
+    (257, 56, 7, 1500000),    # above 10000 hashes kept: a list longer than one wave, 7 passes (the result lands in the other buffer)
+    (1000, 55, 7, 3000000),   # the scale of the genome-search index
+    (65537, 48, 6, 1500000),
+])
+def test_fracminhash_scales_skip_radix_passes(oracle_lib, scale, key_bits, passes, length):
+    O = oracle_lib
+    g = synth.random_genomes(1, length, seed=310 + passes)[0]
+    genomes = [g, g[:length // 7], g[1000:1000 + length // 3]]
+    want, launches = check(O, genomes, dict(k=21, scale=scale), n=1, overlap=0)
+    assert len(want) == 3 and len(launches) == 1
+    assert (launches[0]["key_bits"], launches[0]["passes"]) == (key_bits, passes)
+    assert int(O.lib().ko_max_hash(scale)).bit_length() == key_bits
+    assert max(int(w[3][-1]) for w in want if len(w[3])).bit_length() <= key_bits
+    if scale in (257, 1000):
+        assert len(want[0][3]) > 4096, len(want[0][3])
+
+
+@pytest.mark.parametrize("kw", [dict(k=21, scale=300, syncmer_s=11), dict(k=21, scale=300, minimizer_w=8)], ids=["syncmer", "minimizer"])
+def test_fracminhash_of_syncmers_and_minimizers(oracle_lib, kw):
+    """key_bits < 64 relies on every k-mer kernel form dropping hashes above maxHash"""
+    O = oracle_lib
+    base = synth.random_genomes(1, 700000, seed=320)[0]
+    genomes = [base, decorated(200000, 321), base[5000:5100], base[:70000]]
+    want, launches = check(O, genomes, kw, n=4, overlap=30, min_ref=1000)
+    assert len(want) == 4 + 4 + 1 + 4 and len(launches) == 1
+    assert (launches[0]["key_bits"], launches[0]["passes"]) == (56, 7)
+    assert sum(len(w[3]) for w in want) > 300
+
+
+def test_eight_kmer_sizes(oracle_lib):
+    """eight parts, the upper ones empty for the short genomes"""
+    O = oracle_lib
+    ks = (15, 21, 25, 31, 41, 51, 61, 64)
+    base = synth.random_genomes(1, 40000, seed=330)[0]
+    genomes = [base[:30], base, base[100:164], decorated(9000, 331), base[:63], base[200:215]]
+    assert len(genomes[0]) == 30 and len(genomes[2]) == 64
+    want, launches = check(O, genomes, dict(k=ks), n=1, overlap=0)
+    assert len(want) == len(genomes) and len(launches) == 1
+    cfgs = [O.sketch_cfg(k=k) for k in ks]
+    assert [len(O.generate_kmers(genomes[0], c)) for c in cfgs] == [16, 10, 6, 0, 0, 0, 0, 0]
+    assert [len(O.generate_kmers(genomes[2], c)) for c in cfgs] == [50, 44, 40, 34, 24, 14, 4, 1]
+    assert launches[0]["keys"] == sum(len(O.generate_kmers(g, c)) for g in genomes for c in cfgs)
+    want, _ = check(O, genomes, dict(k=ks), n=3, overlap=20, min_ref=1000)
+    assert len(want) == 1 + 3 + 1 + 3 + 1 + 0
+
+
+def test_chunks_of_an_exact_number_of_kmers(oracle_lib):
+    """lists of 4095, 4096, 4097 and 8192 raw keys (a wave of the sort owns 4096), lists of equal keys and identical neighbours"""
+    O = oracle_lib
+    cfg = O.sketch_cfg(k=21)
+    r = synth.random_genomes(2, 20000, seed=340)
+    rep = r[1][:6000]
+    genomes = [r[0][:4095 + 20], r[0][:4096 + 20], r[0][5000:5000 + 4097 + 20], r[0][10000:10000 + 8192 + 20], b"N" * 200, b"A" * 9000, b"AC" * 4500,
+               rep, rep, rep]
+    raw = [len(O.generate_kmers(g, cfg)) for g in genomes]
+    assert raw == [4095, 4096, 4097, 8192, 0, 8980, 8980, 5980, 5980, 5980]
+    want, launches = check(O, genomes, "plain", n=1, overlap=0)
+    assert len(want) == len(genomes) and [w[0] for w in want] == list(range(len(genomes)))
+    assert [len(w[3]) for w in want[4:7]] == [0, 1, 2]
+    assert np.array_equal(want[7][3], want[8][3]) and np.array_equal(want[8][3], want[9][3])
+    assert launches[0]["keys"] == sum(raw) and launches[0]["passes"] == 8
