@@ -80,6 +80,8 @@ static void warn(const char* fmt, ...) {
 struct Options {
   std::string db_dir, out_file = "-", read1, read2, query_id, sort_by = "qcov", infile_list, log_file;
   std::vector<std::string> name_maps, files;
+  std::vector<std::string> also_dbs;  // --also-db: further databases searched in the same pass, the output merged as kmcp-merge would
+  bool gpus_given = false;
   int min_qlen = 30, min_kmers = 10, dedup = 256, top_scores = 0, threads = 0, device = 0, batch = 131072, gpus = 1, gpu_passes = -1;
   bool batch_given = false;
   // --sliding-step / --sliding-window / --sliding-greedy: every record searched as the windows `seqkit sliding -s S -W W [-g]` would cut
@@ -111,6 +113,10 @@ static void usage() {
       "           --gpu-ids a,b,c (explicit device list)  --gpu-batch int (queries per GPU call, default 131072)\n"
       "           --gpu-passes int (an index larger than the GPU's memory is searched in this many passes per batch, one part\n"
       "                             resident at a time; 0 = as few as fit; default: only when the index does not fit)\n"
+      "           --also-db dir (repeatable, up to 15) search these databases too, in the same pass: all of them resident on the one GPU, the\n"
+      "                             reads parsed once, and the output is what `kmcp-merge -s <the same -s>` makes of one kmcp-search run per\n"
+      "                             database (-d first, then every --also-db in order).  The databases must agree in k, sketching, number of\n"
+      "                             hashes and FPR.  Not with -K, --try-se, -S, -n, -g/-G, --sliding-*, --gpus/--gpu-ids, --gpu-passes.\n"
       "           --parse-only (read the inputs and print records / bases / checksum per file; no database, no GPU)\n"
       "Long reads and contigs (the reference's advice: split them with `seqkit sliding -s 100 -W 300`, search the pieces):\n"
       "           --sliding-step int --sliding-window int [--sliding-greedy]\n"
@@ -144,7 +150,7 @@ static Options parse_args(int argc, char** argv) {
       {"name-map", 'N', 1}, {"default-name-map", 'D', 0}, {"keep-unmatched", 'K', 0}, {"keep-top-scores", 'n', 1}, {"no-header-row", 'H', 0},
       {"sort-by", 's', 1}, {"do-not-sort", 'S', 0}, {"threads", 'j', 1}, {"quiet", 'q', 0}, {"infile-list", 'i', 1}, {"log", 0, 1},
       {"gpu", 0, 1}, {"gpu-batch", 0, 1}, {"gpus", 0, 1}, {"gpu-ids", 0, 1}, {"gpu-passes", 0, 1}, {"parse-only", 0, 0}, {"help", 'h', 0}, {"version", 'V', 0},
-      {"sliding-step", 0, 1}, {"sliding-window", 0, 1}, {"sliding-greedy", 0, 0}};
+      {"sliding-step", 0, 1}, {"sliding-window", 0, 1}, {"sliding-greedy", 0, 0}, {"also-db", 0, 1}};
   auto apply = [&](const std::string& name, const std::string& v) {
     if (name == "db-dir") o.db_dir = v;
     else if (name == "out-file") o.out_file = v;
@@ -187,8 +193,10 @@ static Options parse_args(int argc, char** argv) {
     else if (name == "sliding-step") { o.sliding_step = to_i(name, v); o.sliding_step_given = true; }
     else if (name == "sliding-window") { o.sliding_window = to_i(name, v); o.sliding_window_given = true; }
     else if (name == "sliding-greedy") o.sliding_greedy = true;
-    else if (name == "gpus") o.gpus = to_i(name, v);
+    else if (name == "also-db") o.also_dbs.push_back(v);
+    else if (name == "gpus") { o.gpus = to_i(name, v); o.gpus_given = true; }
     else if (name == "gpu-ids") {
+      o.gpus_given = true;
       size_t b = 0;
       while (b <= v.size()) {
         size_t e = v.find(',', b);
@@ -925,6 +933,17 @@ int main(int argc, char** argv) {
     if (o.whole_file || o.use_filename) die("flags --sliding-step/--sliding-window cannot be combined with -g/--query-whole-file or -G/--use-filename");
     if (!o.query_id.empty()) die("flags --sliding-step/--sliding-window cannot be combined with --query-id");
   }
+  // --also-db: whatever acts per database in separate runs and would act per query on the union is refused here, before a file is
+  // opened or a GPU touched (the library refuses the same through its parameters)
+  if (!o.also_dbs.empty()) {
+    const char* clash = o.keep_unmatched ? "-K/--keep-unmatched" : o.try_se ? "--try-se" : o.do_not_sort ? "-S/--do-not-sort" : o.top_scores != 0 ? "-n/--keep-top-scores"
+                      : o.whole_file ? "-g/--query-whole-file" : o.use_filename ? "-G/--use-filename" : sliding ? "--sliding-step/--sliding-window/--sliding-greedy"
+                      : o.gpus_given ? "--gpus/--gpu-ids" : o.gpu_passes >= 0 ? "--gpu-passes" : nullptr;
+    if (clash)
+      die("flag %s cannot be combined with --also-db: in separate searches it acts per database, on databases searched together it would act per query; "
+          "search the databases one by one and merge the results with kmcp-merge", clash);
+    if (o.also_dbs.size() > 15) die("flag --also-db: at most 15 further databases (%zu given)", o.also_dbs.size());
+  }
   kmcpg_window_spec wspec{(uint64_t)std::max(0ll, o.sliding_step), (uint64_t)std::max(0ll, o.sliding_window), o.sliding_greedy ? 1 : 0, 0};
   if (o.db_dir.empty()) die("flag -d/--db-dir needed");
   if (o.min_kmers < 1) die("value of flag --min-kmers should be positive: %d", o.min_kmers);
@@ -989,11 +1008,12 @@ int main(int argc, char** argv) {
   }
 
   // ---- database: sub-directories holding __db.yml (search.go:299-324)
-  if (verbose) info("checking the database: %s", o.db_dir.c_str());
-  std::vector<std::string> db_dirs;
-  {
-    DIR* d = opendir(o.db_dir.c_str());
-    if (!d) die("read database error: open %s: %s", o.db_dir.c_str(), strerror(errno));
+  std::vector<std::string> db_dirs;  // the R001 directory of -d, then of every --also-db
+  auto resolve_db = [&](const std::string& root) {
+    if (verbose) info("checking the database: %s", root.c_str());
+    std::vector<std::string> found;
+    DIR* d = opendir(root.c_str());
+    if (!d) die("read database error: open %s: %s", root.c_str(), strerror(errno));
     std::vector<std::string> subs;
     while (struct dirent* e = readdir(d)) {
       std::string n = e->d_name;
@@ -1004,13 +1024,16 @@ int main(int argc, char** argv) {
     std::sort(subs.begin(), subs.end());
     for (const auto& n : subs) {
       struct stat st;
-      std::string p = o.db_dir + "/" + n;
+      std::string p = root + "/" + n;
       if (stat(p.c_str(), &st) != 0 || !S_ISDIR(st.st_mode)) continue;
-      if (stat((p + "/__db.yml").c_str(), &st) == 0) db_dirs.push_back(p);
+      if (stat((p + "/__db.yml").c_str(), &st) == 0) found.push_back(p);
     }
-  }
-  if (db_dirs.empty()) die("invalid kmcp database: %s", o.db_dir.c_str());
-  if (db_dirs.size() > 1) die("databases with several repeats (R001, R002, ...) are not supported: `kmcp index` only writes R001");
+    if (found.empty()) die("invalid kmcp database: %s", root.c_str());
+    if (found.size() > 1) die("databases with several repeats (R001, R002, ...) are not supported: `kmcp index` only writes R001");
+    db_dirs.push_back(found[0]);
+  };
+  resolve_db(o.db_dir);
+  for (const auto& a : o.also_dbs) resolve_db(a);
 
   std::unordered_map<std::string, std::string> name_map;
   const bool mapping = !o.name_maps.empty();
@@ -1020,12 +1043,13 @@ int main(int argc, char** argv) {
       for (auto& kv : read_kvs(f)) name_map[kv.first] = kv.second;
     if (verbose) info("  %zu pairs of name mapping values from %zu file(s) loaded", name_map.size(), o.name_maps.size());
   }
-  std::unordered_map<std::string, std::string> default_map;
-  if (o.default_name_map) {
-    struct stat st;
-    std::string f = db_dirs[0] + "/__name_mapping.tsv";
-    if (stat(f.c_str(), &st) == 0) default_map = read_kvs(f);
-  }
+  std::vector<std::unordered_map<std::string, std::string>> default_maps(db_dirs.size());  // -D: every database's own mapping, for its own columns
+  if (o.default_name_map)
+    for (size_t m = 0; m < db_dirs.size(); m++) {
+      struct stat st;
+      std::string f = db_dirs[m] + "/__name_mapping.tsv";
+      if (stat(f.c_str(), &st) == 0) default_maps[m] = read_kvs(f);
+    }
 
   // ---- the reader starts NOW, before the database is opened: parsing the input needs neither the GPU nor the index, and the HIP
   //      runtime alone takes 0.2 s to come up (tools/ubench_init.cpp) — by the time the index is resident the first batches (up to
@@ -1205,7 +1229,13 @@ int main(int argc, char** argv) {
   int32_t paged_passes = 0;
   if (o.gpu_ids.empty() && o.gpus > 1)
     for (int i = 0; i < o.gpus; i++) o.gpu_ids.push_back(i);
-  if (!o.gpu_ids.empty()) {  // one process, several GPUs: blocks partitioned over the devices, hits merged on the host
+  if (db_dirs.size() > 1) {  // --also-db: one handle over all the databases (kmcp_gpu.h kmcpg_open_set)
+    std::vector<const char*> dirs;
+    for (const auto& d : db_dirs) dirs.push_back(d.c_str());
+    kmcpg_opts gopts{o.device, 0, 1, 0};
+    if (kmcpg_open_set(dirs.data(), (uint32_t)dirs.size(), &gopts, &db) != 0) die("open kmcp dbs: %s", kmcpg_last_error());
+    if (verbose) info("  %zu databases searched together, results merged as kmcp-merge would", db_dirs.size());
+  } else if (!o.gpu_ids.empty()) {  // one process, several GPUs: blocks partitioned over the devices, hits merged on the host
     if (kmcpg_open_devices(db_dirs[0].c_str(), o.gpu_ids.data(), (int32_t)o.gpu_ids.size(), &db) != 0)
       die("open kmcp db: %s: %s", db_dirs[0].c_str(), kmcpg_last_error());
     if (verbose) info("  %zu GPUs, exchange of the hit lists: %s", o.gpu_ids.size(), kmcpg_exchange_info(db));
@@ -1267,7 +1297,11 @@ int main(int argc, char** argv) {
   }
   // target names after mapping (util-db-search.go:317-332), resolved once per column
   std::vector<std::string> target(dbi.n_cols);
-  for (uint32_t c = 0; c < dbi.n_cols; c++) {
+  uint32_t member_base[16] = {0}, n_members = 0;
+  if (kmcpg_set_info(db, &n_members, member_base, 16) != 0) die("%s", kmcpg_last_error());
+  for (uint32_t c = 0, member = 0; c < dbi.n_cols; c++) {
+    while (member + 1 < n_members && member + 1 < 16 && c >= member_base[member + 1]) member++;
+    const auto& default_map = default_maps[std::min<size_t>(member, default_maps.size() - 1)];
     const char* nm = nullptr;
     kmcpg_col_info(db, c, &nm, nullptr, nullptr, nullptr);
     target[c] = nm;

@@ -119,6 +119,37 @@ typedef struct {
 /* -- lifecycle: replaces NewUnikIndexDB / NewUnikIndex (util-db-search.go:648-743, 1196-1280) and
  *    UnikIndexDB.Close (:1119-1150).  db_dir is the directory holding __db.yml (e.g. <db>/R001). */
 int kmcpg_open(const char* db_dir, const kmcpg_opts* opts, kmcpg_db** out);
+/* -- database sets: several databases searched in one pass, merged as `kmcp-merge` merges their separate results (the reference's profiling
+ *    workflow: the same reads against GTDB, viral, fungi, then `kmcp merge`, kmcp/cmd/merge.go:40-420).  The members are opened as ONE handle on
+ *    ONE GPU: the blocks of member m follow those of member m - 1, global columns are numbered over all of them (kmcpg_col_info /
+ *    kmcpg_block_info work over the union), every member is resident (KMCPG_ENOMEM with the bytes needed / free, as kmcpg_open, when the
+ *    sum does not fit).  opts->device == -1 opens metadata only.  1 to 16 members; with one member the handle IS a kmcpg_open handle.
+ *    Contract: the result of every query is, byte for byte once printed, what kmcp-merge -s <sort_by> makes of the members' separate
+ *    kmcp-search results — rows ordered by the PRINTED score (%.4f of qCov / tCov / jacc) descending, equal printed scores by member
+ *    (argument order), then in the member's own row order; match_offs[i + 1] - match_offs[i] is the merged `hits`.
+ *    The members must agree in everything a query's k-mers and thresholds depend on — one k-mer size each and the same one, canonical,
+ *    scale, minimizer_w, syncmer_s, numHashes, fpr (the k-mer kernels run once per batch, a query has one NumKmers, the -f bound on the device
+ *    is one table): KMCPG_EUNSUPPORTED names the field and the two directories.  Databases that disagree are searched one by one and merged
+ *    with kmcp-merge.
+ *    Refused on a set of two members or more (KMCPG_EUNSUPPORTED; each acts per member in separate runs and would act per query on the
+ *    union): params try_se, do_not_sort, top_n_scores != 0, k != 0; kmcpg_save_db, kmcpg_submit_windows, kmcpg_submit_packed_windows,
+ *    kmcpg_submit_packed; shard_count > 1.  There is no set form of kmcpg_open_paged / kmcpg_open_devices.  Everything else — kmcpg_submit,
+ *    kmcpg_wait[_pairs], kmcpg_search_batch[_pairs], kmcpg_expand_pairs, paired-end input, lanes and tickets, kmcpg_query_device +
+ *    kmcpg_group_device + kmcpg_finalize[_grouped] — works as on any other handle. */
+int kmcpg_open_set(const char* const* db_dirs, uint32_t n, const kmcpg_opts* opts, kmcpg_db** out);
+/* *n_members = members of the handle (1 for kmcpg_open handles, 0 for synthetic / files-only ones); the first global column of the first
+ * min(*n_members, cap) members is written to first_col */
+int kmcpg_set_info(const kmcpg_db* db, uint32_t* n_members, uint32_t* first_col, uint32_t cap);
+/* What put the segments (the matches of one query) of a set handle into the merge order.  The device words are those of the handle's LAST
+ * K3 launch (kmcpg_submit / kmcpg_search_batch / kmcpg_group_device; the call waits for the device to go idle): segments of 2 .. 512
+ * matches ordered by the wave class of the sort kernels, of up to 4096 by the workgroup class, longer ones left to the host, and the runs
+ * of equal printed score that held matches of more than one member (the tie rule at work).  The host words count what the host half has
+ * ordered itself since that launch (segments above 4096, every segment with KMCPG_DEVICE_FINALIZE=0 or through kmcpg_finalize).  Tests. */
+typedef struct {
+  uint64_t wave_segments, wg_segments, long_segments, device_mixed_runs;
+  uint64_t host_segments, host_mixed_runs;
+} kmcpg_set_order;
+int kmcpg_last_set_order(kmcpg_db* db, kmcpg_set_order* out);
 /* One host process, several GPUs (what a cgo host needs): the blocks are partitioned over `devices`, kmcpg_search_batch fans
  * every batch out to all of them from one host thread per GPU; the per-read hit lists of the shards are gathered on the first
  * GPU with RCCL (grouped ncclSend/ncclRecv over xGMI of exactly the bytes each shard produced; librccl is bound at run time)

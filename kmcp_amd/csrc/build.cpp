@@ -262,6 +262,7 @@ extern "C" int kmcpg_build_db(const char* out_dir, const kmcpg_build_cfg* cfg, c
 // util-db-info.go:46-79).  bench.py's end-to-end leg uses it to put BASELINE configs[1] on /dev/shm.  Every block must be resident.
 extern "C" int kmcpg_save_db(kmcpg_db* db, const char* out_dir) {
   if (!db || !out_dir) return kmcpg_fail(KMCPG_EINVAL, "null argument");
+  if (int rc = kmcpg::set_refuse_entry(db, "kmcpg_save_db")) return rc;
   for (const auto& b : db->blocks)
     if (!b.local) return kmcpg_fail(KMCPG_EINVAL, "kmcpg_save_db needs every block resident on this handle (one GPU, one shard)");
   const std::string dir = std::string(out_dir) + "/R001";

@@ -199,4 +199,14 @@ struct K3Args {
   uint32_t* bad;            // hits naming a read / column that does not exist (an internal error: the caller reports it)
 };
 
+// Database sets (kmcpg_open_set): what the sort kernels of a set handle get beside K3Args (k3_set_order.hpp; layout at the top of
+// k3_finalize.hip).  stats: four device words the kernels add to — segments sorted by the wave class (2 .. K3_WAVE_CAP matches), by the
+// workgroup class (.. K3_WG_CAP), segments left to the host (longer), runs of equal fixed4 holding more than one member.
+constexpr int K3_SET_STATS = 4;
+struct K3SetArgs {
+  uint32_t n_members;   // 2 .. 16
+  uint32_t base[16];    // first global column of every member, ascending
+  uint32_t* stats;
+};
+
 }  // namespace kmcpg

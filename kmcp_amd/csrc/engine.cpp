@@ -30,6 +30,7 @@
 #include "exchange.hpp"
 #include "fpr.hpp"
 #include "kernels.hpp"
+#include "k3_set_order.hpp"
 
 using namespace kmcpg;
 
@@ -508,6 +509,8 @@ int open_like(const kmcpg_db* src, const kmcpg_opts* opts, kmcpg_db** out) {
   const bool meta_only = db->opts.device < 0;
   if (!meta_only) HIPCHK(hipSetDevice(db->opts.device));
   db->db_dir = src->db_dir;
+  db->set_dirs = src->set_dirs;
+  db->set_col_base = src->set_col_base;
   db->ks_desc = src->ks_desc;
   db->info = src->info;
   db->blocks = src->blocks;
@@ -534,8 +537,10 @@ int open_like(const kmcpg_db* src, const kmcpg_opts* opts, kmcpg_db** out) {
 }
 }  // namespace kmcpg
 
-extern "C" int kmcpg_open(const char* db_dir, const kmcpg_opts* opts, kmcpg_db** out) {
-  if (!db_dir || !out) return kmcpg_fail(KMCPG_EINVAL, "null argument");
+// kmcpg_open (n == 1) and kmcpg_open_set: the blocks of member m follow those of member m - 1, global columns are numbered over all of
+// them, and from there on the handle is one database — one partition into groups (blocks of different members that share NumSigs are
+// laid side by side as any others are), one upload, one set of tables.
+static int open_dirs(const char* const* db_dirs, uint32_t n_dirs, const kmcpg_opts* opts, kmcpg_db** out) {
   *out = nullptr;
   DbPtr db(new kmcpg_db());
   int rc = check_opts(opts, &db->opts);
@@ -553,19 +558,38 @@ extern "C" int kmcpg_open(const char* db_dir, const kmcpg_opts* opts, kmcpg_db**
   };
   if (!meta_only) HIPCHK(hipSetDevice(db->opts.device));
   lap("hipSetDevice (runtime init)");
-  const std::string dir(db_dir);
-  db->db_dir = dir;
+  db->db_dir = db_dirs[0];
+  kmcpg_info& I = db->info;
+  uint32_t base = 0;
+  // the blocks of one member, in its __db.yml `files` order, behind those already there
+  auto add_blocks = [&](const std::string& dir, const DbYml& y) -> int {
+    db->set_dirs.push_back(dir);
+    db->set_col_base.push_back(base);
+    for (const auto& fn : y.files) {
+      BlockMeta b;
+      b.path = dir + "/" + fn;
+      const std::string e = read_uniki_header(b.path, &b.h);
+      if (!e.empty()) return kmcpg_fail(e.find("missing") != std::string::npos ? KMCPG_EIO : KMCPG_EFORMAT, "%s", e.c_str());
+      // compatibility checks of NewUnikIndexDB (:689-695) and Header.Compatible (serialization.go:90-99)
+      if (b.h.k != I.k || b.h.canonical != (bool)y.canonical || b.h.num_hashes != y.num_hashes || (y.uniki_version >= 0 && y.uniki_version != b.h.version))
+        return kmcpg_fail(KMCPG_EFORMAT, "index files not compatible");
+      if ((uint64_t)base + b.h.names.size() > 0xffffffffull) return kmcpg_fail(KMCPG_EUNSUPPORTED, "more than 2^32 - 1 columns");
+      b.col_base = base;
+      base += (uint32_t)b.h.names.size();
+      I.matrix_bytes += b.h.num_sigs * (uint64_t)b.h.row_bytes;
+      db->blocks.push_back(std::move(b));
+    }
+    return 0;
+  };
   DbYml y;
-  std::string e = read_db_yml(dir + "/__db.yml", &y);
+  std::string e = read_db_yml(std::string(db_dirs[0]) + "/__db.yml", &y);
   if (!e.empty()) return kmcpg_fail(e.find("open") != std::string::npos ? KMCPG_EIO : KMCPG_EFORMAT, "%s", e.c_str());
   // a database may hold several k-mer sizes (`ks`); queries start with the largest and fall back to smaller ones
   // (util-db-search.go:752-758, :1016-1022); the .uniki headers carry the largest (:690)
   db->ks_desc = y.ks.empty() ? std::vector<int>{y.k} : y.ks;
   std::sort(db->ks_desc.begin(), db->ks_desc.end(), [](int a, int b) { return a > b; });
   db->ks_desc.erase(std::unique(db->ks_desc.begin(), db->ks_desc.end()), db->ks_desc.end());
-  int k = db->ks_desc[0];
-  kmcpg_info& I = db->info;
-  I.k = k;
+  I.k = db->ks_desc[0];
   I.canonical = y.canonical;
   I.num_hashes = y.num_hashes;
   I.scaled = y.scaled;
@@ -575,19 +599,39 @@ extern "C" int kmcpg_open(const char* db_dir, const kmcpg_opts* opts, kmcpg_db**
   I.syncmer = y.syncmer;
   I.syncmer_s = y.syncmer_s;
   I.fpr = y.fpr;
-  uint32_t base = 0;
-  for (const auto& fn : y.files) {
-    BlockMeta b;
-    b.path = dir + "/" + fn;
-    e = read_uniki_header(b.path, &b.h);
-    if (!e.empty()) return kmcpg_fail(e.find("missing") != std::string::npos ? KMCPG_EIO : KMCPG_EFORMAT, "%s", e.c_str());
-    // compatibility checks of NewUnikIndexDB (:689-695) and Header.Compatible (serialization.go:90-99)
-    if (b.h.k != k || b.h.canonical != (bool)y.canonical || b.h.num_hashes != y.num_hashes || (y.uniki_version >= 0 && y.uniki_version != b.h.version))
-      return kmcpg_fail(KMCPG_EFORMAT, "index files not compatible");
-    b.col_base = base;
-    base += (uint32_t)b.h.names.size();
-    I.matrix_bytes += b.h.num_sigs * (uint64_t)b.h.row_bytes;
-    db->blocks.push_back(std::move(b));
+  rc = add_blocks(db_dirs[0], y);
+  if (rc) return rc;
+  // The further members of a set must agree with the first in everything a query's k-mers and thresholds depend on: the k-mer kernels
+  // run once per batch for all members, a query has one NumKmers, and the -f bound on the device is one table.
+  for (uint32_t mi = 1; mi < n_dirs; mi++) {
+    const std::string dir(db_dirs[mi]);
+    DbYml z;
+    e = read_db_yml(dir + "/__db.yml", &z);
+    if (!e.empty()) return kmcpg_fail(e.find("open") != std::string::npos ? KMCPG_EIO : KMCPG_EFORMAT, "%s", e.c_str());
+    auto mismatch = [&](const char* field, const std::string& a, const std::string& b) {
+      return kmcpg_fail(KMCPG_EUNSUPPORTED, "database set: the members disagree in %s (%s in %s, %s in %s): search them separately and merge the results with kmcp-merge",
+                        field, a.c_str(), db_dirs[0], b.c_str(), dir.c_str());
+    };
+    auto ks_of = [](const DbYml& d) {
+      std::vector<int> ks = d.ks.empty() ? std::vector<int>{d.k} : d.ks;
+      std::sort(ks.begin(), ks.end());
+      ks.erase(std::unique(ks.begin(), ks.end()), ks.end());
+      std::string t;
+      for (int k : ks) t += (t.empty() ? "" : ",") + std::to_string(k);
+      return t;
+    };
+    const std::string k0 = ks_of(y), k1 = ks_of(z);
+    if (k0.find(',') != std::string::npos || k1.find(',') != std::string::npos || k0 != k1) return mismatch("k (one k-mer size each, and the same one)", k0, k1);
+    if ((bool)y.canonical != (bool)z.canonical) return mismatch("canonical", std::to_string(y.canonical), std::to_string(z.canonical));
+    if ((bool)y.scaled != (bool)z.scaled || y.scale != z.scale) return mismatch("scale", std::to_string(y.scaled ? y.scale : 1), std::to_string(z.scaled ? z.scale : 1));
+    if ((bool)y.minimizer != (bool)z.minimizer || y.minimizer_w != z.minimizer_w)
+      return mismatch("minimizer_w", std::to_string(y.minimizer ? y.minimizer_w : 0), std::to_string(z.minimizer ? z.minimizer_w : 0));
+    if ((bool)y.syncmer != (bool)z.syncmer || y.syncmer_s != z.syncmer_s)
+      return mismatch("syncmer_s", std::to_string(y.syncmer ? y.syncmer_s : 0), std::to_string(z.syncmer ? z.syncmer_s : 0));
+    if (y.num_hashes != z.num_hashes) return mismatch("numHashes", std::to_string(y.num_hashes), std::to_string(z.num_hashes));
+    if (y.fpr != z.fpr) return mismatch("fpr", std::to_string(y.fpr), std::to_string(z.fpr));
+    rc = add_blocks(dir, z);
+    if (rc) return rc;
   }
   I.n_blocks = (int32_t)db->blocks.size();
   I.n_cols = base;
@@ -606,7 +650,54 @@ extern "C" int kmcpg_open(const char* db_dir, const kmcpg_opts* opts, kmcpg_db**
   rc = finish_open(db.get());
   if (rc) return rc;
   lap("finish_open (tables)");
+  if (db->is_set() && !meta_only) {
+    HIPCHK(hipMalloc((void**)&db->d_set_stats, K3_SET_STATS * sizeof(uint32_t)));
+    HIPCHK(hipMemset(db->d_set_stats, 0, K3_SET_STATS * sizeof(uint32_t)));
+  }
   *out = db.release();
+  return 0;
+}
+
+extern "C" int kmcpg_open(const char* db_dir, const kmcpg_opts* opts, kmcpg_db** out) {
+  if (!db_dir || !out) return kmcpg_fail(KMCPG_EINVAL, "null argument");
+  return open_dirs(&db_dir, 1, opts, out);
+}
+
+extern "C" int kmcpg_open_set(const char* const* db_dirs, uint32_t n, const kmcpg_opts* opts, kmcpg_db** out) {
+  if (!db_dirs || !out) return kmcpg_fail(KMCPG_EINVAL, "null argument");
+  *out = nullptr;
+  if (n < 1 || n > (uint32_t)SET_MAX_MEMBERS) return kmcpg_fail(KMCPG_EINVAL, "a database set has 1 to %d members (%u given)", SET_MAX_MEMBERS, n);
+  for (uint32_t i = 0; i < n; i++)
+    if (!db_dirs[i]) return kmcpg_fail(KMCPG_EINVAL, "null directory");
+  if (n > 1 && opts && opts->shard_count > 1) return kmcpg_fail(KMCPG_EUNSUPPORTED, "database set: shard_count > 1 is not supported (every member is resident on one GPU)");
+  return open_dirs(db_dirs, n, opts, out);
+}
+
+extern "C" int kmcpg_set_info(const kmcpg_db* db, uint32_t* n_members, uint32_t* first_col, uint32_t cap) {
+  if (!db || !n_members || (cap && !first_col)) return kmcpg_fail(KMCPG_EINVAL, "null argument");
+  *n_members = (uint32_t)db->set_col_base.size();
+  for (uint32_t i = 0; i < cap && i < *n_members; i++) first_col[i] = db->set_col_base[i];
+  return 0;
+}
+
+// what ordered the segments of the last batch of a set handle: the device counters of the last K3 launch (read once the device is idle)
+// and what the host half has ordered itself since then
+extern "C" int kmcpg_last_set_order(kmcpg_db* db, kmcpg_set_order* out) {
+  if (!db || !out) return kmcpg_fail(KMCPG_EINVAL, "null argument");
+  if (!db->is_set()) return kmcpg_fail(KMCPG_EINVAL, "not a database set (kmcpg_open_set with two members or more)");
+  memset(out, 0, sizeof *out);
+  out->host_segments = db->set_host_segments.load();
+  out->host_mixed_runs = db->set_host_mixed.load();
+  if (db->opts.device < 0 || !db->d_set_stats) return 0;
+  std::lock_guard<std::mutex> g(db->mu);
+  KMCPG_USE_DEVICE(db);
+  HIPCHK(hipDeviceSynchronize());
+  uint32_t w[K3_SET_STATS] = {};
+  HIPCHK(hipMemcpy(w, db->d_set_stats, sizeof w, hipMemcpyDeviceToHost));
+  out->wave_segments = w[0];
+  out->wg_segments = w[1];
+  out->long_segments = w[2];
+  out->device_mixed_runs = w[3];
   return 0;
 }
 
@@ -756,6 +847,7 @@ extern "C" int kmcpg_close(kmcpg_db* db) {
   db->w_fin_cnt.release();
   db->w_fin_sums.release();
   if (db->d_col_size) (void)hipFree(db->d_col_size);
+  if (db->d_set_stats) (void)hipFree(db->d_set_stats);
   kmcpg::release_fpr_bounds(db);
   kmcpg::async_release(db);
   if (db->k1_stream) (void)hipStreamDestroy(db->k1_stream);

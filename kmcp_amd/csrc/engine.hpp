@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <atomic>
 #include <condition_variable>
 #include <functional>
 #include <memory>
@@ -201,6 +202,14 @@ struct kmcpg_db {
   uint64_t* d_col_size = nullptr;
   kmcpg::DevBuf<uint32_t> w_fin_cnt;
   kmcpg::DevBuf<uint64_t> w_fin_sums;
+  // database set (kmcpg_open_set): the directories of the members and the first global column of each (one entry for every handle that
+  // kmcpg_open / kmcpg_open_set made; a SET in the sense of the merge order and the refusals is a handle with two members or more)
+  std::vector<std::string> set_dirs;
+  std::vector<uint32_t> set_col_base;
+  bool is_set() const { return set_col_base.size() > 1; }
+  uint32_t* d_set_stats = nullptr;  // K3SetArgs::stats of the last K3 launch (kmcpg_last_set_order)
+  // what the host half ordered itself since that launch (finalize.cpp): segments, and runs of equal fixed4 with several members in them
+  mutable std::atomic<uint64_t> set_host_segments{0}, set_host_mixed{0};
   std::vector<kmcpg::FprBoundTable> fpr_bounds;  // -f bound tables (query.cpp fpr_bound): one per (max_fpr, size), never rewritten
   hipEvent_t ev[16] = {};   // ring of 4 calls x (start, COBS start, COBS done, k-mers done)
   uint64_t ev_calls = 0;    // profiled calls so far
@@ -208,6 +217,19 @@ struct kmcpg_db {
 
 
 namespace kmcpg {
+
+// Database sets: what acts per member in separate runs and would act per query on the union is refused (include/kmcp_gpu.h kmcpg_open_set)
+inline int set_refuse_params(const kmcpg_db* db, const kmcpg_params& p) {
+  if (!db->is_set()) return 0;
+  const char* what = p.try_se ? "try_se" : (p.do_not_sort ? "do_not_sort" : (p.top_n_scores != 0 ? "top_n_scores != 0" : (p.k != 0 ? "params->k != 0" : nullptr)));
+  if (!what) return 0;
+  return kmcpg_fail(KMCPG_EUNSUPPORTED, "database set (%zu members): %s is not supported — it acts per member in separate searches and would act per query here; "
+                    "search the databases one by one and merge the results with kmcp-merge", db->set_col_base.size(), what);
+}
+inline int set_refuse_entry(const kmcpg_db* db, const char* entry) {
+  if (!db->is_set()) return 0;
+  return kmcpg_fail(KMCPG_EUNSUPPORTED, "database set (%zu members): %s is not supported on a set handle", db->set_col_base.size(), entry);
+}
 
 inline kmcpg_params default_params() {
   kmcpg_params p{};

@@ -31,6 +31,7 @@
 #include "engine.hpp"
 #include "fpr.hpp"
 #include "kernels.hpp"
+#include "k3_set_order.hpp"
 
 using namespace kmcpg;
 
@@ -107,6 +108,28 @@ bool match_less(const kmcpg_match& x, const kmcpg_match& y, int sort_by) {
   if (s1 != s2) return s1 > s2;
   if (t1 != t2) return t1 > t2;
   return x.col < y.col;  // deterministic tie-break; the reference's order among exact ties is arbitrary
+}
+
+// Database sets (k3_set_order.hpp): records[0 .. m) of one query in the exact order above -> the order kmcp-merge gives the members'
+// separate results; the handle's witness counters are told (kmcpg_last_set_order)
+void set_order_records(const kmcpg_db* db, kmcpg_match* rec, uint64_t m, int sort_by) {
+  if (m == 0) return;
+  const uint32_t* base = db->set_col_base.data();
+  const uint32_t nm = (uint32_t)db->set_col_base.size();
+  const uint64_t mixed = set_order_host(rec, m, [=](const kmcpg_match& x) {
+    return set_host_key(fixed4(sort_by == 1 ? x.tcov : (sort_by == 2 ? x.jacc : x.qcov)), set_member(x.col, base, nm));
+  });
+  if (m > 1) db->set_host_segments.fetch_add(1);
+  if (mixed) db->set_host_mixed.fetch_add(mixed);
+}
+// ... and whether y may follow x in that order (the streaming check of lists that did not come from K3)
+bool set_follows(const kmcpg_db* db, const kmcpg_match& x, const kmcpg_match& y, int sort_by) {
+  const uint32_t* base = db->set_col_base.data();
+  const uint32_t nm = (uint32_t)db->set_col_base.size();
+  auto key = [&](const kmcpg_match& r) { return set_host_key(fixed4(sort_by == 1 ? r.tcov : (sort_by == 2 ? r.jacc : r.qcov)), set_member(r.col, base, nm)); };
+  const uint64_t kx = key(x), ky = key(y);
+  if (kx != ky) return kx < ky;
+  return !match_less(y, x, sort_by);
 }
 
 // Host cores this process may use: the affinity mask capped by the cgroup CPU quota (a GPU box shows 256 cores and grants 16).
@@ -239,6 +262,8 @@ extern "C" int kmcpg_finalize(const kmcpg_db* db, const kmcpg_hit* hits, uint64_
                               const kmcpg_params* params, kmcpg_result* out) {
   if (!db || !out || (!hits && n_hits) || (n_reads && (!qkmers || !qlen))) return kmcpg_fail(KMCPG_EINVAL, "null argument");
   const kmcpg_params p = params ? *params : default_params();
+  if (int rcs = set_refuse_params(db, p)) return rcs;
+  const bool is_set = db->is_set();
   const bool timing = getenv("KMCPG_FIN_TIMING") != nullptr;
   auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   double t_0 = now(), t_1 = 0, t_2 = 0, t_3 = 0, t_4 = 0;
@@ -388,7 +413,7 @@ extern "C" int kmcpg_finalize(const kmcpg_db* db, const kmcpg_hit* hits, uint64_
       // A read with a handful of hits (the usual case) builds its matches in place and sorts the records; a read with many
       // (a database full of close relatives: hundreds) builds them in a scratch array, orders 4-byte indices and writes every
       // 56-byte record once, in its final position.
-      const bool in_place = s1 - s0 <= 8;
+      const bool in_place = s1 - s0 <= 8 || is_set;  // (a set reorders the sorted records once more, where they are)
       static thread_local std::vector<kmcpg_match> tmp;
       if (!in_place && tmp.size() < s1 - s0) tmp.resize(s1 - s0);
       kmcpg_match* const dst = in_place ? mbase + first : tmp.data();
@@ -429,6 +454,7 @@ extern "C" int kmcpg_finalize(const kmcpg_db* db, const kmcpg_hit* hits, uint64_
             std::sort(mbase + first, mbase + pos2, [](const kmcpg_match& x, const kmcpg_match& y) { return x.col < y.col; });
           }
         }
+        if (is_set) set_order_records(db, mbase + first, cnt2, p.sort_by);
       } else if (cnt2 > 0) {
         static thread_local std::vector<uint32_t> order, bucket;
         if (order.size() < cnt2) order.resize(cnt2);
@@ -540,6 +566,8 @@ int finalize_grouped_into(const kmcpg_db* db, const kmcpg_pair* pairs, const uin
                           const kmcpg_params& p, ResultOwner* o, uint32_t read_base, uint64_t match_base, uint64_t* kept_out, bool trusted, int32_t bound_n) {
   const uint64_t n_pairs = read_offs[n_reads];
   const int final_n = trusted ? std::min<int>(bound_n, kFprBoundAlways) : 0;  // segments of queries up to this size are final as they stand
+  if (int rcs = set_refuse_params(db, p)) return rcs;
+  const bool is_set = db->is_set();
   if (n_pairs && !pairs) return kmcpg_fail(KMCPG_EINVAL, "null argument");
   if (read_offs[0] != 0) return kmcpg_fail(KMCPG_EINVAL, "read_offs[0] must be 0");
   if (read_offs[(size_t)n_reads + 1] != 0)
@@ -658,7 +686,7 @@ int finalize_grouped_into(const kmcpg_db* db, const kmcpg_pair* pairs, const uin
           continue;
         }
         if (!trusted) {  // (K3's own segments are in order by construction: the library's pipelines skip the comparison)
-          if (have_prev && (p.do_not_sort ? mm.col < prev.col : match_less(mm, prev, p.sort_by))) {
+          if (have_prev && (is_set ? !set_follows(db, prev, mm, p.sort_by) : (p.do_not_sort ? mm.col < prev.col : match_less(mm, prev, p.sort_by)))) {
             out_of_order = true;
             break;
           }
@@ -691,6 +719,7 @@ int finalize_grouped_into(const kmcpg_db* db, const kmcpg_pair* pairs, const uin
         const int sb = p.sort_by;
         if (!p.do_not_sort) std::sort(tmp.begin(), tmp.begin() + (ptrdiff_t)kept, [sb](const kmcpg_match& x, const kmcpg_match& y) { return match_less(x, y, sb); });
         else std::sort(tmp.begin(), tmp.begin() + (ptrdiff_t)kept, [](const kmcpg_match& x, const kmcpg_match& y) { return x.col < y.col; });
+        if (is_set) set_order_records(db, tmp.data(), kept, sb);
         uint64_t keep = kept;
         if (top) {
           uint64_t i = 0;

@@ -1274,7 +1274,7 @@ int submit_handle(kmcpg_db* db, const kmcpg_params* params, kmcpg_params* p) {
   if (db->shards.empty() && db->opts.device < 0 && db->paged_passes == 0) return kmcpg_fail(KMCPG_EDEVICE, "metadata-only handle (device -1): no GPU work possible");
   *p = params ? *params : default_params();
   if (p->min_matched < 1) return kmcpg_fail(KMCPG_EINVAL, "min_matched must be >= 1");
-  return 0;
+  return set_refuse_params(db, *p);
 }
 }  // namespace
 
@@ -1451,6 +1451,7 @@ extern "C" int kmcpg_submit_packed(kmcpg_db* db, const uint8_t* codes, const uin
                                    const kmcpg_params* params, kmcpg_ticket** out) {
   if (!db || !out || (n_reads && (!codes || !offs)) || (n_exc && !exc)) return kmcpg_fail(KMCPG_EINVAL, "null argument");
   *out = nullptr;
+  if (int rc = set_refuse_entry(db, "kmcpg_submit_packed")) return rc;
   kmcpg_params p;
   if (int rc = submit_handle(db, params, &p)) return rc;
   // handles that read the batch's text again — the smaller k of a multi-k database (retry_unmatched), the passes of a paged index — get text
@@ -1515,6 +1516,7 @@ extern "C" int kmcpg_submit_windows(kmcpg_db* db, const uint8_t* seqs, const uin
                                     const kmcpg_params* params, kmcpg_ticket** out) {
   if (!db || !out || (n_reads && (!seqs || !offs))) return kmcpg_fail(KMCPG_EINVAL, "null argument");
   *out = nullptr;
+  if (int rc = set_refuse_entry(db, "kmcpg_submit_windows")) return rc;
   kmcpg_params p;
   if (int rc = submit_handle(db, params, &p)) return rc;
   if (int rc = window_args(offs, n_reads, spec)) return rc;
@@ -1525,6 +1527,7 @@ extern "C" int kmcpg_submit_packed_windows(kmcpg_db* db, const uint8_t* codes, c
                                            uint32_t n_reads, const kmcpg_window_spec* spec, const kmcpg_params* params, kmcpg_ticket** out) {
   if (!db || !out || (n_reads && (!codes || !offs)) || (n_exc && !exc)) return kmcpg_fail(KMCPG_EINVAL, "null argument");
   *out = nullptr;
+  if (int rc = set_refuse_entry(db, "kmcpg_submit_packed_windows")) return rc;
   kmcpg_params p;
   if (int rc = submit_handle(db, params, &p)) return rc;
   if (int rc = window_args(offs, n_reads, spec)) return rc;
@@ -1679,6 +1682,7 @@ static int search_batch_impl(kmcpg_db* db, const HostBatch& in, const kmcpg_para
   bool took = false;
   if (db && in.n && in.seqs && in.offs && (in.seqs2 == nullptr) == (in.offs2 == nullptr)) {
     const kmcpg_params pp = params ? *params : default_params();
+    if (int rcs = set_refuse_params(db, pp)) return rcs;
     if (pp.min_matched >= 1 && in.offs[0] == 0 && (!in.offs2 || in.offs2[0] == 0)) rc = search_batch_pieces(db, in, pp, as_pairs, out, &took);
   }
   if (took && rc == 0) return 0;

@@ -21,11 +21,23 @@
 //                                                              A = ~bits(c / size)       B = ~c : column
 //   -s jacc: c / (n + size - c) likewise:                      A = ~bits(jacc)           B = ~c : column
 //   -S     : column order (this build's deterministic stand-in for the reference's arrival order): A = column, B = ~c : column
+//
+// Database sets (kmcpg_open_set; k3_set_order.hpp): a query's matches come out in the order `kmcp-merge` gives the members' separate
+// results — printed score ("%.4f", as the integer fixed4) descending, member ascending, then the exact order above.  The set forms of
+// the two sort kernels (k3_sort_wave_set, k3_sort_wg_set) sort a segment by the exact key first, as every handle does; rounding is
+// monotone, so equal fixed4 are then side by side, and a SECOND PASS over the same LDS tile reorders by member inside those runs:
+//   set key:  A = (2^47 - 1 - fixed4) : member (4 bits) : position after the exact sort (13 bits)      B = column : c (the pair itself)
+// The keys replace the exact ones slot by slot (the tile keeps its size: 4 x 512 keys per workgroup of the wave class, 4096 of the
+// workgroup class).  A is unique, so the bitonic network is stable with respect to the exact order; it runs only when some A is out of
+// place (a run of equal fixed4 whose members are not already ascending) — otherwise the segment is in set order as it stands.  The pass
+// also counts the runs of equal fixed4 that hold several members, and the kernels the segments of each size class (K3SetArgs::stats).
+// Handles that are not sets launch the kernels above, unchanged.
 #include <hip/hip_runtime.h>
 
 #include "common.hpp"
 #include "device_utils.hpp"
 #include "k3_keys.hpp"
+#include "k3_set_order.hpp"
 #include "kernels.hpp"
 
 namespace kmcpg {
@@ -251,12 +263,119 @@ __global__ void __launch_bounds__(256) k3_sort_wg(K3Args a) {
   }
 }
 
+// ---- database sets: the sort kernels with the second pass (layout at the top of the file) ----
+template <bool WG>
+__device__ __forceinline__ void tile_sync() {
+  if (WG) __syncthreads();
+  else wave_lds_fence();
+}
+template <bool WG>
+__device__ __forceinline__ bool tile_any(bool c) {  // uniform over the workgroup / the wave; orders the tile's stores before it as tile_sync does
+  if (WG) return __syncthreads_or(c ? 1 : 0) != 0;
+  wave_lds_fence();
+  return __ballot(c) != 0;
+}
+
+// t[0 .. m) = the exact keys of a segment in order, t[m .. P) = padding (all ones, which stays behind every set key); on return the
+// segment's pairs are in a.pairs[s0 ...] in set order.  Called by all `nthreads` threads that share the tile, after a tile_sync.
+template <bool WG>
+__device__ __forceinline__ void set_second_pass(Key* t, uint32_t m, uint32_t P, uint32_t tid, uint32_t nthreads, const K3Args& a, const K3SetArgs& s, uint64_t s0,
+                                                double nh) {
+  for (uint32_t i = tid; i < m; i += nthreads) {  // slot i is read and rewritten by one thread
+    const Key k = t[i];
+    const kmcpg_pair p = pair_of(a.sort_mode, k);
+    // the score the row is printed with: count / NumKmers for -s qcov, otherwise the double the exact key was made of
+    const double score = a.sort_mode == 0 ? (double)p.count / nh : __longlong_as_double((long long)~k.a);
+    t[i] = set_key(fixed4(score), set_member(p.col, s.base, s.n_members), i, p);
+  }
+  bool out_of_place = false;
+  tile_sync<WG>();
+  for (uint32_t i = tid; i + 1 < m; i += nthreads) out_of_place |= t[i + 1].a < t[i].a;
+  if (tile_any<WG>(out_of_place)) {
+    for (uint32_t k = 2; k <= P; k <<= 1)
+      for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+        bitonic_step(t, P, k, j, tid, nthreads);
+        tile_sync<WG>();
+      }
+  }
+  uint32_t mixed = 0;
+  for (uint32_t i = tid; i < m; i += nthreads) {
+    mixed += set_mixed_run_at(t, m, i) ? 1u : 0u;
+    a.pairs[s0 + i] = set_pair_of(t[i]);
+  }
+  if (mixed) atomicAdd(&s.stats[3], mixed);
+  tile_sync<WG>();  // the tile is reused by the next segment
+}
+
+__global__ void __launch_bounds__(256) k3_sort_wave_set(K3Args a, K3SetArgs s) {
+  __shared__ Key tile[4][WAVE_CAP];
+  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const uint64_t r0 = ((uint64_t)blockIdx.x * 4 + wave) * RPW;
+  if (r0 >= a.n_reads) return;
+  const uint64_t mine = a.offs[min(r0 + lane, (uint64_t)a.n_reads)];  // lanes 0..RPW hold offs[r0 + lane]
+  Key* t = tile[wave];
+  uint32_t sorted = 0;
+  for (int q = 0; q < RPW && r0 + q < a.n_reads; q++) {
+    const uint64_t s0 = __shfl(mine, q), s1 = __shfl(mine, q + 1);
+    const uint64_t m = s1 - s0;
+    if (m < 2 || m > WAVE_CAP) continue;  // wave-uniform
+    sorted++;
+    uint32_t P = 2;
+    while (P < m) P <<= 1;
+    const double nh = (double)a.nk[r0 + q];
+    for (uint32_t i = lane; i < P; i += 64) t[i] = i < m ? make_key(a.sort_mode, a.col_size, a.pairs[s0 + i], nh) : Key{~0ull, ~0ull};
+    wave_lds_fence();
+    for (uint32_t k = 2; k <= P; k <<= 1)
+      for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+        bitonic_step(t, P, k, j, lane, 64);
+        wave_lds_fence();
+      }
+    set_second_pass<false>(t, (uint32_t)m, P, lane, 64, a, s, s0, nh);
+  }
+  if (lane == 0 && sorted) atomicAdd(&s.stats[0], sorted);
+}
+
+__global__ void __launch_bounds__(256) k3_sort_wg_set(K3Args a, K3SetArgs s) {
+  __shared__ Key big[WG_CAP];  // 64 KB of the CU's 160 KB
+  __shared__ uint32_t n_found, found[256];
+  for (uint64_t r0 = (uint64_t)blockIdx.x * 256; r0 < a.n_reads; r0 += (uint64_t)gridDim.x * 256) {
+    if (threadIdx.x == 0) n_found = 0;
+    __syncthreads();
+    const uint64_t rr = r0 + threadIdx.x;
+    if (rr < a.n_reads) {
+      const uint64_t mm = a.offs[rr + 1] - a.offs[rr];
+      if (mm > WAVE_CAP && mm <= WG_CAP) found[atomicAdd(&n_found, 1u)] = threadIdx.x;
+      if (mm > WG_CAP) atomicAdd(&s.stats[2], 1u);  // left to the host (rare)
+    }
+    __syncthreads();
+    const uint32_t nf = n_found;
+    if (threadIdx.x == 0 && nf) atomicAdd(&s.stats[1], nf);
+    for (uint32_t f = 0; f < nf; f++) {
+      const uint64_t r = r0 + found[f];
+      const uint64_t s0 = a.offs[r], s1 = a.offs[r + 1];
+      const uint64_t m = s1 - s0;
+      uint32_t P = 2;
+      while (P < m) P <<= 1;
+      const double nh = (double)a.nk[r];
+      for (uint32_t i = threadIdx.x; i < P; i += 256) big[i] = i < m ? make_key(a.sort_mode, a.col_size, a.pairs[s0 + i], nh) : Key{~0ull, ~0ull};
+      __syncthreads();
+      for (uint32_t k = 2; k <= P; k <<= 1)
+        for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+          bitonic_step(big, P, k, j, threadIdx.x, 256);
+          __syncthreads();
+        }
+      set_second_pass<true>(big, (uint32_t)m, P, threadIdx.x, 256, a, s, s0, nh);
+    }
+    __syncthreads();
+  }
+}
+
 }  // namespace
 
 uint32_t k3_scan_tiles_for(uint32_t n) { return (n + SCAN_TILE - 1) / SCAN_TILE; }
 
 // cnt[0 .. n_reads] must be zero on entry (it is again on exit); offs gets n_reads + 1 entries, offs[n_reads] = matches kept
-void launch_k3(const K3Args& a, uint64_t hits_hint, hipStream_t st) {
+void launch_k3(const K3Args& a, uint64_t hits_hint, hipStream_t st, const K3SetArgs* set) {
   if (a.n_reads == 0) return;
   const uint64_t work = hits_hint ? hits_hint : a.hit_cap;
   const unsigned gblocks = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((work + 255) / 256, 16384));
@@ -266,8 +385,13 @@ void launch_k3(const K3Args& a, uint64_t hits_hint, hipStream_t st) {
   hipLaunchKernelGGL(k3_scan_sums, dim3(1), dim3(SCAN_THREADS), 0, st, a.sums, tiles);
   hipLaunchKernelGGL(k3_scan_add, dim3(tiles), dim3(SCAN_THREADS), 0, st, a.offs, a.sums, n);
   hipLaunchKernelGGL(k3_scatter, dim3(gblocks), dim3(256), 0, st, a);
-  hipLaunchKernelGGL(k3_sort_wave, dim3((a.n_reads + 4 * RPW - 1) / (4 * RPW)), dim3(256), 0, st, a);
   const unsigned wgb = (unsigned)std::min<uint32_t>((a.n_reads + 255) / 256, 2048);
+  if (set) {  // a database set: the same two size classes, each with the second pass
+    hipLaunchKernelGGL(k3_sort_wave_set, dim3((a.n_reads + 4 * RPW - 1) / (4 * RPW)), dim3(256), 0, st, a, *set);
+    hipLaunchKernelGGL(k3_sort_wg_set, dim3(wgb), dim3(256), 0, st, a, *set);
+    return;
+  }
+  hipLaunchKernelGGL(k3_sort_wave, dim3((a.n_reads + 4 * RPW - 1) / (4 * RPW)), dim3(256), 0, st, a);
   hipLaunchKernelGGL(k3_sort_wg, dim3(wgb), dim3(256), 0, st, a);
 }
 

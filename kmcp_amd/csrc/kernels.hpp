@@ -38,7 +38,8 @@ int launch_k2_split(const K2Args& a, int lpr, hipStream_t st, K2Log* log);
 void launch_list_long(const int32_t* nk, uint32_t n_reads, int32_t split_min, uint32_t* list, uint32_t* meta, hipStream_t st);
 void launch_threshold_long(const K2Args& a, hipStream_t st);
 // K3: group + filter + order the hit list on the device (k3_finalize.hip); hits_hint = expected number of hits (grid sizing), 0 = hit_cap
-void launch_k3(const K3Args& a, uint64_t hits_hint, hipStream_t st);
+// set != nullptr: a database set — the segments are brought into the merge order (k3_set_order.hpp) by the set forms of the sort kernels
+void launch_k3(const K3Args& a, uint64_t hits_hint, hipStream_t st, const K3SetArgs* set = nullptr);
 uint32_t k3_scan_tiles_for(uint32_t n);
 void launch_max_nk(const int32_t* nk, uint32_t n_reads, unsigned long long* out, hipStream_t st);
 void launch_repack(const uint8_t* src, uint8_t* dst, uint64_t n_rows, uint32_t row_bytes, uint32_t stride, uint32_t byte_off, uint32_t ncols, hipStream_t st);

@@ -392,6 +392,7 @@ int kmcpg::query_device_after(kmcpg_db* db, const DeviceBatch& b, const kmcpg_pa
   if (prologue)
     if (int rcp = (*prologue)()) return rcp;
   const kmcpg_params p = params ? *params : default_params();
+  if (int rcs = set_refuse_params(db, p)) return rcs;
   if (p.min_matched < 1) return kmcpg_fail(KMCPG_EINVAL, "min_matched must be >= 1");  // getFlagPositiveInt (search.go:165)
   if (p.k > 0 && std::find(db->ks_desc.begin(), db->ks_desc.end(), p.k) == db->ks_desc.end())
     return kmcpg_fail(KMCPG_EINVAL, "k=%d is not a k-mer size of this database", p.k);
@@ -618,6 +619,7 @@ extern "C" int kmcpg_group_device(kmcpg_db* db, const kmcpg_hit* d_hits, const u
   std::lock_guard<std::mutex> g(db->mu);
   KMCPG_USE_DEVICE(db);
   const kmcpg_params p = params ? *params : default_params();
+  if (int rcs = set_refuse_params(db, p)) return rcs;
   hipStream_t st = (hipStream_t)stream;
   if (int rc0 = chain_begin(&db->fin_ev, db->fin_ev_valid, st)) return rc0;
   struct FinGuard {  // as WsGuard: every way out leaves the event behind
@@ -647,7 +649,16 @@ extern "C" int kmcpg_group_device(kmcpg_db* db, const kmcpg_hit* d_hits, const u
   a.pairs = d_pairs;
   if (n_reads == 0) HIPCHK(hipMemsetAsync(d_read_offs, 0, 2 * sizeof(uint64_t), st));
   else {
-    launch_k3(a, 0, st);
+    K3SetArgs sa{};
+    if (db->is_set()) {  // a database set: the merge order (k3_set_order.hpp); the counters speak of this launch (kmcpg_last_set_order)
+      sa.n_members = (uint32_t)db->set_col_base.size();
+      for (uint32_t i = 0; i < sa.n_members; i++) sa.base[i] = db->set_col_base[i];
+      sa.stats = db->d_set_stats;
+      HIPCHK(hipMemsetAsync(db->d_set_stats, 0, K3_SET_STATS * sizeof(uint32_t), st));
+      db->set_host_segments.store(0);
+      db->set_host_mixed.store(0);
+    }
+    launch_k3(a, 0, st, db->is_set() ? &sa : nullptr);
     // d_read_offs[n_reads + 1] = the bad-hit count (a 32-bit word widened on the device side of the copy: two words cleared first)
     HIPCHK(hipMemsetAsync(d_read_offs + n_reads + 1, 0, sizeof(uint64_t), st));
     HIPCHK(hipMemcpyAsync(d_read_offs + n_reads + 1, a.bad, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));

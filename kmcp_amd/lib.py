@@ -25,6 +25,7 @@ EXPORTS = [
     "kmcpg_last_density_ms", "kmcpg_stream_probe",
     "kmcpg_sketcher_open", "kmcpg_sketcher_close", "kmcpg_split_bounds", "kmcpg_sketch_genomes", "kmcpg_sketch_result_free",
     "kmcpg_last_sketch_launches", "kmcpg_last_sketch_ms", "kmcpg_sort_segments_device",
+    "kmcpg_open_set", "kmcpg_set_info", "kmcpg_last_set_order",
 ]
 
 
@@ -175,6 +176,12 @@ class SketchLaunch(C.Structure):
                 ("launches", C.c_uint32), ("keys", C.c_uint64)]
 
 
+class SetOrder(C.Structure):
+    """kmcpg_set_order: what put the segments of a set handle's last batch into the merge order"""
+    _fields_ = [("wave_segments", C.c_uint64), ("wg_segments", C.c_uint64), ("long_segments", C.c_uint64), ("device_mixed_runs", C.c_uint64),
+                ("host_segments", C.c_uint64), ("host_mixed_runs", C.c_uint64)]
+
+
 class SynthSpec(C.Structure):
     _fields_ = [("k", C.c_int32), ("num_hashes", C.c_int32), ("fpr", C.c_double), ("n_blocks", C.c_uint32),
                 ("cols_per_block", C.c_uint32), ("num_sigs", C.c_uint64), ("kmers_per_col", C.c_uint64), ("seed", C.c_uint64),
@@ -308,6 +315,9 @@ def load():
     L.kmcpg_last_sketch_ms.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.kmcpg_sort_segments_device.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_int32, C.c_uint32, C.c_uint32, C.c_int32, vp, C.c_uint64, vp,
                                              C.POINTER(SketchLaunch), vp]
+    L.kmcpg_open_set.argtypes = [C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(Opts), C.POINTER(vp)]
+    L.kmcpg_set_info.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32]
+    L.kmcpg_last_set_order.argtypes = [vp, C.POINTER(SetOrder)]
     _lib = L
     return L
 
@@ -557,6 +567,29 @@ class Database:
         o = Opts(device, shard_rank, shard_count, 0)
         _check(load().kmcpg_open(os.fsencode(db_dir), C.byref(o), C.byref(h)))
         return cls(h)
+
+    @classmethod
+    def open_set(cls, dirs, device=0):
+        """kmcpg_open_set: 1 to 16 database directories as one handle on one GPU; a search returns what kmcp-merge makes of the members'
+        separate results (rows by printed score, ties by member, then the member's own order).  device=-1: metadata only."""
+        h = C.c_void_p()
+        arr = (C.c_char_p * max(1, len(dirs)))(*[os.fsencode(d) for d in dirs])
+        o = Opts(device, 0, 1, 0)
+        _check(load().kmcpg_open_set(arr, len(dirs), C.byref(o), C.byref(h)))
+        return cls(h)
+
+    def set_info(self):
+        """kmcpg_set_info: the first global column of every member (one entry for a handle of Database.open)"""
+        n = C.c_uint32(0)
+        buf = (C.c_uint32 * 16)()
+        _check(load().kmcpg_set_info(self._h, C.byref(n), buf, 16))
+        return [int(buf[i]) for i in range(min(16, n.value))]
+
+    def last_set_order(self):
+        """kmcpg_last_set_order: dict(wave_segments, wg_segments, long_segments, device_mixed_runs, host_segments, host_mixed_runs)"""
+        r = SetOrder()
+        _check(load().kmcpg_last_set_order(self._h, C.byref(r)))
+        return {f: int(getattr(r, f)) for f, _ in SetOrder._fields_}
 
     @classmethod
     def open_devices(cls, db_dir, devices):
