@@ -2,7 +2,10 @@
 kmcpg_finalize_grouped expanding (column, count) pairs to Match records on the host — against the round-3 host half
 (kmcpg_finalize on the raw hit list, KMCPG_DEVICE_FINALIZE=0) and against the oracle's order (Matches.Less / SortByTCov /
 SortByJacc, util-db-search.go:105-145; --keep-top-scores :285-311).  Segment classes of the sort: one wave (2..512 matches), one
-workgroup (513..4096), host (more)."""
+workgroup (513..4096), host (more).
+
+These tests feed K3 what K2 emits.  The kernel's own edges — class borders, lanes, broken runs, exact ties, the scan beyond one tile,
+the grid-stride loops — are in tests/test_gpu_k3_alone.py, on hit lists laid out by hand against a numpy restatement."""
 import os
 
 import numpy as np
