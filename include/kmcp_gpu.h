@@ -421,6 +421,50 @@ int kmcpg_kmers_device_packed(kmcpg_db* db, const uint8_t* d_codes, const kmcpg_
                               const uint64_t* d_offs, uint32_t n_reads, uint64_t total_bases, uint32_t max_read_len,
                               const kmcpg_params* params, uint64_t* d_hashes, uint64_t hashes_cap, uint64_t* d_koff, int32_t* d_nk,
                               void* stream);
+/* The same for paired reads: mates in d_seqs2 / d_offs2 (both required), total_bases and hashes_cap over BOTH mates, max_read_len the
+ * longest single mate.  The hashes of pair i — mate 1's list, then mate 2's — start at d_hashes[d_offs[i] + d_offs2[i]], d_nk[i] of them,
+ * as on the query path; d_nk1 (optional, n_reads words) receives the first mate's raw count, what --try-se relies on.  Debug/tests. */
+int kmcpg_kmers_device_paired(kmcpg_db* db, const uint8_t* d_seqs, const uint64_t* d_offs, const uint8_t* d_seqs2, const uint64_t* d_offs2,
+                              uint32_t n_reads, uint64_t total_bases, uint32_t max_read_len, const kmcpg_params* params,
+                              uint64_t* d_hashes, uint64_t hashes_cap, int32_t* d_nk, int32_t* d_nk1, void* stream);
+/* Which k-mer kernels (K1, k1_kmers.hip) the handle's last k-mer stage launched — kmcpg_kmers_device*, kmcpg_query_device, a submit,
+ * kmcpg_plant_reads_device — one record per launch in launch order, written where the kernel is launched from the template
+ * parameters of the function that launches it.  The first record (kernel KMCPG_K1_PLAN) is the plan of the call (k1_plan.hpp): p0 =
+ * the form (KMCPG_K1F_*), p1 = bit 0 codes_direct, bit 1 list_fallback, bit 2 adj_done, left_on_list = for the two list forms
+ * (SegRoll2, WindowsRoll) how many segments / reads the first kernel left to the fallback kernel behind it, read back by the
+ * kmcpg_kmers_device* entries only; UINT32_MAX = not read (every other entry point: nothing is synchronised for it) or no list.
+ * Recorded at profiling level >= 1 only: *n = 0 otherwise, and nothing is added to the stream.  Cleared by every k-mer stage. */
+enum {
+  KMCPG_K1_PLAN = 0,
+  KMCPG_K1_KMERS,         /* k1_kmers<p0 = MODE> */
+  KMCPG_K1_KMERS_WG,      /* k1_kmers_wg<p0 = MODE> */
+  KMCPG_K1_KMERS_WG_GLOBAL,
+  KMCPG_K1_WINDOWS_WAVE,  /* k1_windows_wave<p0 = MODE> */
+  KMCPG_K1_WINDOWS_ROLL,  /* k1_windows_roll<p0 = WSZ, p1 = WAVES> */
+  KMCPG_K1_SEG_ROLL2,
+  KMCPG_K1_SEG_ROLL,
+  KMCPG_K1_SEG_HASH,
+  KMCPG_K1_SEG_PACK,
+  KMCPG_K1_MARK_EXC,
+  KMCPG_K1_UNPACK2_LIST,
+  KMCPG_K1_WIN_HASH,
+  KMCPG_K1_WIN_SCAN,
+  KMCPG_K1_WIN_RANK,
+  KMCPG_K1_WIN_GATHER,
+  KMCPG_K1_KERNELS
+};
+enum { KMCPG_K1F_NONE = 0, KMCPG_K1F_WIN_ONCE, KMCPG_K1F_SEG_ROLL2, KMCPG_K1F_SEG_ROLL, KMCPG_K1F_SEG_HASH, KMCPG_K1F_WINDOWS_ROLL,
+       KMCPG_K1F_WINDOWS_WAVE, KMCPG_K1F_WG_GLOBAL, KMCPG_K1F_WG, KMCPG_K1F_SHORT };
+typedef struct {
+  int32_t kernel;        /* KMCPG_K1_* */
+  int32_t p0, p1;        /* template parameters of the kernel (0 where it has none); the plan record: see above */
+  uint32_t grid, block;  /* workgroups, threads per workgroup */
+  uint32_t lds_bytes;    /* dynamic LDS of the launch */
+  uint32_t left_on_list; /* the plan record only; UINT32_MAX elsewhere */
+  uint32_t reserved;
+} kmcpg_k1_launch;
+/* Copies up to `cap` records to out (may be NULL when cap is 0); *n = how many there are. */
+int kmcpg_last_k1_launches(kmcpg_db* db, kmcpg_k1_launch* out, uint32_t cap, uint32_t* n);
 typedef struct kmcpg_sketch_launch kmcpg_sketch_launch; /* defined with kmcpg_sketch_genomes below */
 /* The segmented sort + unique of kmcpg_sketch_genomes (sort_segments.hip) on lists the caller lays out; needs no handle and runs on
  * the current device.  Debug/tests.  All pointers but rec are device memory.  List s is the concatenation over parts p < parts of

@@ -198,6 +198,10 @@ struct kmcpg_db {
   // optional HIP-event timing of the last kmcpg_query_device call
   int profiling = 0;  // 1: HIP-event timing of the kernels; 2: + count the row loads k2_cobs issues
   std::vector<kmcpg_k2_launch> k2_log;  // the COBS kernels the last kmcpg_query_device call launched (profiling >= 1; kmcpg_last_k2_launches)
+  // the K1 kernels the last k-mer stage launched, the plan's record first (profiling >= 1; kmcpg_last_k1_launches), and — for the two list
+  // forms — the device word that holds what the first kernel left on its list (valid until the slot's next batch)
+  std::vector<kmcpg_k1_launch> k1_log;
+  const uint32_t* k1_left = nullptr;
   // K3 (device half of finalize): Header.Sizes of every global column on the device, per-read counters and scan scratch
   uint64_t* d_col_size = nullptr;
   kmcpg::DevBuf<uint32_t> w_fin_cnt;

@@ -1909,67 +1909,113 @@ __global__ void __launch_bounds__(256) k1_win_gather(const K1Args a, const Windo
   }
 }
 
+// What a launch leaves in the log (kmcpg_last_k1_launches).  Every templated kernel is launched by a function template of the same
+// parameters that writes them itself, so a record cannot name another instantiation than the one that ran.
+static void k1_note(K1Log* log, int kernel, int p0, int p1, unsigned grid, unsigned block, size_t lds) {
+  if (!log) return;
+  kmcpg_k1_launch r{};
+  r.kernel = kernel;
+  r.p0 = p0;
+  r.p1 = p1;
+  r.grid = grid;
+  r.block = block;
+  r.lds_bytes = (uint32_t)lds;
+  r.left_on_list = UINT32_MAX;
+  log->push_back(r);
+}
+template <int MODE>
+static void kmers_launch(const K1Args& a, unsigned grid, hipStream_t st, K1Log* log) {
+  hipLaunchKernelGGL(k1_kmers<MODE>, dim3(grid), dim3(256), 0, st, a);
+  k1_note(log, KMCPG_K1_KMERS, MODE, 0, grid, 256, 0);
+}
+template <int MODE>
+static void kmers_wg_launch(const K1Args& a, unsigned grid, hipStream_t st, K1Log* log) {
+  hipLaunchKernelGGL(k1_kmers_wg<MODE>, dim3(grid), dim3(K1WG), 0, st, a);
+  k1_note(log, KMCPG_K1_KMERS_WG, MODE, 0, grid, K1WG, 0);
+}
+template <int MODE>
+static void windows_wave_launch(const K1Args& a, unsigned grid, hipStream_t st, K1Log* log) {
+  hipLaunchKernelGGL(k1_windows_wave<MODE>, dim3(grid), dim3(K1W_THREADS), 0, st, a);
+  k1_note(log, KMCPG_K1_WINDOWS_WAVE, MODE, 0, grid, K1W_THREADS, 0);
+}
 // k1_windows_roll<WSZ, WAVES>: the 15 forms the plan can name (WSZ 12 / 16 / 20 / 24 / 32 s-mers, 4 / 2 / 1 reads per workgroup)
 template <int WSZ, int WAVES>
-static void windows_roll_launch(const K1Args& a, const K1Plan& p, hipStream_t st) {
+static void windows_roll_launch(const K1Args& a, const K1Plan& p, hipStream_t st, K1Log* log) {
   hipLaunchKernelGGL((k1_windows_roll<WSZ, WAVES>), dim3(p.grid), dim3(64 * WAVES), p.lds_bytes, st, a, p.words);
+  k1_note(log, KMCPG_K1_WINDOWS_ROLL, WSZ, WAVES, p.grid, 64 * WAVES, p.lds_bytes);
 }
 template <int WSZ>
-static void windows_roll_waves(const K1Args& a, const K1Plan& p, hipStream_t st) {
-  if (p.waves == 4) windows_roll_launch<WSZ, 4>(a, p, st);
-  else if (p.waves == 2) windows_roll_launch<WSZ, 2>(a, p, st);
-  else windows_roll_launch<WSZ, 1>(a, p, st);
+static void windows_roll_waves(const K1Args& a, const K1Plan& p, hipStream_t st, K1Log* log) {
+  if (p.waves == 4) windows_roll_launch<WSZ, 4>(a, p, st, log);
+  else if (p.waves == 2) windows_roll_launch<WSZ, 2>(a, p, st, log);
+  else windows_roll_launch<WSZ, 1>(a, p, st, log);
+}
+static void seg_roll_launch(const K1Args& a, unsigned grid, hipStream_t st, K1Log* log) {
+  hipLaunchKernelGGL(k1_seg_roll, dim3(grid), dim3(64 * ROLL_WAVES), 0, st, a);
+  k1_note(log, KMCPG_K1_SEG_ROLL, 0, 0, grid, 64 * ROLL_WAVES, 0);
+}
+static void seg_pack_launch(const K1Args& a, unsigned grid, hipStream_t st, K1Log* log) {
+  hipLaunchKernelGGL(k1_seg_pack, dim3(grid), dim3(256), 0, st, a);
+  k1_note(log, KMCPG_K1_SEG_PACK, 0, 0, grid, 256, 0);
 }
 
 // the kernels of the plan's form, in order (k1_plan.hpp; the table: DESIGN.md §4).  Everything was decided there: `a` is complete, side
 // buffer pointers included, and nothing here looks at the batch again.
-void launch_k1(const K1Args& a, const K1Plan& p, const K1WinOnce& wo, hipStream_t st) {
+void launch_k1(const K1Args& a, const K1Plan& p, const K1WinOnce& wo, hipStream_t st, K1Log* log) {
   switch (p.form) {
     case K1Form::None: break;
     case K1Form::WinOnce:  // sliding windows, each staged base hashed once
       if (p.grid) {
         hipLaunchKernelGGL(k1_win_hash, dim3(p.grid), dim3(256), 0, st, a, wo.w, wo.h, wo.cnt);
+        k1_note(log, KMCPG_K1_WIN_HASH, 0, 0, p.grid, 256, 0);
         hipLaunchKernelGGL(k1_win_scan, dim3(1), dim3(1024), 0, st, wo.cnt, wo.w.n_chunks, wo.cbase);
+        k1_note(log, KMCPG_K1_WIN_SCAN, 0, 0, 1, 1024, 0);
         hipLaunchKernelGGL(k1_win_rank, dim3(p.grid), dim3(256), 0, st, a, wo.w, wo.h, wo.cbase, wo.kept, wo.rank);
+        k1_note(log, KMCPG_K1_WIN_RANK, 0, 0, p.grid, 256, 0);
       } else {
         (void)hipMemsetAsync(wo.cbase, 0, sizeof(uint64_t), st);
       }
       hipLaunchKernelGGL(k1_win_gather, dim3(p.grid2), dim3(256), 0, st, a, wo.w, wo.kept, wo.rank, wo.cbase);
+      k1_note(log, KMCPG_K1_WIN_GATHER, 0, 0, p.grid2, 256, 0);
       break;
     case K1Form::SegRoll2:  // whole genomes: one workgroup per 65536-position segment, then an ordered pack
       (void)hipMemsetAsync(a.seg_nflag, 0, sizeof(uint32_t), st);
       if (p.marks.len) {  // codes with runs of foreign bytes: the segments they reach are marked for the list ...
         (void)hipMemsetAsync(a.seg_exc, 0, p.marks.len * sizeof(uint32_t), st);
         hipLaunchKernelGGL(k_mark_exc, dim3((a.n_exc + 255) / 256), dim3(256), 0, st, a);
+        k1_note(log, KMCPG_K1_MARK_EXC, 0, 0, (a.n_exc + 255) / 256, 256, 0);
       }
       hipLaunchKernelGGL(k1_seg_roll2, dim3(p.grid), dim3(64 * R2_WAVES), 0, st, a);  // 2-bit codes; lists the segments it cannot take
+      k1_note(log, KMCPG_K1_SEG_ROLL2, 0, 0, p.grid, 64 * R2_WAVES, 0);
       if (p.marks.len) {  // ... and only those become text
         hipLaunchKernelGGL(k_unpack2_list, dim3(p.grid2), dim3(256), 0, st, a);
+        k1_note(log, KMCPG_K1_UNPACK2_LIST, 0, 0, p.grid2, 256, 0);
         launch_apply_exc(a.exc, a.n_exc, a.seqs_w, st);
       }
       // the byte kernel does the listed segments: nothing but the read of one counter for a clean batch, where a launch over all segments
       // was up to 2^21 workgroups exiting at once
-      if (p.list_fallback) hipLaunchKernelGGL(k1_seg_roll, dim3(p.grid2), dim3(64 * ROLL_WAVES), 0, st, a);
-      hipLaunchKernelGGL(k1_seg_pack, dim3(p.grid), dim3(256), 0, st, a);
+      if (p.list_fallback) seg_roll_launch(a, p.grid2, st, log);
+      seg_pack_launch(a, p.grid, st, log);
       break;
     case K1Form::SegRoll:
-      hipLaunchKernelGGL(k1_seg_roll, dim3(p.grid), dim3(64 * ROLL_WAVES), 0, st, a);
-      hipLaunchKernelGGL(k1_seg_pack, dim3(p.grid), dim3(256), 0, st, a);
+      seg_roll_launch(a, p.grid, st, log);
+      seg_pack_launch(a, p.grid, st, log);
       break;
     case K1Form::SegHash:
       hipLaunchKernelGGL(k1_seg_hash, dim3(p.grid), dim3(K1WG), 0, st, a);
-      hipLaunchKernelGGL(k1_seg_pack, dim3(p.grid), dim3(256), 0, st, a);
+      k1_note(log, KMCPG_K1_SEG_HASH, 0, 0, p.grid, K1WG, 0);
+      seg_pack_launch(a, p.grid, st, log);
       break;
     case K1Form::WindowsRoll:  // closed syncmers of long reads: the rolling kernel, k1_windows_wave behind it for the reads on its list
       (void)hipMemsetAsync(a.seg_nflag, 0, sizeof(uint32_t), st);
       switch (p.wsz) {
-        case 12: windows_roll_waves<12>(a, p, st); break;
-        case 16: windows_roll_waves<16>(a, p, st); break;
-        case 20: windows_roll_waves<20>(a, p, st); break;
-        case 24: windows_roll_waves<24>(a, p, st); break;
-        default: windows_roll_waves<32>(a, p, st); break;
+        case 12: windows_roll_waves<12>(a, p, st, log); break;
+        case 16: windows_roll_waves<16>(a, p, st, log); break;
+        case 20: windows_roll_waves<20>(a, p, st, log); break;
+        case 24: windows_roll_waves<24>(a, p, st, log); break;
+        default: windows_roll_waves<32>(a, p, st, log); break;
       }
-      hipLaunchKernelGGL(k1_windows_wave<2>, dim3(p.grid2), dim3(K1W_THREADS), 0, st, a);
+      windows_wave_launch<2>(a, p.grid2, st, log);
       if (p.debug) {  // how many reads the rolling kernel left to k1_windows_wave
         uint32_t nf = 0;
         (void)hipStreamSynchronize(st);
@@ -1978,19 +2024,22 @@ void launch_k1(const K1Args& a, const K1Plan& p, const K1WinOnce& wo, hipStream_
       }
       break;
     case K1Form::WindowsWave:  // window sketches of long reads, a wave per read
-      if (a.mode == 2) hipLaunchKernelGGL(k1_windows_wave<2>, dim3(p.grid), dim3(K1W_THREADS), 0, st, a);
-      else hipLaunchKernelGGL(k1_windows_wave<1>, dim3(p.grid), dim3(K1W_THREADS), 0, st, a);
+      if (a.mode == 2) windows_wave_launch<2>(a, p.grid, st, log);
+      else windows_wave_launch<1>(a, p.grid, st, log);
       break;
-    case K1Form::WgGlobal: hipLaunchKernelGGL(k1_kmers_wg_global, dim3(p.grid), dim3(K1WG), 0, st, a); break;
+    case K1Form::WgGlobal:
+      hipLaunchKernelGGL(k1_kmers_wg_global, dim3(p.grid), dim3(K1WG), 0, st, a);
+      k1_note(log, KMCPG_K1_KMERS_WG_GLOBAL, 0, 0, p.grid, K1WG, 0);
+      break;
     case K1Form::Wg:  // long queries: a whole workgroup per read
-      if (a.mode == 2) hipLaunchKernelGGL(k1_kmers_wg<2>, dim3(p.grid), dim3(K1WG), 0, st, a);
-      else if (a.mode == 1) hipLaunchKernelGGL(k1_kmers_wg<1>, dim3(p.grid), dim3(K1WG), 0, st, a);
-      else hipLaunchKernelGGL(k1_kmers_wg<0>, dim3(p.grid), dim3(K1WG), 0, st, a);
+      if (a.mode == 2) kmers_wg_launch<2>(a, p.grid, st, log);
+      else if (a.mode == 1) kmers_wg_launch<1>(a, p.grid, st, log);
+      else kmers_wg_launch<0>(a, p.grid, st, log);
       break;
     case K1Form::Short:  // four reads per workgroup, a wave each
-      if (a.mode == 2) hipLaunchKernelGGL(k1_kmers<2>, dim3(p.grid), dim3(256), 0, st, a);
-      else if (a.mode == 1) hipLaunchKernelGGL(k1_kmers<1>, dim3(p.grid), dim3(256), 0, st, a);
-      else hipLaunchKernelGGL(k1_kmers<0>, dim3(p.grid), dim3(256), 0, st, a);
+      if (a.mode == 2) kmers_launch<2>(a, p.grid, st, log);
+      else if (a.mode == 1) kmers_launch<1>(a, p.grid, st, log);
+      else kmers_launch<0>(a, p.grid, st, log);
       break;
   }
 }

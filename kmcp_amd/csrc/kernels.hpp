@@ -23,7 +23,10 @@ struct K1WinOnce {
 };
 // K1: the kernels of the plan's form (k1_plan.hpp); `a` complete, side buffer pointers included.  Whether adjacent repeats are already
 // dropped afterwards is the plan's adj_done
-void launch_k1(const K1Args& a, const K1Plan& p, const K1WinOnce& wo, hipStream_t st);
+// what launch_k1 notes about every kernel it launches (kmcpg_last_k1_launches): written at the launch site from the template parameters
+// of the launching function.  nullptr = no log (and nothing else differs)
+typedef std::vector<kmcpg_k1_launch> K1Log;
+void launch_k1(const K1Args& a, const K1Plan& p, const K1WinOnce& wo, hipStream_t st, K1Log* log);
 void launch_nk_simple(const int32_t* nk_raw, int32_t* nk_search, uint32_t n, int32_t min_matched, hipStream_t st);
 void launch_dedup(DedupArgs a, uint64_t max_n, hipStream_t st);  // queries above HUGE_MIN are left to huge_dedup
 // what the K2 launchers note about every kernel they launch (kmcpg_last_k2_launches): written at the launch site from the template

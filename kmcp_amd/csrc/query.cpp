@@ -75,6 +75,9 @@ K1Knobs k1_knobs() {
 // K1 (+K1d): hashes of read i end up at d_hashes[offs[i] + offs2[i] ...], NumKmers in d_nk_search
 int run_kmers(kmcpg_db* db, kmcpg_db::Workspace& W, const DeviceBatch& b, const kmcpg_params& p, const KmerOut& o, hipStream_t st, uint64_t* max_n_out) {
   const kmcpg_info& I = db->info;
+  db->k1_log.clear();
+  db->k1_left = nullptr;
+  K1Log* const k1_log = db->profiling >= 1 ? &db->k1_log : nullptr;  // launch_k1 writes it, kmcpg_last_k1_launches reads it
   if (!I.canonical) return kmcpg_fail(KMCPG_EUNSUPPORTED, "non-canonical index");
   const PackedSrc& src = b.packed;   // a batch that came as 2-bit codes (host.cpp: kmcpg_submit_packed, or text stage() packed)
   const WindowSrc& win = b.windows;  // sliding windows (host.cpp kmcpg_submit_windows): every kernel reads a window's bases in place through its view
@@ -138,7 +141,21 @@ int run_kmers(kmcpg_db* db, kmcpg_db::Workspace& W, const DeviceBatch& b, const 
     }
     (plan.codes_direct ? db->k1_codes_direct : db->k1_codes_expanded)++;
   }
-  launch_k1(a, plan, K1WinOnce{win, W.w_win_h.p, W.w_win_kept.p, W.w_win_rank.p, W.w_win_cnt.p, W.w_win_cbase.p}, st);
+  if (k1_log) {  // the plan, once per call; what a list form leaves on its list is read by whoever synchronises anyway (kmers_device)
+    static_assert((int)K1Form::None == KMCPG_K1F_NONE && (int)K1Form::WinOnce == KMCPG_K1F_WIN_ONCE && (int)K1Form::SegRoll2 == KMCPG_K1F_SEG_ROLL2 &&
+                      (int)K1Form::SegRoll == KMCPG_K1F_SEG_ROLL && (int)K1Form::SegHash == KMCPG_K1F_SEG_HASH &&
+                      (int)K1Form::WindowsRoll == KMCPG_K1F_WINDOWS_ROLL && (int)K1Form::WindowsWave == KMCPG_K1F_WINDOWS_WAVE &&
+                      (int)K1Form::WgGlobal == KMCPG_K1F_WG_GLOBAL && (int)K1Form::Wg == KMCPG_K1F_WG && (int)K1Form::Short == KMCPG_K1F_SHORT,
+                  "include/kmcp_gpu.h restates K1Form");
+    kmcpg_k1_launch r{};
+    r.kernel = KMCPG_K1_PLAN;
+    r.p0 = (int)plan.form;
+    r.p1 = (plan.codes_direct ? 1 : 0) | (plan.list_fallback ? 2 : 0) | (plan.adj_done ? 4 : 0);
+    r.left_on_list = UINT32_MAX;
+    k1_log->push_back(r);
+    if (plan.form == K1Form::SegRoll2 || plan.form == K1Form::WindowsRoll) db->k1_left = a.seg_nflag;
+  }
+  launch_k1(a, plan, K1WinOnce{win, W.w_win_h.p, W.w_win_kept.p, W.w_win_rank.p, W.w_win_cnt.p, W.w_win_cbase.p}, st, k1_log);
   uint64_t ub = b.max_read_len >= (uint32_t)a.k ? (uint64_t)(b.max_read_len - a.k + 1) : 0;
   if (b.d_seqs2) ub *= 2;
   *max_n_out = ub;
@@ -314,10 +331,12 @@ int fpr_bound(kmcpg_db* db, double max_fpr, uint64_t max_kmers, hipStream_t st, 
 
 }  // namespace
 
-// the k-mer stage alone on a batch of single reads, text or packed (b.d_seqs = the text, or where its expansion goes)
+// the k-mer stage alone on a batch of reads, text or packed (b.d_seqs = the text, or where its expansion goes), single or paired (d_koff is
+// for single reads: a pair's hashes start at offs[i] + offs2[i]); d_nk1 (optional): the first mate's raw count
 static int kmers_device(kmcpg_db* db, const DeviceBatch& b, const kmcpg_params* params, uint64_t* d_hashes, uint64_t hashes_cap, uint64_t* d_koff, int32_t* d_nk,
-                        void* stream) {
+                        int32_t* d_nk1, void* stream) {
   if (!db || !b.d_seqs || !b.d_offs || !d_hashes || !d_nk) return kmcpg_fail(KMCPG_EINVAL, "null argument");
+  if ((b.d_seqs2 == nullptr) != (b.d_offs2 == nullptr)) return kmcpg_fail(KMCPG_EINVAL, "seqs2 and offs2 must be given together");
   if (hashes_cap < b.total_bases) return kmcpg_fail(KMCPG_EINVAL, "hashes_cap must be >= total_bases");
   KMCPG_NO_FILES_ONLY(db);
   std::lock_guard<std::mutex> g(db->mu);
@@ -333,17 +352,29 @@ static int kmers_device(kmcpg_db* db, const DeviceBatch& b, const kmcpg_params* 
   uint64_t maxn = 0;
   int rc = run_kmers(db, W, b, p, KmerOut{d_hashes, W.w_scratch.p, b.total_bases + 1, W.w_nk_raw.p, W.w_nk1.p, d_nk, ql.p}, st, &maxn);
   if (rc == 0 && d_koff) HIPCHK(hipMemcpyAsync(d_koff, b.d_offs, (size_t)b.n_reads * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
+  if (rc == 0 && d_nk1 && b.n_reads) HIPCHK(hipMemcpyAsync(d_nk1, W.w_nk1.p, (size_t)b.n_reads * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
   hipError_t e = hipStreamSynchronize(st);
   ql.release();
   if (rc) return rc;
   if (e != hipSuccess) return kmcpg_fail(KMCPG_EDEVICE, "k-mer kernel failed: %s", hipGetErrorString(e));
+  // the witness of a list form: what the first kernel left to the one behind it (the stream is idle, the lock held; profiling only)
+  if (db->k1_left && !db->k1_log.empty()) HIPCHK(hipMemcpy(&db->k1_log[0].left_on_list, db->k1_left, sizeof(uint32_t), hipMemcpyDeviceToHost));
   return 0;
 }
 
 extern "C" int kmcpg_kmers_device(kmcpg_db* db, const uint8_t* d_seqs, const uint64_t* d_offs, uint32_t n_reads, uint64_t total_bases,
                                   uint32_t max_read_len, const kmcpg_params* params, uint64_t* d_hashes, uint64_t hashes_cap, uint64_t* d_koff,
                                   int32_t* d_nk, void* stream) {
-  return kmers_device(db, DeviceBatch{d_seqs, d_offs, nullptr, nullptr, n_reads, total_bases, max_read_len}, params, d_hashes, hashes_cap, d_koff, d_nk, stream);
+  return kmers_device(db, DeviceBatch{d_seqs, d_offs, nullptr, nullptr, n_reads, total_bases, max_read_len}, params, d_hashes, hashes_cap, d_koff, d_nk, nullptr,
+                      stream);
+}
+
+extern "C" int kmcpg_kmers_device_paired(kmcpg_db* db, const uint8_t* d_seqs, const uint64_t* d_offs, const uint8_t* d_seqs2, const uint64_t* d_offs2,
+                                         uint32_t n_reads, uint64_t total_bases, uint32_t max_read_len, const kmcpg_params* params, uint64_t* d_hashes,
+                                         uint64_t hashes_cap, int32_t* d_nk, int32_t* d_nk1, void* stream) {
+  if (!d_seqs2 || !d_offs2) return kmcpg_fail(KMCPG_EINVAL, "null argument");
+  return kmers_device(db, DeviceBatch{d_seqs, d_offs, d_seqs2, d_offs2, n_reads, total_bases, max_read_len}, params, d_hashes, hashes_cap, nullptr, d_nk, d_nk1,
+                      stream);
 }
 
 extern "C" int kmcpg_kmers_device_packed(kmcpg_db* db, const uint8_t* d_codes, const kmcpg_exc_run* d_exc, uint32_t n_exc, uint8_t* d_text,
@@ -359,7 +390,7 @@ extern "C" int kmcpg_kmers_device_packed(kmcpg_db* db, const uint8_t* d_codes, c
   b.packed.n_exc = n_exc;
   b.packed.text = d_text;
   b.packed.n_bases = total_bases;
-  return kmers_device(db, b, params, d_hashes, hashes_cap, d_koff, d_nk, stream);
+  return kmers_device(db, b, params, d_hashes, hashes_cap, d_koff, d_nk, nullptr, stream);
 }
 
 extern "C" int kmcpg_k1_codes_batches(kmcpg_db* db, uint64_t* direct, uint64_t* expanded) {
@@ -705,6 +736,19 @@ extern "C" int kmcpg_last_k2_launches(kmcpg_db* db, kmcpg_k2_launch* out, uint32
   const size_t m = std::min<size_t>(cap, db->k2_log.size());
   if (m) memcpy(out, db->k2_log.data(), m * sizeof(kmcpg_k2_launch));
   *n = (uint32_t)db->k2_log.size();
+  return 0;
+}
+
+extern "C" int kmcpg_last_k1_launches(kmcpg_db* db, kmcpg_k1_launch* out, uint32_t cap, uint32_t* n) {
+  static_assert(sizeof(kmcpg_k1_launch) == 32, "eight 4-byte words");
+  if (!db || !n || (cap && !out)) return kmcpg_fail(KMCPG_EINVAL, "null argument");
+  std::lock_guard<std::mutex> g(db->mu);
+  // the records are written while the call enqueues its kernels (left_on_list: after kmers_device has synchronised): nothing to wait for;
+  // without profiling there are none
+  const size_t have = db->profiling >= 1 ? db->k1_log.size() : 0;
+  const size_t m = std::min<size_t>(cap, have);
+  if (m) memcpy(out, db->k1_log.data(), m * sizeof(kmcpg_k1_launch));
+  *n = (uint32_t)have;
   return 0;
 }
 

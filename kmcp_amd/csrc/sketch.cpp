@@ -140,7 +140,7 @@ int sketch_piece(kmcpg_sketcher* s, const std::vector<Chunk>& ch, size_t c0, siz
     a.nk_adj = nullptr;
     a.dedup_threshold = sh.dedup_threshold;
     a.src = s->d_src.p;
-    launch_k1(a, plan, K1WinOnce{}, st);
+    launch_k1(a, plan, K1WinOnce{}, st, nullptr);
   }
   HIPCHK(hipEventRecord(s->ev[1], st));
   SegSortIn in{};

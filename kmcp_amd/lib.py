@@ -19,7 +19,7 @@ EXPORTS = [
     "kmcpg_db_ks", "kmcpg_open_paged", "kmcpg_paged_info", "kmcpg_exchange_info", "kmcpg_batch_hint", "kmcpg_group_device", "kmcpg_finalize_grouped",
     "kmcpg_search_batch_pairs", "kmcpg_wait_pairs", "kmcpg_result_pairs_free", "kmcpg_expand_pairs", "kmcpg_save_db",
     "kmcpg_pack2", "kmcpg_unpack2", "kmcpg_submit_packed", "kmcpg_host_alloc", "kmcpg_host_free",
-    "kmcpg_kmers_device_packed", "kmcpg_k1_codes_batches",
+    "kmcpg_kmers_device_packed", "kmcpg_k1_codes_batches", "kmcpg_kmers_device_paired", "kmcpg_last_k1_launches",
     "kmcpg_submit_windows", "kmcpg_submit_packed_windows", "kmcpg_window_count", "kmcpg_window_locate",
     "kmcpg_density_bins", "kmcpg_block_density", "kmcpg_col_ones", "kmcpg_last_density_launch", "kmcpg_open_files",
     "kmcpg_last_density_ms", "kmcpg_stream_probe",
@@ -137,6 +137,18 @@ class K2Launch(C.Structure):
 
 
 K2_KINDS = ("plain", "split", "pair")
+
+
+class K1Launch(C.Structure):
+    """kmcpg_k1_launch: one K1 kernel launch of a k-mer stage, or (kernel 0) the plan of that stage"""
+    _fields_ = [("kernel", C.c_int32), ("p0", C.c_int32), ("p1", C.c_int32), ("grid", C.c_uint32), ("block", C.c_uint32),
+                ("lds_bytes", C.c_uint32), ("left_on_list", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+# KMCPG_K1_* and KMCPG_K1F_* (include/kmcp_gpu.h)
+K1_KERNELS = ("plan", "k1_kmers", "k1_kmers_wg", "k1_kmers_wg_global", "k1_windows_wave", "k1_windows_roll", "k1_seg_roll2", "k1_seg_roll",
+              "k1_seg_hash", "k1_seg_pack", "k_mark_exc", "k_unpack2_list", "k1_win_hash", "k1_win_scan", "k1_win_rank", "k1_win_gather")
+K1_FORMS = ("None", "WinOnce", "SegRoll2", "SegRoll", "SegHash", "WindowsRoll", "WindowsWave", "WgGlobal", "Wg", "Short")
 
 
 class DensitySpec(C.Structure):
@@ -286,6 +298,8 @@ def load():
     L.kmcpg_last_tail_waves.argtypes = [vp, u64p]
     L.kmcpg_last_hash_bytes.argtypes = [vp, u64p]
     L.kmcpg_last_k2_launches.argtypes = [vp, C.POINTER(K2Launch), C.c_uint32, C.POINTER(C.c_uint32)]
+    L.kmcpg_last_k1_launches.argtypes = [vp, C.POINTER(K1Launch), C.c_uint32, C.POINTER(C.c_uint32)]
+    L.kmcpg_kmers_device_paired.argtypes = [vp, vp, vp, vp, vp, C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(Params), vp, C.c_uint64, vp, vp, vp]
     L.kmcpg_timing_at.argtypes = [vp, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.kmcpg_build_db.argtypes = [C.c_char_p, C.POINTER(BuildCfg), C.POINTER(BuildCol), C.c_uint32, C.c_int32]
     L.kmcpg_save_db.argtypes = [vp, C.c_char_p]
@@ -848,6 +862,37 @@ class Database:
         p = params or default_params()
         _check(load().kmcpg_kmers_device_packed(self._h, d_codes, d_exc, n_exc, d_text, d_offs, n_reads, total_bases, max_read_len, C.byref(p),
                                                 d_hashes, hashes_cap, d_koff, d_nk, stream))
+
+    def kmers_device_paired(self, d_seqs, d_offs, d_seqs2, d_offs2, n_reads, total_bases, max_read_len, d_hashes, hashes_cap, d_nk, d_nk1=None,
+                            params=None, stream=None):
+        """kmers_device on pairs (kmcpg_kmers_device_paired): total_bases over both mates; the hashes of pair i (mate 1's, then mate 2's)
+        start at offs[i] + offs2[i]; d_nk1 receives the first mate's count"""
+        p = params or default_params()
+        _check(load().kmcpg_kmers_device_paired(self._h, d_seqs, d_offs, d_seqs2, d_offs2, n_reads, total_bases, max_read_len, C.byref(p),
+                                                d_hashes, hashes_cap, d_nk, d_nk1, stream))
+
+    def _k1_records(self):
+        n = C.c_uint32(0)
+        _check(load().kmcpg_last_k1_launches(self._h, None, 0, C.byref(n)))
+        buf = (K1Launch * max(1, n.value))()
+        _check(load().kmcpg_last_k1_launches(self._h, buf, n.value, C.byref(n)))
+        return list(buf[:n.value])
+
+    def last_k1_launches(self):
+        """The K1 kernels the handle's last k-mer stage launched, in launch order (profiling level >= 1, [] without): tuples
+        (kernel, p0, p1, grid, block, lds_bytes) with kernel in K1_KERNELS[1:]; p0 / p1 are the kernel's template parameters (MODE, or
+        WSZ and WAVES of k1_windows_roll), 0 where it has none."""
+        return [(K1_KERNELS[r.kernel], r.p0, r.p1, r.grid, r.block, r.lds_bytes) for r in self._k1_records() if r.kernel != 0]
+
+    def last_k1_plan(self):
+        """The plan of that stage (k1_plan.hpp): dict(form in K1_FORMS, codes_direct, list_fallback, adj_done, left_on_list) or None without
+        profiling.  left_on_list: what the first kernel of a list form left to the kernel behind it; None = no list, or not read (only
+        kmers_device* read it back)."""
+        for r in self._k1_records():
+            if r.kernel == 0:
+                return dict(form=K1_FORMS[r.p0], codes_direct=bool(r.p1 & 1), list_fallback=bool(r.p1 & 2), adj_done=bool(r.p1 & 4),
+                            left_on_list=None if r.left_on_list == 0xFFFFFFFF else int(r.left_on_list))
+        return None
 
     def k1_codes_batches(self):
         """(packed batches whose k-mer kernels read the codes directly, packed batches expanded to text first)"""

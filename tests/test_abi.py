@@ -34,6 +34,7 @@ def test_struct_layouts_match_header(L):
     assert C.sizeof(L.Params) == 64
     assert C.sizeof(L.SynthSpec) == 64
     assert C.sizeof(L.K2Launch) == 32
+    assert C.sizeof(L.K1Launch) == 32
 
 
 def test_no_cpu_fallback(L, tmp_path):

@@ -222,7 +222,8 @@ def test_rolling_window_sketch_kernel_at_its_boundaries(G, oracle_lib, monkeypat
     and against k1_windows_wave (KMCPG_K1_FLAGS=35) at the edges of what it takes: reads of exactly WR_MIN_WINDOWS windows and one fewer, window
     counts around multiples of 64 x 16 (the lanes' runs are multiples of 16: the last lanes idle or hold one window), soft-masked reads, one N at
     the very end / start (left to the wave kernel), a low-complexity read whose emissions repeat for hundreds of windows (the adjacent-repeat
-    stitching across lanes), a homopolymer (hash 0 never: all kept), the longest read the LDS takes; -u above and below the emission count."""
+    stitching across lanes), a homopolymer (hash 0 never: all kept); -u above and below the emission count.  (The longest reads the LDS takes, every WSZ x
+    waves instantiation and what the kernel leaves on its list: tests/test_gpu_k1_forms.py.)"""
     import torch
     O = oracle_lib
     lib = G["lib"]
@@ -239,7 +240,9 @@ def test_rolling_window_sketch_kernel_at_its_boundaries(G, oracle_lib, monkeypat
     t_seqs = torch.from_numpy(seqs).to(dev)
     t_offs = torch.from_numpy(offs.view(np.int64)).to(dev)
     out = {}
+    monkeypatch.delenv("KMCPG_WR_WAVES", raising=False)
     with G["Database"].open_synthetic(spec) as db:
+        db.set_profiling(1)
         for flags in ("3", "35"):
             monkeypatch.setenv("KMCPG_K1_FLAGS", flags)
             for thr in (256, 3000):
@@ -250,6 +253,14 @@ def test_rolling_window_sketch_kernel_at_its_boundaries(G, oracle_lib, monkeypat
                                 t_nk.data_ptr(), params=p)
                 torch.cuda.synchronize()
                 out[(flags, thr)] = (t_h.cpu().numpy().view(np.uint64), t_nk.cpu().numpy())
+                # the witness: under flags 3 the rolling kernel ran and took reads (it did not leave them all to the kernel behind it, which
+                # would make the comparison below one of k1_windows_wave with itself); under flags 35 the wave kernel ran alone
+                plan, ran = db.last_k1_plan(), [w[:3] for w in db.last_k1_launches()]
+                if flags == "3":
+                    assert plan["form"] == "WindowsRoll" and ran == [("k1_windows_roll", 2 * (k - s), 2), ("k1_windows_wave", 2, 0)], (plan, ran)
+                    assert 0 < plan["left_on_list"] < len(reads), plan
+                else:
+                    assert plan["form"] == "WindowsWave" and ran == [("k1_windows_wave", 2, 0)] and plan["left_on_list"] is None, (plan, ran)
     for thr in (256, 3000):
         h3, n3 = out[("3", thr)]
         h35, n35 = out[("35", thr)]

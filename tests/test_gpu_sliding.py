@@ -130,6 +130,23 @@ def test_windows_equal_materialized_windows(oracle_lib, tmp_path, genomes, mode)
                 assert have[4] == want[4]
                 hits += len(want[2])
             assert hits > 0
+        # the witness (Database.last_k1_launches): overlapping windows of plain / FracMinHash k-mers ran the four hash-once kernels and
+        # nothing else of K1; windows that do not overlap (step >= window), and the window sketches, did not run them
+        db.set_profiling(1)
+        try:
+            win_once = ["k1_win_hash", "k1_win_scan", "k1_win_rank", "k1_win_gather"]
+            for (S, W, g) in [(100, 300, True), (300, 300, False), (500, 200, True)]:
+                db.wait(db.submit_windows(seqs, offs, S, W, g, default_params()))
+                ran = [w[0] for w in db.last_k1_launches()]
+                plan = db.last_k1_plan()
+                assert plan["left_on_list"] is None, plan  # nothing is read back on the asynchronous path
+                if mode in ("plain", "frac") and S < W:
+                    assert plan["form"] == "WinOnce" and ran == win_once, (mode, S, W, plan, ran)
+                else:
+                    assert plan["form"] != "WinOnce" and ran and not set(ran) & set(win_once), (mode, S, W, plan, ran)
+        finally:
+            db.set_profiling(0)
+        assert db.last_k1_launches() == [] and db.last_k1_plan() is None
     odb.close()
 
 
