@@ -169,14 +169,8 @@ struct K2Args {
   unsigned long long* gathered;  // optional (profiling level 2): 16-byte row loads issued, K2_GATHER_SLOTS counters 128 B apart
   const uint16_t* cmin_fpr;      // optional: [n] = smallest count whose FPR(n, count) passes -f, n <= cmin_fpr_n (query.cpp fpr_bound)
   int32_t cmin_fpr_n;
-  int32_t k2_flags;              // K2F_ bits: only k2_cobs<64, 8|10, false, false, 4> reads them (k2_cobs_body.inc, the short-read path)
+  int32_t k2_flags;              // K2F_ bits (k2_plan.hpp): only k2_cobs<64, 8|10, false, false, 4> reads them (k2_cobs_body.inc, the short-read path)
 };
-// one index phase per (read, run of tiles): `slots` is the class's block-unit list (Slot::tile carries the tile count)
-constexpr int32_t K2F_BLOCK_UNITS = 1;
-// every 128-byte sector steps by the rows its best column proves necessary and stops at its exact row
-constexpr int32_t K2F_EXACT_STOP = 2;
-// what a short-read batch gets without KMCPG_K2_BLOCK_UNITS / KMCPG_K2_EXACT_STOP in the environment (query.cpp)
-constexpr bool K2_BLOCK_UNITS_DEFAULT = false, K2_EXACT_STOP_DEFAULT = true;
 static_assert(sizeof(K2Args) == 208, "k2_flags sits in the tail padding: the argument block of every K2 form keeps its layout");
 
 // K3 (k3_finalize.hip): hit list -> per-read segments of (column, count), filtered by -T, ordered as the reference orders a

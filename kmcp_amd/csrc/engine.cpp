@@ -80,16 +80,14 @@ uint32_t row_align_for(const kmcpg_info& info) {
   return (info.scaled || info.minimizer || info.syncmer || info.num_hashes > 1) ? 128u : 64u;
 }
 
-// lanes per row tile (16 B each): the narrowest form that covers the row, so that no lane of a wave idles (a 128-byte row on the
-// 16-lane form left half of every wave without a row to load)
-int lpr_for_stride(uint32_t stride) {
-  if (const char* e = getenv("KMCPG_LPR8"))
-    if (atoi(e) == 0) return stride <= 64 ? 4 : (stride <= 256 ? 16 : 64);
-  // 257..512 bytes: the 32-lane form, two units per wave (KMCPG_LPR32=0: the 64-lane form with half of its lanes idle, as before round 5)
-  const bool lpr32 = !(getenv("KMCPG_LPR32") && atoi(getenv("KMCPG_LPR32")) == 0);
-  return stride <= 64 ? 4 : (stride <= 128 ? 8 : (stride <= 256 ? 16 : (stride <= 512 && lpr32 ? 32 : 64)));
+// The knobs of the lane cutting (k2_plan.hpp k2_row_parts), read at every open: tests flip them
+K2OpenKnobs k2_open_knobs() {
+  K2OpenKnobs kn;
+  if (const char* e = getenv("KMCPG_LPR8")) kn.lpr8 = atoi(e) != 0;
+  if (const char* e = getenv("KMCPG_LPR32")) kn.lpr32 = atoi(e) != 0;
+  if (const char* e = getenv("KMCPG_SPLIT_TILES")) kn.split_tiles = atoi(e);
+  return kn;
 }
-
 
 // blocks are independent: greedy partition by bytes, largest first
 void assign_shards(kmcpg_db* db) {
@@ -236,6 +234,7 @@ int finish_open(kmcpg_db* db) {
     }
     cls->slots.push_back(Slot{group, byte0 / ((uint32_t)lpr * 16u)});
   };
+  const K2OpenKnobs open_knobs = k2_open_knobs();
   for (size_t g = 0; g < db->groups.size(); g++) {
     const Group& G = db->groups[g];
     BlockDev gd{};
@@ -253,31 +252,9 @@ int finish_open(kmcpg_db* db) {
       gd.ncols += (uint32_t)b.h.names.size();
     }
     db->h_groupdev.push_back(gd);
-    // whole 1-KB tiles go to full waves (64 lanes x 16 B); what is left of the row to the narrowest lane group that covers it
-    const uint32_t full = G.stride / 1024u, rem = G.stride % 1024u;
-    for (uint32_t t = 0; t < full; t++) add_slot(64, (uint32_t)g, t * 1024u);
-    // EXPERIMENT, off (KMCPG_SPLIT_TILES=1: multi-hash databases, 2: all): a remainder of 257..896 bytes on the 64-lane form leaves
-    // 8..47 lanes of every wave without a row to load; cut into power-of-two tiles that fill their waves — 832 = 512 (32 lanes, two
-    // units per wave) + 256 (16 lanes) + 64 (4 lanes), each aligned to its own tile size — the genome search's K2 took 9.35 ms instead
-    // of 4.9 ms (same bytes moved): three launches read the hashes and compute the row indices three times, and the narrow parts run
-    // on the fabric's request rate.  The idle lanes were never the cost (profiles/r05_split_tiles.txt).
-    // Round 6 (profiles/r06_lpr_640.txt, single-hash index, short reads, 23-27 GB): a remainder of 640 bytes as 512 (32-lane form) + 128
-    // (8-lane form) is 11-17 % faster than one 64-lane tile with 40 lanes busy (385 -> 329-347 ms per 1 M reads) and is now what a
-    // single-hash database gets; 576 = 512 + 64 gains 4.6 % and 768 = 512 + 256 gains 6.8 %: below the 10 % bar, left as one tile.
-    const int split_tiles = getenv("KMCPG_SPLIT_TILES") ? atoi(getenv("KMCPG_SPLIT_TILES")) : -1;  // (read at every open: tests flip it; -1 = the rule above)
-    const bool split = rem > 256 && rem <= 896 && __builtin_popcount(rem / 64u) <= 3 &&
-                       (split_tiles == 2 || (split_tiles == 1 && db->info.num_hashes > 1) || (split_tiles < 0 && rem == 640 && db->info.num_hashes == 1));
-    if (rem && split) {
-      uint32_t at = full * 1024u, left = rem;
-      for (uint32_t part = 512; part >= 64 && left; part >>= 1)
-        if (left >= part) {
-          add_slot((int)(part / 16u), (uint32_t)g, at);
-          at += part;
-          left -= part;
-        }
-    } else if (rem) {
-      add_slot(lpr_for_stride(rem), (uint32_t)g, full * 1024u);
-    }
+    // the row's tiles, each a slot of its lane class
+    const K2RowParts parts = k2_row_parts(G.stride, db->info.num_hashes, open_knobs);
+    for (uint32_t i = 0; i < parts.size(); i++) add_slot(parts[i].lpr, (uint32_t)g, parts[i].byte0);
   }
   if (db->opts.device >= 0 && !db->h_blockdev.empty()) {
     HIPCHK(hipMalloc((void**)&db->d_blockdev, db->h_blockdev.size() * sizeof(BlockDev)));

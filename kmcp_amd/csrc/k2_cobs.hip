@@ -64,7 +64,7 @@ __device__ __forceinline__ bool group_col(const Seg* __restrict__ segs, const Bl
 // per-query u32 array with atomics and thresholded by k_threshold_long, so a whole genome spreads over the chip instead
 // of one wave per (query, slot).
 
-// GR = rows gathered between two pruning tests: 8, or 4 where the launch waits for HBM (the host decides, query.cpp).  The
+// GR = rows gathered between two pruning tests: 8, or 4 where the launch waits for HBM (the host decides, k2_plan.hpp).  The
 // short form is its own instantiation (4 rows in flight; 97 VGPRs, the 8-row form 91) built for at most 4 waves per SIMD: the kernel
 // is bound by the L2->fabric path, not by latency (the 8-row form runs as fast at 2 waves per SIMD as at 5), and of the
 // occupancy targets tried for the 4-row form this one is the fastest (GTDB scale: 488 ms; 506-510 ms at 5-6 waves, 510 ms at 3,
@@ -172,8 +172,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((NPL =
   else k2_body<LPRB, NPL, MULTI, false, 8>(b, blockIdx.x - nba);
 }
 
-constexpr uint64_t K2_MAX_BLOCKS = 1ull << 23;  // x 256 threads = 2^31
-
 // Every K2 kernel is launched by launch_k2_form or launch_k2_pair_form and nowhere else: the kernel's template arguments are the
 // function's own, so the record a launch leaves in the log (kmcpg_last_k2_launches) cannot name another form than the one that ran.
 static void note_k2(K2Log* log, int kind, int lpr, int lprb, int npl, bool multi, int gr, unsigned nb) {
@@ -201,108 +199,78 @@ static void launch_k2_pair_form(const K2Args& a, const K2Args& b, unsigned nba, 
   note_k2(log, 2, LPRA, LPRB, NPL, MULTI, 8, nba + nbb);  // both halves are k2_body<..., 8>
 }
 
-template <int LPR, int NPL>
-static void launch_k2_t(const K2Args& a, bool multi, hipStream_t st, K2Log* log) {
-  constexpr int G = 64 / LPR;
-  const uint64_t units = (G > 1 && a.slot_major == 2) ? (uint64_t)a.n_reads * (((uint64_t)a.nslots + G - 1) / G) * G : (uint64_t)a.n_reads * a.nslots;
-  const uint64_t waves = (units + G - 1) / G;
-  const uint64_t blocks = (waves + 3) / 4;
+// The launchers only launch: which kernel, on which grid, is the record's (k2_plan.hpp); they switch over it and visit its grid pieces.
+template <int LPR, int NPL, bool SPLIT, int GR>
+static int launch_k2_pieces(const K2Launch& l, const K2Args& a, hipStream_t st, K2Log* log) {
   K2Args b = a;
-  for (uint64_t b0 = 0; b0 < blocks; b0 += K2_MAX_BLOCKS) {  // a launch holds fewer than 2^32 threads
-    const unsigned nb = (unsigned)std::min<uint64_t>(K2_MAX_BLOCKS, blocks - b0);
-    b.unit_base = b0 * 4 * G;
-    if (NPL <= 10 && a.group_rows == 4) {
-      if (multi)
-        launch_k2_form<LPR, NPL <= 10 ? NPL : 8, true, false, 4>(b, nb, st, log);
-      else
-        launch_k2_form<LPR, NPL <= 10 ? NPL : 8, false, false, 4>(b, nb, st, log);
-    } else if (multi)
-      launch_k2_form<LPR, NPL, true, false, 8>(b, nb, st, log);
+  for (uint64_t i = 0, n = k2_n_pieces(l); i < n; i++) {
+    const K2Piece pc = k2_piece(l, i);
+    b.unit_base = pc.unit_base;
+    if (l.multi)
+      launch_k2_form<LPR, NPL, true, SPLIT, GR>(b, pc.workgroups, st, log);
     else
-      launch_k2_form<LPR, NPL, false, false, 8>(b, nb, st, log);
+      launch_k2_form<LPR, NPL, false, SPLIT, GR>(b, pc.workgroups, st, log);
   }
-}
-
-template <int LPR>
-static int launch_k2_l(const K2Args& a, int npl, bool multi, hipStream_t st, K2Log* log) {
-  switch (npl) {
-    case 8: launch_k2_t<LPR, 8>(a, multi, st, log); return 0;
-    case 10: launch_k2_t<LPR, 10>(a, multi, st, log); return 0;
-    case 16: launch_k2_t<LPR, 16>(a, multi, st, log); return 0;
-    case 24: launch_k2_t<LPR, 24>(a, multi, st, log); return 0;
-    default: return -1;
-  }
-}
-
-int launch_k2(const K2Args& a, int lpr, int npl, hipStream_t st, K2Log* log) {
-  const bool multi = a.num_hashes > 1;
-  switch (lpr) {
-    case 4: return launch_k2_l<4>(a, npl, multi, st, log);
-    case 8: return launch_k2_l<8>(a, npl, multi, st, log);
-    case 16: return launch_k2_l<16>(a, npl, multi, st, log);
-    case 32: return launch_k2_l<32>(a, npl, multi, st, log);
-    case 64: return launch_k2_l<64>(a, npl, multi, st, log);
-    default: return -1;
-  }
-}
-
-// blocks of one lane form's launch (as launch_k2_t counts them)
-static uint64_t k2_blocks(const K2Args& a, int lpr) {
-  const uint64_t G = 64 / (uint64_t)lpr;
-  const uint64_t units = (G > 1 && a.slot_major == 2) ? (uint64_t)a.n_reads * (((uint64_t)a.nslots + G - 1) / G) * G : (uint64_t)a.n_reads * a.nslots;
-  return ((units + G - 1) / G + 3) / 4;
-}
-
-template <int LPRB, int NPL>
-static int launch_k2_pair_t(const K2Args& a, const K2Args& b, bool multi, hipStream_t st, K2Log* log) {
-  const uint64_t nba = k2_blocks(a, 64), nbb = k2_blocks(b, LPRB);
-  if (nba == 0 || nbb == 0 || nba + nbb > K2_MAX_BLOCKS) return -1;
-  K2Args a0 = a, b0 = b;
-  a0.unit_base = b0.unit_base = 0;
-  if (multi)
-    launch_k2_pair_form<64, LPRB, NPL, true>(a0, b0, (unsigned)nba, (unsigned)nbb, st, log);
-  else
-    launch_k2_pair_form<64, LPRB, NPL, false>(a0, b0, (unsigned)nba, (unsigned)nbb, st, log);
   return 0;
 }
 
-// the 64-lane form (args a) and a narrower one (args b, lane form lprb) of the same batch in one grid; -1: not a pair this file has a kernel for
-int launch_k2_pair(const K2Args& a, const K2Args& b, int lprb, int npl, hipStream_t st, K2Log* log) {
-  const bool multi = a.num_hashes > 1;
-  if (npl != 16 || (a.group_rows == 4)) return -1;
-  switch (lprb) {
-    case 32: return launch_k2_pair_t<32, 16>(a, b, multi, st, log);
-    case 16: return launch_k2_pair_t<16, 16>(a, b, multi, st, log);
-    case 8: return launch_k2_pair_t<8, 16>(a, b, multi, st, log);
-    case 4: return launch_k2_pair_t<4, 16>(a, b, multi, st, log);
+// (The kernels stand in the code object in the order the functions below name them: the plain forms, the pairs, the chunked forms.)
+template <int LPR>
+static int launch_k2_plain_l(const K2Launch& l, const K2Args& a, hipStream_t st, K2Log* log) {
+  const bool four = l.gr == 4;  // the 4-row kernels exist at 8 and 10 planes
+  if (!four && l.gr != 8) return -1;
+  switch (l.npl) {
+    case 8: return four ? launch_k2_pieces<LPR, 8, false, 4>(l, a, st, log) : launch_k2_pieces<LPR, 8, false, 8>(l, a, st, log);
+    case 10: return four ? launch_k2_pieces<LPR, 10, false, 4>(l, a, st, log) : launch_k2_pieces<LPR, 10, false, 8>(l, a, st, log);
+    case 16: return four ? -1 : launch_k2_pieces<LPR, 16, false, 8>(l, a, st, log);
+    case 24: return four ? -1 : launch_k2_pieces<LPR, 24, false, 8>(l, a, st, log);
     default: return -1;
   }
 }
 
-template <int LPR>
-static void launch_k2_split_t(const K2Args& a, bool multi, hipStream_t st, K2Log* log) {
-  constexpr int G = 64 / LPR;
-  const uint64_t units = (uint64_t)a.n_long * a.nslots * a.split_chunks;
-  const uint64_t blocks = ((units + G - 1) / G + 3) / 4;
-  K2Args b = a;
-  for (uint64_t b0 = 0; b0 < blocks; b0 += K2_MAX_BLOCKS) {
-    const unsigned nb = (unsigned)std::min<uint64_t>(K2_MAX_BLOCKS, blocks - b0);
-    b.unit_base = b0 * 4 * G;
-    if (multi)
-      launch_k2_form<LPR, 16, true, true, 8>(b, nb, st, log);
-    else
-      launch_k2_form<LPR, 16, false, true, 8>(b, nb, st, log);
+static int launch_k2_plain(const K2Launch& l, const K2Args& a, hipStream_t st, K2Log* log) {
+  switch (l.lpr) {
+    case 4: return launch_k2_plain_l<4>(l, a, st, log);
+    case 8: return launch_k2_plain_l<8>(l, a, st, log);
+    case 16: return launch_k2_plain_l<16>(l, a, st, log);
+    case 32: return launch_k2_plain_l<32>(l, a, st, log);
+    case 64: return launch_k2_plain_l<64>(l, a, st, log);
+    default: return -1;
   }
 }
 
-int launch_k2_split(const K2Args& a, int lpr, hipStream_t st, K2Log* log) {
-  const bool multi = a.num_hashes > 1;
-  switch (lpr) {
-    case 4: launch_k2_split_t<4>(a, multi, st, log); return 0;
-    case 8: launch_k2_split_t<8>(a, multi, st, log); return 0;
-    case 16: launch_k2_split_t<16>(a, multi, st, log); return 0;
-    case 32: launch_k2_split_t<32>(a, multi, st, log); return 0;
-    case 64: launch_k2_split_t<64>(a, multi, st, log); return 0;
+template <int LPRB>
+static int launch_k2_pair_l(const K2Launch& l, const K2Args& a, const K2Args& b, hipStream_t st, K2Log* log) {
+  if (l.multi)
+    launch_k2_pair_form<64, LPRB, 16, true>(a, b, l.nba, l.nbb, st, log);
+  else
+    launch_k2_pair_form<64, LPRB, 16, false>(a, b, l.nba, l.nbb, st, log);
+  return 0;
+}
+
+// a pair record: the 64-lane form (args a) and a narrower one (args b) of the same batch in one grid, both from unit 0.  -1: a record
+// this file has no kernel for
+int launch_k2_pair(const K2Launch& l, const K2Args& a, const K2Args& b, hipStream_t st, K2Log* log) {
+  if (l.kind != K2Kind::Pair || l.lpr != 64 || l.npl != 16 || l.gr != 8) return -1;
+  switch (l.lprb) {
+    case 32: return launch_k2_pair_l<32>(l, a, b, st, log);
+    case 16: return launch_k2_pair_l<16>(l, a, b, st, log);
+    case 8: return launch_k2_pair_l<8>(l, a, b, st, log);
+    case 4: return launch_k2_pair_l<4>(l, a, b, st, log);
+    default: return -1;
+  }
+}
+
+// a plain or a chunked record, every piece of its grid; `a` complete but for unit_base.  -1: no kernel for the record
+int launch_k2(const K2Launch& l, const K2Args& a, hipStream_t st, K2Log* log) {
+  if (l.kind == K2Kind::Plain) return launch_k2_plain(l, a, st, log);
+  if (l.kind != K2Kind::Split || l.npl != 16 || l.gr != 8) return -1;
+  switch (l.lpr) {
+    case 4: return launch_k2_pieces<4, 16, true, 8>(l, a, st, log);
+    case 8: return launch_k2_pieces<8, 16, true, 8>(l, a, st, log);
+    case 16: return launch_k2_pieces<16, 16, true, 8>(l, a, st, log);
+    case 32: return launch_k2_pieces<32, 16, true, 8>(l, a, st, log);
+    case 64: return launch_k2_pieces<64, 16, true, 8>(l, a, st, log);
     default: return -1;
   }
 }

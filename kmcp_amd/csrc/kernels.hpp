@@ -7,6 +7,7 @@
 #include "common.hpp"
 #include "density_core.hpp"
 #include "k1_plan.hpp"
+#include "k2_plan.hpp"
 
 namespace kmcpg {
 
@@ -32,12 +33,11 @@ void launch_dedup(DedupArgs a, uint64_t max_n, hipStream_t st);  // queries abov
 // what the K2 launchers note about every kernel they launch (kmcpg_last_k2_launches): written at the launch site from the template
 // parameters of the kernel launched.  nullptr = no log
 typedef std::vector<kmcpg_k2_launch> K2Log;
-// lpr in {4,8,16,32,64}: lanes per row tile; npl in {8,10,16,24}: counter planes.  <0 on bad arguments.
-int launch_k2(const K2Args& a, int lpr, int npl, hipStream_t st, K2Log* log);
-// two lane forms in one grid (long queries: the 64-lane tiles + the remainder's form); -1 when there is no such kernel: launch them one by one
-int launch_k2_pair(const K2Args& a64, const K2Args& b, int lprb, int npl, hipStream_t st, K2Log* log);
-// long queries: chunked counting into a.long_counts, then one thresholding pass
-int launch_k2_split(const K2Args& a, int lpr, hipStream_t st, K2Log* log);
+// one launch record of the plan (k2_plan.hpp), every grid piece of it; `a` complete but for unit_base.  <0: no kernel for the record
+int launch_k2(const K2Launch& l, const K2Args& a, hipStream_t st, K2Log* log);
+// a pair record: two lane forms in one grid (long queries: the 64-lane tiles + the remainder's form)
+int launch_k2_pair(const K2Launch& l, const K2Args& a64, const K2Args& b, hipStream_t st, K2Log* log);
+// long queries: the chunked launches count into a.long_counts, then one thresholding pass
 void launch_list_long(const int32_t* nk, uint32_t n_reads, int32_t split_min, uint32_t* list, uint32_t* meta, hipStream_t st);
 void launch_threshold_long(const K2Args& a, hipStream_t st);
 // K3: group + filter + order the hit list on the device (k3_finalize.hip); hits_hint = expected number of hits (grid sizing), 0 = hit_cap

@@ -72,6 +72,30 @@ K1Knobs k1_knobs() {
   return kn;
 }
 
+// The K2 knobs read per query, all of them at every call: tests flip them inside one process.  (The knobs of the lane
+// cutting are read at open: engine.cpp k2_open_knobs.)
+K2Knobs k2_knobs() {
+  K2Knobs kn;
+  if (const char* e = getenv("KMCPG_SPLIT_MIN")) kn.split_min = atoi(e), kn.split_min_set = true;
+  if (const char* e = getenv("KMCPG_SPLIT_CHUNK")) kn.split_chunk = atoi(e), kn.split_chunk_set = true;
+  if (const char* e = getenv("KMCPG_NT_LOADS")) kn.nt_loads = atoi(e);
+  if (const char* e = getenv("KMCPG_PRUNE")) kn.prune = atoi(e);
+  if (const char* e = getenv("KMCPG_GROUP_ROWS")) kn.group_rows = atoi(e), kn.group_rows_set = true;
+  if (const char* e = getenv("KMCPG_PRUNE_EVERY")) kn.prune_every = atoi(e);
+  // slot-major unit order: the waves in flight share one (block, tile) slice of the index, so the address range they gather
+  // from is ~1/64 of the index (GTDB scale: 575 -> 510 ms per 524 k reads; profiles/r02_order_exp.txt)
+  if (const char* e = getenv("KMCPG_SLOT_MAJOR")) kn.slot_major = atoi(e);
+  // tail mode of the 16/24-plane kernels on 1-KiB tiles (k2_cobs.hip): KMCPG_TAIL_SECTORS=0 switches it off
+  // (2, not 4: a wave that enters with 3-4 live sectors carries near misses that would have died a little later through the rest of the
+  // query, unpruned — same-box A/B on the genome search: 5.05 ms without, 4.74 with 2, 4.93 with 4; profiles/r06_tail_mode.txt)
+  if (const char* e = getenv("KMCPG_TAIL_SECTORS")) kn.tail_sectors = std::max(0, std::min(atoi(e), 4));
+  if (const char* e = getenv("KMCPG_TAIL_MIN")) kn.tail_min = std::max(1, atoi(e));
+  if (const char* e = getenv("KMCPG_PAIR")) kn.pair = atoi(e) != 0;
+  if (const char* e = getenv("KMCPG_K2_BLOCK_UNITS")) kn.block_units = atoi(e) != 0;
+  if (const char* e = getenv("KMCPG_K2_EXACT_STOP")) kn.exact_stop = atoi(e) != 0;
+  return kn;
+}
+
 // K1 (+K1d): hashes of read i end up at d_hashes[offs[i] + offs2[i] ...], NumKmers in d_nk_search
 int run_kmers(kmcpg_db* db, kmcpg_db::Workspace& W, const DeviceBatch& b, const kmcpg_params& p, const KmerOut& o, hipStream_t st, uint64_t* max_n_out) {
   const kmcpg_info& I = db->info;
@@ -485,42 +509,28 @@ int kmcpg::query_device_after(kmcpg_db* db, const DeviceBatch& b, const kmcpg_pa
   static const int debug_rowsort = getenv("KMCPG_DEBUG_ROWSORT") ? atoi(getenv("KMCPG_DEBUG_ROWSORT")) : 0;
   if (debug_rowsort && !b.d_offs2 && !db->h_groupdev.empty())  // experiment only: profiles/r05_rowsort_gate.txt
     launch_debug_rowsort(W.w_hashes.p, b.d_offs, out.d_qkmers, b.n_reads, db->h_groupdev[0].num_sigs, db->h_groupdev[0].magic_hi, debug_rowsort, st);
-  // long queries (whole genomes, -g) are split into chunks of k-mers so that they spread over the chip; short ones keep
-  // the one-wave-per-(query, slot) kernel.  Which queries are long is only known on the device: one small D2H read.
-  const char* sm_env = getenv("KMCPG_SPLIT_MIN");
-  const int32_t split_min = sm_env ? atoi(sm_env) : 2048;
-  uint32_t long_meta[2] = {0, 0};
-  size_t total_slots = 0;
-  for (const auto& c : db->classes) total_slots += c.slots.size();
-  // The read-back below costs a host round trip in the middle of the batch (~2.5 ms: more than the kernels of a batch of HiFi
-  // reads take).  It is only worth it when splitting could pay: a batch that fills the chip with its (query, slot) pairs anyway
-  // and whose queries are bounded by 32 768 k-mers (HiFi reads, contigs) runs the plain kernel on 16 planes without asking.
-  const bool ask = split_min > 0 && maxn > (uint64_t)split_min && (sm_env || maxn > 32768 || (uint64_t)b.n_reads * total_slots <= 16384);
+  // which COBS kernels, on which grids (k2_plan.hpp)
+  K2Shape s;
+  s.n_reads = b.n_reads;
+  s.max_n = maxn;
+  s.num_hashes = db->info.num_hashes;
+  s.matrix_bytes_local = db->info.matrix_bytes_local;
+  s.n_cols = db->info.n_cols;
+  if (db->classes.size() > (size_t)K2_MAX_CLASSES) return kmcpg_fail(KMCPG_EINVAL, "more lane classes than lane forms");
+  for (const auto& c : db->classes) s.classes[s.n_classes++] = K2Class{c.lpr, (uint32_t)c.slots.size(), c.d_bslots ? (uint32_t)c.bslots.size() : 0u};
+  s.knobs = k2_knobs();
+  // which queries are long is only known on the device: one small D2H read, where the plan has a use for the answer
+  uint32_t long_meta[2] = {0, 0};  // how many above split_min, the largest of them
+  const bool ask = k2_ask_long(s);
   if (ask) {
     if (W.w_long_list.ensure(b.n_reads + 1) || W.w_long_meta.ensure(2)) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
     HIPCHK(hipMemsetAsync(W.w_long_meta.p, 0, 2 * sizeof(uint32_t), st));
-    launch_list_long(out.d_qkmers, b.n_reads, split_min, W.w_long_list.p, W.w_long_meta.p, st);
+    launch_list_long(out.d_qkmers, b.n_reads, s.knobs.split_min, W.w_long_list.p, W.w_long_meta.p, st);
     HIPCHK(hipMemcpyAsync(long_meta, W.w_long_meta.p, sizeof long_meta, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
   }
-  uint32_t n_long = long_meta[0];
-  // splitting pays when the long queries alone would leave the chip idle (few (query, slot) pairs) or need more than 16
-  // counter planes; a batch of thousands of 10-kb reads already fills it and keeps the plain kernel (unless forced by env)
-  // (round 4, genome search with 3 hash functions, same-box A/B over batch sizes: from ~1 500 (query, slot) units on — 1.5 waves per SIMD — the
-  // plain kernel wins, because it prunes (a third of the row bytes are never fetched for 8 000-k-mer sketches at -t 0.4) and needs no atomics:
-  // 192 queries x 8 slots 5.0 vs 6.0 ms, 512 x 8 11.1 vs 16.3 ms; at 128 x 8 the chunked form still leads, 4.1 vs 4.5 ms.)
-  if (n_long && !sm_env && (uint64_t)n_long * total_slots >= 1536 && long_meta[1] <= 65534) n_long = 0;
-  // largest NumKmers the plain kernel will meet: bounded by the read length, and exactly known once the long ones were listed
-  uint64_t max_short = maxn;
-  if (ask)
-    max_short = n_long ? (uint64_t)split_min : std::max<uint64_t>(long_meta[1], (uint64_t)split_min);
-  // counter planes: 8 for single short reads, 10 for pairs (2 x 150 bp = 260 k-mers, up to 2 x 500 bp), 16 for long reads
-  // (one below the planes' range: the largest threshold a query of n k-mers can get is n + 1 — `-t 1`, or an FPR bound no count passes —
-  // and k2_cobs compares counts with it on NPL bits: n + 1 <= 2^NPL - 1 keeps that compare exact.  A threshold past the planes' range
-  // made the kernel's epilogue emit every column with a count above its low bits: filtered again by the host half, so no wrong
-  // match, but a hit list of the whole row for reads of exactly 255 / 1 023 k-mers at -t 1.)
-  const int npl = max_short <= 254 ? 8 : (max_short <= 1022 ? 10 : (max_short <= 65534 ? 16 : (max_short <= 16777214 ? 24 : 0)));
-  if (!npl) return kmcpg_fail(KMCPG_EUNSUPPORTED, "queries with more than 16777214 k-mers need KMCPG_SPLIT_MIN > 0");
+  const K2Plan plan = k2_plan(s, ask, long_meta[0], long_meta[1]);
+  if (!plan.npl) return kmcpg_fail(KMCPG_EUNSUPPORTED, "queries with more than 16777214 k-mers need KMCPG_SPLIT_MIN > 0");
   K2Args a{};
   a.blocks = db->d_groupdev;
   a.segs = db->d_segs;
@@ -532,101 +542,59 @@ int kmcpg::query_device_after(kmcpg_db* db, const DeviceBatch& b, const kmcpg_pa
   a.min_qcov = p.min_qcov;
   a.min_matched = p.min_matched;
   a.num_hashes = db->info.num_hashes;
-  a.nt_loads = getenv("KMCPG_NT_LOADS") ? atoi(getenv("KMCPG_NT_LOADS")) : 1;
-  a.prune = getenv("KMCPG_PRUNE") ? atoi(getenv("KMCPG_PRUNE")) : 1;
-  // Rows gathered between two pruning tests.  4 instead of 8 saves 2.3 % of the row traffic (sectors are dropped ~2 rows sooner)
-  // for ~15 % more VALU work: a gain where the kernel waits for HBM (GTDB scale, 8 planes: 511 -> 488 ms per 524 k reads), a loss
-  // where it runs near its issue limits (16-plane kernels at 3 waves per SIMD: 248 -> 361 ms; indexes that half live in the
-  // Infinity Cache: 17.8 -> 19.6 ms) — profiles/r02_group_rows.txt.
-  a.group_rows = (a.prune && npl <= 10 && db->info.matrix_bytes_local >= (4ull << 30)) ? 4 : 8;
-  if (const char* e = getenv("KMCPG_GROUP_ROWS")) a.group_rows = atoi(e) == 4 ? 4 : 8;
-  // How often the test runs in the 8/10-plane kernels: after every group (they wait for HBM; KMCPG_PRUNE_EVERY = 2/4/8 for experiments).
-  // The 16/24-plane kernels resolve their carries every 32 rows and test there (k2_cobs.hip): the test was a quarter of their VALU
-  // work at one test per group, and they run near their issue limits — same-box A/B tools/ab/r04_call13.sh: equal-width HiFi index
-  // 3.88 -> 3.55 ms per 16 384 reads, genome search 5.73 -> 5.48 ms per 256 genomes with a test every 4th group alone.
-  a.prune_every = 1;
-  if (const char* e = getenv("KMCPG_PRUNE_EVERY")) {
-    const int v = atoi(e);
-    a.prune_every = (v == 2 || v == 4 || v == 8) ? v : 1;
-  }
-  a.split_min = n_long ? split_min : 0;
-  // slot-major unit order: the waves in flight share one (block, tile) slice of the index, so the address range they gather
-  // from is ~1/64 of the index (GTDB scale: 575 -> 510 ms per 524 k reads; profiles/r02_order_exp.txt)
-  a.slot_major = getenv("KMCPG_SLOT_MAJOR") ? atoi(getenv("KMCPG_SLOT_MAJOR")) : 1;
-  // tail mode of the 16/24-plane kernels on 1-KiB tiles (k2_cobs.hip): KMCPG_TAIL_SECTORS=0 switches it off
-  // (2, not 4: a wave that enters with 3-4 live sectors carries near misses that would have died a little later through the rest of the
-  // query, unpruned — same-box A/B on the genome search: 5.05 ms without, 4.74 with 2, 4.93 with 4; profiles/r06_tail_mode.txt)
-  a.tail_sectors = getenv("KMCPG_TAIL_SECTORS") ? std::max(0, std::min(atoi(getenv("KMCPG_TAIL_SECTORS")), 4)) : 2;
-  a.tail_min = getenv("KMCPG_TAIL_MIN") ? std::max(1, atoi(getenv("KMCPG_TAIL_MIN"))) : 64;
+  a.nt_loads = s.knobs.nt_loads;
+  a.prune = s.knobs.prune;
+  a.group_rows = plan.group_rows;
+  a.prune_every = plan.prune_every;
+  a.split_min = plan.split_min;
+  a.slot_major = s.knobs.slot_major;
+  a.tail_sectors = s.knobs.tail_sectors;
+  a.tail_min = s.knobs.tail_min;
+  a.hits = out.d_hits;
+  a.hit_cap = out.hit_cap;
+  a.counter = (unsigned long long*)out.d_counters;
   if (db->profiling >= 2) {
     if (W.w_gathered.ensure((size_t)K2_GATHER_SLOTS * 16)) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
     HIPCHK(hipMemsetAsync(W.w_gathered.p, 0, (size_t)K2_GATHER_SLOTS * 16 * sizeof(uint64_t), st));
     a.gathered = (unsigned long long*)W.w_gathered.p;
   }
-  if (int rcb = fpr_bound(db, p.max_fpr, max_short, st, &a.cmin_fpr, &a.cmin_fpr_n)) return rcb;
+  if (int rcb = fpr_bound(db, p.max_fpr, plan.max_short, st, &a.cmin_fpr, &a.cmin_fpr_n)) return rcb;
   if (bound_n) *bound_n = a.cmin_fpr ? a.cmin_fpr_n : 0;  // both kernel forms apply the table to every query of up to this many k-mers
-  a.hits = out.d_hits;
-  a.hit_cap = out.hit_cap;
-  a.counter = (unsigned long long*)out.d_counters;
   // COBS kernels one batch at a time (the k-mer kernels above may have run beside the previous batch's)
   // (KMCPG_COBS_CHAIN=0, experiment with two kernel streams + two workspace slots: the next batch's COBS kernel may start in the previous
   // one's ragged end — nothing is shared between them but the read-only index; their HIP-event durations then overlap)
   static const bool cobs_chain = !(getenv("KMCPG_COBS_CHAIN") && atoi(getenv("KMCPG_COBS_CHAIN")) == 0);
   if (int rcc = chain_begin(&db->cobs_ev, cobs_chain && db->cobs_ev_valid, st)) return rcc;
   if (db->profiling) HIPCHK(hipEventRecord(pev[1], st));
-  // Long queries on rows cut into a 64-lane tile form + one narrower form: both in one grid (k2_cobs_pair: the second form's workgroups
-  // take the slots the first one's last waves free; KMCPG_PAIR=0: two launches, as before round 6)
-  bool paired = false;
-  if (npl >= 16 && db->classes.size() == 2 && db->classes[0].lpr == 64 && db->classes[1].lpr < 64 && !(getenv("KMCPG_PAIR") && atoi(getenv("KMCPG_PAIR")) == 0)) {
-    K2Args a1 = a, b1 = a;
-    a1.slots = db->classes[0].d_slots;
-    a1.nslots = (uint32_t)db->classes[0].slots.size();
-    b1.slots = db->classes[1].d_slots;
-    b1.nslots = (uint32_t)db->classes[1].slots.size();
-    paired = launch_k2_pair(a1, b1, db->classes[1].lpr, npl, st, k2_log) == 0;
+  // a launch record's slots: its class's, or that class's block-unit list
+  auto with_slots = [&](K2Args x, int cls, const K2Launch& l) {
+    const SlotClass& c = db->classes[(size_t)cls];
+    x.slots = l.block_units ? c.d_bslots : c.d_slots;
+    x.nslots = l.block_units ? (uint32_t)c.bslots.size() : (uint32_t)c.slots.size();
+    x.k2_flags = l.k2_flags;
+    return x;
+  };
+  const char* const no_kernel = "batch too large for one launch: split it";
+  for (int i = 0; i < plan.n_launches; i++) {
+    const K2Launch& l = plan.launches[i];
+    if (l.kind == K2Kind::Split) continue;
+    const int rcl = l.kind == K2Kind::Pair ? launch_k2_pair(l, with_slots(a, l.cls, l), with_slots(a, l.cls_b, l), st, k2_log) : launch_k2(l, with_slots(a, l.cls, l), st, k2_log);
+    if (rcl != 0) return kmcpg_fail(KMCPG_EINVAL, no_kernel);
   }
-  // The short-read path of k2_cobs<64, 8|10, false, false, 4> (k2_cobs_body.inc): KMCPG_K2_BLOCK_UNITS=1 — one index phase per (read, block
-  // group), the tiles of the row one after the other in one wave; KMCPG_K2_EXACT_STOP=1 — every sector steps by the rows its best column
-  // proves necessary and stops at its exact row.  Defaults: DESIGN.md §4 (profiles/k2_exact_stop_ab.txt).
-  int32_t short_flags = 0;
-  if (npl <= 10 && a.group_rows == 4 && a.num_hashes == 1 && a.prune && a.prune_every == 1) {
-    if (getenv("KMCPG_K2_BLOCK_UNITS") ? atoi(getenv("KMCPG_K2_BLOCK_UNITS")) != 0 : K2_BLOCK_UNITS_DEFAULT) short_flags |= K2F_BLOCK_UNITS;
-    if (getenv("KMCPG_K2_EXACT_STOP") ? atoi(getenv("KMCPG_K2_EXACT_STOP")) != 0 : K2_EXACT_STOP_DEFAULT) short_flags |= K2F_EXACT_STOP;
-  }
-  for (const auto& c : db->classes) {
-    if (paired) break;
-    a.slots = c.d_slots;
-    a.nslots = (uint32_t)c.slots.size();
-    a.k2_flags = c.lpr == 64 ? short_flags : 0;
-    if ((a.k2_flags & K2F_BLOCK_UNITS) && c.d_bslots) {
-      a.slots = c.d_bslots;
-      a.nslots = (uint32_t)c.bslots.size();
-    } else {
-      a.k2_flags &= ~K2F_BLOCK_UNITS;
-    }
-    if (launch_k2(a, c.lpr, npl, st, k2_log) != 0) return kmcpg_fail(KMCPG_EINVAL, "batch too large for one launch: split it");
-  }
-  a.k2_flags = 0;
-  if (n_long) {
+  if (plan.n_long) {  // the chunked form: count arrays of plan.group long queries at a time
     a.ncols_total = (uint32_t)db->info.n_cols;
-    // ~64 chunks for the largest query, 1024..8192 k-mers each (at most 8192: the chunk's counts fit 16 planes)
-    uint32_t chk = 1024;
-    while (chk < 8192 && (uint64_t)chk * 64 < long_meta[1]) chk <<= 1;
-    if (const char* e = getenv("KMCPG_SPLIT_CHUNK")) chk = (uint32_t)std::max(64, std::min(atoi(e), 8192));
-    a.split_chk = chk;
-    a.split_chunks = (long_meta[1] + chk - 1) / chk;
-    // count arrays of at most ~2 GB at a time
-    const uint32_t group = (uint32_t)std::max<uint64_t>(1, (2ull << 30) / ((uint64_t)a.ncols_total * 4));
-    if (W.w_long_counts.ensure((size_t)std::min<uint32_t>(group, n_long) * a.ncols_total)) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
+    a.split_chk = plan.split_chk;
+    a.split_chunks = plan.split_chunks;
+    if (W.w_long_counts.ensure((size_t)std::min<uint32_t>(plan.group, plan.n_long) * a.ncols_total)) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
     a.long_counts = W.w_long_counts.p;
-    for (uint32_t g0 = 0; g0 < n_long; g0 += group) {
+    for (uint32_t g0 = 0; g0 < plan.n_long; g0 += plan.group) {
       a.long_list = W.w_long_list.p + g0;
-      a.n_long = std::min<uint32_t>(group, n_long - g0);
+      a.n_long = std::min<uint32_t>(plan.group, plan.n_long - g0);
       HIPCHK(hipMemsetAsync(a.long_counts, 0, (size_t)a.n_long * a.ncols_total * sizeof(uint32_t), st));
-      for (const auto& c : db->classes) {
-        a.slots = c.d_slots;
-        a.nslots = (uint32_t)c.slots.size();
-        if (launch_k2_split(a, c.lpr, st, k2_log) != 0) return kmcpg_fail(KMCPG_EINVAL, "batch too large for one launch: split it");
+      for (int i = 0; i < plan.n_launches; i++) {
+        const K2Launch& l = plan.launches[i];
+        if (l.kind == K2Kind::Split && launch_k2(k2_split_launch(plan, s, l, a.n_long), with_slots(a, l.cls, l), st, k2_log) != 0)
+          return kmcpg_fail(KMCPG_EINVAL, no_kernel);
       }
       launch_threshold_long(a, st);
     }

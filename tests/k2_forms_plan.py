@@ -6,10 +6,11 @@ A form is the tuple (kind, lpr, lprb, npl, multi, group_rows) that `Database.las
 count): kind "plain" = k2_cobs<LPR, NPL, MULTI, false, GR>, "split" = k2_cobs<LPR, 16, MULTI, true> (the chunked long-query form),
 "pair" = k2_cobs_pair<64, LPRB, 16, MULTI>.
 
-The expectations are NOT read from the library: `expect()` below restates the dispatch rules (finish_open in engine.cpp: row pitch ->
-lane classes; query_device_after in query.cpp: longest query -> planes, index size -> rows per group, chunked / pair decisions;
-launch_k2_t / launch_k2_pair in k2_cobs.hip) from the point of view of a test that knows its database and its batch.  A change of
-any of those rules moves a case onto another form and turns its witness assertion red — that is the point."""
+The expectations are NOT read from the library: `expect()` below restates the dispatch rules of kmcp_amd/csrc/k2_plan.hpp (k2_row_parts:
+row pitch -> lane classes; k2_ask_long / k2_plan: longest query -> planes, index size -> rows per group, chunked / pair decisions, the
+kernel that runs) from the point of view of a test that knows its database and its batch.  A change of any of those rules moves a
+case onto another form and turns its witness assertion red — that is the point; test_k2_forms_plan_cpu.py holds this restatement
+against the header compiled for the host, case by case."""
 import itertools
 from collections import namedtuple
 
@@ -18,10 +19,10 @@ K = 21  # k-mer size of every database of the plan
 LPRS = (4, 8, 16, 32, 64)
 # ---- every instantiation the launchers of k2_cobs.hip can launch (the product of their parameter sets) ------------------------
 ALL_FORMS = frozenset(
-    [("plain", l, 0, p, m, 8) for l, p, m in itertools.product(LPRS, (8, 10, 16, 24), (False, True))] +      # launch_k2_t, 8 rows: 40
-    [("plain", l, 0, p, m, 4) for l, p, m in itertools.product(LPRS, (8, 10), (False, True))] +              # launch_k2_t, 4 rows: 20
-    [("split", l, 0, 16, m, 8) for l, m in itertools.product(LPRS, (False, True))] +                          # launch_k2_split_t: 10
-    [("pair", 64, lb, 16, m, 8) for lb, m in itertools.product((4, 8, 16, 32), (False, True))])              # launch_k2_pair_t: 8
+    [("plain", l, 0, p, m, 8) for l, p, m in itertools.product(LPRS, (8, 10, 16, 24), (False, True))] +      # plain, 8 rows: 40
+    [("plain", l, 0, p, m, 4) for l, p, m in itertools.product(LPRS, (8, 10), (False, True))] +              # plain, 4 rows: 20
+    [("split", l, 0, 16, m, 8) for l, m in itertools.product(LPRS, (False, True))] +                          # chunked: 10
+    [("pair", 64, lb, 16, m, 8) for lb, m in itertools.product((4, 8, 16, 32), (False, True))])              # pair: 8
 assert len(ALL_FORMS) == 78
 
 # forms no database reaches by the default rules; the override that reaches them
@@ -89,7 +90,7 @@ def stride_of(db):
 
 
 def lane_classes(stride, nh, open_env=()):
-    """finish_open: whole 1-KiB tiles -> 64 lanes; the remainder -> the narrowest lane form that covers it (a 640-byte remainder of a
+    """k2_row_parts: whole 1-KiB tiles -> 64 lanes; the remainder -> the narrowest lane form that covers it (a 640-byte remainder of a
     single-hash database: 32 + 8).  Lane classes in the order the database gets them, and the slots (tiles) of one group per class."""
     env = dict(open_env)
     full, rem = divmod(stride, 1024)
@@ -158,11 +159,11 @@ def expect(db, batch, env, index_bytes=0):
         gr = 4 if int(env["KMCPG_GROUP_ROWS"]) == 4 else 8
     out = []
     pair = npl >= 16 and len(classes) == 2 and classes[0] == 64 and classes[1] < 64 and env.get("KMCPG_PAIR") != "0"
-    if pair and npl == 16 and gr != 4:        # launch_k2_pair declines at 24 planes and for the 4-row setting
+    if pair and npl == 16 and gr != 4:        # no pair kernel at 24 planes or under the 4-row setting
         out.append(("pair", 64, classes[1], 16, multi, 8))
     else:
         for c in classes:
-            out.append(("plain", c, 0, npl, multi, 4 if (npl <= 10 and gr == 4) else 8))   # launch_k2_t: no 4-row kernels at 16 / 24 planes
+            out.append(("plain", c, 0, npl, multi, 4 if (npl <= 10 and gr == 4) else 8))   # no 4-row kernels at 16 / 24 planes
     if longs:
         out += [("split", c, 0, 16, multi, 8) for c in classes]
     return sorted(out)
