@@ -2,7 +2,7 @@
 // genome files in, a searchable database out, no .unik files in between.
 //
 //   kmcp-makedb -O out.kmcp -k 21 [-n 10 -l 150 -m 1000] [-D scale | -W w | -S s] [-B regexp ...] [-N regexp]
-//               [--num-hash 1 -f 0.3 -b 0 -j 16 -x 10M -X 256 -8 20M -1 200M -a alias --force]
+//               [--num-hash 1 -f 0.3 -b 0 -j 16 -x 10M -X 256 -8 20M -1 200M -a alias --force] [--two-pass [--matrix-budget BYTES]]
 //               {genome.fa[.gz] ... | -i list.txt | -I dir [-r regexp]}
 //
 // One file is one reference: the records whose header no -B expression matches are joined with kMax-1 N's (compute.go:569-627), the
@@ -14,6 +14,12 @@
 //   * files are always joined, also with -n 1 (the reference joins in --split-number / --split-size mode only);
 //   * regular expressions are std::regex (ECMAScript), not RE2; a leading "(?i)" is understood, and matching ignores case as it does there.
 // --dry-run prints "name <tab> joined length <tab> chunks" per reference and touches no GPU.
+//
+// --two-pass builds a database larger than host memory ("Building a database"): pass 1 sketches every file and keeps
+// only the k-mer count of every chunk; the block layout needs no more (kmcpg_builder_plan).  Pass 2 sketches the files again and ORs the
+// lists, which never leave the GPU, into block matrices that stay in HBM (kmcpg_sketch_genomes_to -> kmcpg_builder_scatter_device); when
+// the matrices exceed --matrix-budget together the blocks are built in rounds, each reading only the files it has columns of.  The
+// database is the same bytes; the input is read and inflated twice (or more).
 #include <dirent.h>
 #include <errno.h>
 #include <ftw.h>
@@ -30,6 +36,7 @@
 #include <chrono>
 #include <condition_variable>
 #include <fstream>
+#include <functional>
 #include <mutex>
 #include <regex>
 #include <string>
@@ -77,7 +84,8 @@ struct Args {
   double fpr = 0.3;
   uint64_t kmers_x = 10ull << 20, kmers_8 = 20ull << 20, kmers_1 = 200ull << 20;
   uint64_t batch_bases = 1ull << 28;
-  bool force = false, dry_run = false, verbose = false;
+  uint64_t matrix_budget = 0;  // --two-pass: 0 = the free HBM minus the sketcher's needs
+  bool force = false, dry_run = false, verbose = false, two_pass = false;
 };
 
 static long parse_int(const std::string& flag, const std::string& v) {
@@ -119,6 +127,7 @@ static const char* USAGE =
     "         -N/--ref-name-regexp  -B/--seq-name-filter  -i/--infile-list  -I/--in-dir  -r/--file-regexp\n"
     "index:   --num-hash  -f/--false-positive-rate  -b/--block-size  -j/--threads  -x -X -8 -1 (big-genome blocks)  -a/--alias  --force\n"
     "other:   --device N  --batch-bases N  --dry-run  --verbose\n"
+    "         --two-pass (sketch twice, keep no k-mer list in host memory)  --matrix-budget BYTES (HBM for block matrices per round; k/M/G)\n"
     "refused: --circular  --by-seq  -s/--split-size  (and -n here is --split-number, not the number of hash functions)\n";
 
 static Args parse(int argc, char** argv) {
@@ -136,10 +145,10 @@ static Args parse(int argc, char** argv) {
       {"block-size8-kmers-t", '8', true}, {"block-size1-kmers-t", '1', true}, {"alias", 'a', true}, {"force", 0, false},
       {"circular", 0, false},      {"by-seq", 0, false},         {"device", 0, true},            {"batch-bases", 0, true},
       {"dry-run", 0, false},       {"verbose", 0, false},        {"help", 'h', false},           {"compress", 'c', false},
-      {"quiet", 'q', false},
+      {"quiet", 'q', false},         {"two-pass", 0, false},       {"matrix-budget", 0, true},
   };
   Args a;
-  bool circular = false, by_seq = false, split_size = false;
+  bool circular = false, by_seq = false, split_size = false, budget_given = false;
   for (int i = 1; i < argc; i++) {
     std::string w = argv[i], v;
     const Flag* f = nullptr;
@@ -219,12 +228,18 @@ static Args parse(int argc, char** argv) {
     else if (n == "batch-bases") a.batch_bases = (uint64_t)pos_int(n, v);
     else if (n == "dry-run") a.dry_run = true;
     else if (n == "verbose") a.verbose = true;
+    else if (n == "two-pass") a.two_pass = true;
+    else if (n == "matrix-budget") {
+      a.matrix_budget = byte_size(n, v);
+      budget_given = true;
+    }
     // --compress, --quiet: nothing to do (no .unik files; warnings always go to stderr)
   }
   // what this command does not do, by the flag's name
   if (circular) die("flag --circular is not supported by kmcp-makedb (chunks of a split genome are linear, compute.go:305)");
   if (by_seq) die("flag --by-seq is not supported by kmcp-makedb: one file is one reference");
   if (split_size) die("flag -s/--split-size is not supported by kmcp-makedb: use -n/--split-number");
+  if (budget_given && !a.two_pass) die("flag --matrix-budget needs --two-pass: only the two-pass build keeps block matrices in HBM");
   // compute.go:172-181
   if (a.ks.empty()) die("flag -k/--kmer needed");
   for (int k : a.ks) {
@@ -338,10 +353,236 @@ static void read_genome(const std::string& path, const std::vector<std::regex>& 
   if (g->seq.find_first_not_of('N') == std::string::npos) g->seq.clear();
 }
 
+// A few threads read, inflate and join the files which[0], which[1], ... ahead of the consumer, at most `window` files ahead; body(i) is
+// called for every one in order, on the calling thread, with genomes[i] read (seq empty and skipped set when it holds nothing); the
+// sequence is released after it.
+template <class Body>
+static void for_each_genome(const std::vector<std::string>& files, const std::vector<size_t>& which, const std::vector<std::regex>& filters, int k_max,
+                            int n_readers, std::atomic<uint64_t>* read_us, std::vector<Genome>* genomes, Body&& body) {
+  const size_t window = (size_t)n_readers * 4;
+  std::mutex mu;
+  std::condition_variable cv;
+  size_t next_file = 0, consumed = 0;
+  for (size_t i : which) {
+    Genome& g = (*genomes)[i];
+    g.done = g.skipped = false;
+    std::string().swap(g.seq);
+  }
+  std::vector<std::thread> readers;
+  for (int t = 0; t < n_readers; t++)
+    readers.emplace_back([&] {
+      for (;;) {
+        size_t i;
+        {
+          std::unique_lock<std::mutex> l(mu);
+          cv.wait(l, [&] { return next_file >= which.size() || next_file < consumed + window; });
+          if (next_file >= which.size()) return;
+          i = which[next_file++];
+        }
+        Genome& g = (*genomes)[i];
+        const double t0 = now_s();
+        read_genome(files[i], filters, k_max, &g);
+        *read_us += (uint64_t)((now_s() - t0) * 1e6);
+        if (g.seq.empty()) {
+          g.skipped = true;
+          logf("WARN", "skipping %s: no valid sequences", files[i].c_str());
+        }
+        std::lock_guard<std::mutex> l(mu);
+        g.done = true;
+        cv.notify_all();
+      }
+    });
+  for (size_t p = 0; p < which.size(); p++) {
+    Genome& g = (*genomes)[which[p]];
+    {
+      std::unique_lock<std::mutex> l(mu);
+      cv.wait(l, [&] { return g.done; });
+    }
+    body(which[p]);
+    std::string().swap(g.seq);
+    std::lock_guard<std::mutex> l(mu);
+    consumed = p + 1;
+    cv.notify_all();
+  }
+  for (auto& t : readers) t.join();
+}
+
 static int granted_cpus() {
   cpu_set_t set;
   if (sched_getaffinity(0, sizeof set, &set) == 0) return std::max(1, CPU_COUNT(&set));
   return 1;
+}
+
+// ---- --two-pass
+typedef std::function<void(const std::vector<size_t>&, const std::function<void(size_t)>&)> EachFn;
+
+// one batch of joined genomes on its way through kmcpg_sketch_genomes_to
+struct SinkBatch {
+  std::string seqs;
+  std::vector<uint64_t> offs{0};
+  std::vector<size_t> file;  // genome (file) index of every sequence
+};
+
+struct FilePlace {
+  uint32_t first_col = 0, n_cols = 0;  // the file's chunks are columns first_col .. first_col + n_cols - 1
+  bool sketched = false;
+};
+
+struct TwoPass {
+  const std::vector<std::string>* files;
+  const std::vector<Genome>* genomes;
+  std::vector<FilePlace> place;
+  std::vector<kmcpg_build_colmeta> cols;  // pass 1: all that is kept of a chunk
+  kmcpg_builder* builder = nullptr;
+  const SinkBatch* batch = nullptr;  // the one in flight
+  std::vector<uint32_t> col_ids;
+  std::string err;
+};
+
+// pass 1: the counts alone.  The lists stay where the sort left them
+static int count_sink(void* user, const kmcpg_sketch_piece* p) {
+  TwoPass* tp = (TwoPass*)user;
+  for (uint32_t c = 0; c < p->n_chunks; c++) {
+    const size_t fi = tp->batch->file[p->genome[c]];
+    FilePlace& fp = tp->place[fi];
+    if (!fp.sketched) {
+      fp.sketched = true;
+      fp.first_col = (uint32_t)tp->cols.size();
+      fp.n_cols = p->chunks[c];
+    }
+    kmcpg_build_colmeta m;
+    memset(&m, 0, sizeof m);
+    m.name = (*tp->genomes)[fi].name.c_str();
+    m.gsize = tp->batch->offs[p->genome[c] + 1] - tp->batch->offs[p->genome[c]];
+    m.chunk_idx = p->chunk_idx[c];
+    m.chunks = p->chunks[c];
+    m.n_hashes = p->koff[c + 1] - p->koff[c];
+    tp->cols.push_back(m);
+  }
+  return 0;
+}
+
+// pass 2: every list into its column's block matrix, on the sketcher's stream behind the sort
+static int scatter_sink(void* user, const kmcpg_sketch_piece* p) {
+  TwoPass* tp = (TwoPass*)user;
+  tp->col_ids.resize(p->n_chunks);
+  for (uint32_t c = 0; c < p->n_chunks; c++) {
+    const size_t fi = tp->batch->file[p->genome[c]];
+    const FilePlace& fp = tp->place[fi];
+    if (!fp.sketched || p->chunks[c] != fp.n_cols) {
+      char msg[64];
+      snprintf(msg, sizeof msg, ": %u chunk(s) now, %u in pass 1", p->chunks[c], fp.sketched ? fp.n_cols : 0);
+      tp->err = (*tp->files)[fi] + msg + ": the input changed between the passes";
+      return KMCPG_EINVAL;
+    }
+    tp->col_ids[c] = fp.first_col + p->chunk_idx[c];
+  }
+  return kmcpg_builder_scatter_device(tp->builder, p->d_hashes, p->koff, tp->col_ids.data(), p->n_chunks, p->stream);
+}
+
+static void two_pass(const Args& a, const std::vector<std::string>& files, const std::vector<Genome>& genomes, const kmcpg_split_spec& spec,
+                     kmcpg_sketcher* sk, const kmcpg_build_cfg& bc, int n_readers, const std::atomic<uint64_t>& read_us, const EachFn& each) {
+  const double t_start = now_s();
+  TwoPass tp;
+  tp.files = &files;
+  tp.genomes = &genomes;
+  tp.place.resize(files.size());
+  double sketch_s = 0;
+  // the files `which` through the sketcher in batches, one sketched while the next is read; every piece goes to `sink`
+  auto run = [&](const std::vector<size_t>& which, kmcpg_sketch_sink sink) {
+    std::thread worker;
+    SinkBatch* in_flight = nullptr;
+    int rc = 0;
+    std::string err;
+    auto finish = [&] {
+      if (!in_flight) return;
+      worker.join();
+      if (rc) die("%s", err.c_str());
+      delete in_flight;
+      in_flight = nullptr;
+    };
+    auto launch = [&](SinkBatch* b) {
+      finish();
+      in_flight = b;
+      worker = std::thread([&, b] {
+        const double t0 = now_s();
+        tp.batch = b;
+        tp.err.clear();
+        rc = kmcpg_sketch_genomes_to(sk, (const uint8_t*)b->seqs.data(), b->offs.data(), (uint32_t)b->file.size(), &spec, sink, &tp);
+        if (rc) err = tp.err.empty() ? kmcpg_last_error() : tp.err;
+        sketch_s += now_s() - t0;
+      });
+    };
+    SinkBatch* cur = new SinkBatch();
+    each(which, [&](size_t i) {
+      if (genomes[i].skipped) return;
+      if (!cur->file.empty() && cur->seqs.size() + genomes[i].seq.size() > a.batch_bases) {
+        launch(cur);
+        cur = new SinkBatch();
+      }
+      cur->seqs += genomes[i].seq;
+      cur->offs.push_back(cur->seqs.size());
+      cur->file.push_back(i);
+    });
+    if (!cur->file.empty()) launch(cur);
+    else delete cur;
+    finish();
+  };
+
+  // ---- pass 1: per file its columns, per column its count
+  std::vector<size_t> all_files(files.size());
+  for (size_t i = 0; i < files.size(); i++) all_files[i] = i;
+  run(all_files, count_sink);
+  for (size_t i = 0; i < files.size(); i++)
+    if (!genomes[i].skipped && !tp.place[i].sketched)  // compute.go:720-723
+      logf("WARN", "sequence is too short to split into %ld chunks with an overlap of %ld: %s", a.split_number, a.split_overlap, files[i].c_str());
+  if (tp.cols.empty()) die("no k-mers to index: every input file was skipped");
+  uint64_t total_hashes = 0;
+  for (const auto& c : tp.cols) total_hashes += c.n_hashes;
+  const double t_pass1 = now_s();
+
+  // ---- plan: blocks from the counts, rounds from the budget
+  kmcpg_builder_cfg cfg;
+  memset(&cfg, 0, sizeof cfg);
+  cfg.build = bc;
+  uint64_t piece_bases = 1ull << 28;
+  if (const char* e = getenv("KMCPG_SKETCH_PIECE_BASES")) piece_bases = std::max<uint64_t>(1, strtoull(e, nullptr, 10));
+  cfg.hbm_reserve = 2 * a.batch_bases + 25 * piece_bases;  // the sketcher's workspace ("Building a database")
+  CK(kmcpg_builder_open(&cfg, (int32_t)a.device, &tp.builder));
+  CK(kmcpg_builder_add_cols(tp.builder, tp.cols.data(), (uint32_t)tp.cols.size()));
+  uint32_t n_blocks = 0, n_rounds = 0;
+  CK(kmcpg_builder_plan(tp.builder, a.matrix_budget, &n_blocks, &n_rounds));
+  std::vector<uint32_t> col_round(tp.cols.size());
+  for (uint32_t c = 0; c < tp.cols.size(); c++) CK(kmcpg_builder_col_place(tp.builder, c, nullptr, nullptr, &col_round[c]));
+
+  // ---- pass 2: per round, the files that have a column in one of its blocks
+  size_t files_pass2 = 0;
+  for (uint32_t r = 0; r < n_rounds; r++) {
+    std::vector<size_t> which;
+    for (size_t i = 0; i < files.size(); i++) {
+      bool in = false;
+      for (uint32_t c = 0; c < tp.place[i].n_cols && tp.place[i].sketched && !in; c++) in = col_round[tp.place[i].first_col + c] == r;
+      if (in) which.push_back(i);
+    }
+    CK(kmcpg_builder_begin_round(tp.builder, r));
+    run(which, scatter_sink);
+    CK(kmcpg_builder_end_round(tp.builder, a.out_dir.c_str()));
+    logf("INFO", "round %u of %u: %zu of %zu file(s) read", r + 1, n_rounds, which.size(), files.size());
+    files_pass2 += which.size();
+  }
+  CK(kmcpg_builder_finish(tp.builder, a.out_dir.c_str()));
+  kmcpg_builder_stats st;
+  memset(&st, 0, sizeof st);
+  CK(kmcpg_builder_info(tp.builder, &st));
+  const double t_end = now_s();
+  logf("INFO", "%zu file(s), %zu column(s), %llu k-mers -> %s", files.size(), tp.cols.size(), (unsigned long long)total_hashes, a.out_dir.c_str());
+  logf("INFO", "two-pass: %u block(s) in %u round(s); files read: pass 1 %zu, pass 2 %zu; %llu keys scattered in %.3f ms (%llu launch(es)); peak matrix bytes %llu",
+       n_blocks, n_rounds, files.size(), files_pass2, (unsigned long long)st.keys_scattered, st.scatter_ms, (unsigned long long)st.scatter_launches,
+       (unsigned long long)st.matrix_bytes_peak);
+  logf("INFO", "no k-mer list was held in host memory: the lists went from the sort into the block matrices on the GPU");
+  logf("INFO", "elapsed %.3f s: read + gunzip %.3f s on %d thread(s) (beside the GPU), sketch + scatter %.3f s, pass 1 wall %.3f s, plan + pass 2 wall %.3f s",
+       t_end - t_start, (double)read_us.load() / 1e6, n_readers, sketch_s, t_pass1 - t_start, t_end - t_pass1);
+  kmcpg_builder_close(tp.builder);
 }
 
 int main(int argc, char** argv) {
@@ -398,59 +639,21 @@ int main(int argc, char** argv) {
   spec.k_min = k;
   spec.k_max = k_max;
 
-  // ---- readers: a few threads read, inflate and join files ahead of the consumer, at most `window` files ahead
+  // ---- readers: a few threads read, inflate and join files ahead of the consumer (for_each_genome)
   const int n_readers = std::max(1, std::min({(int)a.threads, granted_cpus(), 8, (int)files.size()}));
-  const size_t window = (size_t)n_readers * 4;
-  std::mutex mu;
-  std::condition_variable cv;
-  size_t next_file = 0, consumed = 0;
   std::atomic<uint64_t> read_us{0};
-  std::vector<std::thread> readers;
-  for (int t = 0; t < n_readers; t++)
-    readers.emplace_back([&] {
-      for (;;) {
-        size_t i;
-        {
-          std::unique_lock<std::mutex> l(mu);
-          cv.wait(l, [&] { return next_file >= files.size() || next_file < consumed + window; });
-          if (next_file >= files.size()) return;
-          i = next_file++;
-        }
-        const double t0 = now_s();
-        read_genome(files[i], filters, k_max, &genomes[i]);
-        read_us += (uint64_t)((now_s() - t0) * 1e6);
-        if (genomes[i].seq.empty()) {
-          genomes[i].skipped = true;
-          logf("WARN", "skipping %s: no valid sequences", files[i].c_str());
-        }
-        std::lock_guard<std::mutex> l(mu);
-        genomes[i].done = true;
-        cv.notify_all();
-      }
-    });
-  auto take = [&](size_t i) {  // blocks until file i is read
-    std::unique_lock<std::mutex> l(mu);
-    cv.wait(l, [&] { return genomes[i].done; });
-  };
-  auto release = [&](size_t i) {
-    std::lock_guard<std::mutex> l(mu);
-    consumed = i + 1;
-    cv.notify_all();
-  };
+  std::vector<size_t> all_files(files.size());
+  for (size_t i = 0; i < files.size(); i++) all_files[i] = i;
+  auto each = [&](const std::vector<size_t>& which, auto&& body) { for_each_genome(files, which, filters, k_max, n_readers, &read_us, &genomes, body); };
 
   if (a.dry_run) {
-    for (size_t i = 0; i < files.size(); i++) {
-      take(i);
-      if (!genomes[i].skipped) {
-        uint64_t n = 0;
-        CK(kmcpg_split_bounds(genomes[i].seq.size(), &spec, nullptr, nullptr, 0, &n));
-        if (n == 0) logf("WARN", "sequence is too short to split into %ld chunks with an overlap of %ld: %s", a.split_number, a.split_overlap, files[i].c_str());
-        printf("%s\t%zu\t%llu\n", genomes[i].name.c_str(), genomes[i].seq.size(), (unsigned long long)n);
-      }
-      std::string().swap(genomes[i].seq);
-      release(i);
-    }
-    for (auto& t : readers) t.join();
+    each(all_files, [&](size_t i) {  // nothing about a two-pass plan is known without sketching: --two-pass changes nothing here
+      if (genomes[i].skipped) return;
+      uint64_t n = 0;
+      CK(kmcpg_split_bounds(genomes[i].seq.size(), &spec, nullptr, nullptr, 0, &n));
+      if (n == 0) logf("WARN", "sequence is too short to split into %ld chunks with an overlap of %ld: %s", a.split_number, a.split_overlap, files[i].c_str());
+      printf("%s\t%zu\t%llu\n", genomes[i].name.c_str(), genomes[i].seq.size(), (unsigned long long)n);
+    });
     return 0;
   }
 
@@ -465,6 +668,36 @@ int main(int argc, char** argv) {
   cfg.syncmer_s = (uint32_t)a.syncmer_s;
   kmcpg_sketcher* sk = nullptr;
   CK(kmcpg_sketcher_open(&cfg, (int32_t)a.device, &sk));
+  kmcpg_build_cfg bc;
+  memset(&bc, 0, sizeof bc);
+  bc.k = k;
+  bc.canonical = 1;
+  bc.num_hashes = (int32_t)a.num_hash;
+  bc.fpr = a.fpr;
+  bc.threads = (int32_t)a.threads;
+  bc.block_size = (int32_t)a.block_size;
+  bc.scale = (uint32_t)a.scale;
+  bc.minimizer_w = (uint32_t)a.minimizer_w;
+  bc.syncmer_s = (uint32_t)a.syncmer_s;
+  bc.split_seq = a.split_number > 1;
+  bc.split_num = a.split_number > 1 ? (int32_t)a.split_number : 0;
+  bc.split_overlap = a.split_number > 1 ? (int32_t)a.split_overlap : 0;
+  std::string alias = a.alias;
+  if (alias.empty()) {  // index.go:294-296
+    std::string o = a.out_dir;
+    while (o.size() > 1 && o.back() == '/') o.pop_back();
+    alias = base_name(o);
+  }
+  bc.alias = alias.c_str();
+  bc.kmers_x = a.kmers_x;
+  bc.block_size_x = (int32_t)a.block_size_x;
+  bc.kmers_8 = a.kmers_8;
+  bc.kmers_1 = a.kmers_1;
+  if (a.two_pass) {
+    two_pass(a, files, genomes, spec, sk, bc, n_readers, read_us, [&](const std::vector<size_t>& which, const std::function<void(size_t)>& body) { each(which, body); });
+    kmcpg_sketcher_close(sk);
+    return 0;
+  }
 
   // ---- batches: one is filled from the readers while the GPU sketches the one before it
   struct Batch {
@@ -498,24 +731,19 @@ int main(int argc, char** argv) {
     });
   };
   Batch* cur = new Batch();
-  for (size_t i = 0; i < files.size(); i++) {
-    take(i);
-    if (!genomes[i].skipped) {
-      if (!cur->file.empty() && cur->seqs.size() + genomes[i].seq.size() > a.batch_bases) {
-        launch(cur);
-        cur = new Batch();
-      }
-      cur->seqs += genomes[i].seq;
-      cur->offs.push_back(cur->seqs.size());
-      cur->file.push_back(i);
+  each(all_files, [&](size_t i) {
+    if (genomes[i].skipped) return;
+    if (!cur->file.empty() && cur->seqs.size() + genomes[i].seq.size() > a.batch_bases) {
+      launch(cur);
+      cur = new Batch();
     }
-    std::string().swap(genomes[i].seq);
-    release(i);
-  }
+    cur->seqs += genomes[i].seq;
+    cur->offs.push_back(cur->seqs.size());
+    cur->file.push_back(i);
+  });
   if (!cur->file.empty()) launch(cur);
   else delete cur;
   finish();
-  for (auto& t : readers) t.join();
   const double t_sketched = now_s();
 
   // ---- index: every list is in host memory until the layout is known (block sizing needs every column's k-mer count)
@@ -542,31 +770,6 @@ int main(int argc, char** argv) {
         logf("WARN", "sequence is too short to split into %ld chunks with an overlap of %ld: %s", a.split_number, a.split_overlap, files[b->file[gi]].c_str());
   }
   if (cols.empty()) die("no k-mers to index: every input file was skipped");
-  kmcpg_build_cfg bc;
-  memset(&bc, 0, sizeof bc);
-  bc.k = k;
-  bc.canonical = 1;
-  bc.num_hashes = (int32_t)a.num_hash;
-  bc.fpr = a.fpr;
-  bc.threads = (int32_t)a.threads;
-  bc.block_size = (int32_t)a.block_size;
-  bc.scale = (uint32_t)a.scale;
-  bc.minimizer_w = (uint32_t)a.minimizer_w;
-  bc.syncmer_s = (uint32_t)a.syncmer_s;
-  bc.split_seq = a.split_number > 1;
-  bc.split_num = a.split_number > 1 ? (int32_t)a.split_number : 0;
-  bc.split_overlap = a.split_number > 1 ? (int32_t)a.split_overlap : 0;
-  std::string alias = a.alias;
-  if (alias.empty()) {  // index.go:294-296
-    std::string o = a.out_dir;
-    while (o.size() > 1 && o.back() == '/') o.pop_back();
-    alias = base_name(o);
-  }
-  bc.alias = alias.c_str();
-  bc.kmers_x = a.kmers_x;
-  bc.block_size_x = (int32_t)a.block_size_x;
-  bc.kmers_8 = a.kmers_8;
-  bc.kmers_1 = a.kmers_1;
   CK(kmcpg_build_db(a.out_dir.c_str(), &bc, cols.data(), (uint32_t)cols.size(), (int32_t)a.device));
   const double t_end = now_s();
   logf("INFO", "%zu file(s), %zu column(s), %llu k-mers -> %s", files.size(), cols.size(), (unsigned long long)total_hashes, a.out_dir.c_str());

@@ -622,6 +622,88 @@ int kmcpg_last_sketch_launches(kmcpg_sketcher* s, kmcpg_sketch_launch* out, uint
 /* HIP-event milliseconds of the last call's device work: the k-mer kernels, and the segmented sort + unique (bench support) */
 int kmcpg_last_sketch_ms(kmcpg_sketcher* s, float* kmers_ms, float* sort_ms);
 
+/* -- sketch lists that stay on the device: kmcpg_sketch_genomes with a sink in place of the copy of the lists to the host.  Per piece
+ *    of the batch (see kmcpg_sketch_genomes) the k-mer kernels and the segmented sort run and koff is read back, exactly as there; then
+ *    the sink is called with the piece's chunks and the lists in device memory.  Work the sink enqueues on `stream` runs behind the
+ *    sort.  After the sink returns the sketcher synchronises its stream before the next piece reuses the buffers, so the sink need not
+ *    wait for what it enqueued; d_hashes is NOT valid after that.  A non-zero return of the sink ends the call with that code (the
+ *    sketcher stays usable).  A sink that reads koff alone counts the k-mers of every chunk without moving a list.
+ *    kmcpg_sketch_genomes itself is this call with an internal sink that copies the lists to page-locked host memory. */
+typedef struct {
+  uint32_t first_chunk, n_chunks;               /* this piece's chunks within the call */
+  const uint32_t *genome, *chunk_idx, *chunks;  /* host, [n_chunks]: as kmcpg_sketch_result */
+  const uint64_t* koff;                         /* host, [n_chunks + 1], offsets into d_hashes (koff[0] == 0) */
+  const uint64_t* d_hashes;                     /* DEVICE: ascending, unique */
+  void* stream;                                 /* hipStream_t: work enqueued here runs behind the sort */
+} kmcpg_sketch_piece;
+typedef int (*kmcpg_sketch_sink)(void* user, const kmcpg_sketch_piece* piece);
+int kmcpg_sketch_genomes_to(kmcpg_sketcher* s, const uint8_t* seqs, const uint64_t* offs, uint32_t n_genomes, const kmcpg_split_spec* spec,
+                            kmcpg_sketch_sink sink, void* user);
+
+/* -- building a database larger than host memory: `kmcp index` in two passes over the input (build_plan.hpp, builder.cpp).  The block
+ *    layout of `kmcp index` needs every column's k-mer COUNT (the columns are sorted by it before blocks are cut, index.go:667) but not
+ *    the lists.  Pass 1 tells the builder the counts (kmcpg_builder_add_cols); kmcpg_builder_plan lays out the blocks exactly as
+ *    kmcpg_build_db does (index.go:657-682, :787-894, :1023) and partitions them, in file order, into rounds whose matrices fit
+ *    `matrix_budget` bytes of HBM together (a block counts its matrix + 8 bytes; a round closes when the next block would exceed the
+ *    budget; a single block above the budget is refused, KMCPG_ENOMEM, with the block, its bytes and the budget).  Pass 2, per round:
+ *    kmcpg_builder_begin_round allocates and zeroes the round's matrices, kmcpg_builder_scatter_device ORs device-resident lists (what a
+ *    kmcpg_sketch_sink receives) into them — one kernel launch per call, whatever number of lists and blocks (build_scatter.hip) —
+ *    and kmcpg_builder_end_round writes the round's _blockNNN.uniki and frees the matrices.  kmcpg_builder_finish writes __db.yml and
+ *    __name_mapping.tsv.  The files are byte-identical to kmcpg_build_db's on the same lists (index/serialization.go:159-300,
+ *    util-db-info.go:46-79).  Host memory is O(columns); no list crosses PCIe.
+ *
+ *    Call order: add_cols* -> plan -> per round (any order of rounds) begin_round / scatter_device* / end_round -> finish.  A call out
+ *    of order returns KMCPG_EINVAL and says which call was expected; the handle stays usable.  Structs are zeroed, then filled, then
+ *    validated (as kmcpg_sketch_cfg).  A builder opened with device -1 plans only: plan (with an explicit budget), col_place and
+ *    block_info work, begin_round returns KMCPG_EDEVICE. */
+typedef struct kmcpg_builder kmcpg_builder;
+typedef struct {
+  kmcpg_build_cfg build;  /* as kmcpg_build_db takes it */
+  uint64_t hbm_reserve;   /* kmcpg_builder_plan with matrix_budget 0: budget = free HBM at the call - hbm_reserve */
+  uint64_t reserved[3];   /* must be 0 */
+} kmcpg_builder_cfg;
+typedef struct {
+  const char* name;    /* reference name (copied) */
+  uint64_t gsize;      /* genome size */
+  uint32_t chunk_idx;  /* index of this chunk */
+  uint32_t chunks;     /* number of chunks of the genome */
+  uint64_t n_hashes;   /* k-mers of the chunk: the length of its sorted-unique list */
+} kmcpg_build_colmeta;
+typedef struct {
+  uint32_t rounds_done;
+  uint32_t slice_keys;            /* keys of one list a wave of the scatter kernel takes */
+  uint64_t scatter_calls;         /* kmcpg_builder_scatter_device calls that passed their checks */
+  uint64_t scatter_launches;      /* kernels launched: == the calls that held at least one key of the open round */
+  uint64_t keys_scattered;
+  uint64_t lists_skipped;         /* lists of columns of other rounds, and entries given as UINT32_MAX */
+  uint64_t matrix_bytes_resident; /* now (padding included) */
+  uint64_t matrix_bytes_peak;
+  double scatter_ms;              /* HIP-event milliseconds of the scatter kernels (waits for those still running) */
+  uint64_t reserved[2];
+} kmcpg_builder_stats;
+int kmcpg_builder_open(const kmcpg_builder_cfg* cfg, int32_t device /* -1: planning only */, kmcpg_builder** out);
+/* pass 1; input order = column id.  A column without k-mers is in no block (index.go:799-801) but keeps its line in __name_mapping.tsv */
+int kmcpg_builder_add_cols(kmcpg_builder* b, const kmcpg_build_colmeta* cols, uint32_t n);
+int kmcpg_builder_plan(kmcpg_builder* b, uint64_t matrix_budget /* 0: free HBM - hbm_reserve */, uint32_t* n_blocks, uint32_t* n_rounds);
+/* block UINT32_MAX (col_in_block and round too): an empty column, in no block */
+int kmcpg_builder_col_place(const kmcpg_builder* b, uint32_t col, uint32_t* block, uint32_t* col_in_block, uint32_t* round);
+int kmcpg_builder_block_info(const kmcpg_builder* b, uint32_t block, uint64_t* num_sigs, uint32_t* n_cols, uint32_t* row_bytes, uint32_t* round);
+int kmcpg_builder_begin_round(kmcpg_builder* b, uint32_t round);
+/* list i is d_hashes[koff[i] .. koff[i + 1]) (DEVICE memory; koff and cols are HOST arrays) and belongs to column cols[i]; UINT32_MAX
+ * = skip the entry.  A list whose column is in a block of another round is skipped silently (lists_skipped).  Refused before anything
+ * is launched (KMCPG_EINVAL): a column id out of range, a column given twice in the round, a list whose length differs from the
+ * n_hashes of pass 1 (a file that changed between the passes; the column and both counts are named).  The kernel is enqueued on
+ * `stream` (hipStream_t); the call does not wait for it, and d_hashes must stay valid until it has run. */
+int kmcpg_builder_scatter_device(kmcpg_builder* b, const uint64_t* d_hashes, const uint64_t* koff, const uint32_t* cols, uint32_t n_lists, void* stream);
+/* waits for the device, writes <out_dir>/R001/_blockNNN.uniki of the round's blocks (rows through a page-locked buffer in pieces of at
+ * most 256 MB) and frees the matrices.  Refuses (KMCPG_EINVAL, nothing written, round still open) while a non-empty column of the round
+ * has not been scattered, naming it: a block file never lacks a column. */
+int kmcpg_builder_end_round(kmcpg_builder* b, const char* out_dir);
+/* __db.yml and __name_mapping.tsv; refuses while a round is open or one was never built */
+int kmcpg_builder_finish(kmcpg_builder* b, const char* out_dir);
+int kmcpg_builder_info(kmcpg_builder* b, kmcpg_builder_stats* out);
+int kmcpg_builder_close(kmcpg_builder* b);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,7 +13,7 @@
 #include <string>
 #include <vector>
 
-#include "fpr.hpp"
+#include "build_plan.hpp"
 #include "engine.hpp"
 #include "fastmod.hpp"
 #include "kernels.hpp"
@@ -24,31 +24,9 @@ using namespace kmcpg;
 
 namespace {
 
-void be32(FILE* f, uint32_t v) {
-  uint8_t b[4] = {(uint8_t)(v >> 24), (uint8_t)(v >> 16), (uint8_t)(v >> 8), (uint8_t)v};
-  fwrite(b, 1, 4, f);
-}
-void be64(FILE* f, uint64_t v) {
-  be32(f, (uint32_t)(v >> 32));
-  be32(f, (uint32_t)v);
-}
-
-// CalcSignatureSize (util-hash.go:46-50)
-uint64_t signature_size(uint64_t n, int h, double fpr) {
-  const double ratio = (double)(-h) / log(1.0 - go_pow(fpr, 1.0 / (double)h));
-  return (uint64_t)ceil((double)n * ratio);
-}
-
-int mkdirs(const std::string& d) {
-  std::string cur;
-  for (size_t i = 0; i <= d.size(); i++) {
-    if (i == d.size() || d[i] == '/') {
-      if (!cur.empty() && mkdir(cur.c_str(), 0755) != 0 && errno != EEXIST) return -1;
-    }
-    if (i < d.size()) cur.push_back(d[i]);
-  }
-  return 0;
-}
+void be32(FILE* f, uint32_t v) { plan_be32(f, v); }
+void be64(FILE* f, uint64_t v) { plan_be64(f, v); }
+int mkdirs(const std::string& d) { return plan_mkdirs(d); }
 
 #define BHIP(expr)                                                                                        \
   do {                                                                                                    \
@@ -59,23 +37,15 @@ int mkdirs(const std::string& d) {
     }                                                                                                     \
   } while (0)
 
-// NumSigs of a block as `kmcp index` sizes it: from its fullest column (index.go:936-946, :1023)
-uint64_t block_num_sigs(const kmcpg_build_cfg& cfg, const std::vector<const kmcpg_build_col*>& cols) {
-  uint64_t max_elems = 0;
-  for (auto* c : cols) max_elems = std::max(max_elems, c->n_hashes);
-  return signature_size(max_elems, cfg.num_hashes, cfg.fpr);
-}
-
-int build_block(const std::string& path, const kmcpg_build_cfg& cfg, const std::vector<const kmcpg_build_col*>& cols, uint64_t num_sigs) {
+// one block: its columns' lists up in groups, one scatter launch per group, the matrix down and behind the header
+int build_block(const std::string& path, const kmcpg_build_cfg& cfg, const kmcpg_build_col* in, const PlanCol* meta, const PlanBlock& b) {
   int rc = 0;
-  const uint32_t n = (uint32_t)cols.size();
-  uint64_t max_elems = 0, total = 0;
-  for (auto* c : cols) {
-    max_elems = std::max(max_elems, c->n_hashes);
-    total += c->n_hashes;
-  }
-  const uint32_t row_bytes = (n + 7) / 8;
-  const uint64_t bytes = num_sigs * (uint64_t)row_bytes;
+  const uint32_t n = (uint32_t)b.cols.size();
+  const uint64_t num_sigs = b.num_sigs;
+  uint64_t max_elems = 0;
+  for (uint32_t c : b.cols) max_elems = std::max(max_elems, in[c].n_hashes);
+  const uint32_t row_bytes = b.row_bytes;
+  const uint64_t bytes = b.matrix_bytes;
   uint8_t* d_sigs = nullptr;
   uint64_t *d_hashes = nullptr, *d_off = nullptr;
   std::vector<uint8_t> host;
@@ -90,8 +60,9 @@ int build_block(const std::string& path, const kmcpg_build_cfg& cfg, const std::
     stage.clear();
     off.assign(1, 0);
     uint32_t c1 = c0;
-    while (c1 < n && (c1 == c0 || stage.size() + cols[c1]->n_hashes <= chunk_cap)) {
-      stage.insert(stage.end(), cols[c1]->hashes, cols[c1]->hashes + cols[c1]->n_hashes);
+    while (c1 < n && (c1 == c0 || stage.size() + in[b.cols[c1]].n_hashes <= chunk_cap)) {
+      const kmcpg_build_col& c = in[b.cols[c1]];
+      stage.insert(stage.end(), c.hashes, c.hashes + c.n_hashes);
       off.push_back(stage.size());
       c1++;
     }
@@ -110,36 +81,13 @@ int build_block(const std::string& path, const kmcpg_build_cfg& cfg, const std::
     rc = kmcpg_fail(KMCPG_EIO, "cannot write %s: %s", path.c_str(), strerror(errno));
     goto done;
   }
-  {
-    fwrite(".kmcpidx", 1, 8, f);
-    const uint8_t meta[4] = {4, (uint8_t)cfg.k, (uint8_t)((cfg.canonical ? 1 : 0) | 2 /* COMPACT = !faster (index.go:207) */), (uint8_t)cfg.num_hashes};
-    fwrite(meta, 1, 4, f);
-    be64(f, num_sigs);
-    be32(f, n);
-    for (auto* c : cols) {
-      be32(f, (uint32_t)strlen(c->name) + 1);
-      fwrite(c->name, 1, strlen(c->name), f);
-      fputc('\n', f);
-    }
-    be32(f, n);
-    for (auto* c : cols) {
-      be32(f, 1);
-      be64(f, c->gsize);
-    }
-    be32(f, n);
-    for (auto* c : cols) {
-      be32(f, 1);
-      be32(f, c->chunk_idx + (c->chunks << 16));  // index.go:1096
-    }
-    for (auto* c : cols) be64(f, c->n_hashes);
-    if (fwrite(host.data(), 1, bytes, f) != bytes) rc = kmcpg_fail(KMCPG_EIO, "short write on %s", path.c_str());
-  }
+  write_uniki_header(f, cfg, meta, b);
+  if (fwrite(host.data(), 1, bytes, f) != bytes) rc = kmcpg_fail(KMCPG_EIO, "short write on %s", path.c_str());
 done:
   if (f) fclose(f);
   if (d_sigs) (void)hipFree(d_sigs);
   if (d_hashes) (void)hipFree(d_hashes);
   if (d_off) (void)hipFree(d_off);
-  (void)total;
   return rc;
 }
 
@@ -153,106 +101,24 @@ extern "C" int kmcpg_build_db(const char* out_dir, const kmcpg_build_cfg* cfg, c
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return kmcpg_fail(KMCPG_EDEVICE, "no HIP device available: libkmcpgpu has no CPU fallback");
   if (device < 0 || device >= ndev) return kmcpg_fail(KMCPG_EINVAL, "device %d out of range", device);
   if (hipSetDevice(device) != hipSuccess) return kmcpg_fail(KMCPG_EDEVICE, "hipSetDevice failed");
-  std::vector<const kmcpg_build_col*> order;
-  uint64_t total = 0;
+  std::vector<PlanCol> meta(n_cols);
+  std::vector<uint64_t> counts(n_cols);
   for (uint32_t i = 0; i < n_cols; i++) {
     if (!cols[i].name || (!cols[i].hashes && cols[i].n_hashes)) return kmcpg_fail(KMCPG_EINVAL, "column %u: null name or hashes", i);
-    order.push_back(&cols[i]);
-    total += cols[i].n_hashes;
+    meta[i] = PlanCol{cols[i].name, cols[i].gsize, cols[i].chunk_idx, cols[i].chunks, cols[i].n_hashes};
+    counts[i] = cols[i].n_hashes;
   }
-  // files sorted by #k-mers ascending (index.go:667); the reference's parallel quicksort is unstable, input order breaks ties here
-  std::stable_sort(order.begin(), order.end(), [](const kmcpg_build_col* a, const kmcpg_build_col* b) { return a->n_hashes < b->n_hashes; });
-  int sblock = cfg->block_size > 0 ? cfg->block_size : ((int)((double)n_cols / (double)std::max(1, cfg->threads)) + 7) / 8 * 8;  // index.go:671-682
-  if (sblock > (int)n_cols) sblock = (int)n_cols;
-  if (sblock < 8) sblock = 8;
   const std::string dir = std::string(out_dir) + "/R001";
   if (mkdirs(dir) != 0) return kmcpg_fail(KMCPG_EIO, "cannot create %s: %s", dir.c_str(), strerror(errno));
-  // Block layout (index.go:787-894).  The reference walks the ascending list with a small state machine; its effect is that the
-  // columns fall into size tiers — up to -x k-mers, up to -8, up to -1, above — and every tier is cut into blocks of its own size
-  // (-b, -X, 8, 1), a tier change closing the open block.  When -X >= -b the -x tier does not exist (index.go:684-689) and the
-  // columns between -8 and -1 keep blocks of -b columns, still separated from the smaller ones.
-  const uint64_t thr_x = cfg->kmers_x ? cfg->kmers_x : 10ull << 20, thr_8 = cfg->kmers_8 ? cfg->kmers_8 : 20ull << 20,
-                 thr_1 = cfg->kmers_1 ? cfg->kmers_1 : 200ull << 20;
-  if (!(thr_x < thr_8 && thr_8 < thr_1)) return kmcpg_fail(KMCPG_EINVAL, "block thresholds must satisfy -x < -8 < -1");  // index.go:242-257
-  int size_x = cfg->block_size_x ? cfg->block_size_x : 256;
-  if (size_x <= 8 || size_x % 8) return kmcpg_fail(KMCPG_EINVAL, "-X/--block-sizeX should be a multiple of 8 greater than 8: %d", size_x);  // :225-230
-  const bool skip_x = size_x >= sblock;
-  auto tier = [&](uint64_t km) { return km > thr_1 ? 3 : km > thr_8 ? 2 : (!skip_x && km > thr_x) ? 1 : 0; };
-  const int tier_size[4] = {sblock, size_x, skip_x ? sblock : 8, 1};
-  std::vector<std::string> files;
-  struct Planned {
-    std::vector<const kmcpg_build_col*> cols;
-    int tier;
-    uint64_t num_sigs;
-  };
-  std::vector<Planned> plan;
-  for (size_t i = 0; i < order.size();) {
-    if (order[i]->n_hashes == 0) {  // empty inputs are skipped (index.go:799-801)
-      i++;
-      continue;
-    }
-    const int t = tier(order[i]->n_hashes);
-    Planned b;
-    b.tier = t;
-    while ((int)b.cols.size() < tier_size[t] && i < order.size() && tier(order[i]->n_hashes) == t) b.cols.push_back(order[i++]);
-    b.num_sigs = block_num_sigs(*cfg, b.cols);
-    plan.push_back(std::move(b));
-  }
-  // uniform_sigs (not in the reference): blocks with EQUAL NumSigs share their row addresses (h % NumSigs), so libkmcpgpu lays them
-  // side by side in HBM and serves them with one wide gather — 46 M reads/s instead of 15 M on a 10 k-chunk `-j 32` index whose
-  // blocks are 39 bytes wide.  `kmcp index` gives every block the size its fullest column asks for, and since
-  // the columns are sorted by k-mer count before they are cut into blocks, (almost) no two blocks agree.  A larger filter only
-  // lowers a block's false-positive rate below the database's `fpr` (the reader takes any per-block NumSigs,
-  // index/serialization.go:383-593), so rounding NumSigs UP is always safe; it costs file size.
-  //   1: every block of a tier gets the tier's largest NumSigs (one group per tier; size cost = how uneven the columns are);
-  //   2: NumSigs is rounded up to a geometric ladder of ratio 5/4 above the tier's smallest (a few groups per tier, < 25 % larger).
-  if (cfg->uniform_sigs == 1 || cfg->uniform_sigs == 2) {
-    for (int t = 0; t < 4; t++) {
-      uint64_t lo = ~0ull, hi = 0;
-      for (const auto& b : plan)
-        if (b.tier == t) {
-          lo = std::min(lo, b.num_sigs);
-          hi = std::max(hi, b.num_sigs);
-        }
-      if (hi == 0) continue;
-      for (auto& b : plan) {
-        if (b.tier != t) continue;
-        if (cfg->uniform_sigs == 1) b.num_sigs = hi;
-        else {
-          uint64_t step = lo;
-          while (step < b.num_sigs) step = step + step / 4 + 1;
-          b.num_sigs = std::min(step, std::max(hi, b.num_sigs));
-        }
-      }
-    }
-  } else if (cfg->uniform_sigs != 0) {
-    return kmcpg_fail(KMCPG_EINVAL, "uniform_sigs must be 0, 1 or 2");
-  }
-  for (const auto& b : plan) {
-    char name[64];
-    snprintf(name, sizeof name, "_block%03zu.uniki", files.size() + 1);  // index.go:1283-1285
-    int rc = build_block(dir + "/" + name, *cfg, b.cols, b.num_sigs);
+  BuildPlan plan;  // the layout is a function of the counts alone (build_plan.hpp)
+  const std::string err = build_plan(counts.data(), n_cols, *cfg, &plan);
+  if (!err.empty()) return kmcpg_fail(KMCPG_EINVAL, "%s", err.c_str());
+  for (size_t bi = 0; bi < plan.blocks.size(); bi++) {
+    int rc = build_block(dir + "/" + block_file_name(bi), *cfg, cols, meta.data(), plan.blocks[bi]);
     if (rc) return rc;
-    files.push_back(name);
   }
-  FILE* f = fopen((dir + "/__db.yml").c_str(), "w");
-  if (!f) return kmcpg_fail(KMCPG_EIO, "cannot write %s/__db.yml", dir.c_str());
-  auto b = [](int v) { return v ? "true" : "false"; };
-  fprintf(f, "version: 4\nunikiVersion: 4\nalias: %s\nk: %d\nks:\n- %d\nhashed: true\ncanonical: %s\n", cfg->alias ? cfg->alias : "kmcp-gpu-db", cfg->k, cfg->k,
-          b(cfg->canonical));
-  fprintf(f, "scaled: %s\nscale: %u\nminimizer: %s\nminimizer-w: %u\nsyncmer: %s\nsyncmer-s: %u\n", b(cfg->scale > 1), cfg->scale > 1 ? cfg->scale : 1,
-          b(cfg->minimizer_w > 0), cfg->minimizer_w, b(cfg->syncmer_s > 0), cfg->syncmer_s);
-  fprintf(f, "split-seq: %s\nsplit-size: %d\nsplit-num: %d\nsplit-overlap: %d\ncompact-size: true\n", b(cfg->split_seq), cfg->split_size, cfg->split_num,
-          cfg->split_overlap);
-  fprintf(f, "hashes: %d\nfpr: %.17g\nnumNameGroups: %u\nblocksize: %d\ntotalKmers: %llu\nfiles:\n", cfg->num_hashes, cfg->fpr, n_cols, sblock,
-          (unsigned long long)total);
-  for (const auto& fn : files) fprintf(f, "- %s\n", fn.c_str());
-  fclose(f);
-  f = fopen((dir + "/__name_mapping.tsv").c_str(), "w");
-  if (f) {
-    for (uint32_t i = 0; i < n_cols; i++) fprintf(f, "%s\t%s\n", cols[i].name, cols[i].name);
-    fclose(f);
-  }
+  if (!write_db_yml(dir, *cfg, n_cols, plan)) return kmcpg_fail(KMCPG_EIO, "cannot write %s/__db.yml", dir.c_str());
+  write_name_mapping(dir, meta.data(), n_cols);
   return 0;
 }
 

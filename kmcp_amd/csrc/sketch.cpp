@@ -73,9 +73,13 @@ struct Chunk {
   uint32_t genome, idx, of;
 };
 
-// one piece: chunks [c0, c1) of the batch (text on the device already) -> sorted-unique lists appended to the owner
-int sketch_piece(kmcpg_sketcher* s, const std::vector<Chunk>& ch, size_t c0, size_t c1, std::vector<uint64_t>& koff_all, std::vector<uint64_t*>& bufs,
-                 std::vector<uint64_t>& buf_n) {
+// the chunks of a call as a sink sees them, [all chunks]
+struct ChunkMeta {
+  std::vector<uint32_t> genome, chunk_idx, chunks;
+};
+
+// one piece: chunks [c0, c1) of the batch (text on the device already) -> sorted-unique lists on the device, handed to the sink
+int sketch_piece(kmcpg_sketcher* s, const std::vector<Chunk>& ch, const ChunkMeta& meta, size_t c0, size_t c1, kmcpg_sketch_sink sink, void* user) {
   const uint32_t n = (uint32_t)(c1 - c0);
   const int nk = s->cfg.n_k;
   hipStream_t st = s->st;
@@ -168,14 +172,91 @@ int sketch_piece(kmcpg_sketcher* s, const std::vector<Chunk>& ch, size_t c0, siz
   s->log.push_back(rec);
   const uint64_t uniq = koff[n];
   if (uniq > koff[n + 1] || koff[n + 1] > total * (uint64_t)nk) return kmcpg_fail(KMCPG_EDEVICE, "segmented sort: inconsistent counts (internal error)");
+  koff[n + 1] = 0;  // the sink's koff has n + 1 entries
+  kmcpg_sketch_piece piece{};
+  piece.first_chunk = (uint32_t)c0;
+  piece.n_chunks = n;
+  piece.genome = meta.genome.data() + c0;
+  piece.chunk_idx = meta.chunk_idx.data() + c0;
+  piece.chunks = meta.chunks.data() + c0;
+  piece.koff = koff.data();
+  piece.d_hashes = d_out;
+  piece.stream = (void*)st;
+  const int rc = sink(user, &piece);
+  // whatever the sink enqueued has run before the next piece (or the next call) reuses the buffers
+  const hipError_t e = hipStreamSynchronize(st);
+  if (rc) return rc;
+  HIPCHK(e);
+  return 0;
+}
+
+// the sink of kmcpg_sketch_genomes: every piece's lists down into page-locked memory of their own
+struct HostSink {
+  std::vector<uint64_t>* koff_all;
+  std::vector<uint64_t*> bufs;
+  std::vector<uint64_t> buf_n;
+};
+
+int host_sink(void* user, const kmcpg_sketch_piece* p) {
+  HostSink* hs = (HostSink*)user;
+  const uint64_t uniq = p->koff[p->n_chunks];
   uint64_t* h = nullptr;
   if (kmcpg_host_alloc(std::max<uint64_t>(uniq, 1) * sizeof(uint64_t), (void**)&h) != 0) return KMCPG_ENOMEM;
-  bufs.push_back(h);
-  buf_n.push_back(uniq);
-  if (uniq) HIPCHK(hipMemcpyAsync(h, d_out, uniq * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  const uint64_t base = koff_all.back();
-  for (uint32_t i = 1; i <= n; i++) koff_all.push_back(base + koff[i]);
+  hs->bufs.push_back(h);
+  hs->buf_n.push_back(uniq);
+  if (uniq) HIPCHK(hipMemcpyAsync(h, p->d_hashes, uniq * sizeof(uint64_t), hipMemcpyDeviceToHost, (hipStream_t)p->stream));
+  const uint64_t base = hs->koff_all->back();
+  for (uint32_t i = 1; i <= p->n_chunks; i++) hs->koff_all->push_back(base + p->koff[i]);
+  return 0;
+}
+
+// the piece loop of both entry points: the genomes cut into chunks and uploaded once, then piece by piece through the sink
+int sketch_run(kmcpg_sketcher* s, const uint8_t* seqs, const uint64_t* offs, uint32_t n_genomes, const kmcpg_split_spec* spec, kmcpg_sketch_sink sink,
+               void* user, ChunkMeta* meta) {
+  const int k_min = *std::min_element(s->cfg.ks, s->cfg.ks + s->cfg.n_k), k_max = *std::max_element(s->cfg.ks, s->cfg.ks + s->cfg.n_k);
+  if (spec->k_min != k_min || spec->k_max != k_max) return kmcpg_fail(KMCPG_EINVAL, "kmcpg_split_spec: k_min / k_max are not those of the sketcher (%d / %d)", k_min, k_max);
+  HIPCHK(hipSetDevice(s->device));
+  s->log.clear();
+  s->kmers_ms = s->sort_ms = 0;
+  const SplitSpec plan = to_plan(*spec);
+  std::vector<Chunk> ch;
+  std::vector<uint64_t> first, end;
+  for (uint32_t gi = 0; gi < n_genomes; gi++) {
+    if (offs[gi + 1] < offs[gi]) return kmcpg_fail(KMCPG_EINVAL, "offs must not decrease");
+    const uint64_t len = offs[gi + 1] - offs[gi];
+    const uint64_t cnt = split_bounds(len, plan, nullptr, nullptr, 0);
+    first.resize(cnt);
+    end.resize(cnt);
+    split_bounds(len, plan, first.data(), end.data(), cnt);
+    for (uint64_t c = 0; c < cnt; c++) ch.push_back(Chunk{offs[gi] + first[c], end[c] - first[c], gi, (uint32_t)c, (uint32_t)cnt});
+  }
+  for (const Chunk& c : ch) {
+    meta->genome.push_back(c.genome);
+    meta->chunk_idx.push_back(c.idx);
+    meta->chunks.push_back(c.of);
+  }
+  if (ch.empty()) return 0;
+  // every genome's bases go up once; the k-mer kernels may read a few bytes past a chunk's end (their staging): zeros behind the text
+  const uint64_t text = offs[n_genomes] - offs[0], pad = 4096;
+  if (s->d_text.ensure(text + pad)) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed (%llu bases of genomes)", (unsigned long long)text);
+  if (hipMemcpyAsync(s->d_text.p, seqs + offs[0], text, hipMemcpyHostToDevice, s->st) != hipSuccess ||
+      hipMemsetAsync(s->d_text.p + text, 0, pad, s->st) != hipSuccess)
+    return kmcpg_fail(KMCPG_EDEVICE, "upload of the genomes failed");
+  for (Chunk& c : ch) c.first -= offs[0];
+  uint64_t piece_max = 1ull << 28;
+  if (const char* e = getenv("KMCPG_SKETCH_PIECE_BASES")) piece_max = std::max<uint64_t>(1, strtoull(e, nullptr, 10));
+  piece_max = std::min<uint64_t>(piece_max, ((1ull << 32) - 1) / (uint64_t)s->cfg.n_k - 1);
+  size_t c0 = 0;
+  while (c0 < ch.size()) {
+    size_t c1 = c0;
+    uint64_t bases = 0;
+    while (c1 < ch.size() && (c1 == c0 || bases + ch[c1].len <= piece_max)) bases += ch[c1++].len;
+    if (int rc = sketch_piece(s, ch, *meta, c0, c1, sink, user)) {
+      (void)hipStreamSynchronize(s->st);  // the text upload of a call that ends early must not outlive the caller's buffer
+      return rc;
+    }
+    c0 = c1;
+  }
   return 0;
 }
 
@@ -265,72 +346,35 @@ extern "C" int kmcpg_sketch_genomes(kmcpg_sketcher* s, const uint8_t* seqs, cons
   if (!s || !out || (n_genomes && (!seqs || !offs))) return kmcpg_fail(KMCPG_EINVAL, "null argument");
   if (int rc = check_spec(spec)) return rc;
   memset(out, 0, sizeof *out);
-  const int k_min = *std::min_element(s->cfg.ks, s->cfg.ks + s->cfg.n_k), k_max = *std::max_element(s->cfg.ks, s->cfg.ks + s->cfg.n_k);
-  if (spec->k_min != k_min || spec->k_max != k_max) return kmcpg_fail(KMCPG_EINVAL, "kmcpg_split_spec: k_min / k_max are not those of the sketcher (%d / %d)", k_min, k_max);
   std::lock_guard<std::mutex> g(s->mu);
-  HIPCHK(hipSetDevice(s->device));
-  s->log.clear();
-  s->kmers_ms = s->sort_ms = 0;
-  const SplitSpec plan = to_plan(*spec);
-  std::vector<Chunk> ch;
-  std::vector<uint64_t> first, end;
-  for (uint32_t gi = 0; gi < n_genomes; gi++) {
-    if (offs[gi + 1] < offs[gi]) return kmcpg_fail(KMCPG_EINVAL, "offs must not decrease");
-    const uint64_t len = offs[gi + 1] - offs[gi];
-    const uint64_t cnt = split_bounds(len, plan, nullptr, nullptr, 0);
-    first.resize(cnt);
-    end.resize(cnt);
-    split_bounds(len, plan, first.data(), end.data(), cnt);
-    for (uint64_t c = 0; c < cnt; c++) ch.push_back(Chunk{offs[gi] + first[c], end[c] - first[c], gi, (uint32_t)c, (uint32_t)cnt});
-  }
   SketchOwner* o = new SketchOwner();
-  std::vector<uint64_t*> bufs;
-  std::vector<uint64_t> buf_n;
+  o->koff.push_back(0);
+  HostSink hs;
+  hs.koff_all = &o->koff;
+  ChunkMeta meta;
   auto fail = [&](int rc) {
-    for (uint64_t* b : bufs) (void)kmcpg_host_free(b);
+    for (uint64_t* b : hs.bufs) (void)kmcpg_host_free(b);
     delete o;
     return rc;
   };
-  o->koff.push_back(0);
-  if (!ch.empty()) {
-    // every genome's bases go up once; the k-mer kernels may read a few bytes past a chunk's end (their staging): zeros behind the text
-    const uint64_t text = offs[n_genomes] - offs[0], pad = 4096;
-    if (s->d_text.ensure(text + pad)) return fail(kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed (%llu bases of genomes)", (unsigned long long)text));
-    if (hipMemcpyAsync(s->d_text.p, seqs + offs[0], text, hipMemcpyHostToDevice, s->st) != hipSuccess ||
-        hipMemsetAsync(s->d_text.p + text, 0, pad, s->st) != hipSuccess)
-      return fail(kmcpg_fail(KMCPG_EDEVICE, "upload of the genomes failed"));
-    for (Chunk& c : ch) c.first -= offs[0];
-    uint64_t piece_max = 1ull << 28;
-    if (const char* e = getenv("KMCPG_SKETCH_PIECE_BASES")) piece_max = std::max<uint64_t>(1, strtoull(e, nullptr, 10));
-    piece_max = std::min<uint64_t>(piece_max, ((1ull << 32) - 1) / (uint64_t)s->cfg.n_k - 1);
-    size_t c0 = 0;
-    while (c0 < ch.size()) {
-      size_t c1 = c0;
-      uint64_t bases = 0;
-      while (c1 < ch.size() && (c1 == c0 || bases + ch[c1].len <= piece_max)) bases += ch[c1++].len;
-      if (int rc = sketch_piece(s, ch, c0, c1, o->koff, bufs, buf_n)) return fail(rc);
-      c0 = c1;
-    }
-  }
+  if (int rc = sketch_run(s, seqs, offs, n_genomes, spec, host_sink, &hs, &meta)) return fail(rc);
   // one contiguous list buffer: the only piece's, or the pieces' copied together
-  if (bufs.size() == 1) {
-    o->hashes = bufs[0];
+  if (hs.bufs.size() == 1) {
+    o->hashes = hs.bufs[0];
   } else {
     const uint64_t all = o->koff.back();
     if (kmcpg_host_alloc(std::max<uint64_t>(all, 1) * sizeof(uint64_t), (void**)&o->hashes) != 0) return fail(KMCPG_ENOMEM);
     uint64_t at = 0;
-    for (size_t i = 0; i < bufs.size(); i++) {
-      memcpy(o->hashes + at, bufs[i], buf_n[i] * sizeof(uint64_t));
-      at += buf_n[i];
-      (void)kmcpg_host_free(bufs[i]);
+    for (size_t i = 0; i < hs.bufs.size(); i++) {
+      memcpy(o->hashes + at, hs.bufs[i], hs.buf_n[i] * sizeof(uint64_t));
+      at += hs.buf_n[i];
+      (void)kmcpg_host_free(hs.bufs[i]);
     }
   }
-  for (const Chunk& c : ch) {
-    o->genome.push_back(c.genome);
-    o->chunk_idx.push_back(c.idx);
-    o->chunks.push_back(c.of);
-  }
-  out->n_chunks = (uint32_t)ch.size();
+  o->genome = std::move(meta.genome);
+  o->chunk_idx = std::move(meta.chunk_idx);
+  o->chunks = std::move(meta.chunks);
+  out->n_chunks = (uint32_t)o->genome.size();
   out->genome = o->genome.data();
   out->chunk_idx = o->chunk_idx.data();
   out->chunks = o->chunks.data();
@@ -338,6 +382,15 @@ extern "C" int kmcpg_sketch_genomes(kmcpg_sketcher* s, const uint8_t* seqs, cons
   out->hashes = o->hashes;
   out->owner = o;
   return 0;
+}
+
+extern "C" int kmcpg_sketch_genomes_to(kmcpg_sketcher* s, const uint8_t* seqs, const uint64_t* offs, uint32_t n_genomes, const kmcpg_split_spec* spec,
+                                       kmcpg_sketch_sink sink, void* user) {
+  if (!s || !sink || (n_genomes && (!seqs || !offs))) return kmcpg_fail(KMCPG_EINVAL, "null argument");
+  if (int rc = check_spec(spec)) return rc;
+  std::lock_guard<std::mutex> g(s->mu);
+  ChunkMeta meta;
+  return sketch_run(s, seqs, offs, n_genomes, spec, sink, user, &meta);
 }
 
 extern "C" int kmcpg_last_sketch_launches(kmcpg_sketcher* s, kmcpg_sketch_launch* out, uint32_t cap, uint32_t* n) {

@@ -26,6 +26,9 @@ EXPORTS = [
     "kmcpg_sketcher_open", "kmcpg_sketcher_close", "kmcpg_split_bounds", "kmcpg_sketch_genomes", "kmcpg_sketch_result_free",
     "kmcpg_last_sketch_launches", "kmcpg_last_sketch_ms", "kmcpg_sort_segments_device",
     "kmcpg_open_set", "kmcpg_set_info", "kmcpg_last_set_order",
+    "kmcpg_sketch_genomes_to", "kmcpg_builder_open", "kmcpg_builder_close", "kmcpg_builder_add_cols", "kmcpg_builder_plan",
+    "kmcpg_builder_col_place", "kmcpg_builder_block_info", "kmcpg_builder_begin_round", "kmcpg_builder_scatter_device",
+    "kmcpg_builder_end_round", "kmcpg_builder_finish", "kmcpg_builder_info",
 ]
 
 
@@ -213,6 +216,27 @@ class BuildCol(C.Structure):
                 ("hashes", C.c_void_p), ("n_hashes", C.c_uint64)]
 
 
+class BuilderCfg(C.Structure):
+    _fields_ = [("build", BuildCfg), ("hbm_reserve", C.c_uint64), ("reserved", C.c_uint64 * 3)]
+
+
+class BuildColMeta(C.Structure):
+    _fields_ = [("name", C.c_char_p), ("gsize", C.c_uint64), ("chunk_idx", C.c_uint32), ("chunks", C.c_uint32), ("n_hashes", C.c_uint64)]
+
+
+class BuilderStats(C.Structure):
+    _fields_ = [("rounds_done", C.c_uint32), ("slice_keys", C.c_uint32), ("scatter_calls", C.c_uint64), ("scatter_launches", C.c_uint64),
+                ("keys_scattered", C.c_uint64), ("lists_skipped", C.c_uint64), ("matrix_bytes_resident", C.c_uint64),
+                ("matrix_bytes_peak", C.c_uint64), ("scatter_ms", C.c_double), ("reserved", C.c_uint64 * 2)]
+
+
+class SketchPiece(C.Structure):
+    _fields_ = [("first_chunk", C.c_uint32), ("n_chunks", C.c_uint32), ("genome", C.POINTER(C.c_uint32)), ("chunk_idx", C.POINTER(C.c_uint32)),
+                ("chunks", C.POINTER(C.c_uint32)), ("koff", C.POINTER(C.c_uint64)), ("d_hashes", C.c_void_p), ("stream", C.c_void_p)]
+
+
+SKETCH_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(SketchPiece))
+
 HIT_DTYPE = np.dtype([("read", np.uint32), ("col", np.uint32), ("count", np.uint32)])
 PAIR_DTYPE = np.dtype([("col", np.uint32), ("count", np.uint32)])
 EXC_DTYPE = np.dtype([("pos", np.uint64), ("len", np.uint32), ("byte", np.uint32)])  # kmcpg_exc_run
@@ -332,6 +356,19 @@ def load():
     L.kmcpg_open_set.argtypes = [C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(Opts), C.POINTER(vp)]
     L.kmcpg_set_info.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32]
     L.kmcpg_last_set_order.argtypes = [vp, C.POINTER(SetOrder)]
+    L.kmcpg_sketch_genomes_to.argtypes = [vp, vp, vp, C.c_uint32, C.POINTER(SplitSpec), SKETCH_SINK, vp]
+    u32p = C.POINTER(C.c_uint32)
+    L.kmcpg_builder_open.argtypes = [C.POINTER(BuilderCfg), C.c_int32, C.POINTER(vp)]
+    L.kmcpg_builder_close.argtypes = [vp]
+    L.kmcpg_builder_add_cols.argtypes = [vp, C.POINTER(BuildColMeta), C.c_uint32]
+    L.kmcpg_builder_plan.argtypes = [vp, C.c_uint64, u32p, u32p]
+    L.kmcpg_builder_col_place.argtypes = [vp, C.c_uint32, u32p, u32p, u32p]
+    L.kmcpg_builder_block_info.argtypes = [vp, C.c_uint32, u64p, u32p, u32p, u32p]
+    L.kmcpg_builder_begin_round.argtypes = [vp, C.c_uint32]
+    L.kmcpg_builder_scatter_device.argtypes = [vp, vp, vp, vp, C.c_uint32, vp]
+    L.kmcpg_builder_end_round.argtypes = [vp, C.c_char_p]
+    L.kmcpg_builder_finish.argtypes = [vp, C.c_char_p]
+    L.kmcpg_builder_info.argtypes = [vp, C.POINTER(BuilderStats)]
     _lib = L
     return L
 
@@ -395,6 +432,94 @@ def build_db(out_dir, columns, k=21, num_hashes=1, fpr=0.3, threads=32, block_si
         arr[i] = BuildCol(name.encode(), gsize, ci, nch, h.ctypes.data, len(h))
     _check(load().kmcpg_build_db(os.fsencode(out_dir), C.byref(cfg), arr, len(columns), device))
     return os.path.join(out_dir, "R001")
+
+
+def copy_from_device(d_ptr, count, dtype=np.uint64, stream=None):
+    """`count` items at the device pointer d_ptr (an integer) -> numpy array: a hipMemcpyAsync on `stream` and a wait for that stream,
+    through the HIP runtime libkmcpgpu.so is bound to.  What a sketch_to sink uses to look at a piece's lists."""
+    out = np.zeros(count, dtype=dtype)
+    if count:
+        L = load()
+        L.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+        L.hipStreamSynchronize.argtypes = [C.c_void_p]
+        if L.hipMemcpyAsync(out.ctypes.data, d_ptr, out.nbytes, 2, stream) != 0 or L.hipStreamSynchronize(stream) != 0:  # 2 = hipMemcpyDeviceToHost
+            raise KmcpGpuError(-4, "copy from the device failed")
+    return out
+
+
+class Builder:
+    """kmcpg_builder: `kmcp index` in two passes — the counts of every column first (add_cols, plan), then device-resident lists ORed
+    into block matrices that stay in HBM, round by round (begin_round, scatter_device, end_round), then finish.  device=-1 plans only."""
+
+    NO_BLOCK = 0xFFFFFFFF
+
+    def __init__(self, k=21, num_hashes=1, fpr=0.3, threads=32, block_size=0, scale=1, minimizer_w=0, syncmer_s=0, device=0, alias="kmcp-gpu-db",
+                 kmers_x=0, block_size_x=0, kmers_8=0, kmers_1=0, uniform_sigs=0, hbm_reserve=0):
+        cfg = BuilderCfg()
+        cfg.build = BuildCfg(k=k, canonical=1, num_hashes=num_hashes, fpr=fpr, threads=threads, block_size=block_size, scale=scale,
+                             minimizer_w=minimizer_w, syncmer_s=syncmer_s, alias=alias.encode(), kmers_x=kmers_x, block_size_x=block_size_x,
+                             kmers_8=kmers_8, kmers_1=kmers_1, uniform_sigs=uniform_sigs)
+        cfg.hbm_reserve = hbm_reserve
+        h = C.c_void_p()
+        _check(load().kmcpg_builder_open(C.byref(cfg), device, C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if self._h:
+            load().kmcpg_builder_close(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def add_cols(self, cols):
+        """cols: list of (name, gsize, chunk_idx, chunks, n_hashes); input order = column id"""
+        arr = (BuildColMeta * max(1, len(cols)))()
+        for i, (name, gsize, ci, nch, n) in enumerate(cols):
+            arr[i] = BuildColMeta(name.encode(), gsize, ci, nch, n)
+        _check(load().kmcpg_builder_add_cols(self._h, arr, len(cols)))
+
+    def plan(self, matrix_budget=0):
+        """-> (blocks, rounds)"""
+        nb, nr = C.c_uint32(0), C.c_uint32(0)
+        _check(load().kmcpg_builder_plan(self._h, matrix_budget, C.byref(nb), C.byref(nr)))
+        return nb.value, nr.value
+
+    def col_place(self, col):
+        """-> (block, column in the block, round); block NO_BLOCK: an empty column, in no block"""
+        b, c, r = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        _check(load().kmcpg_builder_col_place(self._h, col, C.byref(b), C.byref(c), C.byref(r)))
+        return b.value, c.value, r.value
+
+    def block_info(self, block):
+        ns, n, rb, r = C.c_uint64(0), C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        _check(load().kmcpg_builder_block_info(self._h, block, C.byref(ns), C.byref(n), C.byref(rb), C.byref(r)))
+        return dict(num_sigs=ns.value, n_cols=n.value, row_bytes=rb.value, round=r.value)
+
+    def begin_round(self, rnd):
+        _check(load().kmcpg_builder_begin_round(self._h, rnd))
+
+    def scatter_device(self, d_hashes, koff, cols, stream=None):
+        """d_hashes: device pointer (integer); koff [n + 1] and cols [n] are host arrays; cols NO_BLOCK = skip the entry"""
+        koff = np.ascontiguousarray(koff, dtype=np.uint64)
+        cols = np.ascontiguousarray(cols, dtype=np.uint32)
+        assert len(koff) == len(cols) + 1
+        _check(load().kmcpg_builder_scatter_device(self._h, d_hashes, koff.ctypes.data, cols.ctypes.data, len(cols), stream))
+
+    def end_round(self, out_dir):
+        _check(load().kmcpg_builder_end_round(self._h, os.fsencode(out_dir)))
+
+    def finish(self, out_dir):
+        _check(load().kmcpg_builder_finish(self._h, os.fsencode(out_dir)))
+        return os.path.join(out_dir, "R001")
+
+    def info(self):
+        st = BuilderStats()
+        _check(load().kmcpg_builder_info(self._h, C.byref(st)))
+        return {f: getattr(st, f) for f, _ in BuilderStats._fields_ if f != "reserved"}
 
 
 def split_bounds(length, split_number=1, split_overlap=0, split_min_ref=0, k_min=21, k_max=None):
@@ -475,6 +600,34 @@ class Sketcher:
         res = SketchResult()
         _check(load().kmcpg_sketch_genomes(self._h, seqs.ctypes.data, offs.ctypes.data, len(genomes), C.byref(spec), C.byref(res)))
         return Sketch(res)
+
+    def sketch_to(self, genomes, sink, split_number=1, split_overlap=0, split_min_ref=0):
+        """kmcpg_sketch_genomes_to: sink(piece) is called per piece with a dict of first_chunk, genome / chunk_idx / chunks (numpy copies),
+        koff (numpy, n + 1), d_hashes (device pointer as an integer, valid inside the sink only) and stream; it returns None / 0, or an
+        error code that ends the call (raised as KmcpGpuError).  An exception in the sink ends the call too and is re-raised."""
+        seqs, offs = pack_reads(list(genomes))
+        spec = SplitSpec(split_number, split_overlap, split_min_ref, min(self.ks), max(self.ks), 0)
+        raised = []
+
+        def tramp(_user, pp):
+            try:
+                p = pp.contents
+                n = p.n_chunks
+                arr = lambda ptr, m, dt: np.ctypeslib.as_array(ptr, shape=(m,)).copy() if m else np.zeros(0, dtype=dt)  # noqa: E731
+                piece = dict(first_chunk=p.first_chunk, n_chunks=n, genome=arr(p.genome, n, np.uint32), chunk_idx=arr(p.chunk_idx, n, np.uint32),
+                             chunks=arr(p.chunks, n, np.uint32), koff=np.ctypeslib.as_array(p.koff, shape=(n + 1,)).copy(),
+                             d_hashes=p.d_hashes or 0, stream=p.stream)
+                rc = sink(piece)
+                return int(rc) if rc else 0
+            except BaseException as e:  # nothing may cross the C frames
+                raised.append(e)
+                return -1
+
+        cb = SKETCH_SINK(tramp)
+        rc = load().kmcpg_sketch_genomes_to(self._h, seqs.ctypes.data, offs.ctypes.data, len(genomes), C.byref(spec), cb, None)
+        if raised:
+            raise raised[0]
+        _check(rc)
 
     def last_sketch_launches(self):
         n = C.c_uint32(0)

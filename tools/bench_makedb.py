@@ -11,6 +11,10 @@ Both paths start from genomes in host memory and end with sorted-unique lists in
 after one warm-up of each; per shape the script reports the median and the spread (max - min) of both, the launch witness, the
 HIP-event split of the new path (k-mer kernels | segmented sort) and the sort's rate.  The lists of both paths are compared once.
 --makedb times kmcp-makedb end to end on the shape's genomes written as .fa.gz to /dev/shm.
+--makedb --two-pass times `kmcp-makedb --two-pass` against the one-pass default instead, on the same genomes as .fa and as .fa.gz: one
+warm-up of each, then alternating runs (one-pass, two-pass, ...), wall time of the command plus the phases of its log lines; the
+scatter kernel's keys/s (its HIP-event time) beside the one-pass index stage and beside kmcpg_stream_probe over the finished database,
+the yardstick for what the memory system streams.  The two databases are compared file by file.
 
   python tools/bench_makedb.py --shape a --repeats 5 --out profiles/r09_makedb.json
 """
@@ -155,6 +159,71 @@ def run_shape(name, spec, args, lib):
     return res
 
 
+def run_two_pass(name, spec, args, lib):
+    """kmcp-makedb --two-pass against one-pass, end to end"""
+    import filecmp
+    import re
+    n = args.genomes or spec["genomes"]
+    genomes = make_genomes(n, spec["length"])
+    exe = os.path.join(ROOT, "kmcp_amd", "kmcp-makedb")
+    tmp = tempfile.mkdtemp(prefix="bench_two_pass_", dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
+    res = dict(shape=name, genomes=n, length=spec["length"], k=K, scale=spec["scale"], inputs={})
+    med = statistics.median
+    try:
+        for form in ("fa", "fa.gz"):
+            files = []
+            for i, g in enumerate(genomes):
+                p = os.path.join(tmp, f"g{i:05d}.{form}")
+                with (gzip.open(p, "wb", compresslevel=1) if form.endswith("gz") else open(p, "wb")) as fh:
+                    fh.write(b">g%d chromosome\n" % i)
+                    fh.write(b"\n".join(g[j:j + 80] for j in range(0, len(g), 80)) + b"\n")
+                files.append(p)
+            lst = os.path.join(tmp, f"files_{form}.txt")
+            with open(lst, "w") as fh:
+                fh.write("\n".join(files) + "\n")
+            base = [exe, "-k", str(K), "-n", str(SPLIT), "-l", str(OVERLAP), "--num-hash", "1", "-f", "0.3", "-j", "16", "-i", lst, "--force"]
+            if spec["scale"] > 1:
+                base += ["-D", str(spec["scale"])]
+            dirs = dict(one=os.path.join(tmp, "one.kmcp"), two=os.path.join(tmp, "two.kmcp"))
+            cmds = dict(one=base + ["-O", dirs["one"]], two=base + ["--two-pass", "-O", dirs["two"]] + (["--matrix-budget", args.matrix_budget] if args.matrix_budget else []))
+            runs = dict(one=[], two=[])
+            for rep in range(-1, args.repeats):  # -1: warm-up (page cache, code objects)
+                for mode in ("one", "two"):
+                    t0 = time.perf_counter()
+                    r = subprocess.run(cmds[mode], capture_output=True, text=True, timeout=900)
+                    wall = time.perf_counter() - t0
+                    assert r.returncode == 0, r.stderr
+                    if rep >= 0:
+                        runs[mode].append(dict(wall_s=wall, log=[x for x in r.stderr.splitlines() if "elapsed" in x or "two-pass:" in x]))
+            out = dict(files=len(files), bytes=sum(os.path.getsize(f) for f in files))
+            for mode in ("one", "two"):
+                w = [x["wall_s"] for x in runs[mode]]
+                out[mode] = dict(wall_s=dict(median=med(w), min=min(w), max=max(w), spread=max(w) - min(w)), runs=runs[mode])
+            out["two_over_one"] = out["two"]["wall_s"]["median"] / out["one"]["wall_s"]["median"]
+            # the scatter alone: HIP-event time of the kernels of all scatter calls, beside the index stage of one-pass (uploads, its
+            # scatter launches, read-back and file writes together: what the lists cost after the sketch there)
+            sc = [re.search(r"(\d+) keys scattered in ([0-9.]+) ms \((\d+) launch", "\n".join(x["log"])) for x in runs["two"]]
+            ms = [float(m.group(2)) for m in sc]
+            keys = int(sc[0].group(1))
+            out["scatter"] = dict(keys=keys, launches=int(sc[0].group(3)), ms=dict(median=med(ms), min=min(ms), max=max(ms), spread=max(ms) - min(ms)),
+                                  keys_per_s=keys / (med(ms) / 1e3), atomic_bytes_per_s=4 * keys / (med(ms) / 1e3))
+            ix = [float(re.search(r"index ([0-9.]+) s", "\n".join(x["log"])).group(1)) for x in runs["one"]]
+            out["one_pass_index_s"] = dict(median=med(ix), min=min(ix), max=max(ix), spread=max(ix) - min(ix), keys_per_s=keys / med(ix))
+            one_r, two_r = os.path.join(dirs["one"], "R001"), os.path.join(dirs["two"], "R001")
+            names = sorted(os.listdir(one_r))
+            out["databases_equal"] = names == sorted(os.listdir(two_r)) and all(filecmp.cmp(os.path.join(one_r, f), os.path.join(two_r, f), shallow=False)
+                                                                                for f in names if f != "__db.yml")
+            res["inputs"][form] = out
+        from kmcp_amd import Database
+        with Database.open(os.path.join(dirs["two"], "R001"), device=0) as db:
+            probes = [db.stream_probe() for _ in range(4)][1:]
+        pm = med([p[0] for p in probes])
+        res["stream_probe"] = dict(ms=pm, bytes=probes[0][1], bytes_per_s=probes[0][1] / (pm / 1e3))
+        return res
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+
+
 def run_makedb(genomes, spec):
     exe = os.path.join(ROOT, "kmcp_amd", "kmcp-makedb")
     tmp = tempfile.mkdtemp(prefix="bench_makedb_", dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
@@ -192,12 +261,14 @@ def main():
     ap.add_argument("--genomes", type=int, default=0, help="fewer genomes than the shape's (quick look)")
     ap.add_argument("--no-yardstick", action="store_true")
     ap.add_argument("--makedb", action="store_true")
+    ap.add_argument("--two-pass", action="store_true", help="with --makedb: kmcp-makedb --two-pass against one-pass, nothing else")
+    ap.add_argument("--matrix-budget", default="", help="passed to kmcp-makedb --two-pass (several rounds)")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     from kmcp_amd import lib
     out = []
     for name in args.shape.split(","):
-        r = run_shape(name, SHAPES[name], args, lib)
+        r = run_two_pass(name, SHAPES[name], args, lib) if (args.makedb and args.two_pass) else run_shape(name, SHAPES[name], args, lib)
         print(json.dumps(r), flush=True)
         out.append(r)
         if args.out:
