@@ -1,12 +1,21 @@
-// packappend_check.cpp — kmcp-search's batch assembly for -g queries (cli/kmcp_search.cpp, round 6): a query packed on its own and moved
+// packappend_check.cpp — kmcp-search's batch assembly for -g queries (cli/search_batch.hpp, round 6): a query packed on its own and moved
 // behind a batch with Batch::append_packed (byte copy when the batch ends on a byte, shifted otherwise, runs re-based) must leave the batch
 // exactly as packing the same text straight into it with Batch::pack_append does — codes, runs, base count — for every alignment, with N
 // gaps, IUPAC bytes and empty queries in between; and kmcpg_unpack2 of the result must spell the concatenated text.  CPU only.
-#define main kmcp_search_cli_main
-#include "../cli/kmcp_search.cpp"
-#undef main
+#include <stdarg.h>
 
 #include <random>
+
+#include "../cli/search_batch.hpp"
+
+[[noreturn]] void die(const char* fmt, ...) {  // (the header leaves it to the program)
+  va_list ap;
+  va_start(ap, fmt);
+  vfprintf(stderr, fmt, ap);
+  va_end(ap);
+  fputc('\n', stderr);
+  exit(255);
+}
 
 int main() {
   std::mt19937_64 g(11);

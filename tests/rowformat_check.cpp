@@ -3,11 +3,21 @@
 // RowFormatter::row called per match, for short and oversized IDs / target names, every count of matches around the switch
 // between the two paths, FPR strings from the table and from the map; w_f4 must print what "%.4f" prints, ties and large
 // values included.
-#define main kmcp_search_cli_main
-#include "../cli/kmcp_search.cpp"
-#undef main
+#include <stdarg.h>
+#include <stdlib.h>
 
 #include <random>
+
+#include "../cli/row_format.hpp"
+
+[[noreturn]] void die(const char* fmt, ...) {  // (the header leaves it to the program)
+  va_list ap;
+  va_start(ap, fmt);
+  vfprintf(stderr, fmt, ap);
+  va_end(ap);
+  fputc('\n', stderr);
+  exit(255);
+}
 
 int main() {
   std::mt19937_64 g(7);

@@ -347,7 +347,7 @@ def test_cli_empty_and_ragged_inputs(oracle_lib, tmp_path):
 
 def test_cli_paired_ragged_reads_through_the_parallel_reader(oracle_lib, tmp_path):
     """Paired files whose reads have different lengths: the two parser pools cut their files at different records and the
-    mates are re-cut at read 1's batch boundaries (cli/kmcp_search.cpp read_paired).  Small chunks and batches put the cuts
+    mates are re-cut at read 1's batch boundaries (cli/search_batch.hpp read_paired).  Small chunks and batches put the cuts
     everywhere; the TSV must be the oracle's for the pairs in file order."""
     O = oracle_lib
     genomes = synth.random_genomes(5, 4000, seed=31)
