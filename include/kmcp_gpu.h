@@ -480,6 +480,53 @@ typedef struct kmcpg_sketch_launch kmcpg_sketch_launch; /* defined with kmcpg_sk
 int kmcpg_sort_segments_device(const uint64_t* d_keys, const uint64_t* d_in_off, const int32_t* d_cnt, uint64_t part_stride,
                                uint32_t cnt_stride, int32_t parts, uint32_t n_segs, uint32_t max_waves, int32_t key_bits,
                                uint64_t* d_out, uint64_t out_cap, uint64_t* d_koff, kmcpg_sketch_launch* rec, void* stream);
+typedef struct { int32_t dedup_threshold, min_matched, pre, pre_done, key_shift; } kmcpg_dedup_spec;
+/* debug/tests: the dedup stage of the k-mer step alone, on hash lists laid out in device memory by the caller.  Query r's list is
+ * d_hashes[d_offs[r] (+ d_offs2[r]) ...], d_nk_raw[r] long; max_n >= every d_nk_raw[r]; d_scratch is as large as d_hashes.
+ * Above dedup_threshold (-u) a list is sorted and made unique in place and d_nk_search[r] is its new length, at or below it the list
+ * stays as it is and d_nk_search[r] = d_nk_raw[r]; either is 0 where d_nk_raw[r] < min_matched.  pre: adjacent repeats are dropped
+ * first (window sketches), into d_scratch; pre_done: the caller has done that already, for the queries with a raw count in
+ * (max(dedup_threshold, 512), 65536]: their shortened lists are in d_scratch and the lengths in d_nk_search.  key_shift: leading zero
+ * bits of the largest possible key (0, or clz(maxHash) of a FracMinHash database): no key may have a bit set above it.  Slots must
+ * not overlap.  Enqueues on `stream`; a batch with a query above 65 536 keys synchronises it on the way (the handle's workspace
+ * holds the device-wide sort's tables).  KMCPG_DEDUP_BIG_BUCKET is read at every call. */
+int kmcpg_dedup_device(kmcpg_db* db, uint64_t* d_hashes, uint64_t* d_scratch, const uint64_t* d_offs, const uint64_t* d_offs2,
+                       const int32_t* d_nk_raw, int32_t* d_nk_search, uint32_t n_reads, uint64_t max_n,
+                       const kmcpg_dedup_spec* spec, void* stream);
+/* Which kernels the handle's last dedup stage launched (k1_dedup.hip, sort_huge.hip) — the one inside kmcpg_kmers_device*,
+ * kmcpg_query_device, a submit, kmcpg_plant_reads_device, or kmcpg_dedup_device — one record per launch in launch order, written where
+ * the kernel is launched.  The first record names the branch the stage took: KMCPG_DD_LAUNCH_DEDUP (some query may be above -u; no
+ * kernel of its own; its p0, p1, p2 = how many queries the k_dedup_bucket launches of 2048, 4096 and 16384 elements sent to their bitonic
+ * fallback, read from the device when this is called: synchronise the stage's stream first) or KMCPG_DD_NK_SIMPLE (k_nk_simple alone).  In
+ * every other record p0..p2 are the template parameters of the instantiation (CAP, NB, NT
+ * of k_dedup_bucket; NT, CAP of k_dedup), lo / hi the class of elements to sort the launch takes (lo < m <= hi).  The kernels of the
+ * device-wide sort of one query above 65 536 keys: lo = the query, hi = its raw count, p0 = the bit the radix pass starts at (k_rs_*).
+ * Recorded at profiling level >= 1 only: *n = 0 otherwise.  Cleared by every dedup stage. */
+enum {
+  KMCPG_DD_LAUNCH_DEDUP = 0,
+  KMCPG_DD_NK_SIMPLE,
+  KMCPG_DD_WAVE,          /* k_dedup_wave */
+  KMCPG_DD_ADJ_UNIQUE,    /* k_adj_unique */
+  KMCPG_DD_BUCKET,        /* k_dedup_bucket<p0 = CAP, p1 = NB, p2 = NT> */
+  KMCPG_DD_WG,            /* k_dedup<p0 = NT, p1 = CAP> */
+  KMCPG_DD_RS_HIST,
+  KMCPG_DD_SCAN_TILE_SUMS,
+  KMCPG_DD_SCAN_U32,
+  KMCPG_DD_SCAN_TILES,
+  KMCPG_DD_RS_SCATTER,
+  KMCPG_DD_UQ_COUNT,
+  KMCPG_DD_UQ_SCATTER,
+  KMCPG_DD_SET_NK_HUGE,
+  KMCPG_DD_KERNELS
+};
+typedef struct {
+  int32_t kernel;        /* KMCPG_DD_* */
+  int32_t p0, p1, p2;    /* see above; 0 where the kernel has none */
+  uint32_t grid, block;  /* workgroups, threads per workgroup (0 for KMCPG_DD_LAUNCH_DEDUP and KMCPG_DD_NK_SIMPLE: the branch) */
+  int32_t lo, hi;
+} kmcpg_dedup_launch;
+/* Copies up to `cap` records to out (may be NULL when cap is 0); *n = how many there are. */
+int kmcpg_last_dedup_launches(kmcpg_db* db, kmcpg_dedup_launch* out, uint32_t cap, uint32_t* n);
 /* Batches of this handle so far whose k-mer kernels read 2-bit codes directly (packed whole-genome batches), and packed batches that
  * were expanded to text first. */
 int kmcpg_k1_codes_batches(kmcpg_db* db, uint64_t* direct, uint64_t* expanded);

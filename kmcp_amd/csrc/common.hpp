@@ -130,6 +130,7 @@ struct DedupArgs {
   uint64_t* scratch;
   const int32_t* nk_raw;
   int32_t* nk_search;    // NumKmers after dedup, 0 if the read is not searched
+  uint32_t* fallbacks;   // profiling only (else nullptr): k_dedup_bucket counts the queries that took its bitonic fallback here
 };
 
 constexpr int K2_GATHER_SLOTS = 256;

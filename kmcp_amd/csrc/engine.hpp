@@ -151,6 +151,7 @@ struct kmcpg_db {
     kmcpg::DevBuf<uint32_t> w_long_list, w_long_meta, w_long_counts;  // long-query (split) path
     kmcpg::DevBuf<uint64_t> w_huge_info;                             // whole-genome queries: (read, n, offset)
     kmcpg::DevBuf<uint8_t> w_huge_temp;                              // histogram table of the device-wide radix sort
+    kmcpg::DevBuf<uint32_t> w_dedup_fb;                              // profiling: queries per k_dedup_bucket class that took its bitonic fallback
     kmcpg::DevBuf<uint64_t> w_gathered;                              // profiling level 2: the row loads k2_cobs issued
     // sliding windows, hash-once form: per-position hashes, kept hashes in order, ranks, per-chunk counts and their prefix
     kmcpg::DevBuf<uint64_t> w_win_h, w_win_kept, w_win_cbase;
@@ -160,7 +161,7 @@ struct kmcpg_db {
     hipEvent_t in_ev = nullptr, k1_ev = nullptr;  // KMCPG_K1_STREAM: inputs ready on the caller's stream / k-mers ready on k1_stream
     void release() {
       w_hashes.release(); w_scratch.release(); w_nk_raw.release(); w_nk1.release(); w_seg_cnt.release(); w_long_list.release();
-      w_long_meta.release(); w_long_counts.release(); w_huge_info.release(); w_huge_temp.release(); w_gathered.release();
+      w_long_meta.release(); w_long_counts.release(); w_huge_info.release(); w_huge_temp.release(); w_gathered.release(); w_dedup_fb.release();
       w_win_h.release(); w_win_kept.release(); w_win_cbase.release(); w_win_rank.release(); w_win_cnt.release();
       if (ev) (void)hipEventDestroy(ev);
       if (in_ev) (void)hipEventDestroy(in_ev);
@@ -202,6 +203,10 @@ struct kmcpg_db {
   // forms — the device word that holds what the first kernel left on its list (valid until the slot's next batch)
   std::vector<kmcpg_k1_launch> k1_log;
   const uint32_t* k1_left = nullptr;
+  // what the last dedup stage (K1d: query.cpp run_dedup) launched (profiling >= 1; kmcpg_last_dedup_launches).  A log of its own: the K1
+  // log is asserted record by record
+  std::vector<kmcpg_dedup_launch> dedup_log;
+  const uint32_t* dedup_fb = nullptr;  // ... and the three device words its k_dedup_bucket launches count their fallback queries in
   // K3 (device half of finalize): Header.Sizes of every global column on the device, per-read counters and scan scratch
   uint64_t* d_col_size = nullptr;
   kmcpg::DevBuf<uint32_t> w_fin_cnt;

@@ -342,6 +342,7 @@ __global__ void __launch_bounds__(DB_NT) k_dedup_bucket(const DedupArgs a) {
         if (tid + e * DB_NT < m) o[tid + e * DB_NT] = v[e];
       __syncthreads();
       bitonic_sort(o, m, tid, DB_NT);
+      if (tid == 0 && a.fallbacks) atomicAdd(a.fallbacks, 1u);
     }
     const int total = block_unique<DB_NT>(o, m, g, scan, tid);
     // MinMatched is tested on the raw count (:854), NumKmers is the unique count (:910)
@@ -350,36 +351,55 @@ __global__ void __launch_bounds__(DB_NT) k_dedup_bucket(const DedupArgs a) {
   }
 }
 
-void launch_dedup(DedupArgs a, uint64_t max_n, hipStream_t st) {
+// Every templated kernel is launched by a function template of the same parameters that notes them itself, so a record of the log
+// (kmcpg_last_dedup_launches) cannot name another instantiation than the one that ran.
+template <int CAP, int NB, int DB_NT>
+static void bucket_launch(const DedupArgs& a, unsigned grid, hipStream_t st, DedupLog* log) {
+  hipLaunchKernelGGL((k_dedup_bucket<CAP, NB, DB_NT>), dim3(grid), dim3(DB_NT), 0, st, a);
+  dedup_note(log, KMCPG_DD_BUCKET, CAP, NB, DB_NT, grid, DB_NT, a.lo, a.hi);
+}
+template <int NT, int CAP>
+static void wg_launch(const DedupArgs& a, unsigned grid, hipStream_t st, DedupLog* log) {
+  hipLaunchKernelGGL((k_dedup<NT, CAP>), dim3(grid), dim3(NT), 0, st, a);
+  dedup_note(log, KMCPG_DD_WG, NT, CAP, 0, grid, NT, a.lo, a.hi);
+}
+
+void launch_dedup(DedupArgs a, uint64_t max_n, bool big_bucket, hipStream_t st, DedupLog* log) {
   if (a.n_reads == 0) return;
   // the wave class settles every query at or below the dedup threshold and sorts those of at most 512 k-mers
   hipLaunchKernelGGL(k_dedup_wave, dim3((a.n_reads + 3) / 4), dim3(256), 0, st, a);
+  dedup_note(log, KMCPG_DD_WAVE, 0, 0, 0, (a.n_reads + 3) / 4, 256, a.dedup_threshold, DW_CAP);
   if (max_n <= DW_CAP) return;
   a.n_lo = DW_CAP;
   a.n_hi = max_n > HUGE_MIN ? (int32_t)HUGE_MIN : 0x7fffffff;  // beyond that: device-wide sort (sort_huge.hip)
   const unsigned grid = a.n_reads > (1u << 20) ? (1u << 20) : a.n_reads;  // the workgroup kernels stride over the reads
-  if (a.pre && !a.pre_done) hipLaunchKernelGGL(k_adj_unique, dim3(grid), dim3(ADJ_NT), 0, st, a);
+  if (a.pre && !a.pre_done) {
+    hipLaunchKernelGGL(k_adj_unique, dim3(grid), dim3(ADJ_NT), 0, st, a);
+    dedup_note(log, KMCPG_DD_ADJ_UNIQUE, 0, 0, 0, grid, ADJ_NT, a.n_lo, a.n_hi);
+  }
   // classes by the number m of elements to sort; the grids stride over the reads, sized for what the chip holds at once
+  uint32_t* const fb = a.fallbacks;  // one word per distribution class
   a.lo = 0;
   a.hi = 2048;
-  hipLaunchKernelGGL((k_dedup_bucket<2048, 1024>), dim3(std::min(grid, 256u * 12)), dim3(256), 0, st, a);
+  bucket_launch<2048, 1024, 256>(a, std::min(grid, 256u * 12), st, log);
   if (max_n <= 2048) return;
   a.lo = 2048;  // (a query the class before finished shows its NumKmers <= lo here)
   a.hi = 4096;
-  hipLaunchKernelGGL((k_dedup_bucket<4096, 2048>), dim3(std::min(grid, 256u * 6)), dim3(256), 0, st, a);
+  a.fallbacks = fb ? fb + 1 : nullptr;
+  bucket_launch<4096, 2048, 256>(a, std::min(grid, 256u * 6), st, log);
   if (max_n > 4096) {
     // FracMinHash sketches of whole genomes (4 000 - 16 000 hashes, uniform below maxHash): the distribution pass again, 1024 threads and
-    // 144 KB of LDS per query (one workgroup per CU) instead of the bitonic network's 105 barrier-separated stages
-    static const bool big_bucket = !(getenv("KMCPG_DEDUP_BIG_BUCKET") && atoi(getenv("KMCPG_DEDUP_BIG_BUCKET")) == 0);
+    // 144 KB of LDS per query (one workgroup per CU) instead of the bitonic network's 105 barrier-separated stages (big_bucket)
     a.lo = 4096;
     if (big_bucket) {
       a.hi = 16384;
-      hipLaunchKernelGGL((k_dedup_bucket<16384, 2048, 1024>), dim3(std::min(grid, 256u)), dim3(1024), 0, st, a);
+      a.fallbacks = fb ? fb + 2 : nullptr;
+      bucket_launch<16384, 2048, 1024>(a, std::min(grid, 256u), st, log);
       if (max_n <= 16384) return;
       a.lo = 16384;
     }
     a.hi = 0x7fffffff;
-    hipLaunchKernelGGL((k_dedup<1024, 16384>), dim3(std::min(grid, 1024u)), dim3(1024), 0, st, a);
+    wg_launch<1024, 16384>(a, std::min(grid, 1024u), st, log);
   }
 }
 

@@ -29,7 +29,24 @@ struct K1WinOnce {
 typedef std::vector<kmcpg_k1_launch> K1Log;
 void launch_k1(const K1Args& a, const K1Plan& p, const K1WinOnce& wo, hipStream_t st, K1Log* log);
 void launch_nk_simple(const int32_t* nk_raw, int32_t* nk_search, uint32_t n, int32_t min_matched, hipStream_t st);
-void launch_dedup(DedupArgs a, uint64_t max_n, hipStream_t st);  // queries above HUGE_MIN are left to huge_dedup
+// what the dedup stage notes about every kernel it launches (kmcpg_last_dedup_launches): written at the launch site, the template
+// parameters by a launching function template of the same parameters.  nullptr = no log (and nothing else differs)
+typedef std::vector<kmcpg_dedup_launch> DedupLog;
+inline void dedup_note(DedupLog* log, int kernel, int p0, int p1, int p2, unsigned grid, unsigned block, int32_t lo, int32_t hi) {
+  if (!log) return;
+  kmcpg_dedup_launch r{};
+  r.kernel = kernel;
+  r.p0 = p0;
+  r.p1 = p1;
+  r.p2 = p2;
+  r.grid = grid;
+  r.block = block;
+  r.lo = lo;
+  r.hi = hi;
+  log->push_back(r);
+}
+// big_bucket: KMCPG_DEDUP_BIG_BUCKET (the 16384-element distribution class); queries above HUGE_MIN are left to huge_dedup
+void launch_dedup(DedupArgs a, uint64_t max_n, bool big_bucket, hipStream_t st, DedupLog* log);
 // what the K2 launchers note about every kernel they launch (kmcpg_last_k2_launches): written at the launch site from the template
 // parameters of the kernel launched.  nullptr = no log
 typedef std::vector<kmcpg_k2_launch> K2Log;
@@ -91,6 +108,6 @@ size_t huge_dedup_temp_bytes(uint32_t max_n);
 void launch_gather_huge(const uint32_t* list, uint32_t n, const int32_t* nk_raw, const uint64_t* offs, const uint64_t* offs2, uint64_t* out,
                         hipStream_t st);
 int huge_dedup(uint64_t* keys, uint64_t* tmp, uint32_t n, int* d_num, void* d_temp, size_t temp_bytes, int32_t* nk_search, uint32_t r, int min_matched,
-               hipStream_t st);
+               hipStream_t st, DedupLog* log);
 
 }  // namespace kmcpg

@@ -96,6 +96,77 @@ K2Knobs k2_knobs() {
   return kn;
 }
 
+// K1d, the dedup stage of the k-mer step: every query's list sorted + unique where its raw count is above -u, NumKmers (0 below -m, tested
+// on the raw count) in d_nk_search.  Query r's list is d_hashes[d_offs[r] (+ d_offs2[r]) ...], d_nk_raw[r] long; max_n bounds every
+// raw count; pre / pre_done / key_shift: DedupArgs (common.hpp).  Called by the k-mer stage and by kmcpg_dedup_device.
+struct DedupLists {
+  uint64_t *d_hashes, *d_scratch;
+  const uint64_t *d_offs, *d_offs2;
+  const int32_t* d_nk_raw;
+  int32_t* d_nk_search;
+};
+
+int run_dedup(kmcpg_db* db, kmcpg_db::Workspace& W, const DedupLists& o, uint32_t n_reads, uint64_t max_n, const kmcpg_dedup_spec& s, hipStream_t st) {
+  db->dedup_log.clear();
+  db->dedup_fb = nullptr;
+  DedupLog* const log = db->profiling >= 1 ? &db->dedup_log : nullptr;  // the launch sites write it, kmcpg_last_dedup_launches reads it
+  if (max_n > (uint64_t)s.dedup_threshold) {
+    dedup_note(log, KMCPG_DD_LAUNCH_DEDUP, 0, 0, 0, 0, 0, 0, 0);
+    DedupArgs d{};
+    d.offs = o.d_offs;
+    d.offs2 = o.d_offs2;
+    d.n_reads = n_reads;
+    d.dedup_threshold = s.dedup_threshold;
+    d.min_matched = s.min_matched;
+    d.hashes = o.d_hashes;
+    d.scratch = o.d_scratch;
+    d.nk_raw = o.d_nk_raw;
+    d.nk_search = o.d_nk_search;
+    d.pre = s.pre;
+    d.pre_done = s.pre_done;
+    d.key_shift = s.key_shift;
+    if (log) {  // the witness of the distribution classes: how many queries each sent to its fallback (read by kmcpg_last_dedup_launches)
+      if (W.w_dedup_fb.ensure(4)) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
+      HIPCHK(hipMemsetAsync(W.w_dedup_fb.p, 0, 4 * sizeof(uint32_t), st));
+      d.fallbacks = W.w_dedup_fb.p;
+      db->dedup_fb = W.w_dedup_fb.p;
+    }
+    // KMCPG_DEDUP_BIG_BUCKET is read at every call, as the K1 knobs are: tests flip it inside one process
+    const char* const bb = getenv("KMCPG_DEDUP_BIG_BUCKET");
+    launch_dedup(d, max_n, !(bb && atoi(bb) == 0), st, log);
+    if (max_n > HUGE_MIN) {
+      // whole-genome queries: which ones they are is only known on the device -> one small read-back, then a device-wide
+      // sort + unique per such query
+      const int32_t thr = std::max<int32_t>((int32_t)HUGE_MIN, s.dedup_threshold);
+      uint32_t meta[2] = {0, 0};
+      if (W.w_long_list.ensure(n_reads + 1) || W.w_long_meta.ensure(2)) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
+      HIPCHK(hipMemsetAsync(W.w_long_meta.p, 0, 2 * sizeof(uint32_t), st));
+      launch_list_long(o.d_nk_raw, n_reads, thr, W.w_long_list.p, W.w_long_meta.p, st);
+      HIPCHK(hipMemcpyAsync(meta, W.w_long_meta.p, sizeof meta, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+      if (meta[0]) {
+        const size_t tb = huge_dedup_temp_bytes(meta[1]);
+        if (W.w_huge_info.ensure(3 * (size_t)meta[0] + 1) || W.w_huge_temp.ensure(tb + 64)) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
+        launch_gather_huge(W.w_long_list.p, meta[0], o.d_nk_raw, o.d_offs, o.d_offs2, W.w_huge_info.p, st);
+        std::vector<uint64_t> hinfo(3 * (size_t)meta[0]);
+        HIPCHK(hipMemcpyAsync(hinfo.data(), W.w_huge_info.p, hinfo.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        int* d_num = (int*)W.w_huge_temp.p;  // first 64 bytes: the unique count
+        for (uint32_t i = 0; i < meta[0]; i++) {
+          const uint32_t r = (uint32_t)hinfo[3 * i], n = (uint32_t)hinfo[3 * i + 1];
+          const uint64_t koff = hinfo[3 * i + 2];
+          if (huge_dedup(o.d_hashes + koff, o.d_scratch + koff, n, d_num, W.w_huge_temp.p + 64, tb, o.d_nk_search, r, s.min_matched, st, log) != 0)
+            return kmcpg_fail(KMCPG_EDEVICE, "device-wide sort of a %u-k-mer query failed", n);
+        }
+      }
+    }
+  } else {
+    dedup_note(log, KMCPG_DD_NK_SIMPLE, 0, 0, 0, 0, 0, 0, 0);
+    launch_nk_simple(o.d_nk_raw, o.d_nk_search, n_reads, s.min_matched, st);
+  }
+  return 0;
+}
+
 // K1 (+K1d): hashes of read i end up at d_hashes[offs[i] + offs2[i] ...], NumKmers in d_nk_search
 int run_kmers(kmcpg_db* db, kmcpg_db::Workspace& W, const DeviceBatch& b, const kmcpg_params& p, const KmerOut& o, hipStream_t st, uint64_t* max_n_out) {
   const kmcpg_info& I = db->info;
@@ -183,51 +254,13 @@ int run_kmers(kmcpg_db* db, kmcpg_db::Workspace& W, const DeviceBatch& b, const 
   uint64_t ub = b.max_read_len >= (uint32_t)a.k ? (uint64_t)(b.max_read_len - a.k + 1) : 0;
   if (b.d_seqs2) ub *= 2;
   *max_n_out = ub;
-  if (ub > (uint64_t)p.dedup_threshold) {
-    DedupArgs d{};
-    d.offs = b.d_offs;
-    d.offs2 = b.d_offs2;
-    d.n_reads = b.n_reads;
-    d.dedup_threshold = p.dedup_threshold;
-    d.min_matched = p.min_matched;
-    d.hashes = o.d_hashes;
-    d.scratch = o.d_scratch;
-    d.nk_raw = o.d_nk_raw;
-    d.nk_search = o.d_nk_search;
-    d.pre = a.mode != 0;
-    d.pre_done = plan.adj_done;
-    d.key_shift = (I.scaled && a.max_hash) ? __builtin_clzll(a.max_hash) : 0;
-    launch_dedup(d, ub, st);
-    if (ub > HUGE_MIN) {
-      // whole-genome queries: which ones they are is only known on the device -> one small read-back, then a device-wide
-      // sort + unique per such query
-      const int32_t thr = std::max<int32_t>((int32_t)HUGE_MIN, p.dedup_threshold);
-      uint32_t meta[2] = {0, 0};
-      if (W.w_long_list.ensure(b.n_reads + 1) || W.w_long_meta.ensure(2)) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
-      HIPCHK(hipMemsetAsync(W.w_long_meta.p, 0, 2 * sizeof(uint32_t), st));
-      launch_list_long(o.d_nk_raw, b.n_reads, thr, W.w_long_list.p, W.w_long_meta.p, st);
-      HIPCHK(hipMemcpyAsync(meta, W.w_long_meta.p, sizeof meta, hipMemcpyDeviceToHost, st));
-      HIPCHK(hipStreamSynchronize(st));
-      if (meta[0]) {
-        const size_t tb = huge_dedup_temp_bytes(meta[1]);
-        if (W.w_huge_info.ensure(3 * (size_t)meta[0] + 1) || W.w_huge_temp.ensure(tb + 64)) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
-        launch_gather_huge(W.w_long_list.p, meta[0], o.d_nk_raw, b.d_offs, b.d_offs2, W.w_huge_info.p, st);
-        std::vector<uint64_t> hinfo(3 * (size_t)meta[0]);
-        HIPCHK(hipMemcpyAsync(hinfo.data(), W.w_huge_info.p, hinfo.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        int* d_num = (int*)W.w_huge_temp.p;  // first 64 bytes: the unique count
-        for (uint32_t i = 0; i < meta[0]; i++) {
-          const uint32_t r = (uint32_t)hinfo[3 * i], n = (uint32_t)hinfo[3 * i + 1];
-          const uint64_t koff = hinfo[3 * i + 2];
-          if (huge_dedup(o.d_hashes + koff, o.d_scratch + koff, n, d_num, W.w_huge_temp.p + 64, tb, o.d_nk_search, r, p.min_matched, st) != 0)
-            return kmcpg_fail(KMCPG_EDEVICE, "device-wide sort of a %u-k-mer query failed", n);
-        }
-      }
-    }
-  } else {
-    launch_nk_simple(o.d_nk_raw, o.d_nk_search, b.n_reads, p.min_matched, st);
-  }
-  return 0;
+  kmcpg_dedup_spec ds{};
+  ds.dedup_threshold = p.dedup_threshold;
+  ds.min_matched = p.min_matched;
+  ds.pre = a.mode != 0;
+  ds.pre_done = plan.adj_done;
+  ds.key_shift = (I.scaled && a.max_hash) ? __builtin_clzll(a.max_hash) : 0;
+  return run_dedup(db, W, DedupLists{o.d_hashes, o.d_scratch, b.d_offs, b.d_offs2, o.d_nk_raw, o.d_nk_search}, b.n_reads, ub, ds, st);
 }
 
 // The k-mer workspace exists twice (engine.hpp Workspace): calls are enqueued under db->mu and take the slots in turn; a call waits
@@ -717,6 +750,47 @@ extern "C" int kmcpg_last_k1_launches(kmcpg_db* db, kmcpg_k1_launch* out, uint32
   const size_t m = std::min<size_t>(cap, have);
   if (m) memcpy(out, db->k1_log.data(), m * sizeof(kmcpg_k1_launch));
   *n = (uint32_t)have;
+  return 0;
+}
+
+extern "C" int kmcpg_last_dedup_launches(kmcpg_db* db, kmcpg_dedup_launch* out, uint32_t cap, uint32_t* n) {
+  static_assert(sizeof(kmcpg_dedup_launch) == 32, "eight 4-byte words");
+  if (!db || !n || (cap && !out)) return kmcpg_fail(KMCPG_EINVAL, "null argument");
+  std::lock_guard<std::mutex> g(db->mu);
+  // written while the stage enqueues its kernels: nothing to wait for; without profiling there are none
+  const size_t have = db->profiling >= 1 ? db->dedup_log.size() : 0;
+  const size_t m = std::min<size_t>(cap, have);
+  if (m) memcpy(out, db->dedup_log.data(), m * sizeof(kmcpg_dedup_launch));
+  if (m && db->dedup_fb && out[0].kernel == KMCPG_DD_LAUNCH_DEDUP) {  // the fallback counts, as the device holds them now
+    KMCPG_USE_DEVICE(db);
+    uint32_t fb[3] = {0, 0, 0};
+    HIPCHK(hipMemcpy(fb, db->dedup_fb, sizeof fb, hipMemcpyDeviceToHost));
+    out[0].p0 = (int32_t)fb[0];
+    out[0].p1 = (int32_t)fb[1];
+    out[0].p2 = (int32_t)fb[2];
+  }
+  *n = (uint32_t)have;
+  return 0;
+}
+
+// the dedup stage alone (debug/tests): run_dedup on lists the caller laid out, on the first workspace slot as kmcpg_kmers_device.  Enqueue
+// only, but for the read-backs of the whole-genome path.
+extern "C" int kmcpg_dedup_device(kmcpg_db* db, uint64_t* d_hashes, uint64_t* d_scratch, const uint64_t* d_offs, const uint64_t* d_offs2,
+                                  const int32_t* d_nk_raw, int32_t* d_nk_search, uint32_t n_reads, uint64_t max_n, const kmcpg_dedup_spec* spec,
+                                  void* stream) {
+  if (!db || !d_hashes || !d_scratch || !d_offs || !d_nk_raw || !d_nk_search || !spec) return kmcpg_fail(KMCPG_EINVAL, "null argument");
+  if (spec->key_shift < 0 || spec->key_shift > 63) return kmcpg_fail(KMCPG_EINVAL, "key_shift must be in 0..63");
+  if (max_n > 0x7fffffffull) return kmcpg_fail(KMCPG_EINVAL, "max_n must fit a 32-bit count");
+  KMCPG_NO_FILES_ONLY(db);
+  std::lock_guard<std::mutex> g(db->mu);
+  KMCPG_USE_DEVICE(db);
+  hipStream_t st = (hipStream_t)stream;
+  kmcpg_db::Workspace& W = db->ws[0];
+  if (int rc0 = ws_begin(W, st)) return rc0;
+  WsGuard wsg{W, st, st};
+  if (int rc = run_dedup(db, W, DedupLists{d_hashes, d_scratch, d_offs, d_offs2, d_nk_raw, d_nk_search}, n_reads, max_n, *spec, st)) return rc;
+  if (int rc1 = wsg.finish()) return rc1;
+  HIPCHK(hipGetLastError());
   return 0;
 }
 

@@ -131,11 +131,15 @@ __global__ void __launch_bounds__(256) k_scan_tiles(uint32_t* __restrict__ data,
 }
 
 // data[0..total) -> exclusive prefix sums in place; tile_sum: (total + 4095) / 4096 words of scratch; *total_out = grand total
-static void scan_u32(uint32_t* data, uint32_t total, uint32_t* tile_sum, uint32_t* total_out, hipStream_t st) {
+// (r, n: the query the scan belongs to, for the log)
+static void scan_u32(uint32_t* data, uint32_t total, uint32_t* tile_sum, uint32_t* total_out, hipStream_t st, DedupLog* log, uint32_t r, uint32_t n) {
   const uint32_t tiles = (total + SCAN_TILE - 1) / SCAN_TILE;
   hipLaunchKernelGGL(k_scan_tile_sums, dim3(tiles), dim3(256), 0, st, data, total, tile_sum);
+  dedup_note(log, KMCPG_DD_SCAN_TILE_SUMS, 0, 0, 0, tiles, 256, (int32_t)r, (int32_t)n);
   hipLaunchKernelGGL(k_scan_u32, dim3(1), dim3(1024), 0, st, tile_sum, tiles, total_out);
+  dedup_note(log, KMCPG_DD_SCAN_U32, 0, 0, 0, 1, 1024, (int32_t)r, (int32_t)n);
   hipLaunchKernelGGL(k_scan_tiles, dim3(tiles), dim3(256), 0, st, data, total, tile_sum);
+  dedup_note(log, KMCPG_DD_SCAN_TILES, 0, 0, 0, tiles, 256, (int32_t)r, (int32_t)n);
 }
 
 __global__ void __launch_bounds__(256) k_rs_scatter(const uint64_t* __restrict__ in, uint64_t* __restrict__ out, uint32_t n, int shift,
@@ -228,7 +232,7 @@ void launch_gather_huge(const uint32_t* list, uint32_t n, const int32_t* nk_raw,
 
 // keys[0..n) -> sorted, duplicates removed, back in keys[0..*d_num); tmp: n keys of scratch; d_temp: huge_dedup_temp_bytes(n)
 int huge_dedup(uint64_t* keys, uint64_t* tmp, uint32_t n, int* d_num, void* d_temp, size_t temp_bytes, int32_t* nk_search, uint32_t r, int min_matched,
-               hipStream_t st) {
+               hipStream_t st, DedupLog* log) {
   if (n == 0 || temp_bytes < huge_dedup_temp_bytes(n)) return -1;
   const uint32_t nw = n_waves(n);
   const unsigned blocks = (nw + 3) / 4;
@@ -237,17 +241,23 @@ int huge_dedup(uint64_t* keys, uint64_t* tmp, uint32_t n, int* d_num, void* d_te
   uint32_t* tile_sum = wave_cnt + nw;           // (256 * nw + 4095) / 4096
   uint64_t *src = keys, *dst = tmp;
   for (int pass = 0; pass < 8; pass++) {
-    hipLaunchKernelGGL(k_rs_hist, dim3(blocks), dim3(256), 0, st, src, n, pass * 8, hist, nw);
-    scan_u32(hist, 256u * nw, tile_sum, nullptr, st);
-    hipLaunchKernelGGL(k_rs_scatter, dim3(blocks), dim3(256), 0, st, src, dst, n, pass * 8, hist, nw);
+    const int shift = pass * 8;
+    hipLaunchKernelGGL(k_rs_hist, dim3(blocks), dim3(256), 0, st, src, n, shift, hist, nw);
+    dedup_note(log, KMCPG_DD_RS_HIST, shift, 0, 0, blocks, 256, (int32_t)r, (int32_t)n);
+    scan_u32(hist, 256u * nw, tile_sum, nullptr, st, log, r, n);
+    hipLaunchKernelGGL(k_rs_scatter, dim3(blocks), dim3(256), 0, st, src, dst, n, shift, hist, nw);
+    dedup_note(log, KMCPG_DD_RS_SCATTER, shift, 0, 0, blocks, 256, (int32_t)r, (int32_t)n);
     std::swap(src, dst);
   }
   // eight passes: the sorted keys are back in `keys`
   hipLaunchKernelGGL(k_uq_count, dim3(blocks), dim3(256), 0, st, keys, n, wave_cnt, nw);
-  scan_u32(wave_cnt, nw, tile_sum, (uint32_t*)d_num, st);
+  dedup_note(log, KMCPG_DD_UQ_COUNT, 0, 0, 0, blocks, 256, (int32_t)r, (int32_t)n);
+  scan_u32(wave_cnt, nw, tile_sum, (uint32_t*)d_num, st, log, r, n);
   hipLaunchKernelGGL(k_uq_scatter, dim3(blocks), dim3(256), 0, st, keys, n, wave_cnt, tmp, nw);
+  dedup_note(log, KMCPG_DD_UQ_SCATTER, 0, 0, 0, blocks, 256, (int32_t)r, (int32_t)n);
   if (hipMemcpyAsync(keys, tmp, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToDevice, st) != hipSuccess) return -1;
   hipLaunchKernelGGL(k_set_nk_huge, dim3(1), dim3(1), 0, st, nk_search, r, d_num, (int)n, min_matched);
+  dedup_note(log, KMCPG_DD_SET_NK_HUGE, 0, 0, 0, 1, 1, (int32_t)r, (int32_t)n);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

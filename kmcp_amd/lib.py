@@ -24,7 +24,7 @@ EXPORTS = [
     "kmcpg_density_bins", "kmcpg_block_density", "kmcpg_col_ones", "kmcpg_last_density_launch", "kmcpg_open_files",
     "kmcpg_last_density_ms", "kmcpg_stream_probe",
     "kmcpg_sketcher_open", "kmcpg_sketcher_close", "kmcpg_split_bounds", "kmcpg_sketch_genomes", "kmcpg_sketch_result_free",
-    "kmcpg_last_sketch_launches", "kmcpg_last_sketch_ms", "kmcpg_sort_segments_device",
+    "kmcpg_last_sketch_launches", "kmcpg_last_sketch_ms", "kmcpg_sort_segments_device", "kmcpg_dedup_device", "kmcpg_last_dedup_launches",
     "kmcpg_open_set", "kmcpg_set_info", "kmcpg_last_set_order",
     "kmcpg_sketch_genomes_to", "kmcpg_builder_open", "kmcpg_builder_close", "kmcpg_builder_add_cols", "kmcpg_builder_plan",
     "kmcpg_builder_col_place", "kmcpg_builder_block_info", "kmcpg_builder_begin_round", "kmcpg_builder_scatter_device",
@@ -152,6 +152,22 @@ class K1Launch(C.Structure):
 K1_KERNELS = ("plan", "k1_kmers", "k1_kmers_wg", "k1_kmers_wg_global", "k1_windows_wave", "k1_windows_roll", "k1_seg_roll2", "k1_seg_roll",
               "k1_seg_hash", "k1_seg_pack", "k_mark_exc", "k_unpack2_list", "k1_win_hash", "k1_win_scan", "k1_win_rank", "k1_win_gather")
 K1_FORMS = ("None", "WinOnce", "SegRoll2", "SegRoll", "SegHash", "WindowsRoll", "WindowsWave", "WgGlobal", "Wg", "Short")
+
+
+class DedupSpec(C.Structure):
+    """kmcpg_dedup_spec: the five scalars of the dedup stage (-u, -m, and DedupArgs' pre / pre_done / key_shift)"""
+    _fields_ = [("dedup_threshold", C.c_int32), ("min_matched", C.c_int32), ("pre", C.c_int32), ("pre_done", C.c_int32), ("key_shift", C.c_int32)]
+
+
+class DedupLaunch(C.Structure):
+    """kmcpg_dedup_launch: one kernel launch of a dedup stage, or (first record) the branch the stage took"""
+    _fields_ = [("kernel", C.c_int32), ("p0", C.c_int32), ("p1", C.c_int32), ("p2", C.c_int32), ("grid", C.c_uint32), ("block", C.c_uint32),
+                ("lo", C.c_int32), ("hi", C.c_int32)]
+
+
+# KMCPG_DD_* (include/kmcp_gpu.h)
+DEDUP_KERNELS = ("launch_dedup", "k_nk_simple", "k_dedup_wave", "k_adj_unique", "k_dedup_bucket", "k_dedup", "k_rs_hist", "k_scan_tile_sums",
+                 "k_scan_u32", "k_scan_tiles", "k_rs_scatter", "k_uq_count", "k_uq_scatter", "k_set_nk_huge")
 
 
 class DensitySpec(C.Structure):
@@ -351,6 +367,8 @@ def load():
     L.kmcpg_sketch_result_free.restype = None
     L.kmcpg_last_sketch_launches.argtypes = [vp, C.POINTER(SketchLaunch), C.c_uint32, C.POINTER(C.c_uint32)]
     L.kmcpg_last_sketch_ms.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.kmcpg_dedup_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_uint32, C.c_uint64, C.POINTER(DedupSpec), vp]
+    L.kmcpg_last_dedup_launches.argtypes = [vp, C.POINTER(DedupLaunch), C.c_uint32, C.POINTER(C.c_uint32)]
     L.kmcpg_sort_segments_device.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint32, C.c_int32, C.c_uint32, C.c_uint32, C.c_int32, vp, C.c_uint64, vp,
                                              C.POINTER(SketchLaunch), vp]
     L.kmcpg_open_set.argtypes = [C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(Opts), C.POINTER(vp)]
@@ -1046,6 +1064,22 @@ class Database:
                 return dict(form=K1_FORMS[r.p0], codes_direct=bool(r.p1 & 1), list_fallback=bool(r.p1 & 2), adj_done=bool(r.p1 & 4),
                             left_on_list=None if r.left_on_list == 0xFFFFFFFF else int(r.left_on_list))
         return None
+
+    def dedup_device(self, d_hashes, d_scratch, d_offs, d_offs2, d_nk_raw, d_nk_search, n_reads, max_n, dedup_threshold, min_matched=1, pre=0,
+                     pre_done=0, key_shift=0, stream=None):
+        """kmcpg_dedup_device (debug/tests): the dedup stage of the k-mer step alone on hash lists laid out in device memory (pointers as
+        integers; d_offs2 may be None).  Enqueues; the caller synchronises."""
+        spec = DedupSpec(dedup_threshold, min_matched, pre, pre_done, key_shift)
+        _check(load().kmcpg_dedup_device(self._h, d_hashes, d_scratch, d_offs, d_offs2, d_nk_raw, d_nk_search, n_reads, max_n, C.byref(spec), stream))
+
+    def last_dedup_launches(self):
+        """What the handle's last dedup stage launched, in launch order (profiling level >= 1, [] without): tuples
+        (kernel, p0, p1, p2, grid, block, lo, hi) with kernel in DEDUP_KERNELS; the first names the branch (launch_dedup or k_nk_simple)."""
+        n = C.c_uint32(0)
+        _check(load().kmcpg_last_dedup_launches(self._h, None, 0, C.byref(n)))
+        buf = (DedupLaunch * max(1, n.value))()
+        _check(load().kmcpg_last_dedup_launches(self._h, buf, n.value, C.byref(n)))
+        return [(DEDUP_KERNELS[r.kernel], r.p0, r.p1, r.p2, r.grid, r.block, r.lo, r.hi) for r in buf[:n.value]]
 
     def k1_codes_batches(self):
         """(packed batches whose k-mer kernels read the codes directly, packed batches expanded to text first)"""

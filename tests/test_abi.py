@@ -35,6 +35,11 @@ def test_struct_layouts_match_header(L):
     assert C.sizeof(L.SynthSpec) == 64
     assert C.sizeof(L.K2Launch) == 32
     assert C.sizeof(L.K1Launch) == 32
+    assert C.sizeof(L.DedupSpec) == 20
+    assert C.sizeof(L.DedupLaunch) == 32
+    hdr = open(os.path.join(ROOT, "include", "kmcp_gpu.h")).read()
+    names = re.search(r"KMCPG_DD_LAUNCH_DEDUP = 0,(.*?)KMCPG_DD_KERNELS", hdr, re.S).group(1)
+    assert len(L.DEDUP_KERNELS) == 1 + len(re.findall(r"KMCPG_DD_[A-Z0-9_]+", names))
 
 
 def test_no_cpu_fallback(L, tmp_path):
