@@ -82,6 +82,10 @@ static void warn(const char* fmt, ...) {
 struct Options {
   std::string db_dir, out_file = "-", read1, read2, query_id, sort_by = "qcov", infile_list, log_file;
   std::vector<std::string> name_maps, files;
+  // --specific-level / --taxid-map / --taxdump: only the queries whose matches point at one target (strain, assembly) or one species are
+  // written — what `kmcp-filter -f 1 -t 0 --level L -T ... -X ...` makes of the plain output (K4 of the library, kmcpg_set_specific)
+  std::string specific_level, taxdump;
+  std::vector<std::string> taxid_maps;
   std::vector<std::string> also_dbs;  // --also-db: further databases searched in the same pass, the output merged as kmcp-merge would
   bool gpus_given = false;
   int min_qlen = 30, min_kmers = 10, dedup = 256, top_scores = 0, threads = 0, device = 0, batch = 131072, gpus = 1, gpu_passes = -1;
@@ -119,6 +123,12 @@ static void usage() {
       "                             reads parsed once, and the output is what `kmcp-merge -s <the same -s>` makes of one kmcp-search run per\n"
       "                             database (-d first, then every --also-db in order).  The databases must agree in k, sketching, number of\n"
       "                             hashes and FPR.  Not with -K, --try-se, -S, -n, -g/-G, --sliding-*, --gpus/--gpu-ids, --gpu-passes.\n"
+      "           --specific-level species|strain|assembly [--taxid-map file(s) --taxdump dir]\n"
+      "                             write only the queries whose matches point at one target (strain, assembly) or lie under one species:\n"
+      "                             the output is what `kmcp-filter -f 1 -t 0 --level L -T ... -X ...` makes of this command's output\n"
+      "                             without these flags, followed by the trailer; the decision is made on the GPU.  Targets are the printed\n"
+      "                             ones (after -N / -D); at level species every target of the database needs a TaxId.\n"
+      "                             Not with -K, --try-se, -n, --sliding-*, --gpus/--gpu-ids, --gpu-passes.\n"
       "           --parse-only (read the inputs and print records / bases / checksum per file; no database, no GPU)\n"
       "Long reads and contigs (the reference's advice: split them with `seqkit sliding -s 100 -W 300`, search the pieces):\n"
       "           --sliding-step int --sliding-window int [--sliding-greedy]\n"
@@ -152,7 +162,8 @@ static Options parse_args(int argc, char** argv) {
       {"name-map", 'N', 1}, {"default-name-map", 'D', 0}, {"keep-unmatched", 'K', 0}, {"keep-top-scores", 'n', 1}, {"no-header-row", 'H', 0},
       {"sort-by", 's', 1}, {"do-not-sort", 'S', 0}, {"threads", 'j', 1}, {"quiet", 'q', 0}, {"infile-list", 'i', 1}, {"log", 0, 1},
       {"gpu", 0, 1}, {"gpu-batch", 0, 1}, {"gpus", 0, 1}, {"gpu-ids", 0, 1}, {"gpu-passes", 0, 1}, {"parse-only", 0, 0}, {"help", 'h', 0}, {"version", 'V', 0},
-      {"sliding-step", 0, 1}, {"sliding-window", 0, 1}, {"sliding-greedy", 0, 0}, {"also-db", 0, 1}};
+      {"sliding-step", 0, 1}, {"sliding-window", 0, 1}, {"sliding-greedy", 0, 0}, {"also-db", 0, 1},
+      {"specific-level", 0, 1}, {"taxid-map", 0, 1}, {"taxdump", 0, 1}};
   auto apply = [&](const std::string& name, const std::string& v) {
     if (name == "db-dir") o.db_dir = v;
     else if (name == "out-file") o.out_file = v;
@@ -196,6 +207,17 @@ static Options parse_args(int argc, char** argv) {
     else if (name == "sliding-window") { o.sliding_window = to_i(name, v); o.sliding_window_given = true; }
     else if (name == "sliding-greedy") o.sliding_greedy = true;
     else if (name == "also-db") o.also_dbs.push_back(v);
+    else if (name == "specific-level") { o.specific_level = v; for (char& c : o.specific_level) c = (char)tolower((unsigned char)c); }
+    else if (name == "taxdump") o.taxdump = v;
+    else if (name == "taxid-map") {
+      size_t b = 0;  // StringSlice: comma separated and repeatable
+      while (b <= v.size()) {
+        size_t e = v.find(',', b);
+        if (e == std::string::npos) e = v.size();
+        if (e > b) o.taxid_maps.push_back(v.substr(b, e - b));
+        b = e + 1;
+      }
+    }
     else if (name == "gpus") { o.gpus = to_i(name, v); o.gpus_given = true; }
     else if (name == "gpu-ids") {
       o.gpus_given = true;
@@ -251,6 +273,7 @@ static Options parse_args(int argc, char** argv) {
   return o;
 }
 
+#include "../kmcp_amd/csrc/taxonomy.hpp"
 #include "search_batch.hpp"
 #include "row_format.hpp"
 
@@ -413,6 +436,20 @@ static int run_parse_only(const Options& o) {
 // Dies with the first complaint — the ORDER of the checks is what a user with two mistakes sees (tests/test_sliding_cpu.py pins it) — and
 // returns kmcpg_params::sort_by.
 static int validate_flags(const Options& o, bool sliding) {
+  // --specific-level: what would judge something else than a query's final matches, and the handles that do not hold them in one place,
+  // are refused here, before a file or a GPU is touched (the words of kmcp utils filter where it has them, filter.go:93-114)
+  if (o.specific_level.empty() && (!o.taxid_maps.empty() || !o.taxdump.empty())) die("flags --taxid-map and --taxdump are only used with --specific-level");
+  if (!o.specific_level.empty()) {
+    const bool species = o.specific_level == "species";
+    if (!species && o.specific_level != "strain" && o.specific_level != "assembly")
+      die("invalid value for --specific-level, available values: species, strain/assembly");
+    const char* bad = o.keep_unmatched ? "-K/--keep-unmatched" : o.try_se ? "--try-se" : o.top_scores != 0 ? "-n/--keep-top-scores" : sliding ? "--sliding-step/--sliding-window/--sliding-greedy"
+                      : o.gpus_given ? "--gpus/--gpu-ids" : o.gpu_passes >= 0 ? "--gpu-passes" : nullptr;
+    if (bad) die("flag %s cannot be combined with --specific-level", bad);
+    if (!o.taxid_maps.empty() && o.taxdump.empty()) die("flag --taxdump is needed when --taxid-map given");
+    if (o.taxid_maps.empty() && !o.taxdump.empty()) die("flag --taxid-map is needed when --taxdump given");
+    if ((o.taxid_maps.empty() || o.taxdump.empty()) && species) die("TaxID mapping files (--taxid-map) and taxonomy dump files (--taxdump) are needed for --specific-level species");
+  }
   // sliding windows: seqkit sliding has no meaning for pairs, whole files as queries or one ID for everything
   if (sliding) {
     if (!o.sliding_step_given || !o.sliding_window_given) die("flags --sliding-step and --sliding-window are needed together");
@@ -887,6 +924,32 @@ static std::vector<std::string> resolve_targets(const Options& o, kmcpg_db* db, 
   return target;
 }
 
+// --specific-level: the TaxId maps and the taxdump (filter.go:158-205)
+static void load_taxonomy(const Options& o, std::unique_ptr<kmcpg::Taxonomy>& tax, std::unique_ptr<kmcpg::TaxidMap>& map) {
+  std::string err;
+  map.reset(new kmcpg::TaxidMap());
+  for (const auto& f : o.taxid_maps)
+    if (!map->load(f, &err)) die("%s", err.c_str());
+  if (map->ids.empty()) die("no valid TaxIds found in TaxId mapping file");
+  tax.reset(new kmcpg::Taxonomy());
+  if (!tax->load(o.taxdump, &err)) die("%s", err.c_str());
+  if (!o.quiet) info("  %zu pairs of TaxId mapping values from %zu file(s) loaded, %zu taxonomy nodes", map->ids.size(), o.taxid_maps.size(), tax->nodes.size());
+}
+
+// ... and the two integers per column the library judges with (kmcp_amd/csrc/specific_rule.hpp), from the PRINTED target of every
+// column — after -N / -D, as kmcp-filter sees it in the TSV.  At level species every column's target needs a TaxId: the reference dies
+// when such a target is matched, this command before anything is searched.
+static void set_specific(const Options& o, kmcpg_db* db, const std::vector<std::string>& target, const kmcpg::Taxonomy* tax, const kmcpg::TaxidMap* map) {
+  const bool species = o.specific_level == "species";
+  std::vector<uint32_t> cls, sp;
+  uint64_t unknown = 0;
+  std::string missing;
+  if (!kmcpg::specific_classes(target, species ? map : nullptr, species ? tax : nullptr, &cls, species ? &sp : nullptr, &unknown, &missing))
+    die("unknown taxid for %s, please check taxid mapping file(s)", missing.c_str());
+  if (unknown) warn("%llu TaxId(s) of the database's targets are deleted or not in nodes.dmp: they belong to no species", (unsigned long long)unknown);
+  if (kmcpg_set_specific(db, cls.data(), species ? sp.data() : nullptr, (uint32_t)cls.size()) != 0) die("%s", kmcpg_last_error());
+}
+
 static kmcpg_params make_params(const Options& o, int sort_by, bool paired) {
   kmcpg_params params{};
   params.min_qlen = o.min_qlen;
@@ -1249,6 +1312,9 @@ int main(int argc, char** argv) {
   const std::vector<std::string> files = resolve_inputs(o, &paired);
   const std::vector<std::string> db_dirs = resolve_databases(o);
   const NameMaps name_maps = load_name_maps(o, db_dirs);
+  std::unique_ptr<kmcpg::Taxonomy> taxonomy;
+  std::unique_ptr<kmcpg::TaxidMap> taxid_map;
+  if (!o.taxid_maps.empty()) load_taxonomy(o, taxonomy, taxid_map);
 
   const kmcpg_window_spec wspec{(uint64_t)std::max(0ll, o.sliding_step), (uint64_t)std::max(0ll, o.sliding_window), o.sliding_greedy ? 1 : 0, 0};
   Pipeline p(o, paired, sliding, wspec);
@@ -1286,6 +1352,7 @@ int main(int argc, char** argv) {
   }
   p.target = resolve_targets(o, p.db, dbi, name_maps);
   p.params = make_params(o, sort_by, paired);
+  if (!o.specific_level.empty()) set_specific(o, p.db, p.target, taxonomy.get(), taxid_map.get());
 
   p.t_search = Clock::now();
   Out out(o.out_file);

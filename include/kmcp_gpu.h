@@ -344,6 +344,47 @@ int kmcpg_group_device(kmcpg_db* db, const kmcpg_hit* d_hits, const uint64_t* d_
 int kmcpg_finalize_grouped(const kmcpg_db* db, const kmcpg_pair* pairs, const uint64_t* read_offs, const int32_t* qkmers,
                            const int32_t* qlen, uint32_t n_reads, const kmcpg_params* params, kmcpg_result* out);
 
+/* -- species-specific queries (K4, k4_specific.hip): the decision of `kmcp utils filter` (kmcp/cmd/filter.go:306-391) on K3's output,
+ *    which is in device memory grouped by read.  A query is specific when its matches name ONE target, or — with a species table — when
+ *    all its targets lie under one species (kmcp_amd/csrc/specific_rule.hpp states the rule and why it equals the reference's "LCA at
+ *    or below rank species").  Each global column carries two integers: target_class, equal exactly for the columns of one printed
+ *    target, and species_class, the species TaxId the target lies under, or 0.
+ *    The state lives on the handle, not in kmcpg_params.  kmcpg_set_specific uploads the tables (n_cols must be the handle's column count,
+ *    over all members for a kmcpg_open_set handle); species_class == NULL is strain / assembly level (one target only);
+ *    (NULL, NULL, 0) switches the stage off and frees the tables.  KMCPG_EUNSUPPORTED: paged, multi-device and sharded handles.
+ *    kmcpg_specific_device runs the stage alone, as kmcpg_group_device runs K3: d_pairs / d_read_offs as kmcpg_group_device wrote them
+ *    (d_read_offs[n_reads] pairs, at most pair_cap), d_qkmers as kmcpg_query_device wrote them.  Read i gets d_verdicts[i]:
+ *    KMCPG_SPECIFIC_KEEP (its pairs are copied to d_out_pairs[d_out_offs[i] .. d_out_offs[i + 1]) in their order; also every read without
+ *    pairs), KMCPG_SPECIFIC_DROP (an empty segment) or KMCPG_SPECIFIC_HOST: reads of more than final_n k-mers keep all their pairs and are
+ *    judged by the host after its own -f test (their matches may still fall there; for the library's own batches final_n is the
+ *    largest query whose matches are final on the device).  d_out_pairs needs room for out_cap >= the input's pairs, d_out_offs for
+ *    n_reads + 1 words, d_verdicts for n_reads bytes; the outputs must not overlap the inputs.  Only enqueues on `stream`.
+ *    kmcpg_last_specific: the witness of the handle's last K4 launch (the call waits for the device to go idle): reads WITH pairs that
+ *    were kept, dropped, left to the host; pairs in and out; segments judged by a lane group (up to 64 pairs) and by a whole wave;
+ *    segments that did not lie inside pair_cap (treated as empty; must be 0); and, at profiling level >= 1, the HIP-event time of the
+ *    stage's kernels and one record per kernel launched, in launch order (*n_launches = 0 otherwise, and when no K4 launch has been made since the stage was set). */
+#define KMCPG_SPECIFIC_DROP 0
+#define KMCPG_SPECIFIC_KEEP 1
+#define KMCPG_SPECIFIC_HOST 2
+int kmcpg_set_specific(kmcpg_db* db, const uint32_t* target_class, const uint32_t* species_class, uint32_t n_cols);
+int kmcpg_specific_device(kmcpg_db* db, const kmcpg_pair* d_pairs, const uint64_t* d_read_offs, uint64_t pair_cap, const int32_t* d_qkmers,
+                          uint32_t n_reads, int32_t final_n, kmcpg_pair* d_out_pairs, uint64_t out_cap, uint64_t* d_out_offs,
+                          uint8_t* d_verdicts, void* stream);
+enum { KMCPG_K4_VERDICT = 0, KMCPG_K4_SCAN_TILES, KMCPG_K4_SCAN_SUMS, KMCPG_K4_SCAN_ADD, KMCPG_K4_COMPACT, KMCPG_K4_KERNELS };
+typedef struct {
+  int32_t kernel;       /* KMCPG_K4_* */
+  uint32_t grid, block; /* workgroups, threads per workgroup */
+  int32_t cls;          /* segment classes the launch serves: bit 0 lane groups (up to 64 pairs), bit 1 whole waves; 0 for the scan */
+} kmcpg_k4_launch;
+typedef struct {
+  uint64_t kept, dropped, host;               /* reads with pairs, by verdict */
+  uint64_t pairs_in, pairs_out;
+  uint64_t group_segments, wave_segments;     /* segments judged on the device, by size class */
+  uint64_t bad_segments;
+  double k4_ms;                               /* HIP-event time of the stage's kernels at profiling level >= 1; -1 otherwise */
+} kmcpg_specific_stats;
+int kmcpg_last_specific(kmcpg_db* db, kmcpg_specific_stats* out, kmcpg_k4_launch* launches, uint32_t cap, uint32_t* n_launches);
+
 /* -- benchmarking / full-size parity support (no counterpart in the reference) ------------------ */
 typedef struct {
   int32_t k;            /* 21 */

@@ -204,4 +204,26 @@ struct K3SetArgs {
   uint32_t* stats;
 };
 
+// K4 (k4_specific.hip): K3's segments -> a verdict per read and the surviving segments, compacted.  The rule: specific_rule.hpp.
+constexpr uint8_t K4_DROP = 0, K4_KEEP = 1, K4_HOST = 2;  // = KMCPG_SPECIFIC_* (include/kmcp_gpu.h)
+constexpr int K4_STATS = 6;  // reads kept / dropped / left to the host (of those with pairs), lane-group / wave segments, segments outside the buffer
+struct K4Args {
+  const kmcpg_pair* pairs;       // K3's output
+  const uint64_t* offs;          // [n_reads + 1]
+  uint64_t pair_cap;             // pairs there is room for behind `pairs`: a segment that ends behind it is treated as empty
+  const int32_t* nk;             // NumKmers per read
+  uint32_t n_reads;
+  uint32_t n_cols;
+  int32_t final_n;               // reads of more k-mers are left to the host (their pairs may still fall to -f there)
+  const uint32_t* target_class;  // [n_cols]
+  const uint32_t* species_class; // [n_cols] or nullptr: strain / assembly level
+  uint32_t* cnt;                 // [n_reads + 1] scratch: kept lengths
+  uint64_t* sums;                // scan scratch, one word per 4096 reads
+  uint8_t* verdict;              // out [n_reads]
+  kmcpg_pair* out_pairs;         // out: out_offs[n_reads] pairs
+  uint64_t* out_offs;            // out [n_reads + 1]
+  uint64_t out_cap;
+  uint32_t* stats;               // [K4_STATS], zero on entry
+};
+
 }  // namespace kmcpg

@@ -825,6 +825,13 @@ extern "C" int kmcpg_close(kmcpg_db* db) {
   db->w_fin_sums.release();
   if (db->d_col_size) (void)hipFree(db->d_col_size);
   if (db->d_set_stats) (void)hipFree(db->d_set_stats);
+  db->w_spec_cnt.release();
+  db->w_spec_sums.release();
+  if (db->d_spec_target) (void)hipFree(db->d_spec_target);
+  if (db->d_spec_species) (void)hipFree(db->d_spec_species);
+  if (db->d_spec_stats) (void)hipFree(db->d_spec_stats);
+  for (auto& ev : db->spec_ev)
+    if (ev) (void)hipEventDestroy(ev);
   kmcpg::release_fpr_bounds(db);
   kmcpg::async_release(db);
   if (db->k1_stream) (void)hipStreamDestroy(db->k1_stream);

@@ -219,6 +219,20 @@ struct kmcpg_db {
   uint32_t* d_set_stats = nullptr;  // K3SetArgs::stats of the last K3 launch (kmcpg_last_set_order)
   // what the host half ordered itself since that launch (finalize.cpp): segments, and runs of equal fixed4 with several members in them
   mutable std::atomic<uint64_t> set_host_segments{0}, set_host_mixed{0};
+  // K4, the species-specific stage (kmcpg_set_specific; k4_specific.hip): the two per-column tables on the device and on the host, the
+  // stage's scratch (one user at a time: it shares K3's event chain, fin_ev), its counters (K4_STATS 32-bit words, then at byte 32 the
+  // pairs in and out as two 64-bit words) and what its last launch noted (profiling >= 1)
+  uint32_t* d_spec_target = nullptr;
+  uint32_t* d_spec_species = nullptr;
+  std::vector<uint32_t> h_spec_target, h_spec_species;  // species empty: strain level
+  bool spec_on() const { return !h_spec_target.empty(); }
+  kmcpg::DevBuf<uint32_t> w_spec_cnt;
+  kmcpg::DevBuf<uint64_t> w_spec_sums;
+  uint64_t* d_spec_stats = nullptr;
+  bool spec_ran = false;  // a K4 launch since the stage was set
+  hipEvent_t spec_ev[2] = {};  // around the stage's kernels (profiling >= 1)
+  bool spec_timed = false;
+  std::vector<kmcpg_k4_launch> k4_log;
   std::vector<kmcpg::FprBoundTable> fpr_bounds;  // -f bound tables (query.cpp fpr_bound): one per (max_fpr, size), never rewritten
   hipEvent_t ev[16] = {};   // ring of 4 calls x (start, COBS start, COBS done, k-mers done)
   uint64_t ev_calls = 0;    // profiled calls so far
@@ -238,6 +252,19 @@ inline int set_refuse_params(const kmcpg_db* db, const kmcpg_params& p) {
 inline int set_refuse_entry(const kmcpg_db* db, const char* entry) {
   if (!db->is_set()) return 0;
   return kmcpg_fail(KMCPG_EUNSUPPORTED, "database set (%zu members): %s is not supported on a set handle", db->set_col_base.size(), entry);
+}
+
+// The species-specific stage (kmcpg_set_specific): what would judge something else than a query's final matches is refused while it is on
+inline int specific_refuse_params(const kmcpg_db* db, const kmcpg_params& p) {
+  if (!db->spec_on()) return 0;
+  // (the smaller-k retry of a database with several k-mer sizes looks for reads without matches, and a dropped read is not one)
+  const char* what = p.try_se ? "try_se" : (p.top_n_scores != 0 ? "top_n_scores != 0" : (p.k == 0 && db->ks_desc.size() > 1 ? "a database with several k-mer sizes searched with params->k == 0" : nullptr));
+  if (!what) return 0;
+  return kmcpg_fail(KMCPG_EUNSUPPORTED, "species-specific queries (kmcpg_set_specific): %s is not supported — switch the stage off, or filter the results with kmcp-filter", what);
+}
+inline int specific_refuse_entry(const kmcpg_db* db, const char* entry) {
+  if (!db->spec_on()) return 0;
+  return kmcpg_fail(KMCPG_EUNSUPPORTED, "species-specific queries (kmcpg_set_specific): %s is not supported while the stage is on", entry);
 }
 
 inline kmcpg_params default_params() {
@@ -299,9 +326,13 @@ void result_owner_shape(ResultOwner* o, uint32_t n_reads, bool as_pairs);  // as
 // -f bound of short queries and the order of segments up to K3_WG_CAP hold by construction
 int finalize_grouped_into(const kmcpg_db* db, const kmcpg_pair* pairs, const uint64_t* read_offs, const int32_t* qkmers, const int32_t* qlen, uint32_t n_reads,
                           const kmcpg_params& p, ResultOwner* o, uint32_t read_base, uint64_t match_base, uint64_t* kept_out, bool trusted = false,
-                          int32_t bound_n = 0);
+                          int32_t bound_n = 0, const uint8_t* verdicts = nullptr);
 int finalize_grouped_trusted(const kmcpg_db* db, const kmcpg_pair* pairs, const uint64_t* read_offs, const int32_t* qkmers, const int32_t* qlen, uint32_t n_reads,
-                             const kmcpg_params& p, kmcpg_result* out, int32_t bound_n, bool as_pairs);
+                             const kmcpg_params& p, kmcpg_result* out, int32_t bound_n, bool as_pairs, const uint8_t* verdicts = nullptr);
+// verdicts (K4's bytes for these reads, or nullptr): a read marked SPECIFIC_HOST is judged here by the rule of specific_rule.hpp on what
+// the filters above left of it, with the handle's tables; KEEP and DROP were settled on the device.
+// specific_filter_result: the same rule on every read of a finished result of Match records (the paths without K3)
+void specific_filter_result(const kmcpg_db* db, kmcpg_result* out);
 // bound_n: what the kmcpg_query_device call(s) that produced the list actually did — every query of up to bound_n k-mers had the -f bound
 // applied on the device, whichever kernel form served it (0: no bound table in that call).  query_device_after reports the value of its
 // call; host.cpp keeps it with the batch (Lane::bound_n) and hands it to the finalizer, which takes a compact segment as final only for

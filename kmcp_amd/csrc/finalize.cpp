@@ -29,6 +29,7 @@
 #include "common.hpp"
 #include "dbformat.hpp"
 #include "engine.hpp"
+#include "specific_rule.hpp"
 #include "fpr.hpp"
 #include "kernels.hpp"
 #include "k3_set_order.hpp"
@@ -563,11 +564,15 @@ void result_owner_give(ResultOwner* o) { give_owner(o); }
 // kmcpg_search_batch cuts a large batch into pieces that follow each other through the GPU and lands them here one after the other,
 // so that the copy and the expansion of a piece overlap the kernels of the next (host.cpp).
 int finalize_grouped_into(const kmcpg_db* db, const kmcpg_pair* pairs, const uint64_t* read_offs, const int32_t* qkmers, const int32_t* qlen, uint32_t n_reads,
-                          const kmcpg_params& p, ResultOwner* o, uint32_t read_base, uint64_t match_base, uint64_t* kept_out, bool trusted, int32_t bound_n) {
+                          const kmcpg_params& p, ResultOwner* o, uint32_t read_base, uint64_t match_base, uint64_t* kept_out, bool trusted, int32_t bound_n,
+                          const uint8_t* verdicts) {
   const uint64_t n_pairs = read_offs[n_reads];
   const int final_n = trusted ? std::min<int>(bound_n, kFprBoundAlways) : 0;  // segments of queries up to this size are final as they stand
   if (int rcs = set_refuse_params(db, p)) return rcs;
   const bool is_set = db->is_set();
+  // reads K4 left to the host: judged below, on what this function's own filters leave of them
+  const uint32_t* const spec_t = verdicts && db->spec_on() ? db->h_spec_target.data() : nullptr;
+  const uint32_t* const spec_s = spec_t && !db->h_spec_species.empty() ? db->h_spec_species.data() : nullptr;
   if (n_pairs && !pairs) return kmcpg_fail(KMCPG_EINVAL, "null argument");
   if (read_offs[0] != 0) return kmcpg_fail(KMCPG_EINVAL, "read_offs[0] must be 0");
   if (read_offs[(size_t)n_reads + 1] != 0)
@@ -633,7 +638,8 @@ int finalize_grouped_into(const kmcpg_db* db, const kmcpg_pair* pairs, const uin
       // with these params, K3 applied -T and the order) — the segment is final as it stands
       // (final_n is what the query call reported for THIS batch: the device applied the bound table to every query of up to that many
       // k-mers, plain or chunked form — not what the environment says now)
-      if (as_pairs && !host_sort && n > 0 && n <= final_n && !(p.top_n_scores > 0 && !p.do_not_sort)) {
+      const bool judge_here = spec_t && verdicts[r] == SPECIFIC_HOST;
+      if (as_pairs && !host_sort && n > 0 && n <= final_n && !(p.top_n_scores > 0 && !p.do_not_sort) && !judge_here) {
         memcpy(pbase + pos, pairs + s0, (size_t)m * sizeof(kmcpg_pair));
         per_read[r] = m;
         pos += m;
@@ -741,6 +747,14 @@ int finalize_grouped_into(const kmcpg_db* db, const kmcpg_pair* pairs, const uin
           for (uint64_t i = 0; i < keep; i++) store_record(mbase + first + i, tmp[i]);
         kept = keep;
       }
+      if (judge_here && kept) {
+        SpecificAcc acc;
+        for (uint64_t i = 0; i < kept; i++) {
+          const uint32_t col = as_pairs ? pbase[first + i].col : mbase[first + i].col;
+          acc.add(spec_t[col], spec_s ? spec_s[col] : 0u);
+        }
+        if (!specific_keep(acc, spec_s != nullptr)) kept = 0;
+      }
       per_read[r] = kept;
       pos = first + kept;
     }
@@ -763,6 +777,27 @@ int finalize_grouped_into(const kmcpg_db* db, const kmcpg_pair* pairs, const uin
   else o->matches.resize(match_base + total);
   *kept_out = total;
   return 0;
+}
+
+void specific_filter_result(const kmcpg_db* db, kmcpg_result* out) {
+  ResultOwner* o = (ResultOwner*)out->owner;
+  if (!o || !db->spec_on() || o->pairs_mode) return;
+  const uint32_t* const spec_t = db->h_spec_target.data();
+  const uint32_t* const spec_s = db->h_spec_species.empty() ? nullptr : db->h_spec_species.data();
+  uint64_t to = 0, from = 0;
+  for (uint32_t r = 0; r < out->n_reads; r++) {
+    const uint64_t end = o->offs[(size_t)r + 1];
+    SpecificAcc acc;
+    for (uint64_t i = from; i < end; i++) acc.add(spec_t[o->matches[i].col], spec_s ? spec_s[o->matches[i].col] : 0u);
+    if (specific_keep(acc, spec_s != nullptr)) {
+      if (to != from) memmove(&o->matches[to], &o->matches[from], (end - from) * sizeof(kmcpg_match));
+      to += end - from;
+    }
+    from = end;
+    o->offs[(size_t)r + 1] = to;
+  }
+  o->matches.resize(to);
+  out->matches = o->matches.data();
 }
 
 // counts in o->offs[1 ..] -> offsets, and the result's pointers
@@ -792,11 +827,11 @@ void result_owner_shape(ResultOwner* o, uint32_t n_reads, bool as_pairs) {
 
 namespace kmcpg {
 int finalize_grouped_trusted(const kmcpg_db* db, const kmcpg_pair* pairs, const uint64_t* read_offs, const int32_t* qkmers, const int32_t* qlen, uint32_t n_reads,
-                             const kmcpg_params& p, kmcpg_result* out, int32_t bound_n, bool as_pairs) {
+                             const kmcpg_params& p, kmcpg_result* out, int32_t bound_n, bool as_pairs, const uint8_t* verdicts) {
   std::unique_ptr<ResultOwner, OwnerReturn> o(take_owner());
   result_owner_shape(o.get(), n_reads, as_pairs);
   uint64_t kept = 0;
-  if (int rc = finalize_grouped_into(db, pairs, read_offs, qkmers, qlen, n_reads, p, o.get(), 0, 0, &kept, true, bound_n)) return rc;
+  if (int rc = finalize_grouped_into(db, pairs, read_offs, qkmers, qlen, n_reads, p, o.get(), 0, 0, &kept, true, bound_n, verdicts)) return rc;
   result_publish(o.release(), n_reads, p.k > 0 ? p.k : db->info.k, out);
   return 0;
 }

@@ -79,6 +79,13 @@ struct Lane {
   DevBuf<uint64_t> d_roffs;
   PinBuf<kmcpg_pair> h_pairs;
   PinBuf<uint64_t> h_roffs;
+  // K4 (the species-specific stage, when the handle has it on): the surviving segments go into d_hits — dead once K3 has grouped it, and
+  // half again as large as the pairs need —, their offsets and the verdict bytes beside them; d_final = where the batch's final pairs are
+  DevBuf<uint64_t> d_soffs4;
+  DevBuf<uint8_t> d_verd;
+  PinBuf<uint8_t> h_verd;
+  const kmcpg_pair* d_final = nullptr;
+  bool spec = false;  // this batch went through K4: h_roffs / h_pairs hold ITS output, h_verd the verdicts
   // 2-bit packed upload (stage): the batch's bases as codes + the runs of foreign bytes instead of h_seqs; unpacked on the device
   PinBuf<uint8_t> h_pack;
   PinBuf<ExcRun> h_exc;
@@ -115,6 +122,7 @@ struct Lane {
     h_seqs.release(); h_seqs2.release(); h_offs.release(); h_offs2.release(); h_cnt.release(); h_qk.release(); h_ql.release(); h_hits.release();
     d_seqs.release(); d_seqs2.release(); d_offs.release(); d_offs2.release(); d_cnt.release(); d_qk.release(); d_ql.release(); d_hits.release();
     d_pairs.release(); d_roffs.release(); h_pairs.release(); h_roffs.release();
+    d_soffs4.release(); d_verd.release(); h_verd.release();
     h_pack.release(); h_exc.release(); d_pack.release(); d_exc.release();
     h_wmeta.release(); d_soffs.release(); d_wmeta.release(); d_wsrc.release();
     if (done) (void)hipEventDestroy(done);
@@ -453,7 +461,23 @@ int enqueue_query(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p, c
     rc = kmcpg_group_device(db, L->d_hits.p, L->d_cnt.p, L->d_hits.cap, L->d_qk.p, L->n, &p, L->d_pairs.p, L->d_roffs.p, st);
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(L->h_roffs.p, L->d_roffs.p, ((size_t)L->n + 2) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-  }
+    L->d_final = L->d_pairs.p;
+    L->spec = db->spec_on();
+    if (L->spec) {  // K4 right behind K3: only the surviving reads' matches leave the GPU
+      if (L->d_soffs4.ensure((size_t)L->n + 1) || L->d_verd.ensure(L->n) || L->h_verd.ensure(L->n)) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
+      // a segment is final on the device only where the -f bound was applied there (finalize.cpp: final_n); longer queries keep their
+      // pairs and the host judges what its own -f test leaves.  KMCPG_SPECIFIC_DEVICE=0: every read goes that way
+      const char* e = getenv("KMCPG_SPECIFIC_DEVICE");
+      const int32_t final_n = e && atoi(e) == 0 ? -1 : std::min<int32_t>(L->bound_n, kFprBoundAlways);
+      kmcpg_pair* out = (kmcpg_pair*)L->d_hits.p;  // (12 bytes per hit: room for d_hits.cap pairs and more)
+      rc = kmcpg_specific_device(db, L->d_pairs.p, L->d_roffs.p, L->d_hits.cap, L->d_qk.p, L->n, final_n, out, L->d_hits.cap, L->d_soffs4.p, L->d_verd.p, st);
+      if (rc) return rc;
+      // the new offsets over the old ones (in stream order); the word behind them — K3's count of bad hits — stays
+      HIPCHK(hipMemcpyAsync(L->h_roffs.p, L->d_soffs4.p, ((size_t)L->n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+      HIPCHK(hipMemcpyAsync(L->h_verd.p, L->d_verd.p, (size_t)L->n, hipMemcpyDeviceToHost, st));
+      L->d_final = out;
+    }
+  } else L->spec = false;
   return 0;
 }
 
@@ -570,7 +594,7 @@ int enqueue(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p, bool ge
   if (L->copied && L->grouped && !generous_eager) {
     // a small copy (<= 32 pairs per read), in stream order before the lane's completion event (same-box A/B: on a stream of its own it
     // cost the pipelined submit / wait path 8 %)
-    HIPCHK(hipMemcpyAsync(L->h_pairs.p, L->d_pairs.p, L->copied * sizeof(kmcpg_pair), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(L->h_pairs.p, L->d_final, L->copied * sizeof(kmcpg_pair), hipMemcpyDeviceToHost, st));
   } else if (L->copied && L->grouped) {
     // a piece of a large kmcpg_search_batch call: all of its ordered pairs leave on the copy stream, behind K3 only, while the
     // next piece's kernels run
@@ -579,7 +603,7 @@ int enqueue(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p, bool ge
     if (!L->eager_ev) HIPCHK(hipEventCreateWithFlags(&L->eager_ev, hipEventDisableTiming));
     HIPCHK(hipEventRecord(L->k3_ev, st));
     HIPCHK(hipStreamWaitEvent(A->copy_stream, L->k3_ev, 0));
-    HIPCHK(hipMemcpyAsync(L->h_pairs.p, L->d_pairs.p, L->copied * sizeof(kmcpg_pair), hipMemcpyDeviceToHost, A->copy_stream));
+    HIPCHK(hipMemcpyAsync(L->h_pairs.p, L->d_final, L->copied * sizeof(kmcpg_pair), hipMemcpyDeviceToHost, A->copy_stream));
     HIPCHK(hipEventRecord(L->eager_ev, A->copy_stream));
   } else if (L->copied) HIPCHK(hipMemcpyAsync(L->h_hits.p, L->d_hits.p, L->copied * sizeof(kmcpg_hit), hipMemcpyDeviceToHost, st));
   HIPCHK(hipEventRecord(L->done, st));
@@ -618,7 +642,7 @@ int collect(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p, uint64_
         if (L->h_pairs.ensure(kept)) return kmcpg_fail(KMCPG_ENOMEM, "hipHostMalloc failed");
         L->copied = 0;
       }
-      HIPCHK(hipMemcpyAsync(L->h_pairs.p + L->copied, L->d_pairs.p + L->copied, (kept - L->copied) * sizeof(kmcpg_pair), hipMemcpyDeviceToHost, A->copy_stream));
+      HIPCHK(hipMemcpyAsync(L->h_pairs.p + L->copied, L->d_final + L->copied, (kept - L->copied) * sizeof(kmcpg_pair), hipMemcpyDeviceToHost, A->copy_stream));
       HIPCHK(hipStreamSynchronize(A->copy_stream));
       L->copied = kept;
     }
@@ -806,7 +830,8 @@ int finish_raw(kmcpg_ticket* t, kmcpg_result* out, bool as_pairs) {
     int rc = collect(pt.shard, pt.shard->async, pt.lane, t->p, &n_hits);
     if (rc) return rc;
     if (pt.lane->grouped && t->n)
-      return finalize_grouped_trusted(t->db, pt.lane->h_pairs.p, pt.lane->h_roffs.p, pt.lane->h_qk.p, pt.lane->h_ql.p, t->n, t->p, out, pt.lane->bound_n, as_pairs);
+      return finalize_grouped_trusted(t->db, pt.lane->h_pairs.p, pt.lane->h_roffs.p, pt.lane->h_qk.p, pt.lane->h_ql.p, t->n, t->p, out, pt.lane->bound_n, as_pairs,
+                                      pt.lane->spec ? pt.lane->h_verd.p : nullptr);
     hits = pt.lane->h_hits.p;
   } else if (Exchange* x = t->db->exchange) {
     // the shards' lists meet on the first GPU (RCCL send/recv over xGMI, exactly the bytes each shard produced) and come to
@@ -868,7 +893,10 @@ int finish_raw(kmcpg_ticket* t, kmcpg_result* out, bool as_pairs) {
     n_hits = merged.size();
   }
   Lane* L0 = t->parts[0].lane;  // every shard generates the same k-mers
-  return kmcpg_finalize(t->db, hits, n_hits, t->n ? L0->h_qk.p : nullptr, t->n ? L0->h_ql.p : nullptr, t->n, &t->p, out);
+  int rcf = kmcpg_finalize(t->db, hits, n_hits, t->n ? L0->h_qk.p : nullptr, t->n ? L0->h_ql.p : nullptr, t->n, &t->p, out);
+  // the species-specific stage without K3 in front of it (KMCPG_DEVICE_FINALIZE=0): the rule on the finished records
+  if (rcf == 0 && t->db->spec_on()) specific_filter_result(t->db, out);
+  return rcf;
 }
 
 // a small synchronous search on the retry lane(s): the sub-batches of --try-se and of the smaller k of multi-k databases
@@ -1274,6 +1302,7 @@ int submit_handle(kmcpg_db* db, const kmcpg_params* params, kmcpg_params* p) {
   if (db->shards.empty() && db->opts.device < 0 && db->paged_passes == 0) return kmcpg_fail(KMCPG_EDEVICE, "metadata-only handle (device -1): no GPU work possible");
   *p = params ? *params : default_params();
   if (p->min_matched < 1) return kmcpg_fail(KMCPG_EINVAL, "min_matched must be >= 1");
+  if (int rcs = specific_refuse_params(db, *p)) return rcs;
   return set_refuse_params(db, *p);
 }
 }  // namespace
@@ -1517,6 +1546,7 @@ extern "C" int kmcpg_submit_windows(kmcpg_db* db, const uint8_t* seqs, const uin
   if (!db || !out || (n_reads && (!seqs || !offs))) return kmcpg_fail(KMCPG_EINVAL, "null argument");
   *out = nullptr;
   if (int rc = set_refuse_entry(db, "kmcpg_submit_windows")) return rc;
+  if (int rc = specific_refuse_entry(db, "kmcpg_submit_windows")) return rc;
   kmcpg_params p;
   if (int rc = submit_handle(db, params, &p)) return rc;
   if (int rc = window_args(offs, n_reads, spec)) return rc;
@@ -1528,6 +1558,7 @@ extern "C" int kmcpg_submit_packed_windows(kmcpg_db* db, const uint8_t* codes, c
   if (!db || !out || (n_reads && (!codes || !offs)) || (n_exc && !exc)) return kmcpg_fail(KMCPG_EINVAL, "null argument");
   *out = nullptr;
   if (int rc = set_refuse_entry(db, "kmcpg_submit_packed_windows")) return rc;
+  if (int rc = specific_refuse_entry(db, "kmcpg_submit_packed_windows")) return rc;
   kmcpg_params p;
   if (int rc = submit_handle(db, params, &p)) return rc;
   if (int rc = window_args(offs, n_reads, spec)) return rc;
@@ -1616,7 +1647,8 @@ static int search_batch_pieces(kmcpg_db* db, const HostBatch& b, const kmcpg_par
     const double tb = now();
     uint64_t kept = 0;
     if (r == 0)
-      r = finalize_grouped_into(db, q.lane->h_pairs.p, q.lane->h_roffs.p, q.lane->h_qk.p, q.lane->h_ql.p, q.cnt, p, o, q.lo, match_base, &kept, true, q.lane->bound_n);
+      r = finalize_grouped_into(db, q.lane->h_pairs.p, q.lane->h_roffs.p, q.lane->h_qk.p, q.lane->h_ql.p, q.cnt, p, o, q.lo, match_base, &kept, true, q.lane->bound_n,
+                                q.lane->spec ? q.lane->h_verd.p : nullptr);
     if (timing)
       fprintf(stderr, "piece %u: collect from %.2f to %.2f ms, expanded by %.2f ms (%llu hits, %llu kept)\n", next_finish, ta - t_begin, tb - t_begin, now() - t_begin,
               (unsigned long long)n_hits, (unsigned long long)kept);
@@ -1683,6 +1715,7 @@ static int search_batch_impl(kmcpg_db* db, const HostBatch& in, const kmcpg_para
   if (db && in.n && in.seqs && in.offs && (in.seqs2 == nullptr) == (in.offs2 == nullptr)) {
     const kmcpg_params pp = params ? *params : default_params();
     if (int rcs = set_refuse_params(db, pp)) return rcs;
+    if (int rcs = specific_refuse_params(db, pp)) return rcs;
     if (pp.min_matched >= 1 && in.offs[0] == 0 && (!in.offs2 || in.offs2[0] == 0)) rc = search_batch_pieces(db, in, pp, as_pairs, out, &took);
   }
   if (took && rc == 0) return 0;

@@ -374,16 +374,23 @@ __global__ void __launch_bounds__(256) k3_sort_wg_set(K3Args a, K3SetArgs s) {
 
 uint32_t k3_scan_tiles_for(uint32_t n) { return (n + SCAN_TILE - 1) / SCAN_TILE; }
 
+void launch_k3_scan(const uint32_t* cnt, uint64_t* offs, uint64_t* sums, uint32_t n, hipStream_t st, K4Log* log) {
+  const uint32_t tiles = k3_scan_tiles_for(n);
+  hipLaunchKernelGGL(k3_scan_tiles, dim3(tiles), dim3(SCAN_THREADS), 0, st, cnt, offs, sums, n);
+  k4_note(log, KMCPG_K4_SCAN_TILES, tiles, SCAN_THREADS);
+  hipLaunchKernelGGL(k3_scan_sums, dim3(1), dim3(SCAN_THREADS), 0, st, sums, tiles);
+  k4_note(log, KMCPG_K4_SCAN_SUMS, 1, SCAN_THREADS);
+  hipLaunchKernelGGL(k3_scan_add, dim3(tiles), dim3(SCAN_THREADS), 0, st, offs, sums, n);
+  k4_note(log, KMCPG_K4_SCAN_ADD, tiles, SCAN_THREADS);
+}
+
 // cnt[0 .. n_reads] must be zero on entry (it is again on exit); offs gets n_reads + 1 entries, offs[n_reads] = matches kept
 void launch_k3(const K3Args& a, uint64_t hits_hint, hipStream_t st, const K3SetArgs* set) {
   if (a.n_reads == 0) return;
   const uint64_t work = hits_hint ? hits_hint : a.hit_cap;
   const unsigned gblocks = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((work + 255) / 256, 16384));
   hipLaunchKernelGGL(k3_count, dim3(gblocks), dim3(256), 0, st, a);
-  const uint32_t n = a.n_reads + 1, tiles = k3_scan_tiles_for(n);
-  hipLaunchKernelGGL(k3_scan_tiles, dim3(tiles), dim3(SCAN_THREADS), 0, st, a.cnt, a.offs, a.sums, n);
-  hipLaunchKernelGGL(k3_scan_sums, dim3(1), dim3(SCAN_THREADS), 0, st, a.sums, tiles);
-  hipLaunchKernelGGL(k3_scan_add, dim3(tiles), dim3(SCAN_THREADS), 0, st, a.offs, a.sums, n);
+  launch_k3_scan(a.cnt, a.offs, a.sums, a.n_reads + 1, st);
   hipLaunchKernelGGL(k3_scatter, dim3(gblocks), dim3(256), 0, st, a);
   const unsigned wgb = (unsigned)std::min<uint32_t>((a.n_reads + 255) / 256, 2048);
   if (set) {  // a database set: the same two size classes, each with the second pass

@@ -61,6 +61,21 @@ void launch_threshold_long(const K2Args& a, hipStream_t st);
 // set != nullptr: a database set — the segments are brought into the merge order (k3_set_order.hpp) by the set forms of the sort kernels
 void launch_k3(const K3Args& a, uint64_t hits_hint, hipStream_t st, const K3SetArgs* set = nullptr);
 uint32_t k3_scan_tiles_for(uint32_t n);
+// what K4 notes about every kernel it launches (kmcpg_last_specific); nullptr = no log
+typedef std::vector<kmcpg_k4_launch> K4Log;
+inline void k4_note(K4Log* log, int kernel, unsigned grid, unsigned block) {
+  if (!log) return;
+  kmcpg_k4_launch r{};
+  r.kernel = kernel;
+  r.grid = grid;
+  r.block = block;
+  r.cls = kernel == KMCPG_K4_VERDICT || kernel == KMCPG_K4_COMPACT ? 3 : 0;
+  log->push_back(r);
+}
+// the exclusive scan of K3 by itself: cnt[0 .. n) -> offs[0 .. n); sums: k3_scan_tiles_for(n) + 1 words of scratch
+void launch_k3_scan(const uint32_t* cnt, uint64_t* offs, uint64_t* sums, uint32_t n, hipStream_t st, K4Log* log = nullptr);
+// K4: the species-specific stage behind K3 (k4_specific.hip)
+void launch_k4(const K4Args& a, hipStream_t st, K4Log* log);
 void launch_max_nk(const int32_t* nk, uint32_t n_reads, unsigned long long* out, hipStream_t st);
 void launch_repack(const uint8_t* src, uint8_t* dst, uint64_t n_rows, uint32_t row_bytes, uint32_t stride, uint32_t byte_off, uint32_t ncols, hipStream_t st);
 void launch_gather_rows(const uint8_t* rows, uint32_t stride, uint32_t row_bytes, const uint64_t* idx, uint64_t first, uint64_t n, uint8_t* out,

@@ -26,6 +26,7 @@ EXPORTS = [
     "kmcpg_sketcher_open", "kmcpg_sketcher_close", "kmcpg_split_bounds", "kmcpg_sketch_genomes", "kmcpg_sketch_result_free",
     "kmcpg_last_sketch_launches", "kmcpg_last_sketch_ms", "kmcpg_sort_segments_device", "kmcpg_dedup_device", "kmcpg_last_dedup_launches",
     "kmcpg_open_set", "kmcpg_set_info", "kmcpg_last_set_order",
+    "kmcpg_set_specific", "kmcpg_specific_device", "kmcpg_last_specific",
     "kmcpg_sketch_genomes_to", "kmcpg_builder_open", "kmcpg_builder_close", "kmcpg_builder_add_cols", "kmcpg_builder_plan",
     "kmcpg_builder_col_place", "kmcpg_builder_block_info", "kmcpg_builder_begin_round", "kmcpg_builder_scatter_device",
     "kmcpg_builder_end_round", "kmcpg_builder_finish", "kmcpg_builder_info",
@@ -213,6 +214,22 @@ class SetOrder(C.Structure):
                 ("host_segments", C.c_uint64), ("host_mixed_runs", C.c_uint64)]
 
 
+class K4Launch(C.Structure):
+    """kmcpg_k4_launch: one kernel launch of the species-specific stage"""
+    _fields_ = [("kernel", C.c_int32), ("grid", C.c_uint32), ("block", C.c_uint32), ("cls", C.c_int32)]
+
+
+# KMCPG_K4_* and KMCPG_SPECIFIC_* (include/kmcp_gpu.h)
+K4_VERDICT, K4_SCAN_TILES, K4_SCAN_SUMS, K4_SCAN_ADD, K4_COMPACT = range(5)
+SPECIFIC_DROP, SPECIFIC_KEEP, SPECIFIC_HOST = 0, 1, 2
+
+
+class SpecificStats(C.Structure):
+    """kmcpg_specific_stats: the witness of the last K4 launch"""
+    _fields_ = [("kept", C.c_uint64), ("dropped", C.c_uint64), ("host", C.c_uint64), ("pairs_in", C.c_uint64), ("pairs_out", C.c_uint64),
+                ("group_segments", C.c_uint64), ("wave_segments", C.c_uint64), ("bad_segments", C.c_uint64), ("k4_ms", C.c_double)]
+
+
 class SynthSpec(C.Structure):
     _fields_ = [("k", C.c_int32), ("num_hashes", C.c_int32), ("fpr", C.c_double), ("n_blocks", C.c_uint32),
                 ("cols_per_block", C.c_uint32), ("num_sigs", C.c_uint64), ("kmers_per_col", C.c_uint64), ("seed", C.c_uint64),
@@ -374,6 +391,9 @@ def load():
     L.kmcpg_open_set.argtypes = [C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(Opts), C.POINTER(vp)]
     L.kmcpg_set_info.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32]
     L.kmcpg_last_set_order.argtypes = [vp, C.POINTER(SetOrder)]
+    L.kmcpg_set_specific.argtypes = [vp, vp, vp, C.c_uint32]
+    L.kmcpg_specific_device.argtypes = [vp, vp, vp, C.c_uint64, vp, C.c_uint32, C.c_int32, vp, C.c_uint64, vp, vp, vp]
+    L.kmcpg_last_specific.argtypes = [vp, C.POINTER(SpecificStats), C.POINTER(K4Launch), C.c_uint32, C.POINTER(C.c_uint32)]
     L.kmcpg_sketch_genomes_to.argtypes = [vp, vp, vp, C.c_uint32, C.POINTER(SplitSpec), SKETCH_SINK, vp]
     u32p = C.POINTER(C.c_uint32)
     L.kmcpg_builder_open.argtypes = [C.POINTER(BuilderCfg), C.c_int32, C.POINTER(vp)]
@@ -1115,6 +1135,34 @@ class Database:
         -T, ordered per read; d_read_offs needs n_reads + 2 uint64 words."""
         p = params or default_params()
         _check(load().kmcpg_group_device(self._h, d_hits, d_n_hits, hit_cap, d_qkmers, n_reads, C.byref(p), d_pairs, d_read_offs, stream))
+
+    # ---- species-specific queries: K4 behind K3 ----------------------------------------------------------------
+    def set_specific(self, target_class=None, species_class=None):
+        """kmcpg_set_specific: one uint32 per global column each; species_class None = strain / assembly level; no argument = off."""
+        if target_class is None:
+            assert species_class is None
+            _check(load().kmcpg_set_specific(self._h, None, None, 0))
+            return
+        t = np.ascontiguousarray(target_class, dtype=np.uint32)
+        s = None if species_class is None else np.ascontiguousarray(species_class, dtype=np.uint32)
+        assert s is None or len(s) == len(t)
+        _check(load().kmcpg_set_specific(self._h, t.ctypes.data, None if s is None else s.ctypes.data, len(t)))
+
+    def specific_device(self, d_pairs, d_read_offs, pair_cap, d_qkmers, n_reads, final_n, d_out_pairs, out_cap, d_out_offs, d_verdicts, stream=None):
+        """kmcpg_specific_device on device pointers: K3's pairs and offsets -> a verdict byte per read, the surviving segments and
+        their offsets (n_reads + 1 words)."""
+        _check(load().kmcpg_specific_device(self._h, d_pairs, d_read_offs, pair_cap, d_qkmers, n_reads, final_n, d_out_pairs, out_cap, d_out_offs,
+                                            d_verdicts, stream))
+
+    def last_specific(self):
+        """kmcpg_last_specific: (dict of the counters, [K4Launch] of the last K4 launch — empty below profiling level 1)"""
+        st = SpecificStats()
+        n = C.c_uint32(0)
+        _check(load().kmcpg_last_specific(self._h, C.byref(st), None, 0, C.byref(n)))
+        buf = (K4Launch * max(1, n.value))()
+        _check(load().kmcpg_last_specific(self._h, C.byref(st), buf, n.value, C.byref(n)))
+        self.last_k4_ms = float(st.k4_ms)  # HIP-event time of the stage's kernels (profiling level >= 1), else -1
+        return {f: int(getattr(st, f)) for f, _ in SpecificStats._fields_ if f != "k4_ms"}, [buf[i] for i in range(n.value)]
 
     def finalize_grouped(self, pairs, read_offs, qkmers, qlen, params=None, count_only=False):
         """kmcpg_finalize_grouped: pairs uint32 [m, 2] (or PAIR_DTYPE [m]), read_offs uint64 [n + 2] as group_device wrote them."""
