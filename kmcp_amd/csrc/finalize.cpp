@@ -1,4 +1,5 @@
-// finalize.cpp — the host half: float64 thresholds, FPR, Match values, sorting (util-db-search.go:7471-7489, :260-345).
+// finalize.cpp — the host half: float64 thresholds, FPR, Match values, sorting (util-db-search.go:7471-7489, :260-345).  The rule itself
+// (tests, values, order, --keep-top-scores) is stated in match_rule.hpp; here are the two drivers that apply it to a batch.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #if defined(__SSE2__)
@@ -30,6 +31,7 @@
 #include "dbformat.hpp"
 #include "engine.hpp"
 #include "specific_rule.hpp"
+#include "match_rule.hpp"
 #include "fpr.hpp"
 #include "kernels.hpp"
 #include "k3_set_order.hpp"
@@ -99,35 +101,23 @@ inline void records_visible() {
 
 inline bool is_tombstone(const kmcpg_hit& h) { return h.read == 0xffffffffu && h.col == 0xffffffffu; }
 
-bool match_less(const kmcpg_match& x, const kmcpg_match& y, int sort_by) {
-  double s1, s2, t1, t2;
-  switch (sort_by) {  // Matches.Less / SortByTCov.Less / SortByJacc.Less (:105-145)
-    case 1: s1 = x.tcov; s2 = y.tcov; t1 = x.mkmers; t2 = y.mkmers; break;
-    case 2: s1 = x.jacc; s2 = y.jacc; t1 = x.mkmers; t2 = y.mkmers; break;
-    default: s1 = x.qcov; s2 = y.qcov; t1 = x.tcov; t2 = y.tcov; break;
-  }
-  if (s1 != s2) return s1 > s2;
-  if (t1 != t2) return t1 > t2;
-  return x.col < y.col;  // deterministic tie-break; the reference's order among exact ties is arbitrary
-}
-
-// Database sets (k3_set_order.hpp): records[0 .. m) of one query in the exact order above -> the order kmcp-merge gives the members'
-// separate results; the handle's witness counters are told (kmcpg_last_set_order)
-void set_order_records(const kmcpg_db* db, kmcpg_match* rec, uint64_t m, int sort_by) {
-  if (m == 0) return;
+// Database sets (k3_set_order.hpp): the key of a record in the order kmcp-merge gives the members' separate results ...
+auto set_key_of(const kmcpg_db* db, int sort_by) {
   const uint32_t* base = db->set_col_base.data();
   const uint32_t nm = (uint32_t)db->set_col_base.size();
-  const uint64_t mixed = set_order_host(rec, m, [=](const kmcpg_match& x) {
-    return set_host_key(fixed4(sort_by == 1 ? x.tcov : (sort_by == 2 ? x.jacc : x.qcov)), set_member(x.col, base, nm));
-  });
+  return [=](const kmcpg_match& x) { return set_host_key(fixed4(match_score(x, sort_by)), set_member(x.col, base, nm)); };
+}
+// ... records[0 .. m) of one query in the exact order of match_less -> that order; the handle's witness counters are told
+// (kmcpg_last_set_order)
+void set_order_records(const kmcpg_db* db, kmcpg_match* rec, uint64_t m, int sort_by) {
+  if (m == 0) return;
+  const uint64_t mixed = set_order_host(rec, m, set_key_of(db, sort_by));
   if (m > 1) db->set_host_segments.fetch_add(1);
   if (mixed) db->set_host_mixed.fetch_add(mixed);
 }
 // ... and whether y may follow x in that order (the streaming check of lists that did not come from K3)
 bool set_follows(const kmcpg_db* db, const kmcpg_match& x, const kmcpg_match& y, int sort_by) {
-  const uint32_t* base = db->set_col_base.data();
-  const uint32_t nm = (uint32_t)db->set_col_base.size();
-  auto key = [&](const kmcpg_match& r) { return set_host_key(fixed4(sort_by == 1 ? r.tcov : (sort_by == 2 ? r.jacc : r.qcov)), set_member(r.col, base, nm)); };
+  const auto key = set_key_of(db, sort_by);
   const uint64_t kx = key(x), ky = key(y);
   if (kx != ky) return kx < ky;
   return !match_less(y, x, sort_by);
@@ -401,8 +391,6 @@ extern "C" int kmcpg_finalize(const kmcpg_db* db, const kmcpg_hit* hits, uint64_
       if (s0 == s1) continue;
       const uint64_t first = pos2;
       const int n = qkmers[r];
-      const double nh = (double)n;
-      const double thr = nh * p.min_qcov;
       const std::vector<double>* row = nullptr;
       if (n > 0) {
         if (n != row_n) {
@@ -420,41 +408,18 @@ extern "C" int kmcpg_finalize(const kmcpg_db* db, const kmcpg_hit* hits, uint64_
       kmcpg_match* const dst = in_place ? mbase + first : tmp.data();
       uint64_t cnt2 = 0;
       int c_lo = INT32_MAX, c_hi = 0;
+      const auto fpr_of = [&](int n2, int k) { return QueryFpr::value(*row, n2, k); };  // (asked only for n > 0: row is set)
       for (uint64_t i = s0; i < s1; i++) {
         const kmcpg_hit& h = sorted_p[i];
         const int count = (int)h.count;
-        if (count < p.min_matched) continue;
-        const double c = (double)count;
-        if (!(c > thr)) continue;
-        const kmcpg_db::ColMeta cm = col_meta[h.col];
-        const double nt = (double)cm.size;
-        const double T = c / nt;
-        if (!(T >= p.min_tcov)) continue;
-        const double fpr = row ? QueryFpr::value(*row, n, count) : F->get(n, count);
-        if (!(fpr <= p.max_fpr)) continue;
-        kmcpg_match m{};
-        m.col = h.col;
-        m.target_idx = cm.tidx;
-        m.gsize = cm.gsize;
-        m.mkmers = count;
-        m.fpr = fpr;
-        m.qcov = c / nh;
-        m.tcov = T;
-        m.jacc = c / (nh + nt - c);
-        dst[cnt2++] = m;
+        if (!match_accept(h.col, count, n, col_meta[h.col], p, fpr_of, dst + cnt2)) continue;
+        cnt2++;
         c_lo = std::min(c_lo, count);
         c_hi = std::max(c_hi, count);
       }
       pos2 = first + cnt2;
       if (in_place) {
-        if (cnt2 > 1) {
-          if (!p.do_not_sort) {
-            const int sb = p.sort_by;
-            std::sort(mbase + first, mbase + pos2, [sb](const kmcpg_match& x, const kmcpg_match& y) { return match_less(x, y, sb); });
-          } else {
-            std::sort(mbase + first, mbase + pos2, [](const kmcpg_match& x, const kmcpg_match& y) { return x.col < y.col; });
-          }
-        }
+        sort_matches(mbase + first, mbase + pos2, p);
         if (is_set) set_order_records(db, mbase + first, cnt2, p.sort_by);
       } else if (cnt2 > 0) {
         static thread_local std::vector<uint32_t> order, bucket;
@@ -492,31 +457,11 @@ extern "C" int kmcpg_finalize(const kmcpg_db* db, const kmcpg_hit* hits, uint64_
           }
         } else {
           for (uint64_t i = 0; i < cnt2; i++) ord[i] = (uint32_t)i;
-          if (!p.do_not_sort) {
-            const int sb = p.sort_by;
-            std::sort(ord, ord + cnt2, [t, sb](uint32_t x, uint32_t y) { return match_less(t[x], t[y], sb); });
-          } else {
-            std::sort(ord, ord + cnt2, [t](uint32_t x, uint32_t y) { return t[x].col < t[y].col; });
-          }
+          sort_matches(ord, ord + cnt2, t, p);
         }
         for (uint64_t i = 0; i < cnt2; i++) store_record(mbase + first + i, t[ord[i]]);
       }
-      if (cnt2 > 0 && p.top_n_scores > 0 && !p.do_not_sort) {  // --keep-top-scores (:285-311), including its [:i+1]
-        int nn = 0;
-        uint64_t i = 0;
-        double pscore = 1024;
-        for (; i < cnt2; i++) {
-          const kmcpg_match& m = mbase[first + i];
-          const double score = p.sort_by == 1 ? m.tcov : (p.sort_by == 2 ? m.jacc : m.qcov);
-          if (score < pscore) {
-            nn++;
-            if (nn > p.top_n_scores) break;
-            pscore = score;
-          }
-        }
-        if (i >= cnt2) i = cnt2 - 1;
-        pos2 = first + i + 1;
-      }
+      pos2 = first + top_scores_keep(mbase + first, cnt2, p);
       per_read_p[r] = pos2 - first;
     }
     records_visible();
@@ -569,7 +514,7 @@ int finalize_grouped_into(const kmcpg_db* db, const kmcpg_pair* pairs, const uin
   const uint64_t n_pairs = read_offs[n_reads];
   const int final_n = trusted ? std::min<int>(bound_n, kFprBoundAlways) : 0;  // segments of queries up to this size are final as they stand
   if (int rcs = set_refuse_params(db, p)) return rcs;
-  const bool is_set = db->is_set();
+  const bool is_set = db->is_set(), top = top_scores_on(p);
   // reads K4 left to the host: judged below, on what this function's own filters leave of them
   const uint32_t* const spec_t = verdicts && db->spec_on() ? db->h_spec_target.data() : nullptr;
   const uint32_t* const spec_s = spec_t && !db->h_spec_species.empty() ? db->h_spec_species.data() : nullptr;
@@ -614,6 +559,7 @@ int finalize_grouped_into(const kmcpg_db* db, const kmcpg_pair* pairs, const uin
     const uint64_t pos0 = pos;
     int row_n = -1;
     FprRow row;  // held while in use: the cache may drop its own reference at any time
+    const auto fpr_of = [&](int n2, int k) { return QueryFpr::value(*row, n2, k); };  // (asked only for n > 0: row is set)
     static thread_local std::vector<kmcpg_match> tmp;
     for (uint32_t r = lo; r < hi; r++) {
       const uint64_t s0 = read_offs[r], s1 = read_offs[r + 1];
@@ -624,7 +570,6 @@ int finalize_grouped_into(const kmcpg_db* db, const kmcpg_pair* pairs, const uin
         return;
       }
       const int n = qkmers[r];
-      const double nh = (double)n, thr = nh * p.min_qcov;
       if (n > 0 && n != row_n) {
         row_n = n;
         row = F->ensure_row(n);
@@ -639,7 +584,7 @@ int finalize_grouped_into(const kmcpg_db* db, const kmcpg_pair* pairs, const uin
       // (final_n is what the query call reported for THIS batch: the device applied the bound table to every query of up to that many
       // k-mers, plain or chunked form — not what the environment says now)
       const bool judge_here = spec_t && verdicts[r] == SPECIFIC_HOST;
-      if (as_pairs && !host_sort && n > 0 && n <= final_n && !(p.top_n_scores > 0 && !p.do_not_sort) && !judge_here) {
+      if (as_pairs && !host_sort && n > 0 && n <= final_n && !top && !judge_here) {
         memcpy(pbase + pos, pairs + s0, (size_t)m * sizeof(kmcpg_pair));
         per_read[r] = m;
         pos += m;
@@ -654,10 +599,7 @@ int finalize_grouped_into(const kmcpg_db* db, const kmcpg_pair* pairs, const uin
       if (via_tmp && tmp.size() < m) tmp.resize(m);
       const uint64_t first = pos;
       uint64_t kept = 0;
-      // --keep-top-scores while the records go out: matches arrive by descending score
-      int nn = 0;
-      double pscore = 1024;
-      const bool top = p.top_n_scores > 0 && !p.do_not_sort;
+      TopScores top_scores(p.top_n_scores);  // --keep-top-scores while the records go out: matches arrive by descending score
       bool cut = false, out_of_order = false;
       kmcpg_match prev{};
       bool have_prev = false;
@@ -668,25 +610,8 @@ int finalize_grouped_into(const kmcpg_db* db, const kmcpg_pair* pairs, const uin
           bad.store(1);
           return;
         }
-        const int count = (int)h.count;
-        if (count < p.min_matched) continue;
-        const double c = (double)count;
-        if (!(c > thr)) continue;
-        const kmcpg_db::ColMeta cm = col_meta[h.col];
-        const double nt = (double)cm.size;
-        const double T = c / nt;
-        if (!(T >= p.min_tcov)) continue;
-        const double fpr = n > 0 ? QueryFpr::value(*row, n, count) : 1.0;
-        if (!(fpr <= p.max_fpr)) continue;
-        kmcpg_match mm{};
-        mm.col = h.col;
-        mm.target_idx = cm.tidx;
-        mm.gsize = cm.gsize;
-        mm.mkmers = count;
-        mm.fpr = fpr;
-        mm.qcov = c / nh;
-        mm.tcov = T;
-        mm.jacc = c / (nh + nt - c);
+        kmcpg_match mm;
+        if (!match_accept(h.col, (int)h.count, n, col_meta[h.col], p, fpr_of, &mm)) continue;
         if (host_sort) {
           tmp[kept++] = mm;
           continue;
@@ -706,47 +631,21 @@ int finalize_grouped_into(const kmcpg_db* db, const kmcpg_pair* pairs, const uin
         else if (as_pairs) pbase[first + kept] = h;
         else mbase[first + kept] = mm;
         kept++;
-        if (top) {
-          const double score = p.sort_by == 1 ? mm.tcov : (p.sort_by == 2 ? mm.jacc : mm.qcov);
-          if (score < pscore) {
-            nn++;
-            if (nn > p.top_n_scores) cut = true;  // the reference keeps this one too (its [:i+1], :305-309) and stops
-            pscore = score;
-          }
-        }
+        if (top && top_scores.last_kept(match_score(mm, p.sort_by))) cut = true;
       }
       if (out_of_order) {
         host_sort = true;
         goto again;
       }
-      if (via_tmp && !host_sort)
-        for (uint64_t i = 0; i < kept; i++) store_record(mbase + first + i, tmp[i]);
       if (host_sort && kept) {
-        const int sb = p.sort_by;
-        if (!p.do_not_sort) std::sort(tmp.begin(), tmp.begin() + (ptrdiff_t)kept, [sb](const kmcpg_match& x, const kmcpg_match& y) { return match_less(x, y, sb); });
-        else std::sort(tmp.begin(), tmp.begin() + (ptrdiff_t)kept, [](const kmcpg_match& x, const kmcpg_match& y) { return x.col < y.col; });
-        if (is_set) set_order_records(db, tmp.data(), kept, sb);
-        uint64_t keep = kept;
-        if (top) {
-          uint64_t i = 0;
-          for (; i < kept; i++) {
-            const kmcpg_match& x = tmp[i];
-            const double score = p.sort_by == 1 ? x.tcov : (p.sort_by == 2 ? x.jacc : x.qcov);
-            if (score < pscore) {
-              nn++;
-              if (nn > p.top_n_scores) break;
-              pscore = score;
-            }
-          }
-          if (i >= kept) i = kept - 1;
-          keep = i + 1;
-        }
-        if (as_pairs)
-          for (uint64_t i = 0; i < keep; i++) pbase[first + i] = kmcpg_pair{tmp[i].col, (uint32_t)tmp[i].mkmers};
-        else
-          for (uint64_t i = 0; i < keep; i++) store_record(mbase + first + i, tmp[i]);
-        kept = keep;
+        sort_matches(tmp.data(), tmp.data() + kept, p);
+        if (is_set) set_order_records(db, tmp.data(), kept, p.sort_by);
+        kept = top_scores_keep(tmp.data(), kept, p);
       }
+      if (via_tmp && as_pairs)  // (only a host-sorted segment: pairs that stream go straight to their place)
+        for (uint64_t i = 0; i < kept; i++) pbase[first + i] = kmcpg_pair{tmp[i].col, (uint32_t)tmp[i].mkmers};
+      else if (via_tmp)
+        for (uint64_t i = 0; i < kept; i++) store_record(mbase + first + i, tmp[i]);
       if (judge_here && kept) {
         SpecificAcc acc;
         for (uint64_t i = 0; i < kept; i++) {
@@ -870,7 +769,6 @@ extern "C" int kmcpg_expand_pairs(const kmcpg_db* db, int32_t qkmers, const kmcp
   if (n == 0) return 0;
   const size_t n_cols = db->col_meta.size();
   const kmcpg_db::ColMeta* const col_meta = db->col_meta.data();
-  const double nh = (double)qkmers;
   // the row of this NumKmers stays with the thread: consecutive queries of a batch mostly share it (and a formatter thread asks for
   // a few hundred thousand queries per second)
   // (keyed on the FPR table's process-unique id, not on the handle's address: a database opened later may live where a closed one did)
@@ -882,21 +780,12 @@ extern "C" int kmcpg_expand_pairs(const kmcpg_db* db, int32_t qkmers, const kmcp
     row_of = db->fpr->id();
     row_n = qkmers;
   }
+  const auto fpr_of = [r = row.get()](int n2, int k) { return QueryFpr::value(*r, n2, k); };
   for (uint64_t i = 0; i < n; i++) {
     const kmcpg_pair h = pairs[i];
     if (h.col >= n_cols) return kmcpg_fail(KMCPG_EINVAL, "pair %llu names column %u of %zu", (unsigned long long)i, h.col, n_cols);
-    const kmcpg_db::ColMeta cm = col_meta[h.col];
-    const double c = (double)h.count, nt = (double)cm.size;
-    kmcpg_match mm{};
-    mm.col = h.col;
-    mm.target_idx = cm.tidx;
-    mm.gsize = cm.gsize;
-    mm.mkmers = (int32_t)h.count;
-    mm.fpr = qkmers > 0 ? QueryFpr::value(*row, qkmers, (int)h.count) : 1.0;
-    mm.qcov = c / nh;
-    mm.tcov = c / nt;
-    mm.jacc = c / (nh + nt - c);
-    out[i] = mm;
+    const int count = (int)h.count;
+    out[i] = match_values(h.col, count, qkmers, col_meta[h.col], match_fpr(qkmers, count, fpr_of));
   }
   return 0;
 }
