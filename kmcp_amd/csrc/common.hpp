@@ -32,7 +32,7 @@ struct Seg {
   uint32_t ncols;
 };
 
-// 2-bit packed upload of a batch's bases (host.cpp stage / support.hip k_unpack2): a run of bytes that are not A/C/G/T/U in either
+// 2-bit packed upload of a batch's bases (lane.cpp stage / support.hip k_unpack2): a run of bytes that are not A/C/G/T/U in either
 // case, restored after unpacking (positions in bases from the start of the batch)
 struct ExcRun {
   uint64_t pos;

@@ -1,5 +1,5 @@
 // engine.hpp — internals shared by the host-side translation units of libkmcpgpu.so (engine.cpp: residency;
-// query.cpp: GPU half; finalize.cpp: host half; host.cpp: the whole pipeline on host buffers).  Not part of the ABI.
+// query.cpp: GPU half; finalize.cpp: host half; lane.cpp + host*.cpp: the whole pipeline on host buffers, lane.hpp).  Not part of the ABI.
 #pragma once
 #include <stdlib.h>
 #include <hip/hip_runtime.h>
@@ -110,7 +110,7 @@ void release_fpr_bounds(kmcpg_db* db);  // query.cpp
 int plan_passes(kmcpg_db* front, int device, uint64_t* largest_shard_bytes, uint64_t* free_bytes, uint64_t* reserve_bytes = nullptr);  // engine.cpp
 int open_like(const kmcpg_db* src, const kmcpg_opts* opts, kmcpg_db** out);                           // engine.cpp
 struct AsyncState;
-void async_release(kmcpg_db* db);  // host.cpp
+void async_release(kmcpg_db* db);  // lane.cpp
 int async_in_flight(kmcpg_db* db);
 }  // namespace kmcpg
 
@@ -139,7 +139,7 @@ struct kmcpg_db {
   std::mutex mu;      // serialises the enqueueing of GPU-half calls (kernels of one workspace slot follow each other in stream order;
                       // calls on different streams are ordered by the slot's event)
   std::vector<int> ks_desc;    // k-mer sizes of the database, descending (`ks` of __db.yml; one entry for most databases)
-  kmcpg::AsyncState* async = nullptr;  // lanes + stream of kmcpg_submit/kmcpg_wait (host.cpp), created on first use
+  kmcpg::AsyncState* async = nullptr;  // lanes + streams of kmcpg_submit/kmcpg_wait (lane.hpp), created on first use
   // The k-mer workspace of kmcpg_query_device, twice: consecutive calls take the slots in turn, so that the k-mer kernels of batch
   // i + 1 (VALU-bound) may run on another stream BESIDE the COBS kernels of batch i (memory-bound) instead of behind them.  A call
   // waits for the previous user of ITS slot only (Workspace::ev); the COBS kernels themselves stay one batch at a time (cobs_ev:
@@ -335,11 +335,11 @@ int finalize_grouped_trusted(const kmcpg_db* db, const kmcpg_pair* pairs, const 
 void specific_filter_result(const kmcpg_db* db, kmcpg_result* out);
 // bound_n: what the kmcpg_query_device call(s) that produced the list actually did — every query of up to bound_n k-mers had the -f bound
 // applied on the device, whichever kernel form served it (0: no bound table in that call).  query_device_after reports the value of its
-// call; host.cpp keeps it with the batch (Lane::bound_n) and hands it to the finalizer, which takes a compact segment as final only for
+// call; lane.cpp keeps it with the batch (Lane::bound_n) and hands it to the finalizer, which takes a compact segment as final only for
 // n <= bound_n — it does not look at the environment again.
 inline int k1_mode(const kmcpg_info& I) { return I.syncmer ? 2 : (I.minimizer ? 1 : 0); }  // syncmer > minimizer > plain (util-db-search.go:1052-1058)
 // batches of whole genomes (segment forms of the k-mer stage, k1_plan.hpp): the ones whose k-mer kernels run beside the previous batch's COBS
-// kernel by default — second workspace slot (query.cpp pick_slot) and second kernel stream (host.cpp enqueue; bench.py does the same with its streams)
+// kernel by default — second workspace slot (query.cpp pick_slot) and second kernel stream (lane.cpp enqueue; bench.py does the same with its streams)
 bool whole_genome_batch(const kmcpg_db* db, uint32_t max_read_len, bool paired);  // k1_whole_genomes (k1_plan.hpp) of the handle's database
 // KMCPG_FPR_BOUND (default on): K2 leaves out counts that cannot pass -f for queries of up to 512 (1024) k-mers (query.cpp fpr_bound)
 inline bool fpr_bound_enabled() {

@@ -1787,7 +1787,7 @@ __global__ void k_nk_simple(const int32_t* nk_raw, int32_t* nk_search, uint32_t 
 
 
 
-// ---- sliding windows of plain / FracMinHash k-mers, hash-once form (host.cpp kmcpg_submit_windows; launch_k1, form WinOnce) ----------------------
+// ---- sliding windows of plain / FracMinHash k-mers, hash-once form (host_windows.cpp kmcpg_submit_windows; launch_k1, form WinOnce) ----------------------
 // A k-mer's hash and whether it is kept do not depend on the window it is read in, so the staged slices of reads are hashed once — one wave per
 // K1_WIN_CHUNK positions of a slice, the wave form of the short-read kernel (hash_mate_scan) over the chunk's bases — and every window's list is
 // the run of its slice's kept hashes between the ranks of its first and one-past-last k-mer position.  Positions are numbered by the slice's

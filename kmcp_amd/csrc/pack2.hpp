@@ -1,4 +1,4 @@
-// pack2.hpp — the host side of the 2-bit packed upload (host.cpp stage): a batch's bases as 2-bit codes, 4 per byte, plus the runs
+// pack2.hpp — the host side of the 2-bit packed upload (lane.cpp stage): a batch's bases as 2-bit codes, 4 per byte, plus the runs
 // of bytes that are not A/C/G/T/U in either case.  Why this is exact: the k-mer kernels see a base only through the ntHash seed
 // tables (nthash.hpp seed_of: 'a' == 'A', ..., 'U' == 'u' == 'T'; complement = tab[b & 7], the same entry for all spellings of a
 // base), so the canonical spelling the device unpacks — A, C, G, T — hashes exactly like the byte the caller wrote; every other

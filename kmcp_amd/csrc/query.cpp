@@ -174,8 +174,8 @@ int run_kmers(kmcpg_db* db, kmcpg_db::Workspace& W, const DeviceBatch& b, const 
   db->k1_left = nullptr;
   K1Log* const k1_log = db->profiling >= 1 ? &db->k1_log : nullptr;  // launch_k1 writes it, kmcpg_last_k1_launches reads it
   if (!I.canonical) return kmcpg_fail(KMCPG_EUNSUPPORTED, "non-canonical index");
-  const PackedSrc& src = b.packed;   // a batch that came as 2-bit codes (host.cpp: kmcpg_submit_packed, or text stage() packed)
-  const WindowSrc& win = b.windows;  // sliding windows (host.cpp kmcpg_submit_windows): every kernel reads a window's bases in place through its view
+  const PackedSrc& src = b.packed;   // a batch that came as 2-bit codes (host_pack.cpp kmcpg_submit_packed, or text that lane.cpp stage() packed)
+  const WindowSrc& win = b.windows;  // sliding windows (host_windows.cpp kmcpg_submit_windows): every kernel reads a window's bases in place through its view
   // which kernels, on what side buffer (k1_plan.hpp)
   K1Shape s;
   s.mode = k1_mode(I);
@@ -466,7 +466,7 @@ extern "C" int kmcpg_query_device(kmcpg_db* db, const uint8_t* d_seqs, const uin
 }
 
 // kmcpg_query_device with a prologue that runs once the handle's enqueue lock is held, i.e. right in front of this batch's first kernel.
-// host.cpp puts "wait for this batch's upload" (+ the expansion of packed input) there: enqueued BEFORE taking the lock, that wait could
+// lane.cpp enqueue puts "wait for this batch's upload" (+ the expansion of packed input) there: enqueued BEFORE taking the lock, that wait could
 // land in the kernel stream between the k-mer kernels and the COBS kernel of the batch before — a call that reads a word back in the middle
 // (whole-genome queries) releases nothing until it returns — and the earlier batch's COBS kernel then sat behind the later batch's 4.5-ms
 // upload (profiles/r06_h2h.txt: 2.4 ms of idle GPU per batch of 256 assemblies).

@@ -225,7 +225,7 @@ void launch_build_scatter(uint8_t* sigs, uint64_t num_sigs, uint64_t mh, uint32_
 namespace kmcpg {
 
 // ------------------------------------------------------------------------------------------------
-// 2-bit packed upload (host.cpp stage): a batch of long queries is 4x smaller over PCIe as 2-bit codes; K1 reads ASCII as before.
+// 2-bit packed upload (lane.cpp stage): a batch of long queries is 4x smaller over PCIe as 2-bit codes; K1 reads ASCII as before.
 // One thread expands 4 packed bytes to 16 bases (one 16-byte store); the few bytes that are not A/C/G/T/U come as runs and are
 // written over the result (the hash of such a byte depends on its exact value: seed 0, complement by its low 3 bits — nthash.hpp).
 // ------------------------------------------------------------------------------------------------

@@ -10,34 +10,21 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels.hpp"
+#include "window_plan.hpp"
 
 namespace kmcpg {
 
-// one thread per window w of the batch: its slice q (the last q with wpre[q] <= w), then
-//   src[w]  = soffs[q] + j S                          (first base in the staged text)
-//   offs[w] = vpre[q] + bases of windows 0 .. j-1 of the slice   (the window numbering the rest of the pipeline sees)
-// and the last thread writes offs[n_win] = vpre[n_slices].
+// one thread per window w of the batch: src[w] and offs[w] as window_desc_at (window_plan.hpp) states them, and the last thread writes
+// offs[n_win] = vpre[n_slices].
 __global__ void __launch_bounds__(256) k_window_desc(const uint64_t* __restrict__ soffs, const uint64_t* __restrict__ wpre,
                                                      const uint64_t* __restrict__ vpre, uint32_t n_slices, uint64_t n_win, uint64_t S,
                                                      uint64_t W, uint64_t* __restrict__ src, uint64_t* __restrict__ offs) {
   const uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (w >= n_win) return;
-  uint32_t lo = 0, hi = n_slices;
-  while (hi - lo > 1) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (wpre[mid] <= w) lo = mid;
-    else hi = mid;
-  }
-  const uint32_t q = lo;
-  const uint64_t j = w - wpre[q];
-  const uint64_t ls = soffs[q + 1] - soffs[q];
-  const uint64_t full = ls >= W ? (ls - W) / S + 1 : 0;  // windows of the slice that hold W bases
-  uint64_t v;
-  if (j <= full) v = j * W;
-  else  // full windows, then the truncated ones (greedy): sum over t in [full, j) of ls - t S
-    v = full * W + (j - full) * ls - S * ((j * (j - 1)) / 2 - (full * (full - (full > 0 ? 1 : 0))) / 2);
-  src[w] = soffs[q] + j * S;
-  offs[w] = vpre[q] + v;
+  uint64_t s, o;
+  window_desc_at(soffs, wpre, vpre, n_slices, w, S, W, &s, &o);
+  src[w] = s;
+  offs[w] = o;
   if (w == n_win - 1) offs[n_win] = vpre[n_slices];
 }
 

@@ -1,4 +1,4 @@
-"""The 2-bit packed upload (host.cpp stage -> pack2.hpp -> k_unpack2): batches of long queries travel as 2-bit codes plus runs of
+"""The 2-bit packed upload (lane.cpp stage -> pack2.hpp -> k_unpack2): batches of long queries travel as 2-bit codes plus runs of
 foreign bytes and must give exactly what the ASCII upload gives — and what the oracle gives — whatever the bytes are: lower case,
 U, N runs, IUPAC codes (their seed is 0 but their complement entry depends on the byte's low three bits), bytes >= 128.
 KMCPG_PACK is read once per process, so every variant runs in a process of its own."""

@@ -1,4 +1,4 @@
-"""The 2-bit packed upload of long-query batches (kmcp_amd/csrc/pack2.hpp, used by host.cpp's staging): pack + the device's unpack
+"""The 2-bit packed upload of long-query batches (kmcp_amd/csrc/pack2.hpp, used by lane.cpp's staging): pack + the device's unpack
 (restated on the host) reproduce the caller's bases up to spelling (a -> A, u/U -> T: the same ntHash seeds) and every other byte
 verbatim; scalar, AVX2 and multi-threaded paths; garbage input is refused rather than sent as millions of exception runs
 (tests/pack2_check.cpp).  The reference has no counterpart: it hashes the bytes it read (util-db-search.go:1037-1107)."""
