@@ -468,6 +468,21 @@ int kmcpg_kmers_device_packed(kmcpg_db* db, const uint8_t* d_codes, const kmcpg_
 int kmcpg_kmers_device_paired(kmcpg_db* db, const uint8_t* d_seqs, const uint64_t* d_offs, const uint8_t* d_seqs2, const uint64_t* d_offs2,
                               uint32_t n_reads, uint64_t total_bases, uint32_t max_read_len, const kmcpg_params* params,
                               uint64_t* d_hashes, uint64_t hashes_cap, int32_t* d_nk, int32_t* d_nk1, void* stream);
+/* The same on a staged piece of sliding windows (kmcpg_submit_windows), exactly as a lane runs it: the piece's descriptors are built on
+ * the device (k_window_desc, windows.hip), then the k-mer stage (K1 + dedup) reads every window's bases in place.  All pointers are
+ * device memory.  d_text = the staged slices of reads one behind the other, staged_bases of them, with 16 readable bytes behind the last
+ * (the lane's own allowance); d_soffs / d_wpre / d_vpre / d_cpre = n_slices + 1 words each: the prefix sums over the slices of their
+ * bases, their windows, their windows' bases and their chunks of 1 024 k-mer positions (0 for a slice shorter than k), as
+ * kmcp_amd/csrc/window_plan.hpp stage_windows states them; n_chunks = d_cpre[n_slices], n_windows = d_wpre[n_slices], window_bases =
+ * d_vpre[n_slices], max_window_len = the longest window.  Out: d_koff[n_windows + 1] = where each window's list starts in d_hashes
+ * (the prefix of window bases; hashes_cap >= window_bases), d_src[n_windows] = each window's first base in d_text, d_nk[n_windows] =
+ * NumKmers, d_qlen[n_windows] = the window's length.  No window (n_windows = 0): nothing is launched.  KMCPG_EINVAL: a null pointer, a
+ * spec that kmcpg_submit_windows refuses, sizes that contradict each other, hashes_cap too small.  Debug/tests. */
+int kmcpg_kmers_device_windows(kmcpg_db* db, const uint8_t* d_text, const uint64_t* d_soffs, const uint64_t* d_wpre, const uint64_t* d_vpre,
+                               const uint64_t* d_cpre, uint32_t n_slices, uint64_t staged_bases, uint64_t n_chunks, uint32_t n_windows,
+                               uint64_t window_bases, uint32_t max_window_len, const kmcpg_window_spec* spec, const kmcpg_params* params,
+                               uint64_t* d_hashes, uint64_t hashes_cap, uint64_t* d_koff, uint64_t* d_src, int32_t* d_nk, int32_t* d_qlen,
+                               void* stream);
 /* Which k-mer kernels (K1, k1_kmers.hip) the handle's last k-mer stage launched — kmcpg_kmers_device*, kmcpg_query_device, a submit,
  * kmcpg_plant_reads_device — one record per launch in launch order, written where the kernel is launched from the template
  * parameters of the function that launches it.  The first record (kernel KMCPG_K1_PLAN) is the plan of the call (k1_plan.hpp): p0 =

@@ -361,6 +361,38 @@ struct DeviceBatch {
   PackedSrc packed;
   WindowSrc windows;
 };
+// A staged piece of sliding windows on the device (host_windows.cpp submit_window_piece_device stages it, window_plan.hpp states what it
+// holds): the slices' text, their four prefix arrays, and where the descriptors k_window_desc builds from them go.  Stated once for the
+// lanes (lane.cpp) and for the entry that runs the k-mer stage alone on such a piece (kmcpg_kmers_device_windows).
+struct WindowPiece {
+  const uint8_t* d_text = nullptr;  // the slices one behind the other, 16 readable bytes behind the last
+  const uint64_t *d_soffs = nullptr, *d_wpre = nullptr, *d_vpre = nullptr, *d_cpre = nullptr;  // [ns + 1] each
+  uint32_t ns = 0;
+  uint64_t sb = 0, n_chunks = 0;  // staged bases (= soffs[ns]); chunks of K1_WIN_CHUNK k-mer positions (= cpre[ns])
+  uint32_t n_win = 0, wmax = 0;   // windows; the longest of them
+  uint64_t bases = 0;             // of all windows (= vpre[ns])
+  uint64_t step = 0, window = 0;
+  uint64_t* d_src = nullptr;   // [n_win]      k_window_desc: each window's first base in the staged text
+  uint64_t* d_offs = nullptr;  // [n_win + 1]  ... and its place in the window numbering
+  // the batch the GPU half is told about: the windows are its queries, read in place through d_src
+  DeviceBatch batch() const {
+    DeviceBatch b{d_text, d_offs, nullptr, nullptr, n_win, bases, wmax};
+    b.windows.src = d_src;
+    b.windows.soffs = d_soffs;
+    b.windows.wpre = d_wpre;
+    b.windows.cpre = d_cpre;
+    b.windows.ns = ns;
+    b.windows.n_chunks = n_chunks;
+    b.windows.sb = sb;
+    b.windows.step = step;
+    b.windows.window = window;
+    return b;
+  }
+};
+// query.cpp: the piece's descriptors, enqueued in front of the k-mer kernels that read through them
+int describe_windows(const WindowPiece& w, hipStream_t st);
+// host_windows.cpp: the window specs every sliding-window entry refuses (KMCPG_EINVAL)
+int window_spec_args(const kmcpg_window_spec* spec);
 // where the outputs of kmcpg_query_device go
 struct QueryOut {
   kmcpg_hit* d_hits;

@@ -135,12 +135,8 @@ int submit_windows_impl(kmcpg_db* db, const uint8_t* seqs, const uint64_t* offs,
 }
 
 int window_args(const uint64_t* offs, uint32_t n_reads, const kmcpg_window_spec* spec) {
-  if (!spec || (n_reads && !offs)) return kmcpg_fail(KMCPG_EINVAL, "null argument");
-  if (spec->step < 1 || spec->window < 1) return kmcpg_fail(KMCPG_EINVAL, "window spec: step and window must be >= 1");
-  // (a negative value from a caller that meant a signed type arrives as ~2^64: refused, as is anything in the fields the ABI keeps for later)
-  if (spec->step > (1ull << 40) || spec->window > (1ull << 40)) return kmcpg_fail(KMCPG_EINVAL, "window spec: step and window must be <= 2^40");
-  if (spec->greedy != 0 && spec->greedy != 1) return kmcpg_fail(KMCPG_EINVAL, "window spec: greedy must be 0 or 1");
-  if (spec->reserved != 0) return kmcpg_fail(KMCPG_EINVAL, "window spec: reserved must be 0 (zero the struct)");
+  if (n_reads && !offs) return kmcpg_fail(KMCPG_EINVAL, "null argument");
+  if (int rc = window_spec_args(spec)) return rc;
   uint64_t maxlen = 0;
   if (int rc = check_offsets(HostBatch{nullptr, offs, nullptr, nullptr, n_reads}, &maxlen)) return rc;
   if (maxlen > 0x7fffffffULL) return kmcpg_fail(KMCPG_EUNSUPPORTED, "query longer than 2^31-1 bases");
@@ -148,6 +144,16 @@ int window_args(const uint64_t* offs, uint32_t n_reads, const kmcpg_window_spec*
 }
 
 }  // namespace
+
+int window_spec_args(const kmcpg_window_spec* spec) {
+  if (!spec) return kmcpg_fail(KMCPG_EINVAL, "null argument");
+  if (spec->step < 1 || spec->window < 1) return kmcpg_fail(KMCPG_EINVAL, "window spec: step and window must be >= 1");
+  // (a negative value from a caller that meant a signed type arrives as ~2^64: refused, as is anything in the fields the ABI keeps for later)
+  if (spec->step > (1ull << 40) || spec->window > (1ull << 40)) return kmcpg_fail(KMCPG_EINVAL, "window spec: step and window must be <= 2^40");
+  if (spec->greedy != 0 && spec->greedy != 1) return kmcpg_fail(KMCPG_EINVAL, "window spec: greedy must be 0 or 1");
+  if (spec->reserved != 0) return kmcpg_fail(KMCPG_EINVAL, "window spec: reserved must be 0 (zero the struct)");
+  return 0;
+}
 
 // a ticket of several window pieces: their results one behind the other, as one result (the record or the compact form the caller asked for)
 int wait_pieces(kmcpg_ticket* t, kmcpg_result* out, bool as_pairs) {

@@ -248,29 +248,40 @@ int stage_packed(Lane* L, const PackedIn& in, const HostBatch& b) {
 
 namespace {
 
+// the staged piece of windows a lane holds (L->win)
+WindowPiece lane_windows(const Lane* L) {
+  const size_t ns1 = (size_t)L->up_reads + 1;  // d_wmeta: wpre, vpre, cpre one behind the other
+  WindowPiece w;
+  w.d_text = L->d_seqs.p;
+  w.d_soffs = L->d_soffs.p;
+  w.d_wpre = L->d_wmeta.p;
+  w.d_vpre = L->d_wmeta.p + ns1;
+  w.d_cpre = L->d_wmeta.p + 2 * ns1;
+  w.ns = (uint32_t)L->up_reads;
+  w.sb = L->up_bases;
+  w.n_chunks = L->wchunks;
+  w.n_win = L->n;
+  w.wmax = L->maxlen;
+  w.bases = L->tb1;
+  w.step = L->wstep;
+  w.window = L->wwin;
+  w.d_src = L->d_wsrc.p;
+  w.d_offs = L->d_offs.p;
+  return w;
+}
+
 // the lane's batch as the GPU half is told about it.  Packed input: the k-mer stage (query.cpp run_kmers) reads the codes where it can — whole
 // genomes — and expands them to the text in d_seqs where it cannot.  Sliding windows: the k-mer kernels read each window's bases in place
 // (d_wsrc, built by the prologue of the first attempt)
 DeviceBatch lane_batch(const Lane* L) {
-  DeviceBatch b{L->d_seqs.p, L->d_offs.p, L->paired ? L->d_seqs2.p : nullptr, L->paired ? L->d_offs2.p : nullptr, L->n, L->tb1 + L->tb2, L->maxlen};
+  DeviceBatch b = L->win ? lane_windows(L).batch()
+                         : DeviceBatch{L->d_seqs.p, L->d_offs.p, L->paired ? L->d_seqs2.p : nullptr, L->paired ? L->d_offs2.p : nullptr, L->n, L->tb1 + L->tb2, L->maxlen};
   if (L->packed) {
     b.packed.codes = L->d_pack.p;
     b.packed.exc = L->n_exc ? L->d_exc.p : nullptr;
     b.packed.n_exc = L->n_exc;
     b.packed.text = L->d_seqs.p;
     b.packed.n_bases = L->up_bases;
-  }
-  if (L->win) {
-    WindowSrc& w = b.windows;
-    w.src = L->d_wsrc.p;
-    w.soffs = L->d_soffs.p;
-    w.wpre = L->d_wmeta.p;
-    w.cpre = L->d_wmeta.p + 2 * ((size_t)L->up_reads + 1);
-    w.ns = L->up_reads;
-    w.n_chunks = L->wchunks;
-    w.sb = L->up_bases;
-    w.step = L->wstep;
-    w.window = L->wwin;
   }
   return b;
 }
@@ -374,10 +385,7 @@ int enqueue(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p, bool ge
   // lock: see query.cpp query_device_after
   const std::function<int()> after_upload = [&]() -> int {
     HIPCHK(hipStreamWaitEvent(st, L->uploaded, 0));
-    if (L->win) {  // the windows' descriptors, in front of the k-mer kernels that read through them
-      launch_window_desc(L->d_soffs.p, L->d_wmeta.p, L->d_wmeta.p + up_reads + 1, (uint32_t)up_reads, n, L->wstep, L->wwin, L->d_wsrc.p, L->d_offs.p, st);
-      HIPCHK(hipGetLastError());
-    }
+    if (L->win) return describe_windows(lane_windows(L), st);  // the windows' descriptors, in front of the k-mer kernels that read through them
     return 0;
   };
   int rc = enqueue_query(db, A, L, p, &after_upload);

@@ -390,8 +390,9 @@ int fpr_bound(kmcpg_db* db, double max_fpr, uint64_t max_kmers, hipStream_t st, 
 
 // the k-mer stage alone on a batch of reads, text or packed (b.d_seqs = the text, or where its expansion goes), single or paired (d_koff is
 // for single reads: a pair's hashes start at offs[i] + offs2[i]); d_nk1 (optional): the first mate's raw count
+// d_qlen (optional): every query's length as the kernels wrote it; prologue (optional): run under the handle's lock, in front of the first kernel
 static int kmers_device(kmcpg_db* db, const DeviceBatch& b, const kmcpg_params* params, uint64_t* d_hashes, uint64_t hashes_cap, uint64_t* d_koff, int32_t* d_nk,
-                        int32_t* d_nk1, void* stream) {
+                        int32_t* d_nk1, void* stream, int32_t* d_qlen = nullptr, const std::function<int()>* prologue = nullptr) {
   if (!db || !b.d_seqs || !b.d_offs || !d_hashes || !d_nk) return kmcpg_fail(KMCPG_EINVAL, "null argument");
   if ((b.d_seqs2 == nullptr) != (b.d_offs2 == nullptr)) return kmcpg_fail(KMCPG_EINVAL, "seqs2 and offs2 must be given together");
   if (hashes_cap < b.total_bases) return kmcpg_fail(KMCPG_EINVAL, "hashes_cap must be >= total_bases");
@@ -400,14 +401,16 @@ static int kmers_device(kmcpg_db* db, const DeviceBatch& b, const kmcpg_params* 
   KMCPG_USE_DEVICE(db);
   const kmcpg_params p = params ? *params : default_params();
   hipStream_t st = (hipStream_t)stream;
+  if (prologue)
+    if (int rcp = (*prologue)()) return rcp;
   kmcpg_db::Workspace& W = db->ws[0];
   if (int rc0 = ws_begin(W, st)) return rc0;
   WsGuard wsg{W, st, st};
   if (W.w_scratch.ensure(2 * b.total_bases + 2) || W.w_nk_raw.ensure(b.n_reads + 1) || W.w_nk1.ensure(b.n_reads + 1)) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
   DevBuf<int32_t> ql;
-  if (ql.ensure(b.n_reads + 1)) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
+  if (!d_qlen && ql.ensure(b.n_reads + 1)) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
   uint64_t maxn = 0;
-  int rc = run_kmers(db, W, b, p, KmerOut{d_hashes, W.w_scratch.p, b.total_bases + 1, W.w_nk_raw.p, W.w_nk1.p, d_nk, ql.p}, st, &maxn);
+  int rc = run_kmers(db, W, b, p, KmerOut{d_hashes, W.w_scratch.p, b.total_bases + 1, W.w_nk_raw.p, W.w_nk1.p, d_nk, d_qlen ? d_qlen : ql.p}, st, &maxn);
   if (rc == 0 && d_koff) HIPCHK(hipMemcpyAsync(d_koff, b.d_offs, (size_t)b.n_reads * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
   if (rc == 0 && d_nk1 && b.n_reads) HIPCHK(hipMemcpyAsync(d_nk1, W.w_nk1.p, (size_t)b.n_reads * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
   hipError_t e = hipStreamSynchronize(st);
@@ -448,6 +451,46 @@ extern "C" int kmcpg_kmers_device_packed(kmcpg_db* db, const uint8_t* d_codes, c
   b.packed.text = d_text;
   b.packed.n_bases = total_bases;
   return kmers_device(db, b, params, d_hashes, hashes_cap, d_koff, d_nk, nullptr, stream);
+}
+
+int kmcpg::describe_windows(const WindowPiece& w, hipStream_t st) {
+  launch_window_desc(w.d_soffs, w.d_wpre, w.d_vpre, w.ns, w.n_win, w.step, w.window, w.d_src, w.d_offs, st);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// the k-mer stage alone on a staged piece of sliding windows: what a lane does for such a batch (lane.cpp: describe_windows in the prologue,
+// WindowPiece::batch as the batch), then kmers_device
+extern "C" int kmcpg_kmers_device_windows(kmcpg_db* db, const uint8_t* d_text, const uint64_t* d_soffs, const uint64_t* d_wpre, const uint64_t* d_vpre,
+                                          const uint64_t* d_cpre, uint32_t n_slices, uint64_t staged_bases, uint64_t n_chunks, uint32_t n_windows,
+                                          uint64_t window_bases, uint32_t max_window_len, const kmcpg_window_spec* spec, const kmcpg_params* params,
+                                          uint64_t* d_hashes, uint64_t hashes_cap, uint64_t* d_koff, uint64_t* d_src, int32_t* d_nk, int32_t* d_qlen,
+                                          void* stream) {
+  if (!d_text || !d_soffs || !d_wpre || !d_vpre || !d_cpre || !d_koff || !d_src || !d_qlen) return kmcpg_fail(KMCPG_EINVAL, "null argument");
+  if (int rc = window_spec_args(spec)) return rc;
+  if (n_windows && !n_slices) return kmcpg_fail(KMCPG_EINVAL, "windows without a staged slice");
+  // every window lies inside one slice, so the windows hold at most n_windows times the longest one; all k-mer positions lie in the staged text
+  if ((uint64_t)max_window_len > spec->window || window_bases > (uint64_t)n_windows * max_window_len || n_chunks > staged_bases)
+    return kmcpg_fail(KMCPG_EINVAL, "the piece's sizes contradict each other");
+  WindowPiece w;
+  w.d_text = d_text;
+  w.d_soffs = d_soffs;
+  w.d_wpre = d_wpre;
+  w.d_vpre = d_vpre;
+  w.d_cpre = d_cpre;
+  w.ns = n_slices;
+  w.sb = staged_bases;
+  w.n_chunks = n_chunks;
+  w.n_win = n_windows;
+  w.wmax = max_window_len;
+  w.bases = window_bases;
+  w.step = spec->step;
+  w.window = spec->window;
+  w.d_src = d_src;
+  w.d_offs = d_koff;
+  hipStream_t st = (hipStream_t)stream;
+  const std::function<int()> desc = [&]() -> int { return describe_windows(w, st); };
+  return kmers_device(db, w.batch(), params, d_hashes, hashes_cap, nullptr, d_nk, nullptr, stream, d_qlen, &desc);
 }
 
 extern "C" int kmcpg_k1_codes_batches(kmcpg_db* db, uint64_t* direct, uint64_t* expanded) {

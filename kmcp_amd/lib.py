@@ -20,7 +20,7 @@ EXPORTS = [
     "kmcpg_search_batch_pairs", "kmcpg_wait_pairs", "kmcpg_result_pairs_free", "kmcpg_expand_pairs", "kmcpg_save_db",
     "kmcpg_pack2", "kmcpg_unpack2", "kmcpg_submit_packed", "kmcpg_host_alloc", "kmcpg_host_free",
     "kmcpg_kmers_device_packed", "kmcpg_k1_codes_batches", "kmcpg_kmers_device_paired", "kmcpg_last_k1_launches",
-    "kmcpg_submit_windows", "kmcpg_submit_packed_windows", "kmcpg_window_count", "kmcpg_window_locate",
+    "kmcpg_submit_windows", "kmcpg_submit_packed_windows", "kmcpg_window_count", "kmcpg_window_locate", "kmcpg_kmers_device_windows",
     "kmcpg_density_bins", "kmcpg_block_density", "kmcpg_col_ones", "kmcpg_last_density_launch", "kmcpg_open_files",
     "kmcpg_last_density_ms", "kmcpg_stream_probe",
     "kmcpg_sketcher_open", "kmcpg_sketcher_close", "kmcpg_split_bounds", "kmcpg_sketch_genomes", "kmcpg_sketch_result_free",
@@ -357,7 +357,9 @@ def load():
     L.kmcpg_last_k2_launches.argtypes = [vp, C.POINTER(K2Launch), C.c_uint32, C.POINTER(C.c_uint32)]
     L.kmcpg_last_k1_launches.argtypes = [vp, C.POINTER(K1Launch), C.c_uint32, C.POINTER(C.c_uint32)]
     L.kmcpg_kmers_device_paired.argtypes = [vp, vp, vp, vp, vp, C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(Params), vp, C.c_uint64, vp, vp, vp]
-    L.kmcpg_timing_at.argtypes = [vp, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.kmcpg_kmers_device_windows.argtypes = [vp, vp, vp, vp, vp, vp, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32,
+                                             C.POINTER(WindowSpec), C.POINTER(Params), vp, C.c_uint64, vp, vp, vp, vp, vp]
+    L.kmcpg_timing_at.argtypes =[vp, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.kmcpg_build_db.argtypes = [C.c_char_p, C.POINTER(BuildCfg), C.POINTER(BuildCol), C.c_uint32, C.c_int32]
     L.kmcpg_save_db.argtypes = [vp, C.c_char_p]
     L.kmcpg_pack2.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp, C.c_uint64, u64p]
@@ -1061,6 +1063,16 @@ class Database:
         p = params or default_params()
         _check(load().kmcpg_kmers_device_paired(self._h, d_seqs, d_offs, d_seqs2, d_offs2, n_reads, total_bases, max_read_len, C.byref(p),
                                                 d_hashes, hashes_cap, d_nk, d_nk1, stream))
+
+    def kmers_device_windows(self, d_text, d_soffs, d_wpre, d_vpre, d_cpre, n_slices, staged_bases, n_chunks, n_windows, window_bases,
+                             max_window_len, spec, d_hashes, hashes_cap, d_koff, d_src, d_nk, d_qlen, params=None, stream=None):
+        """the k-mer stage alone on a staged piece of sliding windows, as a lane runs it (kmcpg_kmers_device_windows): the slices' text
+        (16 readable bytes behind it) and their four prefix arrays [n_slices + 1] in, per window the hashes at d_hashes[d_koff[w] ...],
+        d_src, d_nk and d_qlen out; spec = WindowSpec(step, window, greedy, 0)"""
+        p = params or default_params()
+        _check(load().kmcpg_kmers_device_windows(self._h, d_text, d_soffs, d_wpre, d_vpre, d_cpre, n_slices, staged_bases, n_chunks, n_windows,
+                                                 window_bases, max_window_len, C.byref(spec), C.byref(p), d_hashes, hashes_cap, d_koff, d_src,
+                                                 d_nk, d_qlen, stream))
 
     def _k1_records(self):
         n = C.c_uint32(0)

@@ -391,7 +391,8 @@ _wave()
 _roll()
 _seg()
 
-# the hash-once window kernels (witness only here; their results are checked in tests/test_gpu_sliding.py)
+# the hash-once window kernels (witness only here; every hash, count and qlen they leave is compared with the oracle in
+# tests/test_gpu_win_forms.py, case plan tests/win_cases.py)
 WIN_ONCE = [("k1_win_hash", 0, 0), ("k1_win_scan", 0, 0), ("k1_win_rank", 0, 0), ("k1_win_gather", 0, 0)]
 
 # every instantiation launch_k1 can be asked for: (kernel, p0, p1)

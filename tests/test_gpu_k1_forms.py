@@ -158,7 +158,8 @@ def _windows_of(L, step, window):
 
 def test_win_once_witness(oracle_lib):
     """overlapping windows of plain k-mers run the four hash-once kernels and no other K1 kernel; windows that do not overlap run none of
-    them.  (What they compute is compared with materialized windows and the oracle in tests/test_gpu_sliding.py; here NumKmers only.)"""
+    them.  (What they compute — every hash, count and qlen, at the kernels' edges — is compared with the oracle in
+    tests/test_gpu_win_forms.py; here NumKmers only.)"""
     from kmcp_amd import default_params, lib
     O = oracle_lib
     key = P.Db(21, "plain", 0, 1)
