@@ -1,5 +1,6 @@
 // common.hpp — structures shared by the host engine and the HIP kernels of libkmcpgpu.so.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/kmcp_gpu.h"
@@ -171,8 +172,12 @@ struct K2Args {
   const uint16_t* cmin_fpr;      // optional: [n] = smallest count whose FPR(n, count) passes -f, n <= cmin_fpr_n (query.cpp fpr_bound)
   int32_t cmin_fpr_n;
   int32_t k2_flags;              // K2F_ bits (k2_plan.hpp): only k2_cobs<64, 8|10, false, false, 4> reads them (k2_cobs_body.inc, the short-read path)
+  // the persistent form of that path (k2_cobs.hip k2_cobs_persist, KMCPG_K2_PERSIST): resident waves take their units from a queue
+  unsigned long long* unit_queue;  // one zeroed counter per launch piece, K2_QUEUE_PITCH words apart (k2_claim.hpp); nullptr: one unit per wave, as launched
+  uint32_t persist_wgs;            // its grid; 0: as many workgroups as the chip holds at once (KMCPG_K2_PERSIST_WGS, for tests)
 };
-static_assert(sizeof(K2Args) == 208, "k2_flags sits in the tail padding: the argument block of every K2 form keeps its layout");
+constexpr int K2_QUEUE_PITCH = 16;  // 128 bytes: the pieces' counters do not share a cache line
+static_assert(sizeof(K2Args) == 224 && offsetof(K2Args, unit_queue) == 208, "new fields go behind k2_flags: what the other K2 forms read keeps its place in the argument block");
 
 // K3 (k3_finalize.hip): hit list -> per-read segments of (column, count), filtered by -T, ordered as the reference orders a
 // query's matches.  Segments of more than K3_WG_CAP matches are grouped but left unordered (the host sorts those).

@@ -153,6 +153,7 @@ struct kmcpg_db {
     kmcpg::DevBuf<uint8_t> w_huge_temp;                              // histogram table of the device-wide radix sort
     kmcpg::DevBuf<uint32_t> w_dedup_fb;                              // profiling: queries per k_dedup_bucket class that took its bitonic fallback
     kmcpg::DevBuf<uint64_t> w_gathered;                              // profiling level 2: the row loads k2_cobs issued
+    kmcpg::DevBuf<uint64_t> w_k2_queue;                              // k2_cobs_persist: the unit counter of every grid piece (k2_claim.hpp)
     // sliding windows, hash-once form: per-position hashes, kept hashes in order, ranks, per-chunk counts and their prefix
     kmcpg::DevBuf<uint64_t> w_win_h, w_win_kept, w_win_cbase;
     kmcpg::DevBuf<uint32_t> w_win_rank, w_win_cnt;
@@ -162,6 +163,7 @@ struct kmcpg_db {
     void release() {
       w_hashes.release(); w_scratch.release(); w_nk_raw.release(); w_nk1.release(); w_seg_cnt.release(); w_long_list.release();
       w_long_meta.release(); w_long_counts.release(); w_huge_info.release(); w_huge_temp.release(); w_gathered.release(); w_dedup_fb.release();
+      w_k2_queue.release();
       w_win_h.release(); w_win_kept.release(); w_win_cbase.release(); w_win_rank.release(); w_win_cnt.release();
       if (ev) (void)hipEventDestroy(ev);
       if (in_ev) (void)hipEventDestroy(in_ev);
