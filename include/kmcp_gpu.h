@@ -433,8 +433,10 @@ typedef struct {
   int32_t npl;        /* counter planes: 8, 10, 16, 24 */
   int32_t multi;      /* 1 = the several-hash-functions form */
   int32_t group_rows; /* rows between two pruning tests: 8 or 4 */
-  uint32_t workgroups;
-  uint32_t reserved;
+  uint32_t workgroups; /* of the launch piece: one wave per unit (lpr 64), four waves per workgroup */
+  uint32_t grid;       /* workgroups the kernel was launched on: = workgroups, except for the persistent short-read kernel
+                        * (k2_cobs_persist, KMCPG_K2_PERSIST), whose resident waves share the piece's units: the only field that tells it from
+                        * the launched form.  kind 2: both halves together */
 } kmcpg_k2_launch;
 /* Copies up to `cap` records to out (may be NULL when cap is 0); *n = how many launches the call made. */
 int kmcpg_last_k2_launches(kmcpg_db* db, kmcpg_k2_launch* out, uint32_t cap, uint32_t* n);

@@ -171,10 +171,10 @@ struct K2Args {
   unsigned long long* gathered;  // optional (profiling level 2): 16-byte row loads issued, K2_GATHER_SLOTS counters 128 B apart
   const uint16_t* cmin_fpr;      // optional: [n] = smallest count whose FPR(n, count) passes -f, n <= cmin_fpr_n (query.cpp fpr_bound)
   int32_t cmin_fpr_n;
-  int32_t k2_flags;              // K2F_ bits (k2_plan.hpp): only k2_cobs<64, 8|10, false, false, 4> reads them (k2_cobs_body.inc, the short-read path)
-  // the persistent form of that path (k2_cobs.hip k2_cobs_persist, KMCPG_K2_PERSIST): resident waves take their units from a queue
-  unsigned long long* unit_queue;  // one zeroed counter per launch piece, K2_QUEUE_PITCH words apart (k2_claim.hpp); nullptr: one unit per wave, as launched
-  uint32_t persist_wgs;            // its grid; 0: as many workgroups as the chip holds at once (KMCPG_K2_PERSIST_WGS, for tests)
+  int32_t k2_flags;              // K2F_ bits (k2_plan.hpp): the short-read unit's (k2_short.hpp; k2_cobs<64, 8|10, false, false, 4> and k2_cobs_persist drive it)
+  // a launch record with `persist` set (k2_plan.hpp; k2_cobs.hip k2_cobs_persist): resident waves take their units from a queue
+  unsigned long long* unit_queue;  // one zeroed counter per launch piece, K2_QUEUE_PITCH words apart (k2_claim.hpp); nullptr: the plan has no such record
+  uint32_t persist_wgs;            // its grid; 0: as many workgroups as the chip holds at once (K2Knobs::persist_wgs, for tests)
 };
 constexpr int K2_QUEUE_PITCH = 16;  // 128 bytes: the pieces' counters do not share a cache line
 static_assert(sizeof(K2Args) == 224 && offsetof(K2Args, unit_queue) == 208, "new fields go behind k2_flags: what the other K2 forms read keeps its place in the argument block");

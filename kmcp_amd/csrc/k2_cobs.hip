@@ -10,6 +10,7 @@
 #include "csa.hpp"
 #include "device_utils.hpp"
 #include "k2_claim.hpp"
+#include "k2_short.hpp"
 #include "kernels.hpp"
 
 namespace kmcpg {
@@ -78,72 +79,6 @@ struct alignas(16) UnitConst {  // one (read, slot) unit as the index phase sees
   int32_t n;        // k-mers of the read handled by this unit
 };
 
-// Hit emission of one tile as a function, for the short-read path of the body, which takes several tiles per wave and emits after each
-// (the body's own epilogue stays where it is: the other forms keep their token stream).  Wave-aggregated as there: bit-sliced compare with
-// cmin, ONE atomic on the global counter for the wave's hits, the tuples side by side; the segment of the previous hit stays in registers.
-template <int NPL>
-__device__ __forceinline__ void k2_emit_tile(const K2Args& a, const BlockDev* __restrict__ bd, uint32_t r, uint32_t boff, uint32_t cmin, bool live,
-                                             const uint32_t (&pl)[4][NPL], int lane) {
-  const bool emit = live && (cmin >> NPL) == 0;  // else: nothing left alive (cmin always fits the planes: query.cpp)
-  uint32_t ge[4];
-  uint32_t mine = 0;
-#pragma unroll
-  for (int d = 0; d < 4; d++) {
-    uint32_t v = emit ? 0xffffffffu : 0u;  // bit-sliced (count >= cmin), LSB to MSB
-#pragma unroll
-    for (int p = 0; p < NPL; p++) v = ((cmin >> p) & 1u) ? (v & pl[d][p]) : (v | pl[d][p]);
-    ge[d] = v;
-    mine += (uint32_t)__popc(v);
-  }
-  if (__ballot(mine != 0) == 0) return;  // wave-uniform: the common case
-  uint32_t incl = mine;  // inclusive prefix sum over the wave
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const uint32_t t = __shfl_up(incl, off);
-    if (lane >= off) incl += t;
-  }
-  const uint32_t total = __shfl(incl, 63);
-  unsigned long long base_idx = 0;
-  if (lane == 63) base_idx = atomicAdd(a.counter, (unsigned long long)total);
-  base_idx = __shfl(base_idx, 63);
-  unsigned long long idx = base_idx + (incl - mine);
-  uint32_t sg_lo = 1, sg_hi = 0, sg_col = 0;  // the segment of the previous hit: bytes [sg_lo, sg_hi), column of its first bit
-  const Seg* __restrict__ segs = a.segs + bd->seg0;
-  const uint32_t nsegs = bd->nsegs;
-#pragma unroll
-  for (int d = 0; d < 4; d++) {
-    uint32_t w = ge[d];
-    while (w) {
-      const int q = __ffs(w) - 1;
-      w &= w - 1;
-      uint32_t count = 0;
-#pragma unroll
-      for (int p = 0; p < NPL; p++) count |= ((pl[d][p] >> q) & 1u) << p;
-      const uint32_t byte = boff + (uint32_t)d * 4u + (uint32_t)(q >> 3);  // bit 7 = first column of the byte (index.go:1157)
-      if (byte < sg_lo || byte >= sg_hi) {
-        for (uint32_t i = 0; i < nsegs; i++) {
-          const Seg sg = segs[i];
-          if (byte < sg.byte_end) {
-            sg_lo = sg.byte_start;
-            sg_hi = sg.byte_end;
-            sg_col = sg.col_base;
-            break;
-          }
-        }
-      }
-      if (idx < a.hit_cap) {
-        kmcpg_hit hit;
-        hit.read = r;
-        hit.col = sg_col + (byte - sg_lo) * 8u + (7u - (uint32_t)(q & 7));
-        hit.count = count;
-        if (byte < sg_lo || byte >= sg_hi) hit = kmcpg_hit{0xffffffffu, 0xffffffffu, 0u};  // a tombstone, as in the body
-        a.hits[idx] = hit;
-      }
-      idx++;
-    }
-  }
-}
-
 // The body lives in k2_cobs_body.inc and is included twice: as the kernel k2_cobs (one launch = one lane form; the token stream the kernel
 // has always had, so the tuned instantiations compile to the ISA they had) and as the device function k2_body, which k2_cobs_pair calls
 // for each of its two lane forms.
@@ -183,21 +118,17 @@ struct K2UnitQueue {
   }
 };
 
-// The short-read path of k2_cobs<64, 8|10, false, false, 4> (k2_cobs_body.inc) as a persistent kernel: as many workgroups as the chip
-// holds at once, and every WAVE takes its (read, slot) units from the piece's queue (k2_claim.hpp) in runs of K2_CLAIM_RUN until a run
-// comes out empty — no wave waits for the other three of its workgroup before it gets new work (under the hardware dispatcher a
-// workgroup's wave slots come back when its slowest wave is done, and units differ in length by what their sectors prove), and the
-// kernel is correct on any grid.  A unit is what it is there: all row indices of the read in LDS, then sector cursors with the exact
-// stop (the loop below is that loop, for one tile), then the hits; the block's constants are loaded again only when the slot changes.
+// The short-read unit (k2_short.hpp) as a persistent kernel: as many workgroups as the chip holds at once, and every WAVE takes its
+// (read, slot) units from the piece's queue (k2_claim.hpp) in runs of K2_CLAIM_RUN until a run comes out empty — no wave waits for the
+// other three of its workgroup before it gets new work (under the hardware dispatcher a workgroup's wave slots come back when its slowest
+// wave is done, and units differ in length by what their sectors prove), and the kernel is correct on any grid.  A unit is what it is in
+// k2_cobs<64, 8|10, false, false, 4>, one tile; the block's constants are loaded again only when the slot changes.
 template <int NPL>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 4))) k2_cobs_persist(const K2Args a, const unsigned piece_workgroups, unsigned long long* __restrict__ queue) {
-  constexpr int NMAX = NPL == 8 ? 256 : 1024;  // the host picks NPL with n + 1 < 2^NPL (k2_plan.hpp): every read of the launch fits
-  __shared__ uint32_t s_all[4][NMAX + 4];  // (+ 4: a group's four index reads stay inside for every cursor <= n)
+  constexpr int NMAX = K2_SHORT_NMAX<NPL>;  // every read of the launch fits
+  __shared__ uint32_t s_all[4][K2_SHORT_ROW<NPL>];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const bool exact = (a.k2_flags & K2F_EXACT_STOP) != 0;
-  const int sec0 = lane & ~7;  // first lane of this lane's sector
-  auto uni = [](uint32_t v) __attribute__((always_inline)) -> uint32_t { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); };
-  auto uni64 = [&](uint64_t v) __attribute__((always_inline)) -> uint64_t { return (uint64_t)uni((uint32_t)v) | ((uint64_t)uni((uint32_t)(v >> 32)) << 32); };
 
   K2UnitQueue q{queue, a.unit_base, k2_piece_units((uint64_t)a.n_reads * a.nslots, a.unit_base, piece_workgroups), lane};
   // the slot the wave works on
@@ -207,144 +138,46 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 4))
   uint64_t ns = 0, mh = 0;
   bool lv0 = false;
   uint32_t g_rows = 0;    // 16-byte row loads this lane issued (profiling level 2)
-  uint64_t g_hashes = 0;  // ... and the hashes of the wave's units: every hash of a read once per unit
+  uint64_t g_hashes = 0;  // ... and the hashes of the wave's units
   for (;;) {
     const uint64_t u = q.take();
     if (u == K2UnitQueue::NONE) break;
-    // today's numbering (k2_cobs_body.inc), one unit per wave
+    // the body's numbering (k2_cobs_body.inc), one unit per wave
     const uint32_t sidx = (uint32_t)(a.slot_major ? u / a.n_reads : u % a.nslots);
-    const uint32_t r0 = (uint32_t)(a.slot_major ? u % a.n_reads : u / a.nslots);
+    const uint32_t r = (uint32_t)(a.slot_major ? u % a.n_reads : u / a.nslots);
     if (sidx != cur_sidx) {  // wave-uniform
       cur_sidx = sidx;
       const Slot slot = a.slots[sidx];
-      bd = a.blocks + uni(slot.block);
-      const uint32_t stride = uni(bd->stride);
-      ns = uni64(bd->num_sigs);
-      mh = uni64(bd->magic_hi);
+      bd = a.blocks + k2_uni(slot.block);
+      const uint32_t stride = k2_uni(bd->stride);
+      ns = k2_uni64(bd->num_sigs);
+      mh = k2_uni64(bd->magic_hi);
       s16 = stride >> 4;  // rows are addressed in 16-byte units
-      tb = (uni(slot.tile) * 64u + (uint32_t)lane) * 16u;
-      tbase = (const uint8_t*)uni64((uint64_t)(uintptr_t)bd->rows) + tb;
+      tb = (k2_uni(slot.tile) * 64u + (uint32_t)lane) * 16u;
+      tbase = (const uint8_t*)k2_uni64((uint64_t)(uintptr_t)bd->rows) + tb;
       lv0 = tb < stride;
     }
-    int n0 = (int)uni((uint32_t)a.nk[r0]);
-    if ((a.split_min > 0 && n0 > a.split_min) || n0 > NMAX) n0 = 0;  // long queries are left to the SPLIT launch
-    if (n0 == 0) continue;
-    {
-      // row indices of the read -> s_all[wave]: four hash loads per lane in flight, then the arithmetic
-      const uint64_t koff = uni64(a.offs[r0] + (a.offs2 ? a.offs2[r0] : 0));
-      for (int c0 = 0; c0 < n0; c0 += 256) {
-        uint64_t hv[4];
-#pragma unroll
-        for (int it = 0; it < 4; it++) hv[it] = c0 + 64 * it + lane < n0 ? a.hashes[koff + (uint64_t)(c0 + 64 * it + lane)] : 0;
-#pragma unroll
-        for (int it = 0; it < 4; it++)
-          if (c0 + 64 * it + lane < n0) s_all[wave][c0 + 64 * it + lane] = (uint32_t)fastmod_u64(hv[it], ns, mh) * s16;
-      }
-      wave_lds_fence();
-    }
-    uint32_t cmin0 = count_threshold(n0, a.min_qcov, a.min_matched);  // integer threshold and the -f bound, as in the body
-    if (a.cmin_fpr && n0 <= a.cmin_fpr_n) cmin0 = max(cmin0, (uint32_t)a.cmin_fpr[n0]);
-    cmin0 = uni(cmin0);
-    const int cm0 = (int)min(cmin0, 1u << NPL);  // (past the planes' range nothing passes, whatever the value)
-    // ---- the unit's sectors: their cursors over the rows s_all[wave] names (k2_cobs_body.inc, the short-read path, for one tile)
+    int n = (int)k2_uni((uint32_t)a.nk[r]);
+    if ((a.split_min > 0 && n > a.split_min) || n > NMAX) n = 0;  // long queries are left to the SPLIT launch
+    if (n == 0) continue;
+    k2_short_index(a, r, ns, mh, s16, n, s_all[wave], lane);
+    const uint32_t cmin = k2_uni(k2_short_cmin(a, n));
+    const int cm = k2_short_clamp<NPL>(cmin);
     bool lv = lv0;
-    uint32_t cp[4][NPL];
-#pragma unroll
-    for (int d = 0; d < 4; d++)
-#pragma unroll
-    for (int p = 0; p < NPL; p++) cp[d][p] = 0;
-    const int nn = n0, cm = cm0;
-    // some column of this lane holds a count >= t_: the bit-sliced compare, LSB to MSB, the choice of `&` or `|` per plane as a mask
-    // word into a majority (csa.hpp MAJ3): t_ may differ from sector to sector
-    auto at_least = [&](int t_) __attribute__((always_inline)) -> bool {
-      uint32_t w[NPL];
-#pragma unroll
-      for (int p = 0; p < NPL; p++) w[p] = (((uint32_t)t_ >> p) & 1u) - 1u;  // all ones where bit p of t_ is clear
-      uint32_t any = 0;
-#pragma unroll
-      for (int d = 0; d < 4; d++) {
-        uint32_t ge = 0xffffffffu;
-#pragma unroll
-        for (int p = 0; p < NPL; p++) ge = MAJ3(ge, cp[d][p], w[p]);
-        any |= ge;
-      }
-      return t_ <= 0 || (((uint32_t)t_ >> NPL) == 0 && any != 0);
-    };
-    auto in_sector = [&](bool b) __attribute__((always_inline)) -> bool { return ((__ballot(b) >> sec0) & 0xffull) != 0; };
-    int done = 0;         // rows this sector has added (the same in its 8 lanes)
-    int sdone = 0;        // ... without K2F_EXACT_STOP: every live sector has added the same rows, a wave-uniform count
-    int credit = 0;       // K2F_EXACT_STOP: rows from the cursor on that are already proven necessary (no test until they are used up)
-    bool try_far = true;  // ... and whether the 16-row test is still worth its cost (wave-uniform)
-    for (;;) {
-      // L: the rows from its cursor on that the sector is certain to need (before the end of the read cuts it); a column must hold
-      // `need` now to stay in the race
-      int L, rem;
-      if (exact) {
-        rem = nn - done;
-        const int need = cm - rem;
-        credit = max(credit, 1 - need);  // counts are >= 0: the first n - cmin + 1 rows of a read need no test at all
-        const int want_rows = min(4, rem);
-        bool ask_ = lv && credit < want_rows;
-        if (__ballot(ask_) != 0) {
-          if (try_far) {  // a column 15 above `need` pays for four groups
-            const bool far = in_sector(lv && at_least(need + 15));
-            credit = ask_ && far ? 16 : credit;
-            ask_ = ask_ && !far;
-            try_far = __ballot(ask_) == 0;
-          }
-          if (__ballot(ask_) != 0) {
-            const bool top = in_sector(lv && at_least(need + 3));
-            credit = ask_ && top ? 4 : credit;
-            ask_ = ask_ && !top;
-            if (__ballot(ask_) != 0) {  // some sector of the wave is within 3 rows of its end: which of 0..3, in two steps
-              const bool t1 = in_sector(lv && at_least(need + 1));
-              const bool t2 = in_sector(lv && at_least(t1 ? need + 2 : need));
-              const int fine = t1 ? (t2 ? 3 : 2) : (t2 ? 1 : 0);
-              credit = ask_ ? fine : credit;
-              lv = lv && !(ask_ && fine == 0);  // no column can reach the threshold any more
-            }
-          }
-        }
-        L = lv ? min(credit, want_rows) : 0;
-        credit -= L;
-      } else {
-        rem = nn - sdone;
-        L = in_sector(lv && at_least(cm - rem)) ? 4 : 0;
-        sdone += min(4, rem);
-        lv = lv && L > 0;  // L == 0: no column can reach the threshold any more (at the end of the read: none has)
-        L = lv ? min(L, rem) : 0;
-      }
-      if (__ballot(L > 0) == 0) break;
-      uint32_t ri[4];
-      uint4 x[4];
-#pragma unroll
-      for (int i = 0; i < 4; i++) ri[i] = s_all[wave][done + i];
-#pragma unroll
-      for (int i = 0; i < 4; i++) {
-        x[i] = make_uint4(0, 0, 0, 0);
-        if (i < L) x[i] = load_row16_global(tbase + ((uint64_t)ri[i] << 4), a.nt_loads);
-      }
-      csa4<NPL>(cp[0], x[0].x, x[1].x, x[2].x, x[3].x);
-      csa4<NPL>(cp[1], x[0].y, x[1].y, x[2].y, x[3].y);
-      csa4<NPL>(cp[2], x[0].z, x[1].z, x[2].z, x[3].z);
-      csa4<NPL>(cp[3], x[0].w, x[1].w, x[2].w, x[3].w);
-      done += L;
-      g_rows += (uint32_t)L;
-    }
-    g_hashes += (uint64_t)nn;
-    k2_emit_tile<NPL>(a, bd, r0, tb, cmin0, lv, cp, lane);
+#define K2T_ROW s_all[wave]
+#define K2T_BASE tbase
+#define K2T_N n
+#define K2T_CM cm
+#include "k2_short_tile.inc"
+#undef K2T_ROW
+#undef K2T_BASE
+#undef K2T_N
+#undef K2T_CM
+    g_hashes += (uint64_t)n;
+    k2_emit_tile<NPL>(a, bd, r, tb, cmin, lv, cp, lane);
   }
-  if (a.gathered) {  // as in the body: one atomic pair per wave
-    unsigned long long rows = g_rows;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) rows += __shfl_xor(rows, off);
-    if (lane == 0) {
-      atomicAdd(a.gathered + (size_t)(blockIdx.x % K2_GATHER_SLOTS) * 16, rows);
-      atomicAdd(a.gathered + (size_t)(blockIdx.x % K2_GATHER_SLOTS) * 16 + 1, (unsigned long long)g_hashes);
-    }
-  }
+  k2_short_account(a, blockIdx.x, g_rows, g_hashes, lane);
 }
-
 
 // Two lane forms of one database in ONE launch (long queries, round 6): the first `nba` workgroups are form A's (the 1-KiB tiles), the rest
 // form B's (the remainder of the same rows).  A batch of 16 384 HiFi reads is five rounds of the chip on the 64-lane form and a round and a
@@ -357,9 +190,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((NPL =
   else k2_body<LPRB, NPL, MULTI, false, 8>(b, blockIdx.x - nba);
 }
 
-// Every K2 kernel is launched by launch_k2_form or launch_k2_pair_form and nowhere else: the kernel's template arguments are the
-// function's own, so the record a launch leaves in the log (kmcpg_last_k2_launches) cannot name another form than the one that ran.
-static void note_k2(K2Log* log, int kind, int lpr, int lprb, int npl, bool multi, int gr, unsigned nb) {
+// Every K2 kernel is launched by launch_k2_form, launch_k2_pair_form or launch_k2_persist_form and nowhere else: the kernel's template
+// arguments are the function's own, so the record a launch leaves in the log (kmcpg_last_k2_launches) cannot name another form than the
+// one that ran.  nb: the workgroups of the piece; grid: those the kernel was launched on where they are not the same (the persistent kernel).
+static void note_k2(K2Log* log, int kind, int lpr, int lprb, int npl, bool multi, int gr, unsigned nb, unsigned grid = 0) {
   if (!log) return;
   kmcpg_k2_launch r{};
   r.kind = kind;
@@ -369,6 +203,7 @@ static void note_k2(K2Log* log, int kind, int lpr, int lprb, int npl, bool multi
   r.multi = multi ? 1 : 0;
   r.group_rows = gr;
   r.workgroups = nb;
+  r.grid = grid ? grid : nb;
   log->push_back(r);
 }
 
@@ -385,7 +220,8 @@ static void launch_k2_pair_form(const K2Args& a, const K2Args& b, unsigned nba, 
 }
 
 // The persistent form of a piece of k2_cobs<64, NPL, false, false, 4>: the piece's units and its own counter on the grid k2_persist_grid
-// names (k2_claim.hpp).  The record is the plan's: what the piece is, not how many waves share it.
+// names (k2_claim.hpp).  The record is the launched form's but for `grid`, the witness that this kernel ran: what the piece is, and how many
+// workgroups share it.
 template <int NPL>
 static int launch_k2_persist_form(const K2Args& b, const K2Piece& pc, uint64_t piece, hipStream_t st, K2Log* log) {
   int dev = 0, cus = 0, per_cu = 0;
@@ -394,7 +230,7 @@ static int launch_k2_persist_form(const K2Args& b, const K2Piece& pc, uint64_t p
     return -1;
   const unsigned nb = k2_persist_grid(pc.workgroups, (unsigned)cus * (unsigned)per_cu, b.persist_wgs);
   hipLaunchKernelGGL((k2_cobs_persist<NPL>), dim3(nb), dim3(256), 0, st, b, pc.workgroups, b.unit_queue + piece * K2_QUEUE_PITCH);
-  note_k2(log, 0, 64, 0, NPL, false, 4, pc.workgroups);
+  note_k2(log, 0, 64, 0, NPL, false, 4, pc.workgroups, nb);
   return 0;
 }
 
@@ -405,12 +241,12 @@ static int launch_k2_pieces(const K2Launch& l, const K2Args& a, hipStream_t st, 
   for (uint64_t i = 0, n = k2_n_pieces(l); i < n; i++) {
     const K2Piece pc = k2_piece(l, i);
     b.unit_base = pc.unit_base;
-    if constexpr (LPR == 64 && NPL <= 10 && !SPLIT && GR == 4) {
-      // short reads on the exact-stop path, tile by tile, with a queue to take them from (query.cpp): the persistent kernel
-      if (!l.multi && b.unit_queue && b.k2_flags != 0 && !(b.k2_flags & K2F_BLOCK_UNITS)) {
-        if (launch_k2_persist_form<NPL>(b, pc, i, st, log) != 0) return -1;
+    if (l.persist) {  // the plan's decision (k2_plan.hpp); the kernel exists for the two forms the plan names, and needs its queue
+      if constexpr (LPR == 64 && NPL <= 10 && !SPLIT && GR == 4) {
+        if (!b.unit_queue || launch_k2_persist_form<NPL>(b, pc, i, st, log) != 0) return -1;
         continue;
       }
+      return -1;
     }
     if (l.multi)
       launch_k2_form<LPR, NPL, true, SPLIT, GR>(b, pc.workgroups, st, log);

@@ -80,41 +80,17 @@
   const uint8_t* __restrict__ base = bd->rows + boff;
   const int nh = MULTI ? a.num_hashes : 1;
 
-  // ---- Short reads on 1-KiB tiles: k2_cobs<64, 8|10, false, false, 4> with K2F_ bits set (query.cpp; DESIGN.md §4).  The wave is one
-  //      (read, slot) unit, and the read is short enough for ALL its row indices to fit LDS: one index phase — hashes, fastmod — per
-  //      unit, and with K2F_BLOCK_UNITS the unit is the whole run of tiles of the group's row (Slot::tile carries their number), taken
-  //      one after the other on the same counter registers with hit emission after each.  With the indices of the whole read at hand a
-  //      sector (8 lanes, 128 bytes) need not march with the wave: it keeps its own row cursor.  K2F_EXACT_STOP: before every group the
-  //      sector asks how many rows its best column proves necessary — with `need` = the count a column must hold NOW to stay in the
-  //      race, a column at need + j keeps the sector alive for j more rows whatever they hold, so rows done + 1 .. done + j + 1 will be
-  //      asked for in any case — and loads exactly those, at most 4 at a time: no row is requested after the sector is lost, none past
-  //      the end of the read.  Proven rows are kept as a credit and used up before the next test: counts are >= 0, so the first
-  //      n - cmin + 1 rows of a read need no test at all; after that one test for 16 rows while some column is 15 ahead, then the test
-  //      for 4, and the two finer ones (3 / 2 / 1 / lost) only when some sector of the wave fails that.  The tests are what this loop
-  //      can afford least (profiles/k2_exact_stop_ab.txt).  Without the bit: 4 rows (what is left of the read, if less) while the
-  //      sector is alive, tested before every group.  Counts and hits are the same either way.
+  // ---- Short reads on 1-KiB tiles: k2_cobs<64, 8|10, false, false, 4> with K2F_ bits set (k2_plan.hpp; DESIGN.md §4).  The wave is one
+  //      (read, slot) unit of k2_short.hpp: one index phase, then its tiles — one, or with K2F_BLOCK_UNITS the whole run of tiles of the
+  //      group's row (Slot::tile carries their number), taken one after the other with hit emission after each.
   constexpr bool SHORT = LPR == 64 && NPL <= 10 && !MULTI && !SPLIT && GR == 4;
   if constexpr (SHORT) {
-    constexpr int NMAX = NPL == 8 ? 256 : 1024;  // the host picks NPL with n + 1 < 2^NPL (query.cpp)
-    if (a.k2_flags != 0 && n <= NMAX) {  // wave-uniform: one unit per wave
-      __shared__ uint32_t s_all[4][NMAX + 4];  // (+ 4: a group's four index reads stay inside for every cursor <= n)
+    if (a.k2_flags != 0 && n <= K2_SHORT_NMAX<NPL>) {  // wave-uniform: one unit per wave
+      __shared__ uint32_t s_all[4][K2_SHORT_ROW<NPL>];
       const int nn = __builtin_amdgcn_readfirstlane(n);
       const uint32_t rr = (uint32_t)__builtin_amdgcn_readfirstlane((int)r);
-      const int cm = __builtin_amdgcn_readfirstlane((int)min(cmin, 1u << NPL));  // (past the planes' range nothing passes, whatever the value)
-      {
-        const uint64_t koff = a.offs[rr] + (a.offs2 ? a.offs2[rr] : 0);
-        const uint64_t ns = bd->num_sigs, mh = bd->magic_hi;
-        const uint32_t s16 = stride >> 4;  // rows are addressed in 16-byte units
-        for (int c0 = 0; c0 < nn; c0 += 256) {  // four hash loads per lane in flight, then the arithmetic
-          uint64_t hv[4];
-#pragma unroll
-          for (int it = 0; it < 4; it++) hv[it] = c0 + 64 * it + lane < nn ? a.hashes[koff + (uint64_t)(c0 + 64 * it + lane)] : 0;
-#pragma unroll
-          for (int it = 0; it < 4; it++)
-            if (c0 + 64 * it + lane < nn) s_all[wave][c0 + 64 * it + lane] = (uint32_t)fastmod_u64(hv[it], ns, mh) * s16;
-        }
-      }
-      wave_lds_fence();
+      k2_short_index(a, rr, bd->num_sigs, bd->magic_hi, stride >> 4, nn, s_all[wave], lane);
+      const int cm = k2_short_clamp<NPL>(cmin);
       uint32_t tile0 = slot.tile;
       int ntiles = 1;
       if (a.k2_flags & K2F_BLOCK_UNITS) {
@@ -122,104 +98,23 @@
         tile0 &= (1u << SLOT_TILE_BITS) - 1u;
       }
       const bool exact = (a.k2_flags & K2F_EXACT_STOP) != 0;
-      const int sec0 = lane & ~7;  // first lane of this lane's sector
-      uint32_t g_rows = 0;         // 16-byte row loads this lane issued (profiling level 2)
+      uint32_t g_rows = 0;
       for (int t = 0; t < ntiles; t++) {
         const uint32_t tb = ((tile0 + (uint32_t)t) * 64u + (uint32_t)lane) * 16u;
         const uint8_t* __restrict__ tbase = bd->rows + tb;
         bool lv = tb < stride;
-        uint32_t cp[4][NPL];
-#pragma unroll
-        for (int d = 0; d < 4; d++)
-#pragma unroll
-          for (int p = 0; p < NPL; p++) cp[d][p] = 0;
-        // some column of this lane holds a count >= t_: the bit-sliced compare, LSB to MSB.  The plain form picks `&` or `|` per plane by
-        // a wave-uniform bit; here t_ may differ from sector to sector, and the choice is a mask word into a majority (csa.hpp MAJ3)
-        auto at_least = [&](int t_) -> bool {
-          uint32_t w[NPL];
-#pragma unroll
-          for (int p = 0; p < NPL; p++) w[p] = (((uint32_t)t_ >> p) & 1u) - 1u;  // all ones where bit p of t_ is clear
-          uint32_t any = 0;
-#pragma unroll
-          for (int d = 0; d < 4; d++) {
-            uint32_t ge = 0xffffffffu;
-#pragma unroll
-            for (int p = 0; p < NPL; p++) ge = MAJ3(ge, cp[d][p], w[p]);
-            any |= ge;
-          }
-          return t_ <= 0 || (((uint32_t)t_ >> NPL) == 0 && any != 0);
-        };
-        auto in_sector = [&](bool b) -> bool { return ((__ballot(b) >> sec0) & 0xffull) != 0; };
-        int done = 0;         // rows this sector has added (the same in its 8 lanes)
-        int sdone = 0;        // ... without K2F_EXACT_STOP: every live sector has added the same rows, a wave-uniform count
-        int credit = 0;       // K2F_EXACT_STOP: rows from the cursor on that are already proven necessary (no test until they are used up)
-        bool try_far = true;  // ... and whether the 16-row test is still worth its cost in this tile (wave-uniform)
-        for (;;) {
-          // L: the rows from its cursor on that the sector is certain to need (before the end of the read cuts it); a column must hold
-          // `need` now to stay in the race
-          int L, rem;
-          if (exact) {
-            rem = nn - done;
-            const int need = cm - rem;
-            credit = max(credit, 1 - need);  // counts are >= 0: the first n - cmin + 1 rows of a read need no test at all
-            const int want_rows = min(4, rem);
-            bool ask = lv && credit < want_rows;
-            if (__ballot(ask) != 0) {
-              if (try_far) {  // a column 15 above `need` pays for four groups
-                const bool far = in_sector(lv && at_least(need + 15));
-                credit = ask && far ? 16 : credit;
-                ask = ask && !far;
-                try_far = __ballot(ask) == 0;
-              }
-              if (__ballot(ask) != 0) {
-                const bool top = in_sector(lv && at_least(need + 3));
-                credit = ask && top ? 4 : credit;
-                ask = ask && !top;
-                if (__ballot(ask) != 0) {  // some sector of the wave is within 3 rows of its end: which of 0..3, in two steps
-                  const bool r1 = in_sector(lv && at_least(need + 1));
-                  const bool r2 = in_sector(lv && at_least(r1 ? need + 2 : need));
-                  const int fine = r1 ? (r2 ? 3 : 2) : (r2 ? 1 : 0);
-                  credit = ask ? fine : credit;
-                  lv = lv && !(ask && fine == 0);  // no column can reach the threshold any more
-                }
-              }
-            }
-            L = lv ? min(credit, want_rows) : 0;
-            credit -= L;
-          } else {
-            rem = nn - sdone;
-            L = in_sector(lv && at_least(cm - rem)) ? 4 : 0;
-            sdone += min(4, rem);
-            lv = lv && L > 0;  // L == 0: no column can reach the threshold any more (at the end of the read: none has)
-            L = lv ? min(L, rem) : 0;
-          }
-          if (__ballot(L > 0) == 0) break;
-          uint32_t ri[4];
-          uint4 x[4];
-#pragma unroll
-          for (int i = 0; i < 4; i++) ri[i] = s_all[wave][done + i];
-#pragma unroll
-          for (int i = 0; i < 4; i++) {
-            x[i] = make_uint4(0, 0, 0, 0);
-            if (i < L) x[i] = load_row16_global(tbase + ((uint64_t)ri[i] << 4), a.nt_loads);
-          }
-          csa4<NPL>(cp[0], x[0].x, x[1].x, x[2].x, x[3].x);
-          csa4<NPL>(cp[1], x[0].y, x[1].y, x[2].y, x[3].y);
-          csa4<NPL>(cp[2], x[0].z, x[1].z, x[2].z, x[3].z);
-          csa4<NPL>(cp[3], x[0].w, x[1].w, x[2].w, x[3].w);
-          done += L;
-          g_rows += (uint32_t)L;
-        }
+#define K2T_ROW s_all[wave]
+#define K2T_BASE tbase
+#define K2T_N nn
+#define K2T_CM cm
+#include "k2_short_tile.inc"
+#undef K2T_ROW
+#undef K2T_BASE
+#undef K2T_N
+#undef K2T_CM
         k2_emit_tile<NPL>(a, bd, rr, tb, cmin, lv, cp, lane);
       }
-      if (a.gathered) {  // as at the end of the body: one atomic pair per wave
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) g_rows += __shfl_xor(g_rows, off);
-        if (lane == 0) {
-          atomicAdd(a.gathered + (size_t)(K2_BID % K2_GATHER_SLOTS) * 16, (unsigned long long)g_rows);
-          atomicAdd(a.gathered + (size_t)(K2_BID % K2_GATHER_SLOTS) * 16 + 1, (unsigned long long)nn);  // every hash of the read once
-        }
-      }
+      k2_short_account(a, K2_BID, g_rows, (uint64_t)nn, lane);
       return;
     }
   }

@@ -40,7 +40,8 @@ constexpr int32_t K2_SPLIT_MIN_DEFAULT = 2048;
 constexpr int K2_CHUNK_MIN = 1024, K2_CHUNK_MAX = 8192, K2_CHUNKS_AIM = 64, K2_CHUNK_ENV_MIN = 64;  // (ENV_MIN: what KMCPG_SPLIT_CHUNK may ask for)
 constexpr uint64_t K2_COUNTS_BYTES = 2ull << 30;  // count arrays of the long queries: at most ~2 GB at a time
 
-// K2Args::k2_flags: only k2_cobs<64, 8|10, false, false, 4> reads them (k2_cobs_body.inc, the short-read path)
+// K2Args::k2_flags: the short-read unit (k2_short.hpp) and its two drivers read them — k2_cobs<64, 8|10, false, false, 4>
+// (k2_cobs_body.inc, the SHORT branch) and k2_cobs_persist (k2_cobs.hip)
 // one index phase per (read, run of tiles): `slots` is the class's block-unit list (Slot::tile carries the tile count)
 constexpr int32_t K2F_BLOCK_UNITS = 1;
 // every 128-byte sector steps by the rows its best column proves necessary and stops at its exact row
@@ -120,6 +121,8 @@ struct K2Knobs {
   int tail_sectors = 2, tail_min = 64;  // KMCPG_TAIL_SECTORS (0..4), KMCPG_TAIL_MIN (>= 1)
   bool pair = true;     // KMCPG_PAIR
   bool block_units = K2_BLOCK_UNITS_DEFAULT, exact_stop = K2_EXACT_STOP_DEFAULT;  // KMCPG_K2_BLOCK_UNITS, KMCPG_K2_EXACT_STOP
+  bool persist = true;       // KMCPG_K2_PERSIST=0: the short-read launch as launched waves, one unit each
+  uint32_t persist_wgs = 0;  // KMCPG_K2_PERSIST_WGS: the persistent kernel's grid, for tests; 0 = what the chip holds at once
 };
 
 struct K2Class {  // a lane class of the database (engine.hpp SlotClass)
@@ -151,6 +154,7 @@ struct K2Launch {
   int cls = 0, cls_b = 0; // whose slots (cls_b: the second half of a pair)
   bool block_units = false;  // the class's block-unit list instead of its slots
   int32_t k2_flags = 0;
+  bool persist = false;      // k2_cobs_persist instead of k2_cobs: resident waves take the launch's units from a queue (k2_claim.hpp)
   uint64_t units = 0;        // Split: 0 here, k2_split_launch gives it per group of long queries
   uint32_t nba = 0, nbb = 0; // Pair: workgroups of the two halves, one grid of nba + nbb
 };
@@ -252,7 +256,7 @@ inline K2Plan k2_plan(const K2Shape& s, bool asked, uint32_t n_long_listed, uint
       paired = true;
     }
   }
-  // The short-read path of k2_cobs<64, 8|10, false, false, 4> (k2_cobs_body.inc): KMCPG_K2_BLOCK_UNITS=1 — one index phase per (read, block
+  // The short-read unit (k2_short.hpp) in k2_cobs<64, 8|10, false, false, 4>: KMCPG_K2_BLOCK_UNITS=1 — one index phase per (read, block
   // group), the tiles of the row one after the other in one wave; KMCPG_K2_EXACT_STOP=1 — every sector steps by the rows its best column
   // proves necessary and stops at its exact row.  Defaults: DESIGN.md §4 (profiles/k2_exact_stop_ab.txt).
   int32_t short_flags = 0;
@@ -270,6 +274,8 @@ inline K2Plan k2_plan(const K2Shape& s, bool asked, uint32_t n_long_listed, uint
     l.block_units = (l.k2_flags & K2F_BLOCK_UNITS) && k.nbslots;
     if (!l.block_units) l.k2_flags &= ~K2F_BLOCK_UNITS;  // a class without the list: tile by tile
     l.units = k2_units(s.n_reads, l.block_units ? k.nbslots : k.nslots, k.lpr, kn.slot_major);
+    // the short-read unit tile by tile on a 1-KiB tile form: the persistent kernel (there are two, k2_cobs_persist<8|10>)
+    l.persist = kn.persist && k.lpr == 64 && l.gr == 4 && l.npl <= 10 && !l.multi && l.k2_flags != 0 && !(l.k2_flags & K2F_BLOCK_UNITS);
   }
   if (p.n_long) {
     int chk = K2_CHUNK_MIN;

@@ -93,6 +93,9 @@ K2Knobs k2_knobs() {
   if (const char* e = getenv("KMCPG_PAIR")) kn.pair = atoi(e) != 0;
   if (const char* e = getenv("KMCPG_K2_BLOCK_UNITS")) kn.block_units = atoi(e) != 0;
   if (const char* e = getenv("KMCPG_K2_EXACT_STOP")) kn.exact_stop = atoi(e) != 0;
+  // the short-read launch of the 64-lane class as resident waves that take their units from a queue (k2_cobs.hip k2_cobs_persist)
+  if (const char* e = getenv("KMCPG_K2_PERSIST")) kn.persist = atoi(e) != 0;
+  if (const char* e = getenv("KMCPG_K2_PERSIST_WGS")) kn.persist_wgs = (uint32_t)std::max(0, atoi(e));
   return kn;
 }
 
@@ -634,20 +637,15 @@ int kmcpg::query_device_after(kmcpg_db* db, const DeviceBatch& b, const kmcpg_pa
     HIPCHK(hipMemsetAsync(W.w_gathered.p, 0, (size_t)K2_GATHER_SLOTS * 16 * sizeof(uint64_t), st));
     a.gathered = (unsigned long long*)W.w_gathered.p;
   }
-  // KMCPG_K2_PERSIST (default 1): the short-read launch of the 64-lane class as resident waves that take their units from a queue
-  // (k2_cobs.hip k2_cobs_persist) — one zeroed counter per grid piece; KMCPG_K2_PERSIST_WGS: its grid, for tests.  Read at every call.
-  if (!(getenv("KMCPG_K2_PERSIST") && atoi(getenv("KMCPG_K2_PERSIST")) == 0)) {
-    uint64_t pieces = 0;
-    for (int i = 0; i < plan.n_launches; i++) {
-      const K2Launch& l = plan.launches[i];
-      if (l.kind == K2Kind::Plain && l.lpr == 64 && l.gr == 4 && l.k2_flags != 0 && !l.block_units) pieces = std::max(pieces, k2_n_pieces(l));
-    }
-    if (pieces) {
-      if (W.w_k2_queue.ensure((size_t)pieces * K2_QUEUE_PITCH)) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
-      HIPCHK(hipMemsetAsync(W.w_k2_queue.p, 0, (size_t)pieces * K2_QUEUE_PITCH * sizeof(uint64_t), st));
-      a.unit_queue = (unsigned long long*)W.w_k2_queue.p;
-      if (const char* e = getenv("KMCPG_K2_PERSIST_WGS")) a.persist_wgs = (uint32_t)std::max(0, atoi(e));
-    }
+  // the persistent launches of the plan (k2_cobs.hip k2_cobs_persist): one zeroed unit counter per grid piece
+  uint64_t pieces = 0;
+  for (int i = 0; i < plan.n_launches; i++)
+    if (plan.launches[i].persist) pieces = std::max(pieces, k2_n_pieces(plan.launches[i]));
+  if (pieces) {
+    if (W.w_k2_queue.ensure((size_t)pieces * K2_QUEUE_PITCH)) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
+    HIPCHK(hipMemsetAsync(W.w_k2_queue.p, 0, (size_t)pieces * K2_QUEUE_PITCH * sizeof(uint64_t), st));
+    a.unit_queue = (unsigned long long*)W.w_k2_queue.p;
+    a.persist_wgs = s.knobs.persist_wgs;
   }
   if (int rcb = fpr_bound(db, p.max_fpr, plan.max_short, st, &a.cmin_fpr, &a.cmin_fpr_n)) return rcb;
   if (bound_n) *bound_n = a.cmin_fpr ? a.cmin_fpr_n : 0;  // both kernel forms apply the table to every query of up to this many k-mers

@@ -137,7 +137,7 @@ class WindowSpec(C.Structure):
 class K2Launch(C.Structure):
     """kmcpg_k2_launch: one COBS kernel launch of a query_device call"""
     _fields_ = [("kind", C.c_int32), ("lpr", C.c_int32), ("lprb", C.c_int32), ("npl", C.c_int32), ("multi", C.c_int32),
-                ("group_rows", C.c_int32), ("workgroups", C.c_uint32), ("reserved", C.c_uint32)]
+                ("group_rows", C.c_int32), ("workgroups", C.c_uint32), ("grid", C.c_uint32)]
 
 
 K2_KINDS = ("plain", "split", "pair")
@@ -1221,14 +1221,22 @@ class Database:
         _check(load().kmcpg_last_tail_waves(self._h, C.byref(n)))
         return n.value
 
-    def last_k2_launches(self):
-        """The COBS kernels the last query_device call launched, in launch order (profiling level >= 1): tuples
-        (kind, lpr, lprb, npl, multi, group_rows, workgroups) with kind in K2_KINDS; lprb is 0 unless kind == "pair"."""
+    def _k2_launch_records(self):
         n = C.c_uint32(0)
         _check(load().kmcpg_last_k2_launches(self._h, None, 0, C.byref(n)))
         buf = (K2Launch * max(1, n.value))()
         _check(load().kmcpg_last_k2_launches(self._h, buf, n.value, C.byref(n)))
-        return [(K2_KINDS[r.kind], r.lpr, r.lprb, r.npl, bool(r.multi), r.group_rows, r.workgroups) for r in buf[:n.value]]
+        return buf[:n.value]
+
+    def last_k2_launches(self):
+        """The COBS kernels the last query_device call launched, in launch order (profiling level >= 1): tuples
+        (kind, lpr, lprb, npl, multi, group_rows, workgroups) with kind in K2_KINDS; lprb is 0 unless kind == "pair"."""
+        return [(K2_KINDS[r.kind], r.lpr, r.lprb, r.npl, bool(r.multi), r.group_rows, r.workgroups) for r in self._k2_launch_records()]
+
+    def last_k2_grids(self):
+        """The workgroups each of those kernels was launched on, in the same order: equal to a record's `workgroups` except for the
+        persistent short-read kernel (k2_cobs_persist), whose grid is what the chip holds at once or KMCPG_K2_PERSIST_WGS."""
+        return [r.grid for r in self._k2_launch_records()]
 
     def last_hash_bytes(self):
         """Bytes of k-mer hashes the COBS kernel(s) of the last query_device call read (profiling level 2)."""

@@ -88,6 +88,9 @@ static void invariants(const K2Shape& s, bool asked, uint32_t listed, uint32_t m
     CHECK(l.gr == 8 || (l.gr == 4 && l.npl <= 10 && l.kind == Kd::Plain));
     CHECK(!l.k2_flags || (l.kind == Kd::Plain && l.lpr == 64 && l.gr == 4 && s.num_hashes == 1));
     CHECK(l.block_units == ((l.k2_flags & K2F_BLOCK_UNITS) != 0) && (!l.block_units || s.classes[l.cls].nbslots));
+    // the persistent kernel: the short-read unit tile by tile on the 64-lane form, where the knob allows it, and nothing else
+    CHECK(!l.persist || (l.kind == Kd::Plain && l.lpr == 64 && l.gr == 4 && l.npl <= 10 && !l.multi && l.k2_flags != 0 && !(l.k2_flags & K2F_BLOCK_UNITS) &&
+                         !l.block_units && s.knobs.persist));
     if (l.kind == Kd::Split) {
       CHECK(l.npl == 16 && l.cls == n_split && l.units == 0 && p.n_long);
       n_split++;
@@ -124,6 +127,7 @@ int main() {
     const K2Knobs kn;
     CHECK(kn.split_min == 2048 && !kn.split_min_set && !kn.split_chunk_set && kn.nt_loads == 1 && kn.prune == 1 && !kn.group_rows_set && kn.prune_every == 1);
     CHECK(kn.slot_major == 1 && kn.tail_sectors == 2 && kn.tail_min == 64 && kn.pair && !kn.block_units && kn.exact_stop);
+    CHECK(kn.persist && kn.persist_wgs == 0 && !K2Launch().persist);
   }
   // ---- planes: the largest NumKmers the plain kernel meets
   CHECK(npl_of(0) == 8 && npl_of(254) == 8 && npl_of(255) == 10 && npl_of(1022) == 10 && npl_of(1023) == 16 && npl_of(65534) == 16 && npl_of(65535) == 24);
@@ -275,6 +279,57 @@ int main() {
     t.n_reads = 100000;
     CHECK(plain(t).launches[0].k2_flags == 0 && plain(group_rows(t, 4)).launches[0].k2_flags == 0);
   }
+  // ---- the persistent kernel: the launch of the 64-lane class that takes the short-read unit tile by tile, unless KMCPG_K2_PERSIST=0
+  {
+    const uint64_t G4 = 4294967296ull;
+    const K2Shape s = bytes(shape(1000, 150, {{64, 10, 3}, {8, 5, 0}}), G4);  // the default short-read shape of the block above
+    K2Plan p = plain(s);
+    CHECK(p.n_launches == 2 && p.launches[0].persist && p.launches[0].k2_flags == K2F_EXACT_STOP && p.launches[0].units == 10000 && !p.launches[1].persist);
+    K2Shape t = s;
+    t.max_n = 1022;  // 10 planes: the other instantiation
+    CHECK(plain(t).launches[0].persist && plain(t).launches[0].npl == 10);
+    t = s;
+    t.knobs.persist_wgs = 3;  // the grid is the launcher's business
+    CHECK(plain(t).launches[0].persist);
+    t = s;
+    t.knobs.persist = false;
+    CHECK(!plain(t).launches[0].persist && plain(t).launches[0].k2_flags == K2F_EXACT_STOP && plain(t).launches[0].gr == 4);
+    t = s;
+    t.knobs.block_units = true;  // block units with a list: several tiles per unit, the launched form
+    CHECK(!plain(t).launches[0].persist && plain(t).launches[0].block_units && plain(t).launches[0].k2_flags == 3);
+    t.classes[0].nbslots = 0;  // a class without the list: the bit is cleared, tile by tile again
+    CHECK(plain(t).launches[0].persist && plain(t).launches[0].k2_flags == K2F_EXACT_STOP && !plain(t).launches[0].block_units);
+    t.knobs.exact_stop = false;  // ... and with no bit left the plain loop of the body
+    CHECK(!plain(t).launches[0].persist && plain(t).launches[0].k2_flags == 0);
+    t = s;
+    t.knobs.exact_stop = false;
+    CHECK(!plain(t).launches[0].persist && plain(t).launches[0].k2_flags == 0);
+    t = s;
+    t.num_hashes = 2;
+    CHECK(!plain(t).launches[0].persist && plain(t).launches[0].multi && plain(t).launches[0].gr == 4);
+    t = s;
+    t.knobs.prune = 0;
+    CHECK(!plain(t).launches[0].persist && !plain(group_rows(t, 4)).launches[0].persist && plain(group_rows(t, 4)).launches[0].gr == 4);
+    t = s;
+    t.knobs.prune_every = 2;
+    CHECK(!plain(t).launches[0].persist && plain(t).launches[0].gr == 4);
+    CHECK(!plain(group_rows(s, 8)).launches[0].persist && plain(group_rows(s, 8)).launches[0].gr == 8);
+    CHECK(!plain(bytes(s, G4 - 1)).launches[0].persist && plain(group_rows(bytes(s, 0), 4)).launches[0].persist);
+    t = s;
+    t.max_n = 1023;  // 16 planes
+    t.n_reads = 100000;
+    CHECK(!plain(t).launches[0].persist && plain(t).launches[0].npl == 16 && !plain(group_rows(t, 4)).launches[0].persist);
+    // lane classes below 64: never, whatever their order
+    p = plain(bytes(shape(1000, 150, {{32, 4, 0}, {16, 2, 0}, {8, 1, 0}, {4, 1, 0}}), G4));
+    CHECK(p.n_launches == 4 && !p.launches[0].persist && !p.launches[1].persist && !p.launches[2].persist && !p.launches[3].persist && p.launches[0].gr == 4);
+    p = plain(bytes(shape(1000, 150, {{16, 2, 0}, {64, 10, 0}}), G4));
+    CHECK(!p.launches[0].persist && p.launches[1].persist);
+    // a pair plan, and the chunked launches behind a persistent one
+    p = plain(group_rows(two(20001, 3000), 8));
+    CHECK(p.n_launches == 1 && p.launches[0].kind == Kd::Pair && !p.launches[0].persist);
+    p = k2_plan(split_min(bytes(wide(100, 70000), G4), 254), true, 3, 70000);
+    CHECK(p.npl == 8 && p.n_launches == 2 && p.launches[0].persist && p.launches[1].kind == Kd::Split && !p.launches[1].persist);
+  }
   // ---- units, workgroups and the grid pieces under K2_MAX_BLOCKS
   {
     CHECK(k2_units(7, 5, 16, 1) == 35 && k2_units(7, 5, 16, 0) == 35 && k2_units(7, 5, 16, 2) == 56 && k2_units(7, 8, 16, 2) == 56 && k2_units(7, 9, 16, 2) == 84);
@@ -400,6 +455,7 @@ int main() {
           s.knobs.slot_major = v >> 5;
           s.knobs.block_units = (v & 8) != 0;
           s.knobs.pair = (v & 64) == 0;
+          s.knobs.persist = (v & 3) != 3;
           const bool ask = k2_ask_long(s);
           for (uint32_t listed : {0u, 1u, 511u, 1536u}) {
             if (listed > n_reads) continue;

@@ -17,7 +17,12 @@ slots: 906 and 246 units, neither a multiple of the claim run of 8, no slot boun
 them), and fewer units than the default grid has waves.  KMCPG_K2_PERSIST_WGS=1 is one workgroup over every unit — hundreds of units
 and every slot change inside a wave; 3 is a grid that is no divisor of anything; 4 096 has waves that find the queue dry at once.
 Two thresholds: the default (0.55: unrelated sectors stop early) and 0.36, in the body of the count distribution (mean 0.3 n), where
-thousands of hits come in runs and few sectors stop."""
+thousands of hits come in runs and few sectors stop.
+
+The witness of the kernel that ran is the record's grid (`Database.last_k2_grids()`): the launched form runs on the piece's
+workgroups, the persistent kernel on the grid it was given — KMCPG_K2_PERSIST_WGS, or what the chip holds at once, cut to the piece.
+Both batches are smaller than a chip, so a third one, p8 nineteen times over (BIG), has a piece no chip holds at once: there the
+default grid must be smaller than the piece."""
 import os
 
 import numpy as np
@@ -31,6 +36,10 @@ PITCH, SECTORS, TILES = 1920, 15, 2
 CAP = 1 << 21
 CLAIM_RUN = 8  # k2_claim.hpp K2_CLAIM_RUN
 QCOVS = (0.55, 0.36)
+# A piece larger than any chip's fill: a workgroup is four waves, a SIMD holds at most 10 (8 on gfx950), so a CU holds at most 10
+# workgroups of this kernel and 16 is beyond any; 256 CUs is the MI355X, and 16 x 256 = 4 096 also exceeds 10 x the 304 CUs of the
+# largest CDNA part.  p8 x 19 = 2 869 reads on six slots: 17 214 units, 4 304 workgroups.  (Its hits, 19 x 41 365, fit CAP.)
+BIG, BIG_REP, CHIP_WORKGROUPS = "p8x19", 19, 16 * 256
 KNOBS = ("KMCPG_GROUP_ROWS", "KMCPG_PRUNE", "KMCPG_PRUNE_EVERY", "KMCPG_SLOT_MAJOR", "KMCPG_NT_LOADS", "KMCPG_SPLIT_MIN", "KMCPG_SPLIT_CHUNK",
          "KMCPG_FPR_BOUND", "KMCPG_K2_BLOCK_UNITS", "KMCPG_K2_EXACT_STOP", "KMCPG_K2_PERSIST", "KMCPG_K2_PERSIST_WGS")
 # batch -> (planes, KMCPG_SPLIT_MIN, k-mers per read in batch order)
@@ -127,6 +136,16 @@ def state(oracle_lib):
                         bt["run"][i][b] = run
                         bt["counts"][i][b * COLS:(b + 1) * COLS] = cum[-1, :COLS]
                     at += n
+        # BIG: the reads of p8 BIG_REP times over — the model's inputs are p8's, read for read
+        src = batches["p8"]
+        lens = np.diff(src["offs"].cpu().numpy())
+        offs = np.zeros(BIG_REP * len(lens) + 1, dtype=np.int64)
+        offs[1:] = np.cumsum(np.tile(lens, BIG_REP))
+        big = dict(src, kms=src["kms"] * BIG_REP, ns=np.tile(src["ns"], BIG_REP), n_reads=BIG_REP * src["n_reads"], total=int(offs[-1]),
+                   seq=src["seq"].repeat(BIG_REP), offs=torch.from_numpy(offs).to(dev), run=src["run"] * BIG_REP, counts=src["counts"] * BIG_REP)
+        units = big["n_reads"] * BLOCKS * TILES
+        assert units % CLAIM_RUN != 0 and big["n_reads"] % CLAIM_RUN != 0 and (units + 3) // 4 > CHIP_WORKGROUPS
+        batches[BIG] = big
         db.set_profiling(2)
         yield dict(db=db, torch=torch, default_params=default_params, batches=batches)
     finally:
@@ -169,30 +188,35 @@ def _run(st, bt, qcov, persist, wgs):
     assert np.array_equal(qk.cpu().numpy(), bt["ns"].astype(np.int32))
     assert int(cnt[0].item()) <= CAP
     h = hits[:int(cnt[0].item())].to(torch.int64).cpu().numpy()
-    return db.last_gathered_bytes(), db.last_hash_bytes(), db.last_k2_launches(), h[np.lexsort((h[:, 1], h[:, 0]))]
+    launches, grids = db.last_k2_launches(), db.last_k2_grids()
+    assert len(grids) == len(launches)
+    return db.last_gathered_bytes(), db.last_hash_bytes(), launches, grids, h[np.lexsort((h[:, 1], h[:, 0]))]
 
 
 def _check(st, name, qcov, persist, wgs):
     bt = st["batches"][name]
-    got_rows, got_hashes, launches, hits = _run(st, bt, qcov, persist, wgs)
+    got_rows, got_hashes, launches, grids, hits = _run(st, bt, qcov, persist, wgs)
     want_rows, want_hashes, want_hits = _model(bt, qcov)
-    print("%s qcov %.2f persist %s wgs %s: row bytes %d (model %d), hash bytes %d (model %d), %d hits (model %d), launches %s" % (
-        name, qcov, persist, wgs, got_rows, want_rows, got_hashes, want_hashes, len(hits), len(want_hits), launches))
+    print("%s qcov %.2f persist %s wgs %s: row bytes %d (model %d), hash bytes %d (model %d), %d hits (model %d), launches %s, grids %s" % (
+        name, qcov, persist, wgs, got_rows, want_rows, got_hashes, want_hashes, len(hits), len(want_hits), launches, grids))
     assert len(want_hits) > 0
     assert np.array_equal(hits, want_hits)
     assert got_rows == want_rows
     assert got_hashes == want_hashes
-    return launches
+    # every launch but the persistent one (the first record, where there is one) runs on its piece's workgroups
+    assert [g for g in grids[1:]] == [w[6] for w in launches[1:]]
+    return launches, grids
 
 
 @pytest.mark.parametrize("name", sorted(BATCHES))
 def test_model_holds_for_the_launched_form(state, name):
     """one unit per wave, as launched (KMCPG_K2_PERSIST=0): the same model, and the record every persistent run must leave too"""
     bt = state["batches"][name]
-    launches = _check(state, name, QCOVS[0], 0, None)
+    launches, grids = _check(state, name, QCOVS[0], 0, None)
     units = bt["n_reads"] * BLOCKS * TILES
     assert launches[0] == ("plain", 64, 0, bt["npl"], False, 4, (units + 3) // 4)
     assert [w[0] for w in launches[1:]] == ["split"]
+    assert grids[0] == launches[0][6]  # one wave per unit: the launched form
     state.setdefault("witness", {})[name] = launches
 
 
@@ -201,10 +225,26 @@ def test_model_holds_for_the_launched_form(state, name):
 @pytest.mark.parametrize("name", sorted(BATCHES))
 def test_persistent_waves(state, name, qcov, wgs):
     bt = state["batches"][name]
-    launches = _check(state, name, qcov, 1, wgs)
+    launches, grids = _check(state, name, qcov, 1, wgs)
     units = bt["n_reads"] * BLOCKS * TILES
     # the witness names the plan's piece, whatever grid its waves ran on: today's record
     assert launches[0] == ("plain", 64, 0, bt["npl"], False, 4, (units + 3) // 4)
     assert [w[0] for w in launches[1:]] == ["split"]
     if name in state.get("witness", {}):
         assert launches == state["witness"][name]
+    # ... and the grid is the persistent kernel's: the one asked for, or the chip's fill cut to the piece
+    if wgs is None:
+        assert 1 <= grids[0] <= launches[0][6]
+    else:
+        assert grids[0] == wgs
+
+
+def test_persistent_grid_is_the_chips_fill(state):
+    """a piece of more workgroups than a chip holds at once: the default grid is smaller than the piece, the hits and bytes the model's"""
+    bt = state["batches"][BIG]
+    launches, grids = _check(state, BIG, QCOVS[0], 1, None)
+    units = bt["n_reads"] * BLOCKS * TILES
+    assert launches[0] == ("plain", 64, 0, bt["npl"], False, 4, (units + 3) // 4)
+    assert [w[0] for w in launches[1:]] == ["split"]
+    assert launches[0][6] > CHIP_WORKGROUPS
+    assert 1 <= grids[0] < launches[0][6]
