@@ -138,8 +138,9 @@ def planes_for(max_n):
 
 
 def expect(db, batch, env, index_bytes=0):
-    """The launches (sorted list of forms) kmcpg_query_device must make for batch `batch` of database `db` under `env`."""
-    ns = BATCH_N[batch]
+    """The launches (sorted list of forms) kmcpg_query_device must make for batch `batch` of database `db` under `env`.
+    `batch`: a plane class of BATCH_N, or the NumKmers of a batch of the caller's own (tests/k2_overflow.py)."""
+    ns = BATCH_N[batch] if isinstance(batch, int) else list(batch)
     classes, slots = lane_classes(stride_of(db), db.nh, db.open_env)
     multi = db.nh > 1
     groups = 1 if LAYOUT[db.layout].step == 0 else LAYOUT[db.layout].blocks

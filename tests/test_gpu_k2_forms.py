@@ -63,7 +63,7 @@ class _Env:
 
 # every variable a case may set is cleared first, so a case runs under its own settings only
 _KNOBS = ("KMCPG_GROUP_ROWS", "KMCPG_PRUNE", "KMCPG_SPLIT_MIN", "KMCPG_SPLIT_CHUNK", "KMCPG_PAIR", "KMCPG_TAIL_SECTORS", "KMCPG_TAIL_MIN", "KMCPG_SLOT_MAJOR",
-          "KMCPG_NT_LOADS", "KMCPG_PRUNE_EVERY")
+          "KMCPG_NT_LOADS", "KMCPG_PRUNE_EVERY", "KMCPG_K2_BLOCK_UNITS", "KMCPG_K2_EXACT_STOP", "KMCPG_K2_PERSIST", "KMCPG_K2_PERSIST_WGS")
 _OPEN_KNOBS = ("KMCPG_ROW_ALIGN", "KMCPG_LPR32", "KMCPG_LPR8", "KMCPG_SPLIT_TILES", "KMCPG_FUSE")
 
 
