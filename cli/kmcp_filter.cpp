@@ -25,75 +25,15 @@
 
 #include "../kmcp_amd/csrc/specific_rule.hpp"
 #include "../kmcp_amd/csrc/taxonomy.hpp"
+#include "tsv_in.hpp"
 #include "tsv_out.hpp"
 
 namespace {
 
+using tsv_in::parse_float;
+using tsv_in::RawLines;
 using tsv_out::die;
 using tsv_out::Out;
-
-// gz-or-plain reader of whole lines, end-of-line kept (zlib reads plain files transparently)
-struct RawLines {
-  gzFile f = nullptr;
-  std::vector<char> buf;
-  size_t pos = 0, end = 0;
-  bool eof = false;
-  explicit RawLines(const std::string& path) : buf(1 << 20) {
-    f = path == "-" ? gzdopen(0, "rb") : gzopen(path.c_str(), "rb");
-    if (!f) die("%s: %s", path.c_str(), strerror(errno));
-    gzbuffer(f, 1 << 18);
-  }
-  ~RawLines() {
-    if (f) gzclose(f);
-  }
-  bool fill() {
-    if (eof) return false;
-    if (pos > 0) {
-      memmove(buf.data(), buf.data() + pos, end - pos);
-      end -= pos;
-      pos = 0;
-    }
-    if (end == buf.size()) buf.resize(buf.size() * 2);
-    const int n = gzread(f, buf.data() + end, (unsigned)(buf.size() - end));
-    if (n < 0) die("read error");
-    if (n == 0) {
-      eof = true;
-      return false;
-    }
-    end += (size_t)n;
-    return true;
-  }
-  // the next line inside the buffer (valid until the next call); *n includes its '\n' when it has one
-  bool next(const char** p, size_t* n) {
-    for (;;) {
-      const char* nl = (const char*)memchr(buf.data() + pos, '\n', end - pos);
-      if (nl) {
-        *p = buf.data() + pos;
-        *n = (size_t)(nl - *p) + 1;
-        pos += *n;
-        return true;
-      }
-      if (!fill()) {
-        if (pos == end) return false;
-        *p = buf.data() + pos;
-        *n = end - pos;
-        pos = end;
-        return true;
-      }
-    }
-  }
-};
-
-// strconv.ParseFloat of a field: the whole field must be a number
-bool parse_float(const char* p, size_t n, double* v) {
-  if (n == 0 || n > 63 || p[0] == ' ' || p[0] == '\t') return false;
-  char tmp[64];
-  memcpy(tmp, p, n);
-  tmp[n] = 0;
-  char* e = nullptr;
-  *v = strtod(tmp, &e);
-  return e == tmp + n;
-}
 
 void usage() {
   fputs(
@@ -184,16 +124,8 @@ int main(int argc, char** argv) {
     }
   }
   if (files.empty()) files.push_back("-");
-  auto clean = [](std::string p) {  // as much of filepath.Clean as two spellings of one path usually differ by
-    while (p.size() > 2 && p[0] == '.' && p[1] == '/') p.erase(0, 2);
-    std::string o;
-    for (char c : p)
-      if (!(c == '/' && !o.empty() && o.back() == '/')) o.push_back(c);
-    while (o.size() > 1 && o.back() == '/') o.pop_back();
-    return o;
-  };
   for (const std::string& f : files)
-    if (f != "-" && clean(f) == clean(out_file)) die("out file should not be one of the input file");
+    if (f != "-" && tsv_in::clean_path(f) == tsv_in::clean_path(out_file)) die("out file should not be one of the input file");
 
   kmcpg::TaxidMap tmap;
   kmcpg::Taxonomy tax;

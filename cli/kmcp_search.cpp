@@ -91,6 +91,12 @@ struct Options {
   int min_qlen = 30, min_kmers = 10, dedup = 256, top_scores = 0, threads = 0, device = 0, batch = 131072, gpus = 1, gpu_passes = -1;
   bool batch_given = false;
   // --sliding-step / --sliding-window / --sliding-greedy: every record searched as the windows `seqkit sliding -s S -W W [-g]` would cut
+  // --regions-bed FILE [--regions-*]: with --specific-level and --sliding-*, the specific windows merged into regions (BED6) — what
+  // kmcp-filter and kmcp-regions make of the sliding search's TSV, without the TSV (K5 of the library, kmcpg_submit_windows_summary)
+  std::string regions_bed, regions_name_species = "species-specific", regions_name_assembly = "assembly-specific";
+  long long regions_min_overlap = 1, regions_max_gap = 0;
+  bool regions_ignore_type = false, out_file_given = false;
+  const char* regions_flag = nullptr;  // the first --regions-* flag other than --regions-bed that was given
   long long sliding_step = 0, sliding_window = 0;
   bool sliding_step_given = false, sliding_window_given = false, sliding_greedy = false;
   std::vector<int32_t> gpu_ids;
@@ -128,8 +134,13 @@ static void usage() {
       "                             the output is what `kmcp-filter -f 1 -t 0 --level L -T ... -X ...` makes of this command's output\n"
       "                             without these flags, followed by the trailer; the decision is made on the GPU.  Targets are the printed\n"
       "                             ones (after -N / -D); at level species every target of the database needs a TaxId.\n"
-      "                             Not with -K, --try-se, -n, --sliding-*, --gpus/--gpu-ids, --gpu-passes.\n"
+      "                             Not with -K, --try-se, -n, --sliding-* (except for --regions-bed), --gpus/--gpu-ids, --gpu-passes.\n"
       "           --parse-only (read the inputs and print records / bases / checksum per file; no database, no GPU)\n"
+      "           --regions-bed file [--regions-min-overlap int (1)] [--regions-max-gap int (0)] [--regions-ignore-type]\n"
+      "                             [--regions-name-species string] [--regions-name-assembly string]\n"
+      "                             with --specific-level AND --sliding-step/--sliding-window: merge the specific windows of every\n"
+      "                             record into regions (BED6; .gz honoured) — what kmcp-filter -f 1 -t 0 and kmcp-regions -f 1 -t 0 make\n"
+      "                             of the sliding search's output, in one pass.  No search result is written: not with -o.\n"
       "Long reads and contigs (the reference's advice: split them with `seqkit sliding -s 100 -W 300`, search the pieces):\n"
       "           --sliding-step int --sliding-window int [--sliding-greedy]\n"
       "                             search every window of every record, as `seqkit sliding -s S -W W [-g] | kmcp search` would,\n"
@@ -163,10 +174,21 @@ static Options parse_args(int argc, char** argv) {
       {"sort-by", 's', 1}, {"do-not-sort", 'S', 0}, {"threads", 'j', 1}, {"quiet", 'q', 0}, {"infile-list", 'i', 1}, {"log", 0, 1},
       {"gpu", 0, 1}, {"gpu-batch", 0, 1}, {"gpus", 0, 1}, {"gpu-ids", 0, 1}, {"gpu-passes", 0, 1}, {"parse-only", 0, 0}, {"help", 'h', 0}, {"version", 'V', 0},
       {"sliding-step", 0, 1}, {"sliding-window", 0, 1}, {"sliding-greedy", 0, 0}, {"also-db", 0, 1},
-      {"specific-level", 0, 1}, {"taxid-map", 0, 1}, {"taxdump", 0, 1}};
+      {"specific-level", 0, 1}, {"taxid-map", 0, 1}, {"taxdump", 0, 1},
+      {"regions-bed", 0, 1}, {"regions-min-overlap", 0, 1}, {"regions-max-gap", 0, 1}, {"regions-ignore-type", 0, 0},
+      {"regions-name-species", 0, 1}, {"regions-name-assembly", 0, 1}};
+  auto regions_flag = [&](const char* flag) {
+    if (!o.regions_flag) o.regions_flag = flag;
+  };
   auto apply = [&](const std::string& name, const std::string& v) {
     if (name == "db-dir") o.db_dir = v;
-    else if (name == "out-file") o.out_file = v;
+    else if (name == "out-file") { o.out_file = v; o.out_file_given = true; }
+    else if (name == "regions-bed") o.regions_bed = v;
+    else if (name == "regions-min-overlap") { o.regions_min_overlap = to_i(name, v); regions_flag("--regions-min-overlap"); }
+    else if (name == "regions-max-gap") { o.regions_max_gap = to_i(name, v); regions_flag("--regions-max-gap"); }
+    else if (name == "regions-ignore-type") { o.regions_ignore_type = true; regions_flag("--regions-ignore-type"); }
+    else if (name == "regions-name-species") { o.regions_name_species = v; regions_flag("--regions-name-species"); }
+    else if (name == "regions-name-assembly") { o.regions_name_assembly = v; regions_flag("--regions-name-assembly"); }
     else if (name == "read1") o.read1 = v;
     else if (name == "read2") o.read2 = v;
     else if (name == "try-se") o.try_se = true;
@@ -274,6 +296,7 @@ static Options parse_args(int argc, char** argv) {
 }
 
 #include "../kmcp_amd/csrc/taxonomy.hpp"
+#include "../kmcp_amd/csrc/regions_rule.hpp"
 #include "search_batch.hpp"
 #include "row_format.hpp"
 
@@ -443,7 +466,8 @@ static int validate_flags(const Options& o, bool sliding) {
     const bool species = o.specific_level == "species";
     if (!species && o.specific_level != "strain" && o.specific_level != "assembly")
       die("invalid value for --specific-level, available values: species, strain/assembly");
-    const char* bad = o.keep_unmatched ? "-K/--keep-unmatched" : o.try_se ? "--try-se" : o.top_scores != 0 ? "-n/--keep-top-scores" : sliding ? "--sliding-step/--sliding-window/--sliding-greedy"
+    const char* bad = o.keep_unmatched ? "-K/--keep-unmatched" : o.try_se ? "--try-se" : o.top_scores != 0 ? "-n/--keep-top-scores"
+                      : sliding && o.regions_bed.empty() ? "--sliding-step/--sliding-window/--sliding-greedy"  // (with --regions-bed: the windows' summaries, below)
                       : o.gpus_given ? "--gpus/--gpu-ids" : o.gpu_passes >= 0 ? "--gpu-passes" : nullptr;
     if (bad) die("flag %s cannot be combined with --specific-level", bad);
     if (!o.taxid_maps.empty() && o.taxdump.empty()) die("flag --taxdump is needed when --taxid-map given");
@@ -482,6 +506,15 @@ static int validate_flags(const Options& o, bool sliding) {
   else die("invalid value for flag -s/--sort-by: %s. Available: qcov/tsov/jacc", o.sort_by.c_str());
   if (o.min_qcov < 0 || o.min_qcov > 1) die("value of -t/--min-query-cov should be in range [0, 1]");
   if (o.min_tcov < 0 || o.min_tcov > 1) die("value of -T/-target-cov should be in range [0, 1]");
+  // --regions-bed: the windows of --sliding-* judged by --specific-level, merged into regions; no search result is written
+  if (o.regions_bed.empty() && o.regions_flag) die("flag %s is only used with --regions-bed", o.regions_flag);
+  if (!o.regions_bed.empty()) {
+    if (o.specific_level.empty()) die("flag --regions-bed needs --specific-level: regions are merged from species- or assembly-specific windows");
+    if (!sliding) die("flag --regions-bed needs --sliding-step and --sliding-window: regions are merged from the windows of the input");
+    if (o.out_file_given) die("flag -o/--out-file cannot be combined with --regions-bed: no search result is written, the regions go to the BED file");
+    if (o.regions_min_overlap < 1) die("value of flag --regions-min-overlap should be positive");
+    if (o.regions_max_gap < 0) die("value of flag --regions-max-gap should not be negative");
+  }
   if (!o.quiet) {
     info("kmcp-search v%s (MI355X build of the kmcp search hot path)", VERSION);
     info("  https://github.com/shenwei356/kmcp");
@@ -626,6 +659,7 @@ struct Pipeline {
   // ---- constant context: nothing below is written while a thread that reads it runs
   const Options& o;  // (main goes on writing o.batch and o.gpu_ids while it opens the database: no thread reads those two)
   const bool paired, sliding;
+  bool regions() const { return !o.regions_bed.empty(); }
   const kmcpg_window_spec wspec;
   // set by main after the database open and before the searchers start; the reader never looks at them
   kmcpg_db* db = nullptr;
@@ -1037,8 +1071,8 @@ struct Searcher {
     std::unique_ptr<Batch> bb = std::move(fl.front().second);
     fl.pop_front();
     const auto t0 = Clock::now();
-    const int rc = kmcpg_wait_pairs(t, &bb->res);
-    if (rc == KMCPG_ENOMEM) search_sync(*bb);  // (kmcpg_wait consumed the ticket; the batch's buffers are still ours)
+    const int rc = p.regions() ? kmcpg_wait_summaries(t, &bb->sres) : kmcpg_wait_pairs(t, &bb->res);
+    if (rc == KMCPG_ENOMEM && !p.regions()) search_sync(*bb);  // (kmcpg_wait consumed the ticket; the batch's buffers are still ours)
     else if (rc != 0) die("%s", kmcpg_last_error());
     my_gpu += seconds_since(t0);
     publish(std::move(bb));
@@ -1046,6 +1080,7 @@ struct Searcher {
 
   // the asynchronous form that takes the batch as the reader left it: the records' windows, packed codes, or text
   int submit(Batch& b, kmcpg_ticket** t) {
+    if (b.windows && p.regions()) return kmcpg_submit_windows_summary(p.db, b.seqs.data(), b.offs.data(), (uint32_t)(b.offs.size() - 1), &p.wspec, &p.params, t);
     if (b.windows) return kmcpg_submit_windows(p.db, b.seqs.data(), b.offs.data(), (uint32_t)(b.offs.size() - 1), &p.wspec, &p.params, t);
     if (b.packed) return kmcpg_submit_packed(p.db, b.codes.data(), b.offs.data(), b.exc.data(), b.n_exc, (uint32_t)b.size(), &p.params, t);
     return kmcpg_submit(p.db, b.seqs.data(), b.offs.data(), b.paired ? b.seqs2.data() : nullptr, b.paired ? b.offs2.data() : nullptr, (uint32_t)b.size(),
@@ -1080,6 +1115,7 @@ struct Searcher {
         if (!b->windows) break;
         std::this_thread::sleep_for(std::chrono::microseconds(200));
       }
+      if (rc == KMCPG_ENOMEM && p.regions()) die("%s", kmcpg_last_error());  // (summaries have no one-call form)
       if (rc == KMCPG_EBUSY || rc == KMCPG_ENOMEM) {  // no lane / a batch that must be halved: the one-call form
         search_sync(*b);
         my_gpu += seconds_since(t0);
@@ -1205,6 +1241,7 @@ static uint64_t format_part(const Pipeline& p, const Batch& b, uint32_t lo, uint
 // the batch's vectors go back to the reader (fastx_reader.hpp ChunkPool)
 static void recycle(Batch& b) {
   kmcpg_result_pairs_free(&b.res);
+  kmcpg_result_summaries_free(&b.sres);
   ChunkPool::get().give(b.id_buf, b.id_offs, b.seqs, b.offs);
   if (b.paired) {
     std::vector<char> no_ids;
@@ -1263,6 +1300,35 @@ static void write_results(Pipeline& p, Out& out) {
   }
   q_flush.close();
   flusher.join();
+}
+
+// --regions-bed: the batches in input order through ONE streaming merger (kmcp_amd/csrc/regions_rule.hpp); a window with a summary is a
+// query of the filtered TSV, named <record>_sliding:<start + 1>-<end>: the record's name is the region's reference
+static void write_regions(Pipeline& p, Out& out, kmcpg::RegionMerger& merger) {
+  std::map<uint64_t, std::unique_ptr<Batch>> pending;
+  uint64_t next_seq = 0;
+  std::string bed;
+  while (std::unique_ptr<Batch> b = next_in_order(p, pending, next_seq)) {
+    next_seq += b->n_seq;
+    const auto tf0 = Clock::now();
+    const kmcpg_result_summaries& r = b->sres;
+    size_t wr = 0;
+    for (uint32_t i = 0; i < r.n_windows; i++) {
+      if (r.s[i].n_targets == 0) continue;
+      while (b->wpre[wr + 1] <= i) wr++;
+      const WindowSpan w = window_span(b->offs[wr + 1] - b->offs[wr], i - b->wpre[wr], p.wspec);
+      const std::string_view rid = b->id(wr);
+      merger.add(rid.data(), rid.size(), (int64_t)w.start + 1, (int64_t)w.end, r.s[i].n_targets, r.s[i].score, &bed);
+      p.matched++;
+    }
+    out.write(bed);
+    bed.clear();
+    p.total += r.n_windows;
+    recycle(*b);
+    p.t_fmt += seconds_since(tf0);
+  }
+  merger.finish(&bed);
+  out.write(bed);
 }
 
 // ---- the end of a run
@@ -1355,8 +1421,8 @@ int main(int argc, char** argv) {
   if (!o.specific_level.empty()) set_specific(o, p.db, p.target, taxonomy.get(), taxid_map.get());
 
   p.t_search = Clock::now();
-  Out out(o.out_file);
-  if (!o.no_header) out.write("#query\tqLen\tqKmers\tFPR\thits\ttarget\tchunkIdx\tchunks\ttLen\tkSize\tmKmers\tqCov\ttCov\tjacc\tqueryIdx\n");
+  Out out(p.regions() ? o.regions_bed : o.out_file);
+  if (!o.no_header && !p.regions()) out.write("#query\tqLen\tqKmers\tFPR\thits\ttarget\tchunkIdx\tchunks\ttLen\tkSize\tmKmers\tqCov\ttCov\tjacc\tqueryIdx\n");
   open_gate(p, dbi.k);
 
   const int n_search = p.paged_passes > 1 ? 1 : 2;  // (see Searcher)
@@ -1365,12 +1431,29 @@ int main(int argc, char** argv) {
   std::vector<std::thread> searchers;
   for (int si = 0; si < n_search; si++) searchers.emplace_back(&Searcher::run, &searcher_state.emplace_back(p));
 
-  write_results(p, out);
+  kmcpg::RegionParams region_params;
+  region_params.min_overlap = o.regions_min_overlap;
+  region_params.max_gap = o.regions_max_gap;
+  region_params.ignore_type = o.regions_ignore_type;
+  region_params.name_species = o.regions_name_species;
+  region_params.name_assembly = o.regions_name_assembly;
+  kmcpg::RegionMerger merger(region_params);
+  if (p.regions()) write_regions(p, out, merger);
+  else write_results(p, out);
   reader.join();
   for (auto& t : searchers) t.join();
 
-  if (!o.quiet) print_summary(p);
-  write_trailer(p, out);
+  if (p.regions()) {
+    if (!o.quiet) {
+      fprintf(stderr, "\n");
+      info("specific regions: %llu windows, %llu with a summary (species- or assembly-specific), %llu regions saved to: %s", (unsigned long long)p.total,
+           (unsigned long long)p.matched, (unsigned long long)merger.n_regions, o.regions_bed.c_str());
+    }
+    out.close();
+  } else {
+    if (!o.quiet) print_summary(p);
+    write_trailer(p, out);
+  }
   // Everything the user asked for is on disk.  Giving back pinned staging buffers, streams and a resident index one by one takes
   // ~0.1 s and the runtime's own exit handlers as long again (profiles/r06_cli_e2e.txt) — a short-lived process leaves that to the
   // kernel driver, which reclaims a dead process's GPU memory anyway (the Go reference exits the same way: search.go:1027).

@@ -385,6 +385,66 @@ typedef struct {
 } kmcpg_specific_stats;
 int kmcpg_last_specific(kmcpg_db* db, kmcpg_specific_stats* out, kmcpg_k4_launch* launches, uint32_t cap, uint32_t* n_launches);
 
+/* -- window summaries for region merging (K5, k5_summary.hip): what `kmcp utils merge-regions` derives from the rows of one query before
+ *    it merges (kmcp/cmd/merge-regions.go:256-279; kmcp_amd/csrc/regions_rule.hpp states the rule): n_targets = the distinct targets among
+ *    the window's surviving matches (0: no rows — unmatched, or dropped by K4), score = the printed qCov ("%.4f", parsed back) of the
+ *    first row of each distinct target, added in print order in float64 and divided by n_targets when it is above 1.  Bit for bit what
+ *    kmcp-regions computes from the TSV rows of the window.
+ *    kmcpg_summarize_device runs the stage alone on device pointers, as kmcpg_specific_device runs K4, whose outputs it takes: d_pairs /
+ *    d_offs = the surviving segments (at most pair_cap pairs), d_verdicts, d_qkmers, n windows; the tables are those of
+ *    kmcpg_set_specific (KMCPG_EINVAL while the stage is off).  Window i gets d_out[i].  A window the device does not summarise — several
+ *    targets among more than 64 pairs, and every window with verdict KMCPG_SPECIFIC_HOST, whose pairs still face the host's -f test — has
+ *    flags = KMCPG_SUMMARY_LEFT (| KMCPG_SUMMARY_HOST), n_targets = the number of its pairs, and its pairs, and only those, are copied to d_left_pairs[d_left_offs[i] ..
+ *    d_left_offs[i + 1]) in their order (d_left_offs: n + 1 words; left_cap >= pair_cap).  A window of one target is summarised on the
+ *    device at any length.  Only enqueues on `stream`.
+ *    kmcpg_last_summary: the witness of the handle's last K5 launch (the call waits for the device to go idle): windows summarised as a
+ *    single target, by the wave (several targets), left to the host, and empty or dropped — the four add up to the windows —; the pairs
+ *    of the LEFT windows; segments that did not lie inside pair_cap (treated as empty; must be 0); and, at profiling level >= 1, the
+ *    HIP-event time of the stage's kernels and one record per kernel launched (the scan's records carry KMCPG_K4_SCAN_*). */
+#define KMCPG_SUMMARY_LEFT 1u
+#define KMCPG_SUMMARY_HOST 2u  /* with LEFT: the window's verdict was KMCPG_SPECIFIC_HOST */
+typedef struct {
+  uint32_t n_targets;  /* LEFT (kmcpg_summarize_device only): the number of the window's pairs in d_left_pairs */
+  uint32_t flags;      /* bit 0: KMCPG_SUMMARY_LEFT, bit 1: KMCPG_SUMMARY_HOST; 0 in every record of kmcpg_wait_summaries */
+  double score;
+} kmcpg_window_summary;
+enum { KMCPG_K5_SUMMARY = 16, KMCPG_K5_COMPACT = 17 };  /* kmcpg_k4_launch.kernel of K5's own kernels */
+typedef struct {
+  uint64_t single, wave, left, empty;  /* windows by the class they took */
+  uint64_t left_pairs;                 /* pairs of the LEFT windows (kmcpg_wait_summaries: downloaded for them) */
+  uint64_t bytes_d2h;                  /* kmcpg_wait_summaries: bytes that came from the device for the ticket; 0 after kmcpg_summarize_device */
+  uint64_t bad_segments;
+  double k5_ms;                        /* HIP-event time of the stage's kernels at profiling level >= 1; -1 otherwise */
+} kmcpg_summary_stats;
+int kmcpg_summarize_device(kmcpg_db* db, const kmcpg_pair* d_pairs, const uint64_t* d_offs, uint64_t pair_cap, const uint8_t* d_verdicts,
+                           const int32_t* d_qkmers, uint32_t n, kmcpg_window_summary* d_out, kmcpg_pair* d_left_pairs, uint64_t left_cap,
+                           uint64_t* d_left_offs, void* stream);
+int kmcpg_last_summary(kmcpg_db* db, kmcpg_summary_stats* out, kmcpg_k4_launch* launches, uint32_t cap, uint32_t* n_launches);
+/*    kmcpg_submit_windows_summary: kmcpg_submit_windows with the species-specific stage ON (KMCPG_EINVAL while it is off) and K5 behind
+ *    it: the result is one summary per window instead of its matches — what `kmcp-search --regions-bed` merges into regions.  Per window
+ *    16 bytes of summary and its qlen / qkmers leave the GPU, no pairs and no offsets; the windows the device LEFT have their pairs
+ *    downloaded and are summarised by the host half (its -f test, the rule of specific_rule.hpp where the verdict was HOST, then
+ *    regions_rule.hpp), so every record the caller sees is final and has flags = 0.  KMCPG_EUNSUPPORTED as for the stage (try_se,
+ *    top_n_scores != 0, several k-mer sizes with k == 0) and on database sets.  Windows cut into pieces, KMCPG_WINDOWS_HOST=1 (window
+ *    text), KMCPG_SPECIFIC_DEVICE=0 (every window with matches LEFT) and KMCPG_DEVICE_FINALIZE=0 (no K3: the summaries come from the
+ *    finished records) give the same records.  The ticket is consumed by kmcpg_wait_summaries ONLY: kmcpg_wait and kmcpg_wait_pairs
+ *    refuse it (KMCPG_EINVAL, the ticket stays valid), and kmcpg_wait_summaries refuses every other ticket.  kmcpg_submit_windows and
+ *    kmcpg_submit_packed_windows keep refusing a handle with the stage on.  After kmcpg_wait_summaries kmcpg_last_summary reports the
+ *    TICKET: its windows by who summarised them (single / wave: the device, left: the host, empty: no rows), the pairs downloaded for
+ *    the LEFT windows and the bytes that came from the device. */
+typedef struct {
+  uint32_t n_windows;
+  uint32_t reserved;
+  int32_t* qlen;
+  int32_t* qkmers;
+  kmcpg_window_summary* s;  /* [n_windows] */
+  void* owner;              /* internal */
+} kmcpg_result_summaries;
+int kmcpg_submit_windows_summary(kmcpg_db* db, const uint8_t* seqs, const uint64_t* offs, uint32_t n_reads, const kmcpg_window_spec* spec,
+                                 const kmcpg_params* params, kmcpg_ticket** out);
+int kmcpg_wait_summaries(kmcpg_ticket* ticket, kmcpg_result_summaries* out);
+void kmcpg_result_summaries_free(kmcpg_result_summaries* r);
+
 /* -- benchmarking / full-size parity support (no counterpart in the reference) ------------------ */
 typedef struct {
   int32_t k;            /* 21 */

@@ -231,4 +231,26 @@ struct K4Args {
   uint32_t* stats;               // [K4_STATS], zero on entry
 };
 
+// K5 (k5_summary.hip): K4's surviving segments -> one 16-byte summary per window (regions_rule.hpp); the segments it cannot summarise
+// exactly are LEFT to the host and compacted.
+constexpr uint32_t K5_CAP = 64;  // longest segment of several targets the device summarises
+constexpr int K5_STATS = 5;      // windows single-target / by the wave / LEFT / empty or dropped, segments outside the buffer
+struct K5Args {
+  const kmcpg_pair* pairs;       // K4's output: the surviving segments in print order
+  const uint64_t* offs;          // [n_reads + 1]
+  uint64_t pair_cap;             // pairs there is room for behind `pairs`: a segment that ends behind it is treated as empty
+  const uint8_t* verdict;        // [n_reads] K4's bytes: DROP = no rows, HOST = LEFT
+  const int32_t* nk;             // NumKmers per window
+  uint32_t n_reads;
+  uint32_t n_cols;
+  const uint32_t* target_class;  // [n_cols]
+  kmcpg_window_summary* out;     // out [n_reads]
+  uint32_t* cnt;                 // [n_reads + 1] scratch: the LEFT lengths
+  uint64_t* sums;                // scan scratch, one word per 4096 windows
+  kmcpg_pair* left_pairs;        // out: left_offs[n_reads] pairs
+  uint64_t* left_offs;           // out [n_reads + 1]
+  uint64_t left_cap;
+  uint32_t* stats;               // [K5_STATS], zero on entry
+};
+
 }  // namespace kmcpg

@@ -832,6 +832,9 @@ extern "C" int kmcpg_close(kmcpg_db* db) {
   if (db->d_spec_stats) (void)hipFree(db->d_spec_stats);
   for (auto& ev : db->spec_ev)
     if (ev) (void)hipEventDestroy(ev);
+  if (db->d_sum_stats) (void)hipFree(db->d_sum_stats);
+  for (auto& ev : db->sum_ev)
+    if (ev) (void)hipEventDestroy(ev);
   kmcpg::release_fpr_bounds(db);
   kmcpg::async_release(db);
   if (db->k1_stream) (void)hipStreamDestroy(db->k1_stream);

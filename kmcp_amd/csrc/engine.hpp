@@ -235,6 +235,16 @@ struct kmcpg_db {
   hipEvent_t spec_ev[2] = {};  // around the stage's kernels (profiling >= 1)
   bool spec_timed = false;
   std::vector<kmcpg_k4_launch> k4_log;
+  // K5, the window summaries behind K4 (k5_summary.hip): its counters (K5_STATS 32-bit words, then at byte 32 the LEFT pairs as a 64-bit
+  // word) and what its last launch noted; the scratch is K4's
+  uint64_t* d_sum_stats = nullptr;
+  bool sum_ran = false;
+  hipEvent_t sum_ev[2] = {};
+  bool sum_timed = false;
+  std::vector<kmcpg_k4_launch> k5_log;
+  // ... or, after kmcpg_wait_summaries, what that ticket's batches came to (all its pieces; counted on the host from the records)
+  bool sum_from_ticket = false;
+  kmcpg_summary_stats sum_ticket{};
   std::vector<kmcpg::FprBoundTable> fpr_bounds;  // -f bound tables (query.cpp fpr_bound): one per (max_fpr, size), never rewritten
   hipEvent_t ev[16] = {};   // ring of 4 calls x (start, COBS start, COBS done, k-mers done)
   uint64_t ev_calls = 0;    // profiled calls so far

@@ -1,6 +1,7 @@
 // host.cpp — what is above a lane (lane.hpp) in the pipeline on host buffers: a ticket over the handle's GPUs (submit_impl), the host half
 // of a wait (finish_raw), the retry walk of --try-se and of multi-k databases (retry_unmatched), the pieces and the ENOMEM halves of
-// kmcpg_search_batch, and the submit / wait / search entries with kmcpg_batch_hint.
+// kmcpg_search_batch, the host half of a summary ticket (finish_summary: K5's records, the windows it left), and the submit / wait / search
+// entries with kmcpg_batch_hint.
 // Reference counterparts: handleQuery (util-db-search.go:763-1025), :831-850, :1001-1014.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -15,16 +16,20 @@
 #include <vector>
 
 #include "exchange.hpp"
+#include "k3_set_order.hpp"
 #include "lane.hpp"
+#include "regions_rule.hpp"
+#include "specific_rule.hpp"
 
 namespace kmcpg {
 
-int submit_impl(kmcpg_db* db, const HostBatch& b, const kmcpg_params& p, bool retry, bool block, kmcpg_ticket** out, const PackedIn* packed) {
+int submit_impl(kmcpg_db* db, const HostBatch& b, const kmcpg_params& p, bool retry, bool block, kmcpg_ticket** out, const PackedIn* packed, bool summary) {
   std::unique_ptr<kmcpg_ticket> t(new kmcpg_ticket());
   t->db = db;
   t->n = b.n;
   t->paired = b.seqs2 != nullptr;
   t->p = p;
+  t->summary = summary;
   if (db->paged_passes > 0) {
     int rc = search_paged(db, b, p, t.get());
     if (rc) return rc;
@@ -54,6 +59,7 @@ int submit_impl(kmcpg_db* db, const HostBatch& b, const kmcpg_params& p, bool re
   auto one = [&](size_t i) {
     auto& pt = t->parts[i];
     rcs[i] = packed ? stage_packed(pt.lane, *packed, b) : stage(pt.lane, b, can_pack);
+    if (rcs[i] == 0) pt.lane->summary = summary;
     if (rcs[i] == 0) rcs[i] = enqueue(pt.shard, pt.shard->async, pt.lane, p);
     if (rcs[i]) errs[i] = kmcpg_err_ref();
   };
@@ -329,6 +335,115 @@ int wait_impl(kmcpg_ticket* t, kmcpg_result* out, bool as_pairs) {
   return rc;
 }
 
+namespace {
+
+// the summary of reads [0, r.n_reads) of a finished result of Match records (their final rows, in print order) by the rule of
+// regions_rule.hpp over target_class; x = the qCov as "%.4f" prints it, parsed back (k3_set_order.hpp fixed4) — the operations of K5
+void summaries_of_records(const kmcpg_db* db, const kmcpg_result& r, kmcpg_window_summary* s) {
+  const uint32_t* const cls = db->h_spec_target.data();
+  WindowSummaryAcc acc;
+  for (uint32_t i = 0; i < r.n_reads; i++) {
+    acc.clear();
+    for (uint64_t j = r.match_offs[i]; j < r.match_offs[i + 1]; j++) acc.add(cls[r.matches[j].col], (double)fixed4(r.matches[j].qcov) / 10000.0);
+    s[i] = kmcpg_window_summary{acc.n, 0u, acc.n ? acc.score() : 0.0};
+  }
+}
+
+// one batch of a summary ticket.  K5 ran behind K4 (Lane::summarized): the records are here; the windows it LEFT — several targets among
+// more than K5_CAP pairs, and those whose pairs the host's -f test may still thin out — get their pairs now and go through the host half
+// as a small batch of their own.  Every other path (no K3: KMCPG_DEVICE_FINALIZE=0) finishes the records and summarises those.
+int finish_summary(kmcpg_ticket* t, SummaryPart* out) {
+  const uint32_t n = t->n;
+  out->s.assign(n, kmcpg_window_summary{});
+  out->qlen.assign(n, 0);
+  out->qkmers.assign(n, 0);
+  if (n == 0) return 0;
+  auto& pt = t->parts[0];
+  Lane* L = pt.lane;
+  if (t->paged || t->parts.size() != 1 || t->db->exchange || !L->summarized()) {
+    kmcpg_result r{};
+    if (int rc = finish_raw(t, &r, false)) return rc;
+    summaries_of_records(t->db, r, out->s.data());
+    memcpy(out->qlen.data(), r.qlen, (size_t)n * sizeof(int32_t));
+    memcpy(out->qkmers.data(), r.qkmers, (size_t)n * sizeof(int32_t));
+    for (uint32_t i = 0; i < n; i++)
+      if (r.match_offs[i + 1] > r.match_offs[i]) out->left++, out->left_pairs += r.match_offs[i + 1] - r.match_offs[i];  // all of them the host's
+      else out->empty++;
+    kmcpg_result_free(&r);
+    return 0;
+  }
+  uint64_t n_hits = 0;
+  if (int rc = collect(pt.shard, pt.shard->async, L, t->p, &n_hits, false)) return rc;
+  if (L->h_roffs.p[(size_t)n + 1] != 0)
+    return kmcpg_fail(KMCPG_EINVAL, "%llu hit(s) named a read or column that does not exist", (unsigned long long)L->h_roffs.p[(size_t)n + 1]);
+  memcpy(out->s.data(), L->h_sum.p, (size_t)n * sizeof(kmcpg_window_summary));
+  memcpy(out->qlen.data(), L->h_ql.p, (size_t)n * sizeof(int32_t));
+  memcpy(out->qkmers.data(), L->h_qk.p, (size_t)n * sizeof(int32_t));
+  out->bytes_d2h = (uint64_t)n * (sizeof(kmcpg_window_summary) + 2 * sizeof(int32_t)) + 4 * sizeof(uint64_t);  // + K2's two counters, K3's two last words
+  // the LEFT windows: a record carries the segment's length (n_targets) and whether the host still judges it
+  std::vector<uint32_t> idx;
+  std::vector<uint64_t> offs(1, 0);
+  for (uint32_t i = 0; i < n; i++)
+    if (out->s[i].flags & KMCPG_SUMMARY_LEFT) {
+      idx.push_back(i);
+      offs.push_back(offs.back() + out->s[i].n_targets);
+    } else (out->s[i].n_targets == 0 ? out->empty : out->s[i].n_targets == 1 ? out->single : out->wave)++;
+  out->left = idx.size();
+  if (idx.empty()) return 0;
+  const uint64_t total = offs.back();
+  if (total > L->h_roffs.p[n] || total > L->d_pairs.cap) return kmcpg_fail(KMCPG_EDEVICE, "internal: K5 left %llu pairs of %llu", (unsigned long long)total, (unsigned long long)L->h_roffs.p[n]);
+  if (L->h_pairs.ensure(total)) return kmcpg_fail(KMCPG_ENOMEM, "hipHostMalloc failed");
+  {
+    kmcpg_db* sh = pt.shard;
+    KMCPG_USE_DEVICE(sh);
+    HIPCHK(hipMemcpyAsync(L->h_pairs.p, L->d_final, total * sizeof(kmcpg_pair), hipMemcpyDeviceToHost, sh->async->copy_stream));
+    HIPCHK(hipStreamSynchronize(sh->async->copy_stream));
+  }
+  out->left_pairs = total;
+  out->bytes_d2h += total * sizeof(kmcpg_pair);
+  const uint32_t nl = (uint32_t)idx.size();
+  offs.push_back(0);  // (the word behind the offsets: no bad hits)
+  std::vector<int32_t> qk(nl), ql(nl);
+  std::vector<uint8_t> verd(nl);
+  for (uint32_t j = 0; j < nl; j++) {
+    qk[j] = out->qkmers[idx[j]];
+    ql[j] = out->qlen[idx[j]];
+    verd[j] = out->s[idx[j]].flags & KMCPG_SUMMARY_HOST ? SPECIFIC_HOST : SPECIFIC_KEEP;
+  }
+  kmcpg_result r{};
+  if (int rc = finalize_grouped_trusted(t->db, L->h_pairs.p, offs.data(), qk.data(), ql.data(), nl, t->p, &r, L->bound_n, false, verd.data())) return rc;
+  std::vector<kmcpg_window_summary> s(nl);
+  summaries_of_records(t->db, r, s.data());
+  kmcpg_result_free(&r);
+  for (uint32_t j = 0; j < nl; j++) out->s[idx[j]] = s[j];
+  return 0;
+}
+
+}  // namespace
+
+int wait_summary_impl(kmcpg_ticket* t, SummaryPart* out) {
+  int rc = 0;
+  if (t->pieces.empty()) rc = finish_summary(t, out);
+  else {
+    *out = SummaryPart();
+    for (size_t i = 0; i < t->pieces.size() && rc == 0; i++) {
+      SummaryPart one;
+      if (t->pieces[i]) {
+        kmcpg_ticket* w = t->pieces[i];
+        t->pieces[i] = nullptr;
+        rc = wait_summary_impl(w, &one);
+      } else one = std::move(t->piece_sum[i]);
+      if (rc) break;
+      out->qlen.insert(out->qlen.end(), one.qlen.begin(), one.qlen.end());
+      out->qkmers.insert(out->qkmers.end(), one.qkmers.begin(), one.qkmers.end());
+      out->s.insert(out->s.end(), one.s.begin(), one.s.end());
+      out->count(one);
+    }
+  }
+  drop_after(t, rc);
+  return rc;
+}
+
 int submit_handle(kmcpg_db* db, const kmcpg_params* params, kmcpg_params* p) {
   KMCPG_NO_FILES_ONLY(db);
   if (db->opts.shard_count != 1)
@@ -363,6 +478,7 @@ extern "C" int kmcpg_wait(kmcpg_ticket* t, kmcpg_result* out) {
     if (t) drop_ticket(t);
     return kmcpg_fail(KMCPG_EINVAL, "null argument");
   }
+  if (t->summary) return kmcpg_fail(KMCPG_EINVAL, "kmcpg_wait: a ticket of kmcpg_submit_windows_summary is consumed by kmcpg_wait_summaries (the ticket is still valid)");
   return wait_impl(t, out, false);
 }
 
@@ -560,6 +676,7 @@ extern "C" int kmcpg_wait_pairs(kmcpg_ticket* t, kmcpg_result_pairs* out) {
     if (t) drop_ticket(t);
     return kmcpg_fail(KMCPG_EINVAL, "null argument");
   }
+  if (t->summary) return kmcpg_fail(KMCPG_EINVAL, "kmcpg_wait_pairs: a ticket of kmcpg_submit_windows_summary is consumed by kmcpg_wait_summaries (the ticket is still valid)");
   memset(out, 0, sizeof *out);
   const bool native = !may_retry(t->db, t->p, t->paired);
   kmcpg_result r{};

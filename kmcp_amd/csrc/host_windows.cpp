@@ -1,6 +1,6 @@
 // host_windows.cpp — sliding windows of long queries above the lanes (kmcpg_submit_windows and its kin): a batch's windows are cut into
 // pieces (window_plan.hpp), a piece is searched with its windows read in place on the device or cut into text on the host, and the pieces'
-// results come back as one.  The geometry itself — counts, pieces, what a piece stages — is window_plan.hpp's.
+// results come back as one — as matches, or as one summary per window (kmcpg_submit_windows_summary, K5).  The geometry itself — counts, pieces, what a piece stages — is window_plan.hpp's.
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 #include <string.h>
@@ -28,7 +28,7 @@ uint64_t window_budget(const kmcpg_db* db) {
 // device path: the slices of reads the piece's windows cover go up as they are (a batch of reads, packed by stage() where that pays); the
 // windows are descriptors built on the device (windows.hip) and read in place by the k-mer kernels
 int submit_window_piece_device(kmcpg_db* db, const uint8_t* seqs, const uint64_t* offs, const kmcpg_window_spec& s, const WinPiece& pc,
-                               const kmcpg_params& p, kmcpg_ticket** out) {
+                               const kmcpg_params& p, bool summary, kmcpg_ticket** out) {
   static thread_local std::vector<uint8_t> text;
   static thread_local WinStaging ws;
   stage_windows(offs, s, pc, (uint64_t)(p.k > 0 ? p.k : db->info.k), &ws);
@@ -39,6 +39,7 @@ int submit_window_piece_device(kmcpg_db* db, const uint8_t* seqs, const uint64_t
   t->db = db;
   t->n = (uint32_t)pc.n_win;
   t->p = p;
+  t->summary = summary;
   AsyncState* A = nullptr;
   if (int rc = async_state(db, &A)) return rc;
   Lane* L = acquire_lane(A, false, false);
@@ -57,6 +58,7 @@ int submit_window_piece_device(kmcpg_db* db, const uint8_t* seqs, const uint64_t
     L->wstep = s.step;
     L->wwin = s.window;
     L->wchunks = ws.cpre.back();
+    L->summary = summary;
     rc = enqueue(db, A, L, p);
   }
   if (rc) {
@@ -71,7 +73,7 @@ int submit_window_piece_device(kmcpg_db* db, const uint8_t* seqs, const uint64_t
 
 // host path (paged and multi-device handles, multi-k databases without an explicit k): the windows cut into text, searched as reads
 int submit_window_piece_text(kmcpg_db* db, const uint8_t* seqs, const uint64_t* offs, const kmcpg_window_spec& s, const WinPiece& pc,
-                             const kmcpg_params& p, kmcpg_ticket** out) {
+                             const kmcpg_params& p, bool summary, kmcpg_ticket** out) {
   static thread_local std::vector<uint8_t> text;
   static thread_local std::vector<uint64_t> woffs;
   text.clear();
@@ -84,22 +86,23 @@ int submit_window_piece_text(kmcpg_db* db, const uint8_t* seqs, const uint64_t* 
       woffs.push_back(text.size());
     }
   }
-  return submit_impl(db, HostBatch{text.data(), woffs.data(), nullptr, nullptr, (uint32_t)pc.n_win}, p, false, false, out);
+  return submit_impl(db, HostBatch{text.data(), woffs.data(), nullptr, nullptr, (uint32_t)pc.n_win}, p, false, false, out, nullptr, summary);
 }
 
+// summary: the ticket is one of kmcpg_submit_windows_summary (K5 behind K4, consumed by kmcpg_wait_summaries)
 int submit_windows_impl(kmcpg_db* db, const uint8_t* seqs, const uint64_t* offs, uint32_t n, const kmcpg_window_spec& s, const kmcpg_params& p,
-                        kmcpg_ticket** out) {
+                        kmcpg_ticket** out, bool summary = false) {
   // which handles read the windows in place: one GPU holding the whole index, and no search of the window text again (rereads_text: the
   // smaller k of a multi-k database).  KMCPG_WINDOWS_HOST=1 cuts text everywhere (A/B runs).
   static const bool host_env = getenv("KMCPG_WINDOWS_HOST") && atoi(getenv("KMCPG_WINDOWS_HOST")) == 1;
   const bool device = !host_env && db->paged_passes == 0 && db->shards.empty() && !rereads_text(db, p);
   const std::vector<WinPiece> pieces = plan_windows(offs, n, s, window_budget(db), 1ull << 22);
   auto one = [&](const WinPiece& pc, kmcpg_ticket** o) {
-    return device ? submit_window_piece_device(db, seqs, offs, s, pc, p, o) : submit_window_piece_text(db, seqs, offs, s, pc, p, o);
+    return device ? submit_window_piece_device(db, seqs, offs, s, pc, p, summary, o) : submit_window_piece_text(db, seqs, offs, s, pc, p, summary, o);
   };
   if (pieces.empty()) {  // no read yields a window: an empty batch
     static const uint64_t zero = 0;
-    return submit_impl(db, HostBatch{nullptr, &zero, nullptr, nullptr, 0}, p, false, false, out);
+    return submit_impl(db, HostBatch{nullptr, &zero, nullptr, nullptr, 0}, p, false, false, out, nullptr, summary);
   }
   if (pieces.size() == 1) return one(pieces[0], out);
   uint64_t total = 0;
@@ -109,8 +112,10 @@ int submit_windows_impl(kmcpg_db* db, const uint8_t* seqs, const uint64_t* offs,
   t->db = db;
   t->n = (uint32_t)total;
   t->p = p;
+  t->summary = summary;
   t->pieces.assign(pieces.size(), nullptr);
   t->piece_res.assign(pieces.size(), kmcpg_result{});
+  if (summary) t->piece_sum.resize(pieces.size());
   size_t oldest = 0;  // pieces before this one are finished or waited for
   for (size_t i = 0; i < pieces.size(); i++) {
     for (;;) {
@@ -122,7 +127,7 @@ int submit_windows_impl(kmcpg_db* db, const uint8_t* seqs, const uint64_t* offs,
       if (rc == KMCPG_EBUSY && oldest < i) {
         kmcpg_ticket* w = t->pieces[oldest];
         t->pieces[oldest] = nullptr;
-        rc = wait_impl(w, &t->piece_res[oldest], false);
+        rc = summary ? wait_summary_impl(w, &t->piece_sum[oldest]) : wait_impl(w, &t->piece_res[oldest], false);
       }
       if (rc) {
         keeping_error([&] { drop_ticket(t.release(), true); });
@@ -241,4 +246,58 @@ extern "C" int kmcpg_submit_packed_windows(kmcpg_db* db, const uint8_t* codes, c
   text.resize(tb + 1);
   if (int rc = kmcpg_unpack2(codes, tb, exc, n_exc, text.data())) return rc;
   return submit_windows_impl(db, text.data(), offs, n_reads, *spec, p, out);
+}
+
+// ---- window summaries (K5 behind K4): the entry of kmcp-search --regions-bed
+namespace {
+struct SummaryOwner {
+  SummaryPart part;
+};
+}  // namespace
+
+extern "C" int kmcpg_submit_windows_summary(kmcpg_db* db, const uint8_t* seqs, const uint64_t* offs, uint32_t n_reads, const kmcpg_window_spec* spec,
+                                            const kmcpg_params* params, kmcpg_ticket** out) {
+  if (!db || !out || (n_reads && (!seqs || !offs))) return kmcpg_fail(KMCPG_EINVAL, "null argument");
+  *out = nullptr;
+  if (int rc = set_refuse_entry(db, "kmcpg_submit_windows_summary")) return rc;
+  if (!db->spec_on()) return kmcpg_fail(KMCPG_EINVAL, "kmcpg_submit_windows_summary: the species-specific stage is off: call kmcpg_set_specific first");
+  kmcpg_params p;
+  if (int rc = submit_handle(db, params, &p)) return rc;
+  if (int rc = window_args(offs, n_reads, spec)) return rc;
+  return submit_windows_impl(db, seqs, offs, n_reads, *spec, p, out, true);
+}
+
+extern "C" int kmcpg_wait_summaries(kmcpg_ticket* t, kmcpg_result_summaries* out) {
+  if (!t || !out) {
+    if (t) drop_ticket(t);
+    return kmcpg_fail(KMCPG_EINVAL, "null argument");
+  }
+  if (!t->summary) return kmcpg_fail(KMCPG_EINVAL, "kmcpg_wait_summaries: the ticket is not one of kmcpg_submit_windows_summary (it is still valid: kmcpg_wait / kmcpg_wait_pairs)");
+  memset(out, 0, sizeof *out);
+  kmcpg_db* db = t->db;
+  std::unique_ptr<SummaryOwner> o(new SummaryOwner());
+  if (int rc = wait_summary_impl(t, &o->part)) return rc;
+  SummaryPart& s = o->part;
+  kmcpg_summary_stats st{};
+  st.single = s.single, st.wave = s.wave, st.left = s.left, st.empty = s.empty;
+  st.left_pairs = s.left_pairs;
+  st.bytes_d2h = s.bytes_d2h;
+  {
+    std::lock_guard<std::mutex> g(db->mu);
+    db->sum_ticket = st;
+    db->sum_from_ticket = true;
+    db->sum_ran = true;
+  }
+  out->n_windows = (uint32_t)s.s.size();
+  out->qlen = s.qlen.data();
+  out->qkmers = s.qkmers.data();
+  out->s = s.s.data();
+  out->owner = o.release();
+  return 0;
+}
+
+extern "C" void kmcpg_result_summaries_free(kmcpg_result_summaries* r) {
+  if (!r) return;
+  delete (SummaryOwner*)r->owner;
+  memset(r, 0, sizeof *r);
 }

@@ -152,8 +152,14 @@ void launch_k4(const K4Args& a, hipStream_t st, K4Log* log) {
   hipLaunchKernelGGL(k4_verdict, dim3(grid), dim3(256), 0, st, a);
   k4_note(log, KMCPG_K4_VERDICT, grid, 256);
   launch_k3_scan(a.cnt, a.out_offs, a.sums, a.n_reads + 1, st, log);
+  launch_k4_compact(a, st, log);
+}
+
+void launch_k4_compact(const K4Args& a, hipStream_t st, K4Log* log, int kernel_id) {
+  if (a.n_reads == 0) return;
+  const unsigned grid = (unsigned)(((uint64_t)a.n_reads + 4 * RPW - 1) / (4 * RPW));
   hipLaunchKernelGGL(k4_compact, dim3(grid), dim3(256), 0, st, a);
-  k4_note(log, KMCPG_K4_COMPACT, grid, 256);
+  k4_note(log, kernel_id, grid, 256);
 }
 
 }  // namespace kmcpg

@@ -168,7 +168,7 @@ bool pack_wanted(uint64_t total_bases, uint32_t n) {
 int lane_begin(Lane* L, const HostBatch& b) {
   L->up_reads = L->n = b.n;
   L->up_bases = L->tb1 = L->tb2 = 0;
-  L->packed = L->win = false;
+  L->packed = L->win = L->summary = false;
   L->n_exc = 0;
   L->ext_pack = nullptr;
   L->paired = b.seqs2 != nullptr;
@@ -296,9 +296,11 @@ int enqueue_query(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p, c
     if (L->d_pairs.ensure(L->d_hits.cap) || L->d_roffs.ensure((size_t)L->n + 2) || L->h_roffs.ensure((size_t)L->n + 2)) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
     rc = kmcpg_group_device(db, L->d_hits.p, L->d_cnt.p, L->d_hits.cap, L->d_qk.p, L->n, &p, L->d_pairs.p, L->d_roffs.p, st);
     if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(L->h_roffs.p, L->d_roffs.p, ((size_t)L->n + 2) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    L->d_final = L->d_pairs.p;
     L->spec = db->spec_on();
+    // (a batch K5 summarises needs K3's last two words only: the pairs it kept, and its count of bad hits)
+    const size_t skip = L->summarized() ? L->n : 0;
+    HIPCHK(hipMemcpyAsync(L->h_roffs.p + skip, L->d_roffs.p + skip, ((size_t)L->n + 2 - skip) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    L->d_final = L->d_pairs.p;
     if (L->spec) {  // K4 right behind K3: only the surviving reads' matches leave the GPU
       if (L->d_soffs4.ensure((size_t)L->n + 1) || L->d_verd.ensure(L->n) || L->h_verd.ensure(L->n)) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
       // a segment is final on the device only where the -f bound was applied there (finalize.cpp: final_n); longer queries keep their
@@ -308,10 +310,20 @@ int enqueue_query(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p, c
       kmcpg_pair* out = (kmcpg_pair*)L->d_hits.p;  // (12 bytes per hit: room for d_hits.cap pairs and more)
       rc = kmcpg_specific_device(db, L->d_pairs.p, L->d_roffs.p, L->d_hits.cap, L->d_qk.p, L->n, final_n, out, L->d_hits.cap, L->d_soffs4.p, L->d_verd.p, st);
       if (rc) return rc;
+      L->d_final = out;
+      if (L->summary) {
+        // K5 right behind K4: 16 bytes per window leave the GPU; the pairs of the windows LEFT to the host go into d_pairs — dead once K4
+        // has compacted it — and come down on demand (collect_summary).  No offsets, no verdict bytes: the LEFT records carry both
+        if (L->d_sum.ensure(L->n) || L->h_sum.ensure(L->n) || L->d_loffs.ensure((size_t)L->n + 1)) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
+        rc = kmcpg_summarize_device(db, out, L->d_soffs4.p, L->d_hits.cap, L->d_verd.p, L->d_qk.p, L->n, L->d_sum.p, L->d_pairs.p, L->d_hits.cap, L->d_loffs.p, st);
+        if (rc) return rc;
+        HIPCHK(hipMemcpyAsync(L->h_sum.p, L->d_sum.p, (size_t)L->n * sizeof(kmcpg_window_summary), hipMemcpyDeviceToHost, st));
+        L->d_final = L->d_pairs.p;
+        return 0;
+      }
       // the new offsets over the old ones (in stream order); the word behind them — K3's count of bad hits — stays
       HIPCHK(hipMemcpyAsync(L->h_roffs.p, L->d_soffs4.p, ((size_t)L->n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
       HIPCHK(hipMemcpyAsync(L->h_verd.p, L->d_verd.p, (size_t)L->n, hipMemcpyDeviceToHost, st));
-      L->d_final = out;
     }
   } else L->spec = false;
   return 0;
@@ -414,6 +426,7 @@ int enqueue(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p, bool ge
   HIPCHK(hipMemcpyAsync(L->h_ql.p, L->d_ql.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
   L->copied = A->hits_stay_on_device ? 0 : std::min<uint64_t>(first, L->d_hits.cap);
   L->eager_aside = false;
+  if (L->summarized()) L->copied = 0;  // no eager copy of pairs: what the host needs of them (the LEFT windows') it asks for by itself
   if (L->copied && L->grouped && !generous_eager) {
     // a small copy (<= 32 pairs per read), in stream order before the lane's completion event (same-box A/B: on a stream of its own it
     // cost the pipelined submit / wait path 8 %)

@@ -70,6 +70,13 @@ struct Lane {
   DevBuf<uint8_t> d_verd;
   PinBuf<uint8_t> h_verd;
   const kmcpg_pair* d_final = nullptr;
+  // K5 (window summaries, kmcpg_submit_windows_summary): the batch's result is h_sum, 16 bytes per window; the pairs of the windows LEFT
+  // to the host lie in d_pairs (= d_final) one behind the other and come down on demand; of K3's offsets only the last two words do
+  bool summary = false;  // the caller asked for summaries (set after lane_begin, before enqueue)
+  DevBuf<kmcpg_window_summary> d_sum;
+  PinBuf<kmcpg_window_summary> h_sum;
+  DevBuf<uint64_t> d_loffs;
+  bool summarized() const { return summary && grouped && spec; }  // K5 ran: h_sum is the result
   bool spec = false;  // this batch went through K4: h_roffs / h_pairs hold ITS output, h_verd the verdicts
   // 2-bit packed upload (stage): the batch's bases as codes + the runs of foreign bytes instead of h_seqs; unpacked on the device
   PinBuf<uint8_t> h_pack;
@@ -108,6 +115,7 @@ struct Lane {
     d_seqs.release(); d_seqs2.release(); d_offs.release(); d_offs2.release(); d_cnt.release(); d_qk.release(); d_ql.release(); d_hits.release();
     d_pairs.release(); d_roffs.release(); h_pairs.release(); h_roffs.release();
     d_soffs4.release(); d_verd.release(); h_verd.release();
+    d_sum.release(); h_sum.release(); d_loffs.release();
     h_pack.release(); h_exc.release(); d_pack.release(); d_exc.release();
     h_wmeta.release(); d_soffs.release(); d_wmeta.release(); d_wsrc.release();
     if (done) (void)hipEventDestroy(done);
@@ -159,6 +167,17 @@ struct PackedIn {
   uint64_t n_exc;
 };
 
+// the summaries of a batch (or of one piece of it) with what the witness counts (kmcpg_last_summary)
+struct SummaryPart {
+  std::vector<int32_t> qlen, qkmers;
+  std::vector<kmcpg_window_summary> s;
+  uint64_t single = 0, wave = 0, left = 0, empty = 0;  // windows by who summarised them: the device (one target, several), the host, nobody (no rows)
+  uint64_t left_pairs = 0, bytes_d2h = 0;
+  void count(const SummaryPart& o) {
+    single += o.single, wave += o.wave, left += o.left, empty += o.empty, left_pairs += o.left_pairs, bytes_d2h += o.bytes_d2h;
+  }
+};
+
 }  // namespace kmcpg
 
 // one batch in flight; single-device handles have one part, kmcpg_open_devices handles one part per GPU
@@ -186,6 +205,10 @@ struct kmcpg_ticket {
   // lane for a later one has its result in piece_res[i] instead (pieces[i] == nullptr).  Such a ticket holds no lane itself.
   std::vector<kmcpg_ticket*> pieces;
   std::vector<kmcpg_result> piece_res;
+  // kmcpg_submit_windows_summary: the ticket (and its pieces) is consumed by kmcpg_wait_summaries only; a piece finished early has its
+  // summaries in piece_sum[i]
+  bool summary = false;
+  std::vector<kmcpg::SummaryPart> piece_sum;
 };
 
 namespace kmcpg {
@@ -235,9 +258,12 @@ void drop_ticket(kmcpg_ticket* t, bool failed = false);
 // ---- host.cpp
 // the submit family works on a handle that holds the whole database and can reach a GPU; *p = the caller's params or the defaults
 int submit_handle(kmcpg_db* db, const kmcpg_params* params, kmcpg_params* p);
-int submit_impl(kmcpg_db* db, const HostBatch& b, const kmcpg_params& p, bool retry, bool block, kmcpg_ticket** out, const PackedIn* packed = nullptr);
+int submit_impl(kmcpg_db* db, const HostBatch& b, const kmcpg_params& p, bool retry, bool block, kmcpg_ticket** out, const PackedIn* packed = nullptr,
+                bool summary = false);
 // kmcpg_wait / kmcpg_wait_pairs: the ticket's result, as_pairs = in the compact form where the path it took collects that natively; gives the ticket back
 int wait_impl(kmcpg_ticket* t, kmcpg_result* out, bool as_pairs);
+// kmcpg_wait_summaries: the summaries of a ticket of kmcpg_submit_windows_summary (one batch or its pieces); gives the ticket back
+int wait_summary_impl(kmcpg_ticket* t, SummaryPart* out);
 // np results (of n reads together) one behind the other as one result, in the form asked for — a part that arrived in the other form is
 // converted; the parts are freed
 void concat_results(const kmcpg_db* db, kmcpg_result* parts, size_t np, uint32_t n, bool as_pairs, int k_used, kmcpg_result* out);

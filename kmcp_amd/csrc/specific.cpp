@@ -1,4 +1,4 @@
-// specific.cpp — the host side of K4 (k4_specific.hip): the tables on the handle, the stage alone, its witness.
+// specific.cpp — the host side of K4 (k4_specific.hip) and of K5 (k5_summary.hip): the tables on the handle, each stage alone, its witness.
 #include <cstring>
 
 #include "engine.hpp"
@@ -46,6 +46,8 @@ extern "C" int kmcpg_set_specific(kmcpg_db* db, const uint32_t* target_class, co
   db->h_spec_species.clear();
   db->spec_ran = false;
   db->k4_log.clear();
+  db->sum_ran = false;
+  db->k5_log.clear();
   if (off || n_cols == 0) return 0;
   if (dev) {
     const size_t bytes = (size_t)n_cols * sizeof(uint32_t);
@@ -157,6 +159,112 @@ extern "C" int kmcpg_last_specific(kmcpg_db* db, kmcpg_specific_stats* out, kmcp
   const size_t have = db->profiling >= 1 ? db->k4_log.size() : 0;
   const size_t m = std::min<size_t>(cap, have);
   if (m) memcpy(launches, db->k4_log.data(), m * sizeof(kmcpg_k4_launch));
+  *n_launches = (uint32_t)have;
+  return 0;
+}
+
+// ---- K5: window summaries behind K4
+extern "C" int kmcpg_summarize_device(kmcpg_db* db, const kmcpg_pair* d_pairs, const uint64_t* d_offs, uint64_t pair_cap, const uint8_t* d_verdicts,
+                                      const int32_t* d_qkmers, uint32_t n, kmcpg_window_summary* d_out, kmcpg_pair* d_left_pairs, uint64_t left_cap,
+                                      uint64_t* d_left_offs, void* stream) {
+  static_assert(sizeof(kmcpg_window_summary) == 16, "two 4-byte words and a double");
+  static_assert(K5_STATS * sizeof(uint32_t) <= 32, "the 64-bit word starts at byte 32");
+  if (!db || !d_offs || !d_left_offs || (n && (!d_qkmers || !d_verdicts || !d_out)) || (pair_cap && (!d_pairs || !d_left_pairs)))
+    return kmcpg_fail(KMCPG_EINVAL, "null argument");
+  if (left_cap < pair_cap) return kmcpg_fail(KMCPG_EINVAL, "left_cap (%llu) must be at least pair_cap (%llu)", (unsigned long long)left_cap, (unsigned long long)pair_cap);
+  if (n == 0xffffffffu) return kmcpg_fail(KMCPG_EINVAL, "too many windows");
+  if (int rc = refuse_handle(db)) return rc;
+  std::lock_guard<std::mutex> g(db->mu);
+  KMCPG_USE_DEVICE(db);
+  if (!db->spec_on() || !db->d_spec_target) return kmcpg_fail(KMCPG_EINVAL, "the stage is off: call kmcpg_set_specific first");
+  hipStream_t st = (hipStream_t)stream;
+  // the scratch has one user at a time: K3's chain (kmcpg_group_device), K4 (kmcpg_specific_device)
+  if (!db->fin_ev) HIPCHK(hipEventCreateWithFlags(&db->fin_ev, hipEventDisableTiming));
+  if (db->fin_ev_valid) HIPCHK(hipStreamWaitEvent(st, db->fin_ev, 0));
+  struct FinGuard {  // every way out leaves the event behind
+    kmcpg_db* db;
+    hipStream_t st;
+    ~FinGuard() {
+      if (db->fin_ev && hipEventRecord(db->fin_ev, st) == hipSuccess) db->fin_ev_valid = true;
+    }
+  } fing{db, st};
+  if (db->w_spec_cnt.ensure((size_t)n + 2) || db->w_spec_sums.ensure((size_t)k3_scan_tiles_for(n + 1) + 1)) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
+  if (!db->d_sum_stats) HIPCHK(hipMalloc((void**)&db->d_sum_stats, SPEC_STATS_BYTES));
+  HIPCHK(hipMemsetAsync(db->d_sum_stats, 0, SPEC_STATS_BYTES, st));
+  db->k5_log.clear();
+  db->sum_ran = true;
+  db->sum_from_ticket = false;
+  if (n == 0) {
+    db->sum_timed = false;
+    HIPCHK(hipMemsetAsync(d_left_offs, 0, sizeof(uint64_t), st));
+    return 0;
+  }
+  K5Args a{};
+  a.pairs = d_pairs;
+  a.offs = d_offs;
+  a.pair_cap = pair_cap;
+  a.verdict = d_verdicts;
+  a.nk = d_qkmers;
+  a.n_reads = n;
+  a.n_cols = (uint32_t)db->h_spec_target.size();
+  a.target_class = db->d_spec_target;
+  a.out = d_out;
+  a.cnt = db->w_spec_cnt.p;
+  a.sums = db->w_spec_sums.p;
+  a.left_pairs = d_left_pairs;
+  a.left_offs = d_left_offs;
+  a.left_cap = left_cap;
+  a.stats = (uint32_t*)db->d_sum_stats;
+  db->sum_timed = db->profiling >= 1;
+  if (db->sum_timed) {
+    for (auto& ev : db->sum_ev)
+      if (!ev) HIPCHK(hipEventCreate(&ev));
+    HIPCHK(hipEventRecord(db->sum_ev[0], st));
+  }
+  launch_k5(a, st, db->sum_timed ? &db->k5_log : nullptr);
+  if (db->sum_timed) HIPCHK(hipEventRecord(db->sum_ev[1], st));
+  // the witness's LEFT pairs: the last offset, kept where the caller's buffers need not outlive the call
+  HIPCHK(hipMemcpyAsync(db->d_sum_stats + 4, d_left_offs + n, sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int kmcpg_last_summary(kmcpg_db* db, kmcpg_summary_stats* out, kmcpg_k4_launch* launches, uint32_t cap, uint32_t* n_launches) {
+  if (!db || !out || !n_launches || (cap && !launches)) return kmcpg_fail(KMCPG_EINVAL, "null argument");
+  memset(out, 0, sizeof *out);
+  out->k5_ms = -1;
+  *n_launches = 0;
+  std::lock_guard<std::mutex> g(db->mu);
+  if (!db->sum_ran || db->opts.device < 0) return 0;
+  if (!db->d_sum_stats) {  // a ticket no batch of which reached K5 (KMCPG_DEVICE_FINALIZE=0)
+    if (db->sum_from_ticket) *out = db->sum_ticket, out->k5_ms = -1;
+    return 0;
+  }
+  KMCPG_USE_DEVICE(db);
+  HIPCHK(hipDeviceSynchronize());
+  if (db->sum_from_ticket) {
+    *out = db->sum_ticket;
+    out->k5_ms = -1;
+  }
+  uint64_t w[SPEC_STATS_BYTES / 8] = {};
+  HIPCHK(hipMemcpy(w, db->d_sum_stats, SPEC_STATS_BYTES, hipMemcpyDeviceToHost));
+  uint32_t s[K5_STATS];
+  memcpy(s, w, sizeof s);
+  out->bad_segments = s[4];
+  if (!db->sum_from_ticket) {
+    out->single = s[0];
+    out->wave = s[1];
+    out->left = s[2];
+    out->empty = s[3];
+    out->left_pairs = w[4];
+  }
+  if (db->sum_timed && db->sum_ev[1]) {
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, db->sum_ev[0], db->sum_ev[1]) == hipSuccess) out->k5_ms = ms;
+  }
+  const size_t have = db->profiling >= 1 ? db->k5_log.size() : 0;
+  const size_t m = std::min<size_t>(cap, have);
+  if (m) memcpy(launches, db->k5_log.data(), m * sizeof(kmcpg_k4_launch));
   *n_launches = (uint32_t)have;
   return 0;
 }

@@ -27,6 +27,7 @@ EXPORTS = [
     "kmcpg_last_sketch_launches", "kmcpg_last_sketch_ms", "kmcpg_sort_segments_device", "kmcpg_dedup_device", "kmcpg_last_dedup_launches",
     "kmcpg_open_set", "kmcpg_set_info", "kmcpg_last_set_order",
     "kmcpg_set_specific", "kmcpg_specific_device", "kmcpg_last_specific",
+    "kmcpg_summarize_device", "kmcpg_last_summary", "kmcpg_submit_windows_summary", "kmcpg_wait_summaries", "kmcpg_result_summaries_free",
     "kmcpg_sketch_genomes_to", "kmcpg_builder_open", "kmcpg_builder_close", "kmcpg_builder_add_cols", "kmcpg_builder_plan",
     "kmcpg_builder_col_place", "kmcpg_builder_block_info", "kmcpg_builder_begin_round", "kmcpg_builder_scatter_device",
     "kmcpg_builder_end_round", "kmcpg_builder_finish", "kmcpg_builder_info",
@@ -230,6 +231,28 @@ class SpecificStats(C.Structure):
                 ("group_segments", C.c_uint64), ("wave_segments", C.c_uint64), ("bad_segments", C.c_uint64), ("k4_ms", C.c_double)]
 
 
+class WindowSummary(C.Structure):
+    """kmcpg_window_summary: what region merging needs of one window"""
+    _fields_ = [("n_targets", C.c_uint32), ("flags", C.c_uint32), ("score", C.c_double)]
+
+
+SUMMARY_DTYPE = np.dtype([("n_targets", "<u4"), ("flags", "<u4"), ("score", "<f8")])
+SUMMARY_LEFT, SUMMARY_HOST = 1, 2
+K5_SUMMARY, K5_COMPACT = 16, 17  # KMCPG_K5_*: kmcpg_k4_launch.kernel of K5's own kernels
+
+
+class SummaryStats(C.Structure):
+    """kmcpg_summary_stats: the witness of the last K5 launch, or of the last ticket of wait_summaries"""
+    _fields_ = [("single", C.c_uint64), ("wave", C.c_uint64), ("left", C.c_uint64), ("empty", C.c_uint64), ("left_pairs", C.c_uint64),
+                ("bytes_d2h", C.c_uint64), ("bad_segments", C.c_uint64), ("k5_ms", C.c_double)]
+
+
+class ResultSummaries(C.Structure):
+    """kmcpg_result_summaries"""
+    _fields_ = [("n_windows", C.c_uint32), ("reserved", C.c_uint32), ("qlen", C.POINTER(C.c_int32)), ("qkmers", C.POINTER(C.c_int32)),
+                ("s", C.POINTER(WindowSummary)), ("owner", C.c_void_p)]
+
+
 class SynthSpec(C.Structure):
     _fields_ = [("k", C.c_int32), ("num_hashes", C.c_int32), ("fpr", C.c_double), ("n_blocks", C.c_uint32),
                 ("cols_per_block", C.c_uint32), ("num_sigs", C.c_uint64), ("kmers_per_col", C.c_uint64), ("seed", C.c_uint64),
@@ -396,6 +419,12 @@ def load():
     L.kmcpg_set_specific.argtypes = [vp, vp, vp, C.c_uint32]
     L.kmcpg_specific_device.argtypes = [vp, vp, vp, C.c_uint64, vp, C.c_uint32, C.c_int32, vp, C.c_uint64, vp, vp, vp]
     L.kmcpg_last_specific.argtypes = [vp, C.POINTER(SpecificStats), C.POINTER(K4Launch), C.c_uint32, C.POINTER(C.c_uint32)]
+    L.kmcpg_summarize_device.argtypes = [vp, vp, vp, C.c_uint64, vp, vp, C.c_uint32, vp, vp, C.c_uint64, vp, vp]
+    L.kmcpg_last_summary.argtypes = [vp, C.POINTER(SummaryStats), C.POINTER(K4Launch), C.c_uint32, C.POINTER(C.c_uint32)]
+    L.kmcpg_submit_windows_summary.argtypes = [vp, vp, vp, C.c_uint32, C.POINTER(WindowSpec), C.POINTER(Params), C.POINTER(vp)]
+    L.kmcpg_wait_summaries.argtypes = [vp, C.POINTER(ResultSummaries)]
+    L.kmcpg_result_summaries_free.argtypes = [C.POINTER(ResultSummaries)]
+    L.kmcpg_result_summaries_free.restype = None
     L.kmcpg_sketch_genomes_to.argtypes = [vp, vp, vp, C.c_uint32, C.POINTER(SplitSpec), SKETCH_SINK, vp]
     u32p = C.POINTER(C.c_uint32)
     L.kmcpg_builder_open.argtypes = [C.POINTER(BuilderCfg), C.c_int32, C.POINTER(vp)]
@@ -1175,6 +1204,44 @@ class Database:
         _check(load().kmcpg_last_specific(self._h, C.byref(st), buf, n.value, C.byref(n)))
         self.last_k4_ms = float(st.k4_ms)  # HIP-event time of the stage's kernels (profiling level >= 1), else -1
         return {f: int(getattr(st, f)) for f, _ in SpecificStats._fields_ if f != "k4_ms"}, [buf[i] for i in range(n.value)]
+
+    # ---- window summaries for region merging: K5 behind K4 ------------------------------------------------------
+    def summarize_device(self, d_pairs, d_offs, pair_cap, d_verdicts, d_qkmers, n, d_out, d_left_pairs, left_cap, d_left_offs, stream=None):
+        """kmcpg_summarize_device on device pointers: K4's surviving segments -> one 16-byte record per window (SUMMARY_DTYPE), the pairs of
+        the windows LEFT to the host compacted behind d_left_pairs with their offsets (n + 1 words)."""
+        _check(load().kmcpg_summarize_device(self._h, d_pairs, d_offs, pair_cap, d_verdicts, d_qkmers, n, d_out, d_left_pairs, left_cap, d_left_offs, stream))
+
+    def last_summary(self):
+        """kmcpg_last_summary: (dict of the counters, [K4Launch] of the last K5 launch — empty below profiling level 1)"""
+        st = SummaryStats()
+        n = C.c_uint32(0)
+        _check(load().kmcpg_last_summary(self._h, C.byref(st), None, 0, C.byref(n)))
+        buf = (K4Launch * max(1, n.value))()
+        _check(load().kmcpg_last_summary(self._h, C.byref(st), buf, n.value, C.byref(n)))
+        self.last_k5_ms = float(st.k5_ms)  # HIP-event time of the stage's kernels (profiling level >= 1), else -1
+        return {f: int(getattr(st, f)) for f, _ in SummaryStats._fields_ if f != "k5_ms"}, [buf[i] for i in range(n.value)]
+
+    def submit_windows_summary(self, seqs, offs, step, window, greedy=False, params=None):
+        """kmcpg_submit_windows_summary: submit_windows with the species-specific stage on and K5 behind it (wait_summaries)"""
+        p = params or default_params()
+        spec = WindowSpec(step, window, 1 if greedy else 0, 0)
+        t = C.c_void_p()
+        n = len(offs) - 1
+        _check(load().kmcpg_submit_windows_summary(self._h, seqs.ctypes.data, offs.ctypes.data, n, C.byref(spec), C.byref(p), C.byref(t)))
+        return t
+
+    def wait_summaries(self, ticket):
+        """kmcpg_wait_summaries: (summaries SUMMARY_DTYPE [n_windows], qlen int32, qkmers int32)"""
+        r = ResultSummaries()
+        _check(load().kmcpg_wait_summaries(ticket, C.byref(r)))
+        n = int(r.n_windows)
+        try:
+            if n == 0:
+                return np.zeros(0, dtype=SUMMARY_DTYPE), np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int32)
+            s = np.frombuffer(C.string_at(r.s, n * C.sizeof(WindowSummary)), dtype=SUMMARY_DTYPE).copy()
+            return s, np.ctypeslib.as_array(r.qlen, shape=(n,)).copy(), np.ctypeslib.as_array(r.qkmers, shape=(n,)).copy()
+        finally:
+            load().kmcpg_result_summaries_free(C.byref(r))
 
     def finalize_grouped(self, pairs, read_offs, qkmers, qlen, params=None, count_only=False):
         """kmcpg_finalize_grouped: pairs uint32 [m, 2] (or PAIR_DTYPE [m]), read_offs uint64 [n + 2] as group_device wrote them."""
