@@ -313,7 +313,7 @@ int kmcpg_submit_packed(kmcpg_db* db, const uint8_t* codes, const uint64_t* offs
  *    they stop at the first such window (a read shorter than `window` has none).  Each window is an ordinary query (qlen e - i, -m, -u,
  *    multi-k retries, -K, -n, -s / -S, -f apply per window); the result has ONE ROW PER WINDOW, read by read, start ascending, and is
  *    consumed by kmcpg_wait / kmcpg_wait_pairs as any other ticket.  The bases of each read are uploaded once and the k-mer kernels read a
- *    window's bases in place (windows.hip, k1_kmers.hip) on single-device handles; paged (kmcpg_open_paged) and multi-device
+ *    window's bases in place (windows.hip, k1_device.hpp) on single-device handles; paged (kmcpg_open_paged) and multi-device
  *    (kmcpg_open_devices) handles, and databases with several k-mer sizes searched without an explicit k, cut the windows into text on
  *    the host and search that (same results).  Windows that do not fit one batch of the handle (kmcpg_batch_hint, in window bases) are
  *    cut into pieces by the library — a read's windows may span several — and the ticket answers for all of them. */
@@ -518,7 +518,7 @@ int kmcpg_kmers_device(kmcpg_db* db, const uint8_t* d_seqs, const uint64_t* d_of
 /* The same on a batch that is on the device as 2-bit codes (the layout of kmcpg_submit_packed: base j of the batch in bits 2 (j % 4)
  * of d_codes[j / 4], 16 readable bytes behind the last one, 4-byte aligned; d_exc = its n_exc runs of foreign bytes on the device)
  * and d_text = total_bases + 16 writable bytes for whatever has to be expanded: whole genomes (k <= 128, plain or FracMinHash k-mers)
- * are hashed from the codes directly and only the 65 536-position segments a foreign byte reaches become text (k1_kmers.hip);
+ * are hashed from the codes directly and only the 65 536-position segments a foreign byte reaches become text (k1_seg.hip);
  * every other shape of batch is expanded whole first.  Debug/tests. */
 int kmcpg_kmers_device_packed(kmcpg_db* db, const uint8_t* d_codes, const kmcpg_exc_run* d_exc, uint32_t n_exc, uint8_t* d_text,
                               const uint64_t* d_offs, uint32_t n_reads, uint64_t total_bases, uint32_t max_read_len,

@@ -1,4 +1,4 @@
-// kernels.hpp — host-callable launchers of the HIP kernels in k1_kmers.hip, k1_dedup.hip, k2_cobs.hip, support.hip and sort_huge.hip.
+// kernels.hpp — host-callable launchers of the HIP kernels in k1_kmers.hip (K1 entry; kernels in k1_reads.hip, k1_windows.hip, k1_seg.hip, k1_win_once.hip), k1_dedup.hip, k2_cobs.hip, support.hip and sort_huge.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -120,7 +120,7 @@ void launch_stream_probe(const uint8_t* buf, uint64_t bytes, uint32_t* out, hipS
 void launch_debug_rowsort(uint64_t* hashes, const uint64_t* offs, const int32_t* nk, uint32_t n_reads, uint64_t num_sigs, uint64_t mh, int mode, hipStream_t st);
 
 // queries of up to this many emissions above -u are sorted by one wave (k_dedup_wave), which reads them from hashes[]; the
-// long-read sketch kernels keep the raw emissions of such queries for it (k1_kmers.hip)
+// long-read sketch kernels keep the raw emissions of such queries for it (k1_reads.hip, k1_windows.hip)
 constexpr int DEDUP_WAVE_CAP = 512;
 // queries with more than HUGE_MIN k-mers: device-wide sort + unique (sort_huge.hip)
 constexpr uint32_t HUGE_MIN = 65536;

@@ -1,15 +1,19 @@
 // nthash.hpp — ntHash v1 as kmcp uses it (will-rowe/nthash v0.4.0 behind bio/sketches; canonical hash = min(forward, reverse),
 // util-db-search.go:1037-1107 generateKmers), the parts that are plain arithmetic: the seed table, the rotations, and the ROLLING form
-// of the recurrence that k1_seg_roll walks along a lane's run of positions.  Compiles for the host as well: tests/nthash_check.cpp
-// runs the start-up + roll against the CPU restatement of the reference's k-mer hashes (tests/test_nthash_cpu.py).
+// of the recurrence that k1_seg_roll walks along a lane's run of positions, and the 2-bit form with its staging and tables (k1_seg_roll2,
+// k1_windows_roll).  Compiles for the host as well: tests/nthash_check.cpp runs the staging and the start-up + roll against the CPU
+// restatement of the reference's k-mer hashes (tests/test_nthash_cpu.py).
 #pragma once
 #include <stdint.h>
+#include <string.h>
 
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 #define KMCPG_NT_HD __host__ __device__ __forceinline__
+#define KMCPG_NT_UNROLL _Pragma("unroll")
 #else
 #define KMCPG_NT_HD inline
+#define KMCPG_NT_UNROLL
 #endif
 
 namespace kmcpg {
@@ -88,6 +92,57 @@ KMCPG_NT_HD uint32_t nt2_canon4(uint32_t c) {
 #endif
 }
 KMCPG_NT_HD bool nt2_valid4(uint32_t w, uint32_t c) { return (w & 0xDFDFDFDFu) == nt2_canon4(c); }
+// The staging rule of k1_windows_roll and k1_seg_roll2, and what tests/nthash_check.cpp stages with (tests/test_nthash_cpu.py pins it alone).
+// The two kernels keep this text written out in their prologues, and their pair tables likewise (nt2_fill_tables below): a call in its
+// place, whole or in parts, changes their compiled code; only nt2_fill_seeds is called from them.  The bases s[b0 .. b0 + 16) of a
+// stretch of nb bases become one word of 16 codes, base b0 + j at bit 2 j.  A whole group (b0 + 16 <= nb) is one 16-byte load — the source is wherever the read
+// starts: unaligned — and four bytes at a time: the code of each byte in its byte, back to letters to see that nothing else was there,
+// four codes folded into one byte; the last group of a stretch goes byte by byte; past nb the word is zero.  `bad` is raised (never
+// cleared) by a byte below nb that is not A / C / G / T in either case; what lies at or behind nb is not looked at.
+KMCPG_NT_HD uint32_t nt2_stage16(const uint8_t* s, int b0, int nb, bool& bad) {
+  uint32_t word = 0;
+  if (b0 + 16 <= nb) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef uint32_t u32x4_any __attribute__((ext_vector_type(4), aligned(1)));
+    const u32x4_any v = *reinterpret_cast<const u32x4_any*>(s + b0);
+    const uint32_t in[4] = {v.x, v.y, v.z, v.w};
+#else
+    uint32_t in[4];
+    memcpy(in, s + b0, 16);  // (little-endian hosts: byte j of a dword at bit 8 j, as on the device)
+#endif
+    KMCPG_NT_UNROLL
+    for (int d = 0; d < 4; d++) {
+      const uint32_t c = nt2_codes4(in[d]);
+      bad |= !nt2_valid4(in[d], c);
+      word |= nt2_fold4(c) << (8 * d);
+    }
+  } else if (b0 < nb) {
+    for (int j = 0; b0 + j < nb; j++) {
+      const uint32_t ch = s[b0 + j], c = (ch >> 1) & 3u;
+      bad |= (ch & 0xDFu) != (uint32_t)nt2_letter((int)c);
+      word |= c << (2 * j);
+    }
+  }
+  return word;
+}
+// What thread tid (< 16) of a workgroup contributes to the tables of the 2-bit roll: entry tid = (out << 2) | in of the kk-mer pair tables,
+// and (tid < 4) the seed of code tid and of its complement (complement of base b = tab[b & 7]).
+struct Nt2Pair {
+  uint64_t f2, r2;
+};
+KMCPG_NT_HD Nt2Pair nt2_pair(int tid, int kk) { return Nt2Pair{nt2_f2(tid >> 2, tid & 3, kk), nt2_r2(tid >> 2, tid & 3, kk)}; }
+KMCPG_NT_HD void nt2_fill_seeds(uint64_t* S, uint64_t* RC, int tid) {
+  S[tid] = seed_of(nt2_letter(tid));
+  RC[tid] = seed_of(nt2_letter(tid) & 7);
+}
+KMCPG_NT_HD void nt2_fill_tables(uint64_t* F2, uint64_t* R2, uint64_t* S, uint64_t* RC, int kk, int tid) {
+  if (tid < 16) {
+    const Nt2Pair p = nt2_pair(tid, kk);
+    F2[tid] = p.f2;
+    R2[tid] = p.r2;
+    if (tid < 4) nt2_fill_seeds(S, RC, tid);
+  }
+}
 // 8 two-bit fields (16 bits) -> the low halves of 8 nibbles; (spread(out) << 2) | spread(in) = the table index of 8 rolls, a nibble each
 KMCPG_NT_HD uint32_t nt2_spread(uint32_t x) {
   x = (x | (x << 8)) & 0x00FF00FFu;

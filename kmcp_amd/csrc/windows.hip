@@ -1,7 +1,7 @@
 // windows.hip — sliding windows of long queries (kmcpg_submit_windows, `kmcp-search --sliding-step/--sliding-window`): the window
 // descriptors of a batch, built on the device from the offsets of the reads' bases.  The bases of every read are uploaded once; a window is
 // (first base in the staged text, its place in the batch's window numbering) and the k-mer kernels read its bases where they are
-// (K1Args::src, k1_kmers.hip) — never a copy of the window as text.
+// (K1Args::src, k1_bases in k1_device.hpp) — never a copy of the window as text.
 //
 // Enumeration (seqkit sliding, restated in INTEGRATION.md): windows of a read of length L start at i = 0, S, 2S, ... and end at
 // e = min(i + W, L); without greedy only windows with i + W <= L exist, with greedy every i < L does.  The host stages, per read, the

@@ -59,7 +59,7 @@ def reference(case):
 
 
 def pre_done_state(case):
-    """what the fused k-mer kernel (wg_reads_windows, k1_kmers.hip) leaves for the stage when pre_done: per query (m, the list without
+    """what the fused k-mer kernel (wg_reads_windows, k1_reads.hip) leaves for the stage when pre_done: per query (m, the list without
     adjacent repeats) — in scratch and nk_search — for raw counts in (max(u, 512), 65536], (None, None) for the others, whose raw lists
     stay in hashes"""
     out = []

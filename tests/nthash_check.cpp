@@ -28,8 +28,8 @@ extern "C" long nt_roll_all(const unsigned char* seq, long len, int k, int scale
   return n;
 }
 
-// The 2-bit form of k1_seg_roll2, as one lane with a run as long as the sequence: bases folded to codes four at a time exactly as the
-// kernel's staging does (codes, validity, fold), then the start-up over the first window and one roll per position with the pair tables
+// The 2-bit form of k1_seg_roll2, as one lane with a run as long as the sequence: bases staged as codes by nt2_stage16 (codes, validity,
+// fold; the byte-wise tail), the tables filled by nt2_fill_tables, then the start-up over the first window and one roll per position with the pair tables
 // F2 / R2, the table index of every roll taken from the nibble words the kernel builds (spread + funnel shift by k).  Returns -1 when a
 // byte is not A / C / G / T in either case (the kernel hands such a segment to the byte kernel).
 extern "C" long nt_roll2_all(const unsigned char* seq, long len, int k, int scaled, unsigned long long max_hash, unsigned long long* out) {
@@ -38,38 +38,13 @@ extern "C" long nt_roll2_all(const unsigned char* seq, long len, int k, int scal
   const long nwords = len / 16 + 12;
   uint32_t* W = new uint32_t[(size_t)nwords]();
   bool bad = false;
-  for (long g = 0; g * 16 < len; g++) {
-    uint32_t word = 0;
-    if (g * 16 + 16 <= len) {
-      for (int d = 0; d < 4; d++) {
-        uint32_t in = 0;
-        for (int b = 0; b < 4; b++) in |= (uint32_t)seq[g * 16 + d * 4 + b] << (8 * b);
-        const uint32_t c = nt2_codes4(in);
-        bad |= !nt2_valid4(in, c);
-        word |= nt2_fold4(c) << (8 * d);
-      }
-    } else {
-      for (int j = 0; g * 16 + j < len; j++) {
-        const uint32_t ch = seq[g * 16 + j], c = (ch >> 1) & 3u;
-        bad |= (ch & 0xDFu) != (uint32_t)nt2_letter((int)c);
-        word |= c << (2 * j);
-      }
-    }
-    W[g] = word;
-  }
+  for (long g = 0; g * 16 < len; g++) W[g] = nt2_stage16(seq, (int)(g * 16), (int)len, bad);
   if (bad) {
     delete[] W;
     return -1;
   }
   uint64_t S[4], RC[4], F2[16], R2[16];
-  for (int i = 0; i < 16; i++) {
-    F2[i] = nt2_f2(i >> 2, i & 3, k);
-    R2[i] = nt2_r2(i >> 2, i & 3, k);
-  }
-  for (int i = 0; i < 4; i++) {
-    S[i] = seed_of(nt2_letter(i));
-    RC[i] = seed_of(nt2_letter(i) & 7);
-  }
+  for (int tid = 0; tid < 16; tid++) nt2_fill_tables(F2, R2, S, RC, k, tid);  // (the kernel: one entry per thread)
   uint64_t fh = 0, rh = 0;
   for (int j = 0; j < k; j++) {
     const uint32_t c = (W[j >> 4] >> (2 * (j & 15))) & 3u;
@@ -92,4 +67,13 @@ extern "C" long nt_roll2_all(const unsigned char* seq, long len, int k, int scal
   }
   delete[] W;
   return n;
+}
+
+// nt2_stage16 alone: the word of 16 codes for the bases seq[b0 .. b0 + 16) of a stretch of nb bases; *bad_out = 1 if it raised `bad`.
+// seq must be readable up to b0 + 16 where b0 + 16 <= nb, up to nb otherwise.
+extern "C" unsigned nt_stage16(const unsigned char* seq, int b0, int nb, int* bad_out) {
+  bool bad = false;
+  const uint32_t w = kmcpg::nt2_stage16(seq, b0, nb, bad);
+  *bad_out = bad ? 1 : 0;
+  return w;
 }

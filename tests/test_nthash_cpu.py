@@ -75,3 +75,49 @@ def test_two_bit_rolling_form_equals_the_oracle(nt, oracle_lib):
             s = base.copy()
             s[pos] = ch
             assert nt.nt_roll2_all(s.tobytes(), 200, 21, 0, 0, out.ctypes.data) == -1, (pos, ch)
+
+
+def test_stage16_alone_word_tail_and_foreign_bytes(nt):
+    """nt2_stage16 (nthash.hpp) alone, the staging rule of k1_seg_roll2 and k1_windows_roll: for every stretch length nb of 0 .. 40 and the
+    words at b0 = 0, 16, 32 (whole groups, the byte-wise tail, and words past the end) the word is code = (byte >> 1) & 3 at bit 2 j for
+    the bases below nb and zero beyond; one foreign byte at a position below nb raises `bad` in the word that covers it (and in no other),
+    the same byte at or beyond nb raises nothing and changes no word."""
+    nt.nt_stage16.restype = C.c_uint
+    nt.nt_stage16.argtypes = [C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_int)]
+    bad = C.c_int(0)
+
+    def stage(buf, b0, nb):
+        w = nt.nt_stage16(bytes(buf), b0, nb, C.byref(bad))
+        return int(w), bad.value
+
+    def plain(buf, b0, nb):
+        w = 0
+        for j in range(16):
+            if b0 + j < nb:
+                w |= ((buf[b0 + j] >> 1) & 3) << (2 * j)
+        return w
+
+    acgt = np.frombuffer(b"ACGTacgt", dtype=np.uint8)
+    n_words = 0
+    for seed in (1, 2, 3):
+        rng = np.random.default_rng(seed)
+        for nb in range(41):
+            seq = bytearray(acgt[rng.integers(0, 8, size=48)].tobytes())
+            clean = {}
+            for b0 in (0, 16, 32):
+                w, b = stage(seq, b0, nb)
+                assert w == plain(seq, b0, nb), (seed, nb, b0, hex(w))
+                assert b == 0, (seed, nb, b0)
+                clean[b0] = w
+                n_words += 1
+            for foreign in (ord("N"), ord("n"), ord("R"), ord("U"), 0x00, 0xFF):
+                for pos in range(48):
+                    buf = bytearray(seq)
+                    buf[pos] = foreign
+                    for b0 in (0, 16, 32):
+                        w, b = stage(buf, b0, nb)
+                        covers = pos < nb and b0 <= pos < b0 + 16
+                        assert b == int(covers), (seed, nb, b0, pos, foreign)
+                        if not covers:
+                            assert w == clean[b0], (seed, nb, b0, pos, foreign)
+    assert n_words == 3 * 41 * 3

@@ -1,5 +1,5 @@
 """The sliding-window test plan of the k-mer stage: the hash-once kernels k1_win_hash / k1_win_scan / k1_win_rank / k1_win_gather (form WinOnce
-of kmcp_amd/csrc/k1_kmers.hip), k_window_desc (windows.hip) and the window view (K1Args::src, k1_bases) through which every other K1 form reads
+of kmcp_amd/csrc/k1_win_once.hip), k_window_desc (windows.hip) and the window view (K1Args::src, k1_bases) through which every other K1 form reads
 a window's bases in place — with the smallest batches that reach each edge of them, and the witness every case must produce.
 
 A case is a database (open_synthetic: k, sketch mode, w or s, scale), reads with (step, window, greedy), an optional explicit cut of its
