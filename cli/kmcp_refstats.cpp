@@ -1,0 +1,310 @@
+// kmcp-refstats: which references are in the sample — host-side mirror of stage 1/4 of `kmcp profile` ("counting matches and unique
+// matches for filtering out low-confidence references", kmcp/cmd/profile.go:761-1099; row parser util-profile.go:94-182).  Host only, no GPU.
+//
+//   kmcp-refstats [-o out.tsv[.gz]] [-f 0.01] [-t 0.55] [-n 0] [--keep-perfect-matches] [--keep-main-matches] [--max-qcov-gap 0.4]
+//                 [-m 3] [-p frac] [-H qcov] [--level species|strain|assembly] [-T map.tsv[,more.tsv]]... [-X taxdump/] [-i list.txt]
+//                 [a.tsv[.gz] ...]
+//
+// Semantics restated from the reference (the counting rule, the verdict and the presets are kmcp_amd/csrc/refstats_rule.hpp):
+//   * blank lines and every line that starts with '#' are dropped;
+//   * a row is cut at its first 12 tabs (fewer than 13 fields is fatal); qCov (field 12) is parsed and the row dropped when it is below
+//     -t, THEN FPR (field 4) is parsed and the row dropped when it is above -f; then the integer fields are parsed (a bad one is fatal);
+//   * the remaining rows of consecutive equal query names form a query (per input file; counters accumulate across files); within a query
+//     --keep-perfect-matches, --keep-main-matches / --max-qcov-gap and -n cut later rows;
+//   * a reference's chunks and tLen are those of its first row; at --level species a target without a TaxId is fatal;
+//   * -m picks H and p (mode 0 also --keep-main-matches); -H / -p override the preset only when given; the VALUE of -H (0.75 when not
+//     given) must lie in [-t, 1], as in the reference, whatever the mode.
+// The reference prints none of this (it goes on to stages 2-4); the output format is this tool's:
+//   # matched reads: N
+//   # unique reads: U
+//   #ref chunks tLen reads ureads hicUreads chunksFrac verdict chunkReads chunkFirsts chunkUreads chunkHicUreads
+// one line per reference with at least one row, in ascending byte order of the name; the four per-chunk lists are comma-joined.
+#include <unistd.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <fstream>
+#include <string>
+#include <unordered_map>
+#include <vector>
+
+#include "../kmcp_amd/csrc/refstats_rule.hpp"
+#include "../kmcp_amd/csrc/taxonomy.hpp"
+#include "tsv_in.hpp"
+#include "tsv_out.hpp"
+
+namespace {
+
+using tsv_in::parse_float;
+using tsv_in::RawLines;
+using tsv_out::die;
+using tsv_out::Out;
+
+void usage() {
+  fputs(
+      "Count matches and unique matches per reference and judge which references are in the sample (stage 1/4 of kmcp profile)\n\n"
+      "Usage:\n  kmcp-refstats [flags] [<search results> ...]\n\n"
+      "Flags:\n"
+      "  -o, --out-file string             Out file, supports a \".gz\" suffix (\"-\" for stdout). (default \"-\")\n"
+      "  -f, --max-fpr float               Maximum false positive rate of a read in search result. (default 0.01)\n"
+      "  -t, --min-query-cov float         Minimum query coverage of a read in search result. (default 0.55)\n"
+      "  -n, --keep-top-qcovs int          Keep matches with the top N qCovs for a query, 0 for all.\n"
+      "      --keep-perfect-matches        Only keep the perfect matches (qCov == 1) if there are.\n"
+      "      --keep-main-matches           Only keep main matches, abandon matches with sharply decreased qCov (> --max-qcov-gap).\n"
+      "      --max-qcov-gap float          Max qCov gap between adjacent matches. (default 0.4)\n"
+      "  -m, --mode int                    Profiling mode, 0-5. (default 3)\n"
+      "  -p, --min-chunks-fraction float   Minimum fraction of matched reference chunks with reads. (default 0.8)\n"
+      "  -H, --min-hic-ureads-qcov float   Minimum query coverage of high-confidence uniquely matched reads. (default 0.75)\n"
+      "  -T, --taxid-map strings           Tabular two-column file(s) mapping reference IDs to TaxIds.\n"
+      "  -X, --taxdump string              Directory of NCBI taxonomy dump files: nodes.dmp, optional with merged.dmp and delnodes.dmp.\n"
+      "      --level string                Level to estimate abundance at. available values: species, strain/assembly. (default \"species\")\n"
+      "      --line-chunk-size int         Accepted for command-line compatibility. (default 5000)\n"
+      "  -i, --infile-list string          File of input files list (one file per line).\n",
+      stderr);
+}
+
+// strconv.Atoi / ParseUint of a whole field
+bool parse_int(const char* p, size_t n, bool sign_ok, uint64_t* v, bool* neg) {
+  size_t i = 0;
+  *neg = false;
+  if (sign_ok && n && (p[0] == '-' || p[0] == '+')) *neg = p[0] == '-', i = 1;
+  if (i == n) return false;
+  uint64_t x = 0;
+  for (; i < n; i++) {
+    if (p[i] < '0' || p[i] > '9') return false;
+    const uint64_t d = (uint64_t)(p[i] - '0');
+    if (x > (UINT64_MAX - d) / 10) return false;
+    x = x * 10 + d;
+  }
+  if (sign_ok && x > (uint64_t)INT64_MAX) return false;
+  *v = x;
+  return true;
+}
+
+struct Ref {
+  uint32_t target_class, species_class;
+  uint64_t chunks, tlen, base;  // its counters: 4 words per chunk from counters[4 * base]
+};
+
+}  // namespace
+
+int main(int argc, char** argv) {
+  std::string out_file = "-", level = "species", taxdump, infile_list;
+  std::vector<std::string> map_files, files;
+  double max_fpr = 0.01, min_qcov = 0.55, flag_h = 0.75, flag_p = 0.8, max_gap = 0.4;
+  bool given_h = false, given_p = false, keep_perfect = false, keep_main = false;
+  long chunk = 5000, top_n = 0, mode = kmcpg::REFSTATS_DEFAULT_MODE;
+  auto need = [&](int& i) -> const char* {
+    if (i + 1 >= argc) die("flag needs an argument: %s", argv[i]);
+    return argv[++i];
+  };
+  auto num = [&](const char* flag, const char* v) {
+    double x = 0;
+    if (!parse_float(v, strlen(v), &x)) die("invalid argument \"%s\" for \"%s\" flag", v, flag);
+    return x;
+  };
+  auto integer = [&](const char* flag, const char* v) {
+    uint64_t x = 0;
+    bool neg = false;
+    if (!parse_int(v, strlen(v), true, &x, &neg)) die("invalid argument \"%s\" for \"%s\" flag", v, flag);
+    return neg ? -(long)x : (long)x;
+  };
+  // `kmcp-refstats ref-stats ...` = `kmcp utils ref-stats ...`: the sub-command word, accepted (only) as the first argument
+  for (int i = (argc > 1 && strcmp(argv[1], "ref-stats") == 0) ? 2 : 1; i < argc; i++) {
+    const std::string a = argv[i];
+    if (a == "-o" || a == "--out-file") out_file = need(i);
+    else if (a == "-f" || a == "--max-fpr") max_fpr = num("-f, --max-fpr", need(i));
+    else if (a == "-t" || a == "--min-query-cov") min_qcov = num("-t, --min-query-cov", need(i));
+    else if (a == "-n" || a == "--keep-top-qcovs") top_n = integer("-n, --keep-top-qcovs", need(i));
+    else if (a == "--keep-perfect-matches") keep_perfect = true;
+    else if (a == "--keep-main-matches") keep_main = true;
+    else if (a == "--max-qcov-gap") max_gap = num("--max-qcov-gap", need(i));
+    else if (a == "-m" || a == "--mode") mode = integer("-m, --mode", need(i));
+    else if (a == "-p" || a == "--min-chunks-fraction") flag_p = num("-p, --min-chunks-fraction", need(i)), given_p = true;
+    else if (a == "-H" || a == "--min-hic-ureads-qcov") flag_h = num("-H, --min-hic-ureads-qcov", need(i)), given_h = true;
+    else if (a == "-T" || a == "--taxid-map") {
+      std::string v = need(i);  // a StringSlice flag: repeatable, each value a comma list
+      size_t at = 0;
+      for (;;) {
+        const size_t c = v.find(',', at);
+        const std::string one = v.substr(at, c == std::string::npos ? std::string::npos : c - at);
+        if (!one.empty()) map_files.push_back(one);
+        if (c == std::string::npos) break;
+        at = c + 1;
+      }
+    } else if (a == "-X" || a == "--taxdump") taxdump = need(i);
+    else if (a == "--level") level = need(i);
+    else if (a == "--line-chunk-size") chunk = integer("--line-chunk-size", need(i));
+    else if (a == "-i" || a == "--infile-list") infile_list = need(i);
+    else if (a == "-j" || a == "--threads" || a == "--log") need(i);  // accepted for command-line compatibility
+    else if (a == "-q" || a == "--quiet") {
+    } else if (a == "-h" || a == "--help") {
+      usage();
+      return 0;
+    } else if (a.size() > 1 && a[0] == '-') die("unknown flag: %s", a.c_str());
+    else files.push_back(a);
+  }
+  // profile.go:315-485, in its order
+  if (mode < 0) die("value of flag --mode should be greater than or equal to 0");
+  if (mode >= kmcpg::REFSTATS_MODES) die("invalid profiling mode: %ld", mode);
+  if (max_fpr <= 0) die("value of flag --max-fpr should be greater than 0");
+  if (min_qcov < 0) die("value of flag --min-query-cov should be greater than or equal to 0");
+  if (top_n < 0) die("value of flag --keep-top-qcovs should be greater than or equal to 0");
+  if (flag_p < 0) die("value of flag --min-chunks-fraction should be greater than or equal to 0");
+  if (flag_p > 1) die("the value of -p/--min-chunks-fraction (%f) should be in range of [0, 1]", flag_p);
+  if (flag_h <= 0) die("value of flag --min-hic-ureads-qcov should be greater than 0");
+  if (flag_h > 1 || flag_h < min_qcov) die("the value of -H/--min-hic-ureads-qcov (%f) should be in range of [<-t/--min-query-cov>, 1]", flag_h);
+  kmcpg::RefstatsMode preset = kmcpg::refstats_mode((int)mode);
+  const double H = given_h ? flag_h : preset.hic_min_qcov, min_frac = given_p ? flag_p : preset.min_chunks_fraction;
+  keep_main = keep_main || preset.keep_main;
+  for (char& c : level) c = (char)tolower((unsigned char)c);
+  bool level_species = false;
+  if (level == "species") level_species = true;
+  else if (level != "strain" && level != "assembly") die("invalid value for --level, available values: species, strain/assembly");
+  if (!map_files.empty() && taxdump.empty()) die("flag -X/--taxdump is needed when -T/--taxid-map given");
+  if (map_files.empty() && !taxdump.empty()) die("flag -T/--taxid-map is needed when -X/--taxdump given");
+  if (level_species && map_files.empty()) die("-T/--taxid-map needed for --level species");
+  if (chunk <= 0) die("value of flag --line-chunk-size should be greater than 0");
+
+  for (const std::string& f : files)
+    if (f != "-" && access(f.c_str(), F_OK) != 0) die("%s: stat %s: %s", f.c_str(), f.c_str(), strerror(errno));
+  if (!infile_list.empty()) {
+    std::ifstream fh(infile_list);
+    if (!fh) die("read file list from '%s': %s", infile_list.c_str(), strerror(errno));
+    std::string l;
+    while (std::getline(fh, l)) {
+      if (l.find_first_not_of(" \t\r\n") == std::string::npos) continue;
+      if (!l.empty() && l.back() == '\r') l.pop_back();
+      if (l != "-" && access(l.c_str(), F_OK) != 0) die("check file '%s': stat %s: %s", l.c_str(), l.c_str(), strerror(errno));
+      files.push_back(l);
+    }
+  }
+  if (files.empty()) files.push_back("-");
+  for (const std::string& f : files)
+    if (f != "-" && tsv_in::clean_path(f) == tsv_in::clean_path(out_file)) die("out file should not be one of the input file");
+
+  kmcpg::TaxidMap tmap;
+  kmcpg::Taxonomy tax;
+  if (!map_files.empty()) {
+    std::string err;
+    for (const std::string& f : map_files)
+      if (!tmap.load(f, &err)) die("%s", err.c_str());
+    if (tmap.ids.empty()) {
+      std::string all;
+      for (const std::string& f : map_files) all += (all.empty() ? "" : ", ") + f;
+      die("no valid TaxIds found in TaxId mapping file: %s", all.c_str());
+    }
+    if (!tax.load(taxdump, &err)) die("%s", err.c_str());
+  }
+
+  // target name -> its classes and counters, filled as targets are met (chunks and tLen: the first row's)
+  std::unordered_map<std::string, Ref> refs;
+  std::vector<uint64_t> counters;
+  std::string name;
+  auto ref_of = [&](const char* p, size_t n, uint64_t chunks, uint64_t tlen) -> const Ref& {
+    name.assign(p, n);
+    auto it = refs.find(name);
+    if (it != refs.end()) return it->second;
+    if (chunks > 65535) die("%s: %llu chunks (IdxNum); an index holds at most 65535 per reference", name.c_str(), (unsigned long long)chunks);
+    Ref r{(uint32_t)refs.size(), 0, chunks, tlen, counters.size() / kmcpg::REFSTATS_WORDS};
+    if (level_species) {
+      auto t = tmap.ids.find(name);
+      if (t == tmap.ids.end()) die("unknown taxid for %s, please check taxid mapping file(s)", name.c_str());
+      r.species_class = tax.species_of(t->second);
+    }
+    counters.resize(counters.size() + (size_t)chunks * kmcpg::REFSTATS_WORDS, 0);
+    return refs.emplace(name, r).first->second;
+  };
+
+  uint64_t matched = 0, unique = 0;
+  kmcpg::RefstatsCut cut;
+  cut.keep_perfect = keep_perfect, cut.keep_main = keep_main, cut.max_gap = max_gap, cut.top_n = (int)std::min<long>(top_n, INT32_MAX);
+  for (const std::string& file : files) {
+    RawLines in(file);
+    std::string query;  // the name of the previous row that passed -t / -f
+    bool any = false;
+    std::vector<kmcpg::RefstatsRow> rows;  // the current query's kept rows
+    auto flush = [&] {
+      if (rows.empty()) return;
+      matched++;
+      if (kmcpg::refstats_count_query(rows.data(), rows.size(), level_species, H, [&](uint64_t col, int w) { counters[col * kmcpg::REFSTATS_WORDS + w]++; })) unique++;
+      rows.clear();
+    };
+    const char* p = nullptr;
+    size_t n = 0;
+    while (in.next(&p, &n)) {
+      size_t len = n;  // without the end of line
+      if (len && p[len - 1] == '\n') len--;
+      if (len && p[len - 1] == '\r') len--;
+      if (len == 0 || p[0] == '#') continue;
+      size_t tab[13];
+      int nt = 0;
+      for (size_t i = 0; i < len && nt < 12; i++)
+        if (p[i] == '\t') tab[nt++] = i;
+      if (nt < 12) die("invalid kmcp search result format");
+      auto field = [&](int k, const char** fp) -> size_t {  // field k = 1..12 (the 13th keeps the rest of the line)
+        *fp = k == 1 ? p : p + tab[k - 2] + 1;
+        return tab[k - 1] - (size_t)(*fp - p);
+      };
+      const char* fp;
+      size_t fn;
+      double fpr = 0, qcov = 0;
+      fn = field(12, &fp);
+      if (!parse_float(fp, fn, &qcov)) die("failed to parse qCov: %.*s", (int)fn, fp);
+      if (qcov < min_qcov) continue;
+      fn = field(4, &fp);
+      if (!parse_float(fp, fn, &fpr)) die("failed to parse FPR: %.*s", (int)fn, fp);
+      if (fpr > max_fpr) continue;
+      uint64_t v[12] = {};
+      bool neg[12] = {};
+      static const struct {
+        int k;
+        const char* what;
+      } ints[] = {{2, "qLen"}, {3, "qKmers"}, {5, "hits"}, {7, "chunkIdx"}, {8, "IdxNum"}, {9, "genomeSize"}, {10, "K"}, {11, "mKmers"}};
+      for (const auto& f : ints) {
+        fn = field(f.k, &fp);
+        if (!parse_int(fp, fn, f.k != 9, &v[f.k], &neg[f.k])) die("failed to parse %s: %.*s", f.what, (int)fn, fp);
+      }
+      const bool first = !any || query.size() != tab[0] || memcmp(query.data(), p, tab[0]) != 0;
+      if (first) {
+        flush();
+        query.assign(p, tab[0]);
+        any = true;
+      }
+      if (!cut.keep(first, qcov)) continue;
+      fn = field(6, &fp);
+      const uint64_t chunks = neg[8] ? 0 : v[8];
+      const Ref& r = ref_of(fp, fn, chunks, v[9]);
+      if (neg[7] || v[7] >= r.chunks) die("chunkIdx %s%llu of %.*s is outside its %llu chunks", neg[7] ? "-" : "", (unsigned long long)v[7], (int)fn, fp, (unsigned long long)r.chunks);
+      rows.push_back(kmcpg::RefstatsRow{r.target_class, r.species_class, r.base + v[7], qcov});
+    }
+    flush();
+  }
+
+  Out out(out_file, -1);
+  char line[256];
+  out.write(line, (size_t)snprintf(line, sizeof line, "# matched reads: %llu\n# unique reads: %llu\n", (unsigned long long)matched, (unsigned long long)unique));
+  out.write("#ref\tchunks\ttLen\treads\tureads\thicUreads\tchunksFrac\tverdict\tchunkReads\tchunkFirsts\tchunkUreads\tchunkHicUreads\n");
+  std::vector<const std::pair<const std::string, Ref>*> order;
+  for (const auto& kv : refs) order.push_back(&kv);
+  std::sort(order.begin(), order.end(), [](auto* a, auto* b) { return a->first < b->first; });
+  std::string s;
+  for (const auto* kv : order) {
+    const Ref& r = kv->second;
+    const uint64_t* w = counters.data() + r.base * kmcpg::REFSTATS_WORDS;
+    const kmcpg::RefstatsRef t = kmcpg::refstats_rollup(r.chunks, min_frac, [&](uint64_t c) { return w + c * kmcpg::REFSTATS_WORDS; });
+    s = kv->first;
+    s.append(line, (size_t)snprintf(line, sizeof line, "\t%llu\t%llu\t%llu\t%llu\t%llu\t%.4f\t%s", (unsigned long long)r.chunks, (unsigned long long)r.tlen,
+                                    (unsigned long long)t.reads, (unsigned long long)t.ureads, (unsigned long long)t.hic_ureads, t.chunks_frac,
+                                    kmcpg::refstats_verdict_name(t.verdict)));
+    for (int j = 0; j < kmcpg::REFSTATS_WORDS; j++)
+      for (uint64_t c = 0; c < r.chunks; c++) {
+        s.push_back(c ? ',' : '\t');
+        s += std::to_string(w[c * kmcpg::REFSTATS_WORDS + j]);
+      }
+    s.push_back('\n');
+    out.write(s);
+  }
+  out.close();
+  return 0;
+}

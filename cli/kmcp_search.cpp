@@ -86,6 +86,13 @@ struct Options {
   // written — what `kmcp-filter -f 1 -t 0 --level L -T ... -X ...` makes of the plain output (K4 of the library, kmcpg_set_specific)
   std::string specific_level, taxdump;
   std::vector<std::string> taxid_maps;
+  // --ref-stats FILE [--ref-stats-*]: stage 1/4 of `kmcp profile` counted on the GPU while the search runs — the file is what
+  // `kmcp-refstats -f 1 -t 0 -m N --level L ...` writes from this run's unfiltered TSV (K6 of the library, kmcpg_set_refstats)
+  std::string ref_stats, ref_stats_level;
+  int ref_stats_mode = 3;
+  double ref_stats_h = 0.75, ref_stats_p = 0.8;
+  bool ref_stats_h_given = false, ref_stats_p_given = false;
+  const char* ref_stats_flag = nullptr;  // the first --ref-stats-* flag other than --ref-stats that was given
   std::vector<std::string> also_dbs;  // --also-db: further databases searched in the same pass, the output merged as kmcp-merge would
   bool gpus_given = false;
   int min_qlen = 30, min_kmers = 10, dedup = 256, top_scores = 0, threads = 0, device = 0, batch = 131072, gpus = 1, gpu_passes = -1;
@@ -135,6 +142,14 @@ static void usage() {
       "                             without these flags, followed by the trailer; the decision is made on the GPU.  Targets are the printed\n"
       "                             ones (after -N / -D); at level species every target of the database needs a TaxId.\n"
       "                             Not with -K, --try-se, -n, --sliding-* (except for --regions-bed), --gpus/--gpu-ids, --gpu-passes.\n"
+      "           --ref-stats file [--ref-stats-mode int (3)] [--ref-stats-min-hic-ureads-qcov float] [--ref-stats-min-chunks-fraction float]\n"
+      "                             [--ref-stats-level species|strain|assembly] [--taxid-map file(s) --taxdump dir]\n"
+      "                             count, on the GPU while the search runs, what stage 1/4 of `kmcp profile` counts per reference (reads,\n"
+      "                             uniquely matched reads, high-confidence ones, chunks covered) and judge which references are in the\n"
+      "                             sample: the file is what `kmcp-refstats -f 1 -t 0 -m N --level L ...` writes from this command's\n"
+      "                             unfiltered output, which is written as before.  Modes 1-5 are kmcp profile's presets (mode 0 cuts\n"
+      "                             rows: use kmcp-refstats).  The level defaults to species with --taxid-map and --taxdump, else strain.\n"
+      "                             Not with what --specific-level refuses.\n"
       "           --parse-only (read the inputs and print records / bases / checksum per file; no database, no GPU)\n"
       "           --regions-bed file [--regions-min-overlap int (1)] [--regions-max-gap int (0)] [--regions-ignore-type]\n"
       "                             [--regions-name-species string] [--regions-name-assembly string]\n"
@@ -175,6 +190,7 @@ static Options parse_args(int argc, char** argv) {
       {"gpu", 0, 1}, {"gpu-batch", 0, 1}, {"gpus", 0, 1}, {"gpu-ids", 0, 1}, {"gpu-passes", 0, 1}, {"parse-only", 0, 0}, {"help", 'h', 0}, {"version", 'V', 0},
       {"sliding-step", 0, 1}, {"sliding-window", 0, 1}, {"sliding-greedy", 0, 0}, {"also-db", 0, 1},
       {"specific-level", 0, 1}, {"taxid-map", 0, 1}, {"taxdump", 0, 1},
+      {"ref-stats", 0, 1}, {"ref-stats-mode", 0, 1}, {"ref-stats-min-hic-ureads-qcov", 0, 1}, {"ref-stats-min-chunks-fraction", 0, 1}, {"ref-stats-level", 0, 1},
       {"regions-bed", 0, 1}, {"regions-min-overlap", 0, 1}, {"regions-max-gap", 0, 1}, {"regions-ignore-type", 0, 0},
       {"regions-name-species", 0, 1}, {"regions-name-assembly", 0, 1}};
   auto regions_flag = [&](const char* flag) {
@@ -229,6 +245,11 @@ static Options parse_args(int argc, char** argv) {
     else if (name == "sliding-window") { o.sliding_window = to_i(name, v); o.sliding_window_given = true; }
     else if (name == "sliding-greedy") o.sliding_greedy = true;
     else if (name == "also-db") o.also_dbs.push_back(v);
+    else if (name == "ref-stats") o.ref_stats = v;
+    else if (name == "ref-stats-mode") { o.ref_stats_mode = to_i(name, v); if (!o.ref_stats_flag) o.ref_stats_flag = "--ref-stats-mode"; }
+    else if (name == "ref-stats-min-hic-ureads-qcov") { o.ref_stats_h = to_f(name, v); o.ref_stats_h_given = true; if (!o.ref_stats_flag) o.ref_stats_flag = "--ref-stats-min-hic-ureads-qcov"; }
+    else if (name == "ref-stats-min-chunks-fraction") { o.ref_stats_p = to_f(name, v); o.ref_stats_p_given = true; if (!o.ref_stats_flag) o.ref_stats_flag = "--ref-stats-min-chunks-fraction"; }
+    else if (name == "ref-stats-level") { o.ref_stats_level = v; for (char& c : o.ref_stats_level) c = (char)tolower((unsigned char)c); if (!o.ref_stats_flag) o.ref_stats_flag = "--ref-stats-level"; }
     else if (name == "specific-level") { o.specific_level = v; for (char& c : o.specific_level) c = (char)tolower((unsigned char)c); }
     else if (name == "taxdump") o.taxdump = v;
     else if (name == "taxid-map") {
@@ -297,6 +318,7 @@ static Options parse_args(int argc, char** argv) {
 
 #include "../kmcp_amd/csrc/taxonomy.hpp"
 #include "../kmcp_amd/csrc/regions_rule.hpp"
+#include "../kmcp_amd/csrc/refstats_rule.hpp"
 #include "search_batch.hpp"
 #include "row_format.hpp"
 
@@ -461,7 +483,7 @@ static int run_parse_only(const Options& o) {
 static int validate_flags(const Options& o, bool sliding) {
   // --specific-level: what would judge something else than a query's final matches, and the handles that do not hold them in one place,
   // are refused here, before a file or a GPU is touched (the words of kmcp utils filter where it has them, filter.go:93-114)
-  if (o.specific_level.empty() && (!o.taxid_maps.empty() || !o.taxdump.empty())) die("flags --taxid-map and --taxdump are only used with --specific-level");
+  if (o.specific_level.empty() && o.ref_stats.empty() && (!o.taxid_maps.empty() || !o.taxdump.empty())) die("flags --taxid-map and --taxdump are only used with --specific-level");
   if (!o.specific_level.empty()) {
     const bool species = o.specific_level == "species";
     if (!species && o.specific_level != "strain" && o.specific_level != "assembly")
@@ -473,6 +495,26 @@ static int validate_flags(const Options& o, bool sliding) {
     if (!o.taxid_maps.empty() && o.taxdump.empty()) die("flag --taxdump is needed when --taxid-map given");
     if (o.taxid_maps.empty() && !o.taxdump.empty()) die("flag --taxid-map is needed when --taxdump given");
     if ((o.taxid_maps.empty() || o.taxdump.empty()) && species) die("TaxID mapping files (--taxid-map) and taxonomy dump files (--taxdump) are needed for --specific-level species");
+  }
+  // --ref-stats: the same refusals as --specific-level, for the same reason (what is counted must be every query's final matches, counted
+  // once); mode 0 cuts rows of a query, which only the TSV route can do
+  if (o.ref_stats.empty() && o.ref_stats_flag) die("flag %s is only used with --ref-stats", o.ref_stats_flag);
+  if (!o.ref_stats.empty()) {
+    const char* bad = o.keep_unmatched ? "-K/--keep-unmatched" : o.try_se ? "--try-se" : o.top_scores != 0 ? "-n/--keep-top-scores"
+                      : sliding ? "--sliding-step/--sliding-window/--sliding-greedy" : o.gpus_given ? "--gpus/--gpu-ids" : o.gpu_passes >= 0 ? "--gpu-passes" : nullptr;
+    if (bad) die("flag %s cannot be combined with --ref-stats", bad);
+    if (o.ref_stats_mode < 0 || o.ref_stats_mode >= kmcpg::REFSTATS_MODES) die("invalid profiling mode: %d", o.ref_stats_mode);
+    if (o.ref_stats_mode == 0)
+      die("flag --ref-stats-mode 0 is not supported: its main-match cut (--keep-main-matches) drops rows of a query before they are counted; run kmcp-refstats -m 0 on the search result");
+    if (o.ref_stats_p < 0 || o.ref_stats_p > 1) die("the value of --ref-stats-min-chunks-fraction (%f) should be in range of [0, 1]", o.ref_stats_p);
+    if (!(o.ref_stats_h > 0) || o.ref_stats_h > 1) die("the value of --ref-stats-min-hic-ureads-qcov (%f) should be in range of (0, 1]", o.ref_stats_h);
+    const bool both = !o.taxid_maps.empty() && !o.taxdump.empty();
+    const std::string& lv = o.ref_stats_level;
+    if (!lv.empty() && lv != "species" && lv != "strain" && lv != "assembly") die("invalid value for --ref-stats-level, available values: species, strain/assembly");
+    if (!o.taxid_maps.empty() && o.taxdump.empty()) die("flag --taxdump is needed when --taxid-map given");
+    if (o.taxid_maps.empty() && !o.taxdump.empty()) die("flag --taxid-map is needed when --taxdump given");
+    if (lv == "species" && !both) die("TaxID mapping files (--taxid-map) and taxonomy dump files (--taxdump) are needed for --ref-stats-level species");
+    if (o.ref_stats == o.out_file) die("flag --ref-stats: the statistics file must not be the search result's file");
   }
   // sliding windows: seqkit sliding has no meaning for pairs, whole files as queries or one ID for everything
   if (sliding) {
@@ -984,6 +1026,79 @@ static void set_specific(const Options& o, kmcpg_db* db, const std::vector<std::
   if (kmcpg_set_specific(db, cls.data(), species ? sp.data() : nullptr, (uint32_t)cls.size()) != 0) die("%s", kmcpg_last_error());
 }
 
+// --ref-stats: the level (species by default where there is a taxonomy), the preset, and the library's stage with tables of its own
+static bool ref_stats_species(const Options& o) { return o.ref_stats_level.empty() ? !o.taxid_maps.empty() && !o.taxdump.empty() : o.ref_stats_level == "species"; }
+static void set_ref_stats(const Options& o, kmcpg_db* db, const std::vector<std::string>& target, const kmcpg::Taxonomy* tax, const kmcpg::TaxidMap* map) {
+  const bool species = ref_stats_species(o);
+  std::vector<uint32_t> cls, sp;
+  uint64_t unknown = 0;
+  std::string missing;
+  if (!kmcpg::specific_classes(target, species ? map : nullptr, species ? tax : nullptr, &cls, species ? &sp : nullptr, &unknown, &missing))
+    die("unknown taxid for %s, please check taxid mapping file(s)", missing.c_str());
+  if (unknown && o.specific_level.empty()) warn("%llu TaxId(s) of the database's targets are deleted or not in nodes.dmp: they belong to no species", (unsigned long long)unknown);
+  const double H = o.ref_stats_h_given ? o.ref_stats_h : kmcpg::refstats_mode(o.ref_stats_mode).hic_min_qcov;
+  if (kmcpg_set_refstats(db, cls.data(), species ? sp.data() : nullptr, (uint32_t)cls.size(), H) != 0) die("%s", kmcpg_last_error());
+}
+
+// ... and the file, once every batch has been waited for: kmcp-refstats' format (cli/kmcp_refstats.cpp), the references by name, each from
+// the counters of its columns (kmcp_amd/csrc/refstats_rule.hpp); returns the references written
+static uint64_t write_ref_stats(const Options& o, kmcpg_db* db, const std::vector<std::string>& target, uint64_t* reruns) {
+  const uint32_t n_cols = (uint32_t)target.size();
+  std::vector<kmcpg_col_stats> cols(n_cols);
+  kmcpg_refstats_totals tot;
+  if (kmcpg_refstats_read(db, cols.data(), n_cols, &tot) != 0) die("%s", kmcpg_last_error());
+  *reruns = tot.skipped_launches;
+  struct Ref {
+    uint64_t chunks = 0, tlen = 0;
+    std::vector<uint64_t> w;  // [chunks][4]
+  };
+  std::map<std::string, Ref> refs;  // ascending byte order of the name
+  for (uint32_t c = 0; c < n_cols; c++) {
+    if (cols[c].rows == 0) continue;
+    uint32_t tidx = 0;
+    uint64_t gsize = 0;
+    kmcpg_col_info(db, c, nullptr, &tidx, &gsize, nullptr);
+    Ref& r = refs[target[c]];
+    if (r.w.empty()) {  // chunks and tLen: the reference's first column with rows
+      r.chunks = tidx >> 16;
+      r.tlen = gsize;
+      r.w.assign((size_t)r.chunks * kmcpg::REFSTATS_WORDS, 0);
+    }
+    const uint64_t chunk = (uint16_t)tidx;
+    if (chunk >= r.chunks) die("--ref-stats: chunk %llu of %s is outside its %llu chunks", (unsigned long long)chunk, target[c].c_str(), (unsigned long long)r.chunks);
+    const uint64_t v[kmcpg::REFSTATS_WORDS] = {cols[c].rows, cols[c].firsts, cols[c].ureads, cols[c].hic_ureads};
+    for (int j = 0; j < kmcpg::REFSTATS_WORDS; j++) r.w[chunk * kmcpg::REFSTATS_WORDS + j] += v[j];
+  }
+  const double min_frac = o.ref_stats_p_given ? o.ref_stats_p : kmcpg::refstats_mode(o.ref_stats_mode).min_chunks_fraction;
+  std::string s;
+  char line[256];
+  s.append(line, (size_t)snprintf(line, sizeof line, "# matched reads: %llu\n# unique reads: %llu\n", (unsigned long long)tot.matched_reads, (unsigned long long)tot.unique_reads));
+  s += "#ref\tchunks\ttLen\treads\tureads\thicUreads\tchunksFrac\tverdict\tchunkReads\tchunkFirsts\tchunkUreads\tchunkHicUreads\n";
+  for (const auto& kv : refs) {
+    const Ref& r = kv.second;
+    const kmcpg::RefstatsRef t = kmcpg::refstats_rollup(r.chunks, min_frac, [&](uint64_t c) { return r.w.data() + c * kmcpg::REFSTATS_WORDS; });
+    s += kv.first;
+    s.append(line, (size_t)snprintf(line, sizeof line, "\t%llu\t%llu\t%llu\t%llu\t%llu\t%.4f\t%s", (unsigned long long)r.chunks, (unsigned long long)r.tlen,
+                                    (unsigned long long)t.reads, (unsigned long long)t.ureads, (unsigned long long)t.hic_ureads, t.chunks_frac,
+                                    kmcpg::refstats_verdict_name(t.verdict)));
+    for (int j = 0; j < kmcpg::REFSTATS_WORDS; j++)
+      for (uint64_t c = 0; c < r.chunks; c++) {
+        s.push_back(c ? ',' : '\t');
+        s += std::to_string(r.w[c * kmcpg::REFSTATS_WORDS + j]);
+      }
+    s.push_back('\n');
+  }
+  const std::string& path = o.ref_stats;
+  if (path.size() > 3 && path.compare(path.size() - 3, 3, ".gz") == 0) {
+    gzFile f = gzopen(path.c_str(), "wb");
+    if (!f || (!s.empty() && gzwrite(f, s.data(), (unsigned)s.size()) != (int)s.size()) || gzclose(f) != Z_OK) die("%s: write error", path.c_str());
+  } else {
+    FILE* f = path == "-" ? stdout : fopen(path.c_str(), "wb");
+    if (!f || fwrite(s.data(), 1, s.size(), f) != s.size() || (f == stdout ? fflush(f) : fclose(f)) != 0) die("%s: write error", path.c_str());
+  }
+  return refs.size();
+}
+
 static kmcpg_params make_params(const Options& o, int sort_by, bool paired) {
   kmcpg_params params{};
   params.min_qlen = o.min_qlen;
@@ -1419,6 +1534,7 @@ int main(int argc, char** argv) {
   p.target = resolve_targets(o, p.db, dbi, name_maps);
   p.params = make_params(o, sort_by, paired);
   if (!o.specific_level.empty()) set_specific(o, p.db, p.target, taxonomy.get(), taxid_map.get());
+  if (!o.ref_stats.empty()) set_ref_stats(o, p.db, p.target, taxonomy.get(), taxid_map.get());
 
   p.t_search = Clock::now();
   Out out(p.regions() ? o.regions_bed : o.out_file);
@@ -1453,6 +1569,13 @@ int main(int argc, char** argv) {
   } else {
     if (!o.quiet) print_summary(p);
     write_trailer(p, out);
+  }
+  if (!o.ref_stats.empty()) {
+    uint64_t reruns = 0;
+    const uint64_t n_refs = write_ref_stats(o, p.db, p.target, &reruns);
+    if (!o.quiet)
+      info("reference statistics (mode %d, level %s): %llu references saved to: %s (%llu batches counted by their rerun after a hit-buffer overflow)", o.ref_stats_mode,
+           ref_stats_species(o) ? "species" : "strain", (unsigned long long)n_refs, o.ref_stats.c_str(), (unsigned long long)reruns);
   }
   // Everything the user asked for is on disk.  Giving back pinned staging buffers, streams and a resident index one by one takes
   // ~0.1 s and the runtime's own exit handlers as long again (profiles/r06_cli_e2e.txt) — a short-lived process leaves that to the

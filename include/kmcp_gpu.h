@@ -445,6 +445,57 @@ int kmcpg_submit_windows_summary(kmcpg_db* db, const uint8_t* seqs, const uint64
 int kmcpg_wait_summaries(kmcpg_ticket* ticket, kmcpg_result_summaries* out);
 void kmcpg_result_summaries_free(kmcpg_result_summaries* r);
 
+/* -- reference statistics (K6, k6_refstats.hip): what stage 1/4 of `kmcp profile` counts per reference (kmcp/cmd/profile.go:761-1099;
+ *    kmcp_amd/csrc/refstats_rule.hpp states the rule), on K3's output while it is in device memory.  Every global column — a chunk of a
+ *    reference — has four counters: rows (matches of the column), firsts (queries whose first row of the column's target is this column),
+ *    ureads (of those, the queries that name one target or — with a species table — one species), hic_ureads (of those, the ones whose
+ *    printed qCov of that first row is >= hic_min_qcov).  The tables are those of kmcpg_set_specific but the stage's own: it does NOT
+ *    filter, the result of every call is byte for byte what it is with the stage off, and both stages may be on together.
+ *    kmcpg_set_refstats uploads the tables and allocates zeroed counters; (NULL, NULL, 0, 0) switches the stage off and frees them.
+ *    KMCPG_EUNSUPPORTED as for kmcpg_set_specific: paged, multi-device and sharded handles; while the stage is on, batches with try_se,
+ *    top_n_scores != 0 or several k-mer sizes with k == 0, and every window submit.
+ *    While the stage is on, every batch of kmcpg_submit / kmcpg_search_batch (and their _pairs / _packed forms) is counted: on the device
+ *    behind K3 — as the batch's last kernel, after K4 where that stage is on too: K6 reads K3's pairs, which K4 leaves where they are —
+ *    for the reads whose matches are final there, by the host half at wait time for the others (queries of more k-mers
+ *    than the device's -f bound covers, segments above 4096 pairs, several targets among more than 64 pairs; KMCPG_DEVICE_FINALIZE=0:
+ *    every read) — its own -f test first, then the same rule.  A batch that is run again because its hit buffer overflowed is counted once
+ *    (totals.skipped_launches counts the launches that left the counting to the rerun).  A kmcpg_search_batch call whose pieces fail part
+ *    of the way and which is then searched again as a whole marks the counters as a failed batch does (below).
+ *    kmcpg_refstats_read waits for the device and adds device and host counters; valid once every ticket has been waited for.
+ *    KMCPG_EDEVICE if a batch failed after its reads had been counted (call kmcpg_refstats_reset).  totals may be NULL.
+ *    kmcpg_refstats_device runs K6 alone on device pointers, as kmcpg_specific_device runs K4: d_left[i] = 1 for the reads it does not
+ *    count (n_reads bytes).  d_n_hits may be NULL; otherwise the launch counts nothing when *d_n_hits > hit_cap (the batch will be run
+ *    again).  Only enqueues on `stream`.
+ *    kmcpg_last_refstats: the witness of the handle's last K6 launch (the call waits for the device to go idle; one set of witness words
+ *    per handle, zeroed by every launch: meaningful only with ONE batch in flight — the counters themselves are not affected): reads by class, adds to
+ *    the workgroups' LDS tables, adds to global memory (table flushes and spills) and the spills among them, whether the overflow guard
+ *    skipped the launch, segments outside pair_cap (must be 0), the grid and the table size; at profiling level >= 1 the HIP-event
+ *    time and one launch record.  KMCPG_REFSTATS_SLOTS (read by kmcpg_set_refstats): slots of a workgroup's table, a power of two up to
+ *    2048, 0 = no table. */
+typedef struct {
+  uint64_t rows, firsts, ureads, hic_ureads;
+} kmcpg_col_stats;
+typedef struct {
+  uint64_t matched_reads, unique_reads;  /* queries with at least one row; of those the unique ones */
+  uint64_t host_reads;                   /* of matched_reads, counted by the host half */
+  uint64_t skipped_launches;             /* K6 launches that counted nothing because the batch's hit buffer had overflowed (the rerun counted) */
+} kmcpg_refstats_totals;
+enum { KMCPG_K6_REFSTATS = 32 };  /* kmcpg_k4_launch.kernel of K6's kernel */
+typedef struct {
+  uint64_t empty, single, wave, left;            /* reads by the class they took; the four add up to the reads */
+  uint64_t lds_adds, global_adds, spilled_adds;  /* spilled_adds is part of global_adds */
+  uint64_t skipped;                              /* 1: the overflow guard skipped the launch */
+  uint64_t bad_segments;
+  uint32_t grid, slots;
+  double k6_ms;                                  /* HIP-event time of the kernel at profiling level >= 1; -1 otherwise */
+} kmcpg_refstats_stats;
+int kmcpg_set_refstats(kmcpg_db* db, const uint32_t* target_class, const uint32_t* species_class, uint32_t n_cols, double hic_min_qcov);
+int kmcpg_refstats_device(kmcpg_db* db, const kmcpg_pair* d_pairs, const uint64_t* d_read_offs, uint64_t pair_cap, const int32_t* d_qkmers,
+                          uint32_t n_reads, int32_t final_n, const uint64_t* d_n_hits, uint64_t hit_cap, uint8_t* d_left, void* stream);
+int kmcpg_refstats_read(kmcpg_db* db, kmcpg_col_stats* out, uint32_t n_cols, kmcpg_refstats_totals* totals);
+int kmcpg_refstats_reset(kmcpg_db* db);
+int kmcpg_last_refstats(kmcpg_db* db, kmcpg_refstats_stats* out, kmcpg_k4_launch* launches, uint32_t cap, uint32_t* n_launches);
+
 /* -- benchmarking / full-size parity support (no counterpart in the reference) ------------------ */
 typedef struct {
   int32_t k;            /* 21 */

@@ -253,4 +253,32 @@ struct K5Args {
   uint32_t* stats;               // [K5_STATS], zero on entry
 };
 
+// K6 (k6_refstats.hip): K3's segments -> four counters per column, the counts of stage 1 of `kmcp profile` (refstats_rule.hpp); the reads
+// it cannot count exactly are LEFT to the host (a byte per read).
+constexpr uint32_t K6_CAP = 64;  // longest segment of several targets the device counts
+constexpr uint32_t K6_MAX_SLOTS = 2048, K6_DEFAULT_SLOTS = 1024, K6_PROBES = 8;  // the workgroup's table in LDS: 20 bytes per slot
+// the witness: reads empty / single target / by the wave / LEFT, adds to LDS / to global memory (flushes and spills) / of those the spills,
+// launches the overflow guard skipped, segments outside the buffer; then the three totals that persist beside the counters
+enum { K6_EMPTY = 0, K6_SINGLE, K6_WAVE, K6_LEFT, K6_LDS_ADDS, K6_GLOBAL_ADDS, K6_SPILLED, K6_SKIPPED, K6_BAD, K6_STATS };
+struct K6Args {
+  const kmcpg_pair* pairs;             // K3's output, in print order
+  const uint64_t* offs;                // [n_reads + 1]
+  uint64_t pair_cap;                   // pairs there is room for behind `pairs`: a segment that ends behind it is treated as empty
+  const int32_t* nk;                   // NumKmers per read
+  uint32_t n_reads;
+  uint32_t n_cols;
+  int32_t final_n;                     // reads of more k-mers are LEFT (their pairs may still fall to -f on the host)
+  uint32_t slots;                      // table slots per workgroup: a power of two up to K6_MAX_SLOTS, or 0 = every add goes to global memory
+  const uint32_t* target_class;        // [n_cols]
+  const uint32_t* species_class;       // [n_cols] or nullptr: strain / assembly level
+  double hic_min_qcov;                 // H
+  const unsigned long long* n_hits;    // device word or nullptr: the batch's hit counter ...
+  uint64_t hit_cap;                    // ... above this the batch will be run again: nothing is counted now
+  unsigned long long* counters;        // [4 * n_cols]: rows, firsts, ureads, hic of column c at 4 * c (refstats_rule.hpp)
+  unsigned long long* totals;          // [3]: matched reads, unique reads (of the reads counted here), launches the guard skipped
+  uint8_t* left;                       // out [n_reads]: 1 = LEFT to the host
+  unsigned long long* stats;           // [K6_STATS], zero on entry
+};
+
+
 }  // namespace kmcpg

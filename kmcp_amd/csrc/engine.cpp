@@ -835,6 +835,12 @@ extern "C" int kmcpg_close(kmcpg_db* db) {
   if (db->d_sum_stats) (void)hipFree(db->d_sum_stats);
   for (auto& ev : db->sum_ev)
     if (ev) (void)hipEventDestroy(ev);
+  if (db->d_rs_target) (void)hipFree(db->d_rs_target);
+  if (db->d_rs_species) (void)hipFree(db->d_rs_species);
+  if (db->d_rs_counters) (void)hipFree(db->d_rs_counters);
+  if (db->d_rs_stats) (void)hipFree(db->d_rs_stats);
+  for (auto& ev : db->rs_ev)
+    if (ev) (void)hipEventDestroy(ev);
   kmcpg::release_fpr_bounds(db);
   kmcpg::async_release(db);
   if (db->k1_stream) (void)hipStreamDestroy(db->k1_stream);

@@ -245,6 +245,26 @@ struct kmcpg_db {
   // ... or, after kmcpg_wait_summaries, what that ticket's batches came to (all its pieces; counted on the host from the records)
   bool sum_from_ticket = false;
   kmcpg_summary_stats sum_ticket{};
+  // K6, the reference statistics behind K3 (kmcpg_set_refstats; k6_refstats.hip, refstats.cpp): tables of its own (the stage does not filter
+  // and is independent of K4), H, the device counters (4 words per column, then matched / unique reads), the witness words of the last
+  // launch, and the host half's counters (the reads the device LEFT, and every read of a batch that did not go through K3; under rs_mu)
+  uint32_t* d_rs_target = nullptr;
+  uint32_t* d_rs_species = nullptr;
+  std::vector<uint32_t> h_rs_target, h_rs_species;  // species empty: strain level
+  bool refstats_on() const { return !h_rs_target.empty(); }
+  double rs_hic = 0;
+  unsigned long long* d_rs_counters = nullptr;  // [4 * n_cols + 3]
+  unsigned long long* d_rs_stats = nullptr;     // [K6_STATS]
+  uint32_t rs_slots = 0;                        // KMCPG_REFSTATS_SLOTS, read when the stage is set
+  unsigned rs_max_wgs = 0, rs_grid = 0;         // the chip's resident workgroups (KMCPG_REFSTATS_WGS: fewer, for tests); the last launch's grid
+  std::mutex rs_mu;
+  std::vector<uint64_t> h_rs_counters;          // [4 * n_cols]
+  uint64_t h_rs_matched = 0, h_rs_unique = 0, h_rs_reads = 0;
+  bool rs_tainted = false;  // a batch failed after its reads were counted: the counters may hold reads that are searched again
+  bool rs_ran = false;      // a K6 launch since the stage was set
+  hipEvent_t rs_ev[2] = {};
+  bool rs_timed = false;
+  std::vector<kmcpg_k4_launch> k6_log;
   std::vector<kmcpg::FprBoundTable> fpr_bounds;  // -f bound tables (query.cpp fpr_bound): one per (max_fpr, size), never rewritten
   hipEvent_t ev[16] = {};   // ring of 4 calls x (start, COBS start, COBS done, k-mers done)
   uint64_t ev_calls = 0;    // profiled calls so far
@@ -277,6 +297,19 @@ inline int specific_refuse_params(const kmcpg_db* db, const kmcpg_params& p) {
 inline int specific_refuse_entry(const kmcpg_db* db, const char* entry) {
   if (!db->spec_on()) return 0;
   return kmcpg_fail(KMCPG_EUNSUPPORTED, "species-specific queries (kmcpg_set_specific): %s is not supported while the stage is on", entry);
+}
+
+// The reference statistics (kmcpg_set_refstats): the same refusals as the species-specific stage, for the same reason — what is counted
+// must be a query's final matches, counted once
+inline int refstats_refuse_params(const kmcpg_db* db, const kmcpg_params& p) {
+  if (!db->refstats_on()) return 0;
+  const char* what = p.try_se ? "try_se" : (p.top_n_scores != 0 ? "top_n_scores != 0" : (p.k == 0 && db->ks_desc.size() > 1 ? "a database with several k-mer sizes searched with params->k == 0" : nullptr));
+  if (!what) return 0;
+  return kmcpg_fail(KMCPG_EUNSUPPORTED, "reference statistics (kmcpg_set_refstats): %s is not supported — switch the stage off, or count the results with kmcp-refstats", what);
+}
+inline int refstats_refuse_entry(const kmcpg_db* db, const char* entry) {
+  if (!db->refstats_on()) return 0;
+  return kmcpg_fail(KMCPG_EUNSUPPORTED, "reference statistics (kmcpg_set_refstats): %s is not supported while the stage is on", entry);
 }
 
 inline kmcpg_params default_params() {
@@ -345,6 +378,15 @@ int finalize_grouped_trusted(const kmcpg_db* db, const kmcpg_pair* pairs, const 
 // the filters above left of it, with the handle's tables; KEEP and DROP were settled on the device.
 // specific_filter_result: the same rule on every read of a finished result of Match records (the paths without K3)
 void specific_filter_result(const kmcpg_db* db, kmcpg_result* out);
+// The host half of K6 (refstats.cpp).  refstats_host_batch: the reads of a batch the device LEFT (left == nullptr: every read), from K3's
+// pairs — the host's own tests (-f among them) first, the host's order for segments above K3_WG_CAP, then the rule of refstats_rule.hpp,
+// added to the handle's host counters.  refstats_host_result: every read of a finished result of Match records (the paths without K3).
+int refstats_host_batch(kmcpg_db* db, const kmcpg_pair* pairs, const uint64_t* read_offs, const int32_t* qkmers, uint32_t n_reads, const kmcpg_params& p,
+                        const uint8_t* left);
+void refstats_host_result(kmcpg_db* db, const kmcpg_result* out);
+// K6 behind K3 for a lane's batch (refstats.cpp): what kmcpg_refstats_device does, without the public entry's argument checks
+int refstats_enqueue(kmcpg_db* db, const kmcpg_pair* d_pairs, const uint64_t* d_read_offs, uint64_t pair_cap, const int32_t* d_qkmers, uint32_t n_reads,
+                     int32_t final_n, const uint64_t* d_n_hits, uint64_t hit_cap, uint8_t* d_left, hipStream_t st);
 // bound_n: what the kmcpg_query_device call(s) that produced the list actually did — every query of up to bound_n k-mers had the -f bound
 // applied on the device, whichever kernel form served it (0: no bound table in that call).  query_device_after reports the value of its
 // call; lane.cpp keeps it with the batch (Lane::bound_n) and hands it to the finalizer, which takes a compact segment as final only for

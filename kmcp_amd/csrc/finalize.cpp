@@ -31,6 +31,7 @@
 #include "dbformat.hpp"
 #include "engine.hpp"
 #include "specific_rule.hpp"
+#include "refstats_rule.hpp"
 #include "match_rule.hpp"
 #include "fpr.hpp"
 #include "kernels.hpp"
@@ -697,6 +698,66 @@ void specific_filter_result(const kmcpg_db* db, kmcpg_result* out) {
   }
   o->matches.resize(to);
   out->matches = o->matches.data();
+}
+
+// ---- the host half of K6 (k6_refstats.hip): refstats_rule.hpp on the reads the device does not count
+namespace {
+// one query's final rows -> the handle's host counters (rows: scratch of the caller)
+void refstats_count_rows(kmcpg_db* db, const kmcpg_match* m, uint64_t n, int32_t qkmers, std::vector<RefstatsRow>& rows) {
+  if (n == 0) return;
+  const bool species = !db->h_rs_species.empty();
+  rows.resize(n);
+  for (uint64_t i = 0; i < n; i++)
+    rows[i] = RefstatsRow{db->h_rs_target[m[i].col], species ? db->h_rs_species[m[i].col] : 0u, m[i].col, printed_qcov((uint32_t)m[i].mkmers, qkmers)};
+  std::lock_guard<std::mutex> g(db->rs_mu);
+  const bool unique = refstats_count_query(rows.data(), rows.size(), species, db->rs_hic, [&](uint64_t col, int w) { db->h_rs_counters[col * REFSTATS_WORDS + w]++; });
+  db->h_rs_reads++;
+  db->h_rs_matched++;
+  if (unique) db->h_rs_unique++;
+}
+}  // namespace
+
+int refstats_host_batch(kmcpg_db* db, const kmcpg_pair* pairs, const uint64_t* read_offs, const int32_t* qkmers, uint32_t n_reads, const kmcpg_params& p,
+                        const uint8_t* left) {
+  if (!db->refstats_on()) return 0;
+  const size_t n_cols = db->col_meta.size();
+  const uint64_t n_pairs = read_offs[n_reads];
+  std::vector<kmcpg_match> tmp;
+  std::vector<RefstatsRow> rows;
+  FprRow row;
+  int row_n = -1;
+  const auto fpr_of = [&](int n2, int k) { return QueryFpr::value(*row, n2, k); };
+  for (uint32_t r = 0; r < n_reads; r++) {
+    if (left && !left[r]) continue;
+    const uint64_t s0 = read_offs[r], s1 = read_offs[r + 1];
+    if (s1 == s0) continue;
+    if (s1 < s0 || s1 > n_pairs) return kmcpg_fail(KMCPG_EINVAL, "grouped hit list: offsets out of range");
+    const int n = qkmers[r];
+    if (n > 0 && n != row_n) {
+      row_n = n;
+      row = db->fpr->ensure_row(n);
+    }
+    tmp.clear();
+    for (uint64_t i = s0; i < s1; i++) {
+      if (pairs[i].col >= n_cols) return kmcpg_fail(KMCPG_EINVAL, "grouped hit list: columns out of range");
+      kmcpg_match mm;
+      if (match_accept(pairs[i].col, (int)pairs[i].count, n, db->col_meta[pairs[i].col], p, fpr_of, &mm)) tmp.push_back(mm);
+    }
+    if (s1 - s0 > (uint64_t)K3_WG_CAP && !tmp.empty()) {  // K3 leaves these unordered: the host's order, as finalize_grouped_into gives them
+      sort_matches(tmp.data(), tmp.data() + tmp.size(), p);
+      if (db->is_set()) set_order_records(db, tmp.data(), tmp.size(), p.sort_by);
+    }
+    refstats_count_rows(db, tmp.data(), tmp.size(), n, rows);
+  }
+  return 0;
+}
+
+void refstats_host_result(kmcpg_db* db, const kmcpg_result* out) {
+  const ResultOwner* o = (const ResultOwner*)out->owner;
+  if (!o || !db->refstats_on() || o->pairs_mode) return;
+  std::vector<RefstatsRow> rows;
+  for (uint32_t r = 0; r < out->n_reads; r++)
+    refstats_count_rows(db, o->matches.data() + o->offs[r], o->offs[(size_t)r + 1] - o->offs[r], o->qkmers[r], rows);
 }
 
 // counts in o->offs[1 ..] -> offsets, and the result's pointers

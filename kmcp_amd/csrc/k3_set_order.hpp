@@ -39,6 +39,11 @@ KMCPG_K3_HD uint64_t fixed4(double x) {
   return q + ((rem > half || (rem == half && (q & 1))) ? 1u : 0u);
 }
 
+// A row's qCov as a consumer of the TSV parses it back: the digits "%.4f" prints of count / qkmers, divided by 10^4 again (both divisions
+// correctly rounded: -ffp-contract=off, no fast-math).  What kmcp-regions adds up (k5_summary.hip) and what `kmcp profile` compares with
+// --min-hic-ureads-qcov (k6_refstats.hip, refstats.cpp).
+KMCPG_K3_HD double printed_qcov(uint32_t count, int32_t qkmers) { return (double)fixed4((double)count / (double)qkmers) / 10000.0; }
+
 // the score `-s` sorts by, with the operations (and therefore the bits) of the Match record the row is printed from
 // (util-db-search.go:7487-7489; finalize.cpp kmcpg_expand_pairs)
 KMCPG_K3_HD double set_score(int32_t sort_mode, uint32_t count, uint64_t size, double nh) {

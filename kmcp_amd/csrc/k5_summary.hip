@@ -42,7 +42,7 @@ static_assert(K5_CAP == 64, "the wave class holds one pair per lane");
 __device__ __forceinline__ uint32_t class_of(const K5Args& a, kmcpg_pair p) {
   return p.col < a.n_cols ? a.target_class[p.col] : 0xffffffffu;  // (K3 emits no such column: never out of the table)
 }
-__device__ __forceinline__ double x_of(kmcpg_pair p, int32_t qk) { return (double)fixed4((double)p.count / (double)qk) / 10000.0; }
+__device__ __forceinline__ double x_of(kmcpg_pair p, int32_t qk) { return printed_qcov(p.count, qk); }  // (k3_set_order.hpp)
 
 struct MinMax {
   uint32_t tmin, tmax;

@@ -297,6 +297,7 @@ int enqueue_query(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p, c
     rc = kmcpg_group_device(db, L->d_hits.p, L->d_cnt.p, L->d_hits.cap, L->d_qk.p, L->n, &p, L->d_pairs.p, L->d_roffs.p, st);
     if (rc) return rc;
     L->spec = db->spec_on();
+    L->rs = false;  // (a lane keeps its fields from batch to batch: the summary path below returns before K6's turn)
     // (a batch K5 summarises needs K3's last two words only: the pairs it kept, and its count of bad hits)
     const size_t skip = L->summarized() ? L->n : 0;
     HIPCHK(hipMemcpyAsync(L->h_roffs.p + skip, L->d_roffs.p + skip, ((size_t)L->n + 2 - skip) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
@@ -325,7 +326,20 @@ int enqueue_query(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p, c
       HIPCHK(hipMemcpyAsync(L->h_roffs.p, L->d_soffs4.p, ((size_t)L->n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
       HIPCHK(hipMemcpyAsync(L->h_verd.p, L->d_verd.p, (size_t)L->n, hipMemcpyDeviceToHost, st));
     }
-  } else L->spec = false;
+    L->rs = db->refstats_on();
+    if (L->rs) {
+      // K6 on K3's output, which K4 leaves where it is (it compacts into d_hits).  The LAST step that can fail for want of memory: a batch
+      // that is enqueued again after KMCPG_ENOMEM has not been counted yet.  One whose hit buffer overflowed is not counted either (the
+      // kernel looks at the hit counter itself): collect() runs it again.  KMCPG_REFSTATS_DEVICE=0: every read goes to the host half
+      if (L->d_left.ensure(L->n) || L->h_left.ensure(L->n) || (L->spec && L->h_roffs3.ensure((size_t)L->n + 1))) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
+      const char* e = getenv("KMCPG_REFSTATS_DEVICE");
+      const int32_t final_n = e && atoi(e) == 0 ? -1 : std::min<int32_t>(L->bound_n, kFprBoundAlways);
+      rc = refstats_enqueue(db, L->d_pairs.p, L->d_roffs.p, L->d_hits.cap, L->d_qk.p, L->n, final_n, L->d_cnt.p, L->d_hits.cap, L->d_left.p, st);
+      if (rc) return rc;
+      HIPCHK(hipMemcpyAsync(L->h_left.p, L->d_left.p, (size_t)L->n, hipMemcpyDeviceToHost, st));
+      if (L->spec) HIPCHK(hipMemcpyAsync(L->h_roffs3.p, L->d_roffs.p, ((size_t)L->n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    }
+  } else L->spec = L->rs = false;
   return 0;
 }
 
@@ -446,10 +460,36 @@ int enqueue(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p, bool ge
   return 0;
 }
 
+namespace {
+int refstats_collect(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p, bool fetched) {
+  bool any = false;
+  for (uint32_t r = 0; r < L->n && !any; r++) any = L->h_left.p[r] != 0;
+  if (!any) return 0;
+  if (!L->spec && fetched) return refstats_host_batch(db, L->h_pairs.p, L->h_roffs.p, L->h_qk.p, L->n, p, L->h_left.p);
+  const uint64_t* offs = L->spec ? L->h_roffs3.p : L->h_roffs.p;
+  std::vector<kmcpg_pair, NoInitAlloc<kmcpg_pair>> k3(offs[L->n]);
+  if (!k3.empty()) {
+    HIPCHK(hipMemcpyAsync(k3.data(), L->d_pairs.p, k3.size() * sizeof(kmcpg_pair), hipMemcpyDeviceToHost, A->copy_stream));
+    HIPCHK(hipStreamSynchronize(A->copy_stream));
+  }
+  return refstats_host_batch(db, k3.data(), offs, L->h_qk.p, L->n, p, L->h_left.p);
+}
+}  // namespace
+
 int collect(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p, uint64_t* n_hits, bool fetch) {
   *n_hits = 0;
   if (L->n == 0) return 0;
   KMCPG_USE_DEVICE(db);
+  struct Taint {  // a batch that fails from here on may have been counted by K6 already, and a caller may search its reads again
+    kmcpg_db* db;
+    const Lane* L;
+    bool ok = false;
+    ~Taint() {
+      if (ok || !L->rs || !L->grouped || !db->refstats_on() || L->h_cnt.p[0] > L->d_hits.cap) return;  // (an overflowing attempt was not counted: the kernel's guard)
+      std::lock_guard<std::mutex> g(db->rs_mu);
+      db->rs_tainted = true;
+    }
+  } taint{db, L};
   HIPCHK(hipEventSynchronize(L->done));
   uint64_t cnt = L->h_cnt.p[0];
   for (int attempt = 0; cnt > L->d_hits.cap; attempt++) {  // the hit buffer was too small: rerun with room for every hit
@@ -490,9 +530,15 @@ int collect(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p, uint64_
     HIPCHK(hipStreamSynchronize(A->copy_stream));
     L->copied = cnt;
   }
+  if (L->rs && L->grouped && db->refstats_on()) {
+    // the host half of K6: the reads the device LEFT, from K3's pairs — which are the lane's result itself, or, behind K4, still in d_pairs
+    int rc = refstats_collect(db, A, L, p, fetch);
+    if (rc) return rc;
+  }
   // a batch large enough to say something about the data (one genome with 5 000 matches does not)
   if (L->n >= 1024) A->hits_hint.store(hits_hint_after(A->hits_hint.load(), cnt, L->n));
   *n_hits = cnt;
+  taint.ok = true;
   return 0;
 }
 

@@ -28,6 +28,7 @@ EXPORTS = [
     "kmcpg_open_set", "kmcpg_set_info", "kmcpg_last_set_order",
     "kmcpg_set_specific", "kmcpg_specific_device", "kmcpg_last_specific",
     "kmcpg_summarize_device", "kmcpg_last_summary", "kmcpg_submit_windows_summary", "kmcpg_wait_summaries", "kmcpg_result_summaries_free",
+    "kmcpg_set_refstats", "kmcpg_refstats_device", "kmcpg_refstats_read", "kmcpg_refstats_reset", "kmcpg_last_refstats",
     "kmcpg_sketch_genomes_to", "kmcpg_builder_open", "kmcpg_builder_close", "kmcpg_builder_add_cols", "kmcpg_builder_plan",
     "kmcpg_builder_col_place", "kmcpg_builder_block_info", "kmcpg_builder_begin_round", "kmcpg_builder_scatter_device",
     "kmcpg_builder_end_round", "kmcpg_builder_finish", "kmcpg_builder_info",
@@ -247,6 +248,22 @@ class SummaryStats(C.Structure):
                 ("bytes_d2h", C.c_uint64), ("bad_segments", C.c_uint64), ("k5_ms", C.c_double)]
 
 
+COL_STATS_DTYPE = np.dtype([("rows", "<u8"), ("firsts", "<u8"), ("ureads", "<u8"), ("hic_ureads", "<u8")])  # kmcpg_col_stats
+K6_REFSTATS = 32  # KMCPG_K6_REFSTATS: kmcpg_k4_launch.kernel of K6's kernel
+
+
+class RefstatsTotals(C.Structure):
+    """kmcpg_refstats_totals"""
+    _fields_ = [("matched_reads", C.c_uint64), ("unique_reads", C.c_uint64), ("host_reads", C.c_uint64), ("skipped_launches", C.c_uint64)]
+
+
+class RefstatsStats(C.Structure):
+    """kmcpg_refstats_stats: the witness of the last K6 launch"""
+    _fields_ = [("empty", C.c_uint64), ("single", C.c_uint64), ("wave", C.c_uint64), ("left", C.c_uint64), ("lds_adds", C.c_uint64),
+                ("global_adds", C.c_uint64), ("spilled_adds", C.c_uint64), ("skipped", C.c_uint64), ("bad_segments", C.c_uint64),
+                ("grid", C.c_uint32), ("slots", C.c_uint32), ("k6_ms", C.c_double)]
+
+
 class ResultSummaries(C.Structure):
     """kmcpg_result_summaries"""
     _fields_ = [("n_windows", C.c_uint32), ("reserved", C.c_uint32), ("qlen", C.POINTER(C.c_int32)), ("qkmers", C.POINTER(C.c_int32)),
@@ -425,6 +442,11 @@ def load():
     L.kmcpg_wait_summaries.argtypes = [vp, C.POINTER(ResultSummaries)]
     L.kmcpg_result_summaries_free.argtypes = [C.POINTER(ResultSummaries)]
     L.kmcpg_result_summaries_free.restype = None
+    L.kmcpg_set_refstats.argtypes = [vp, vp, vp, C.c_uint32, C.c_double]
+    L.kmcpg_refstats_device.argtypes = [vp, vp, vp, C.c_uint64, vp, C.c_uint32, C.c_int32, vp, C.c_uint64, vp, vp]
+    L.kmcpg_refstats_read.argtypes = [vp, vp, C.c_uint32, C.POINTER(RefstatsTotals)]
+    L.kmcpg_refstats_reset.argtypes = [vp]
+    L.kmcpg_last_refstats.argtypes = [vp, C.POINTER(RefstatsStats), C.POINTER(K4Launch), C.c_uint32, C.POINTER(C.c_uint32)]
     L.kmcpg_sketch_genomes_to.argtypes = [vp, vp, vp, C.c_uint32, C.POINTER(SplitSpec), SKETCH_SINK, vp]
     u32p = C.POINTER(C.c_uint32)
     L.kmcpg_builder_open.argtypes = [C.POINTER(BuilderCfg), C.c_int32, C.POINTER(vp)]
@@ -1204,6 +1226,42 @@ class Database:
         _check(load().kmcpg_last_specific(self._h, C.byref(st), buf, n.value, C.byref(n)))
         self.last_k4_ms = float(st.k4_ms)  # HIP-event time of the stage's kernels (profiling level >= 1), else -1
         return {f: int(getattr(st, f)) for f, _ in SpecificStats._fields_ if f != "k4_ms"}, [buf[i] for i in range(n.value)]
+
+    # ---- reference statistics: K6 behind K3 ---------------------------------------------------------------------
+    def set_refstats(self, target_class=None, species_class=None, hic_min_qcov=0.75):
+        """kmcpg_set_refstats: one uint32 per global column each; species_class None = strain / assembly level; no argument = off."""
+        if target_class is None:
+            assert species_class is None
+            _check(load().kmcpg_set_refstats(self._h, None, None, 0, 0.0))
+            return
+        t = np.ascontiguousarray(target_class, dtype=np.uint32)
+        s = None if species_class is None else np.ascontiguousarray(species_class, dtype=np.uint32)
+        assert s is None or len(s) == len(t)
+        _check(load().kmcpg_set_refstats(self._h, t.ctypes.data, None if s is None else s.ctypes.data, len(t), float(hic_min_qcov)))
+
+    def refstats_device(self, d_pairs, d_read_offs, pair_cap, d_qkmers, n_reads, final_n, d_left, d_n_hits=None, hit_cap=0, stream=None):
+        """kmcpg_refstats_device on device pointers: K3's pairs and offsets -> the handle's counters and a LEFT byte per read."""
+        _check(load().kmcpg_refstats_device(self._h, d_pairs, d_read_offs, pair_cap, d_qkmers, n_reads, final_n, d_n_hits, hit_cap, d_left, stream))
+
+    def refstats_read(self, n_cols):
+        """kmcpg_refstats_read: (COL_STATS_DTYPE [n_cols], dict of the totals) — device and host counters added"""
+        out = np.zeros(n_cols, dtype=COL_STATS_DTYPE)
+        tot = RefstatsTotals()
+        _check(load().kmcpg_refstats_read(self._h, out.ctypes.data, n_cols, C.byref(tot)))
+        return out, {f: int(getattr(tot, f)) for f, _ in RefstatsTotals._fields_}
+
+    def refstats_reset(self):
+        _check(load().kmcpg_refstats_reset(self._h))
+
+    def last_refstats(self):
+        """kmcpg_last_refstats: (dict of the counters, [K4Launch] of the last K6 launch — empty below profiling level 1)"""
+        st = RefstatsStats()
+        n = C.c_uint32(0)
+        _check(load().kmcpg_last_refstats(self._h, C.byref(st), None, 0, C.byref(n)))
+        buf = (K4Launch * max(1, n.value))()
+        _check(load().kmcpg_last_refstats(self._h, C.byref(st), buf, n.value, C.byref(n)))
+        self.last_k6_ms = float(st.k6_ms)  # HIP-event time of the kernel (profiling level >= 1), else -1
+        return {f: int(getattr(st, f)) for f, _ in RefstatsStats._fields_ if f != "k6_ms"}, [buf[i] for i in range(n.value)]
 
     # ---- window summaries for region merging: K5 behind K4 ------------------------------------------------------
     def summarize_device(self, d_pairs, d_offs, pair_cap, d_verdicts, d_qkmers, n, d_out, d_left_pairs, left_cap, d_left_offs, stream=None):
