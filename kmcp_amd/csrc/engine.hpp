@@ -4,7 +4,9 @@
 #include <stdlib.h>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 
+#include <algorithm>
 #include <atomic>
 #include <condition_variable>
 #include <functional>
@@ -284,6 +286,64 @@ inline int set_refuse_params(const kmcpg_db* db, const kmcpg_params& p) {
 inline int set_refuse_entry(const kmcpg_db* db, const char* entry) {
   if (!db->is_set()) return 0;
   return kmcpg_fail(KMCPG_EUNSUPPORTED, "database set (%zu members): %s is not supported on a set handle", db->set_col_base.size(), entry);
+}
+
+// The stages behind K3 that need a query's matches from EVERY block (K4 / K5: specific.cpp, K6: refstats.cpp) refuse the handles that
+// search the index in parts.  "<refused> are not supported on <the handle>: <why>"
+inline int refuse_handle(const kmcpg_db* db, const char* refused, const char* why) {
+  const char* what = db->paged_passes > 0 ? "a paged handle (kmcpg_open_paged)"
+                     : !db->shards.empty() ? "a multi-device handle (kmcpg_open_devices)"
+                     : db->opts.shard_count > 1 ? "a handle with shard_count > 1"
+                                                : nullptr;
+  if (!what) return 0;
+  return kmcpg_fail(KMCPG_EUNSUPPORTED, "%s are not supported on %s: %s", refused, what, why);
+}
+
+// a per-handle event of its own kind (COBS kernels one batch at a time; K3's scratch one user at a time): the next user waits for it
+inline int chain_begin(hipEvent_t* ev, bool valid, hipStream_t st) {
+  if (!*ev) HIPCHK(hipEventCreateWithFlags(ev, hipEventDisableTiming));
+  if (valid) HIPCHK(hipStreamWaitEvent(st, *ev, 0));
+  return 0;
+}
+// K3's scratch and K4's (one user at a time: K3's chain, K4, K5) on the chain of fin_ev: wait() orders the call behind the previous user;
+// from then on every way out, error paths included, leaves the event behind for the next one — kernels that use the scratch may already
+// be on the stream when a later step fails
+struct FinGuard {
+  kmcpg_db* db;
+  hipStream_t st;
+  bool armed = false;
+  int wait() {
+    if (int rc = chain_begin(&db->fin_ev, db->fin_ev_valid, st)) return rc;
+    armed = true;
+    return 0;
+  }
+  ~FinGuard() {
+    if (armed && db->fin_ev && hipEventRecord(db->fin_ev, st) == hipSuccess) db->fin_ev_valid = true;
+  }
+};
+
+// A stage's launches between its two timing events (created on first use), when the call is timed (profiling >= 1) ...
+template <class Launch>
+int timed_launches(hipEvent_t (&ev)[2], bool timed, hipStream_t st, Launch launch) {
+  if (timed) {
+    for (auto& e : ev)
+      if (!e) HIPCHK(hipEventCreate(&e));
+    HIPCHK(hipEventRecord(ev[0], st));
+  }
+  launch();
+  if (timed) HIPCHK(hipEventRecord(ev[1], st));
+  return 0;
+}
+// ... and what kmcpg_last_* reports of them (the device is idle): the milliseconds between the events (*ms stays as it is where the call
+// was not timed), and the launch log — its length always, its first `cap` records — at profiling >= 1
+inline void timed_launches_report(const kmcpg_db* db, const hipEvent_t (&ev)[2], bool timed, const std::vector<kmcpg_k4_launch>& log, double* ms,
+                                  kmcpg_k4_launch* launches, uint32_t cap, uint32_t* n_launches) {
+  float f = 0;
+  if (timed && ev[1] && hipEventElapsedTime(&f, ev[0], ev[1]) == hipSuccess) *ms = f;
+  const size_t have = db->profiling >= 1 ? log.size() : 0;
+  const size_t m = std::min<size_t>(cap, have);
+  if (m) memcpy(launches, log.data(), m * sizeof(kmcpg_k4_launch));
+  *n_launches = (uint32_t)have;
 }
 
 // The species-specific stage (kmcpg_set_specific): what would judge something else than a query's final matches is refused while it is on

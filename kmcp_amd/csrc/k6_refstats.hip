@@ -6,14 +6,14 @@
 // which columns are one printed target and which species it lies under.  A row's qCov as the TSV route parses it back is printed_qcov
 // (k3_set_order.hpp), so "first.qCov >= H" has the bits `kmcp profile` compares.
 //
-//   k6_refstats  persistent workgroups; a wave takes RPW = 16 consecutive reads at a time in a grid-stride loop, the walk of k4_verdict /
-//                k5_summary: lanes 0..16 hold the offsets, a read's lane group (4 lanes) reduces min / max of both classes over segments
-//                of up to 64 pairs, the whole wave the longer ones.
+//   k6_refstats  persistent workgroups; a wave takes 16 consecutive reads at a time in a grid-stride loop, each time the walk of
+//                seg_walk.hpp (a read's lane group reduces min / max of both classes over segments of up to 64 pairs, the whole wave the
+//                longer ones — and counts their rows then and there when they have one target).
 //                  empty    no pairs                                                        nothing to count
 //                  single   min == max of target_class (any length up to K3_WG_CAP)         rows for every pair; the first pair is the
 //                                                                                           target's first row
-//                  wave     several targets, up to K6_CAP pairs: lane i holds pair i; K5's loop clears "first of its class" in the later
-//                           lanes of equal class; unique from min / max of species_class
+//                  wave     several targets, up to K6_CAP pairs: lane i holds pair i and whether it is the first of its class
+//                           (first_of_class, seg_walk.hpp); unique from min / max of species_class
 //                  LEFT     more than final_n k-mers (the pairs still face the host's -f test), more than K3_WG_CAP pairs (K3 leaves them
 //                           unordered: "first row" is not known), several targets among more than K6_CAP pairs: left[r] = 1, nothing counted
 //
@@ -31,45 +31,14 @@
 #include "common.hpp"
 #include "k3_set_order.hpp"
 #include "kernels.hpp"
+#include "seg_walk.hpp"
 
 namespace kmcpg {
 
 namespace {
 
-constexpr int RPW = 16, LPR = 64 / RPW;  // reads per wave, lanes per read
-constexpr uint32_t GROUP_CAP = 64;        // longest segment a lane group reduces
 constexpr uint32_t NO_KEY = 0xffffffffu;
-static_assert(K6_CAP == 64, "the wave class holds one pair per lane");
-
-struct MinMax {
-  uint32_t tmin, tmax, smin, smax;
-};
-__device__ __forceinline__ void take(MinMax& v, const K6Args& a, kmcpg_pair p) {
-  const uint32_t t = p.col < a.n_cols ? a.target_class[p.col] : 0xffffffffu;  // (K3 emits no such column: never out of the table)
-  v.tmin = min(v.tmin, t);
-  v.tmax = max(v.tmax, t);
-  if (a.species_class) {
-    const uint32_t s = p.col < a.n_cols ? a.species_class[p.col] : 0u;
-    v.smin = min(v.smin, s);
-    v.smax = max(v.smax, s);
-  }
-}
-__device__ __forceinline__ void fold(MinMax& v, int d) {
-  v.tmin = min(v.tmin, (uint32_t)__shfl_xor((int)v.tmin, d, 64));
-  v.tmax = max(v.tmax, (uint32_t)__shfl_xor((int)v.tmax, d, 64));
-  v.smin = min(v.smin, (uint32_t)__shfl_xor((int)v.smin, d, 64));
-  v.smax = max(v.smax, (uint32_t)__shfl_xor((int)v.smax, d, 64));
-}
-// specific_rule.hpp: one target, or one species that is not 0
-__device__ __forceinline__ bool unique_of(const MinMax& v, bool species) { return v.tmin == v.tmax || (species && v.smin == v.smax && v.smin != 0); }
-
-// the segment of read r0 + q as the wave's lanes hold the offsets (lane i: offs[r0 + i], i <= RPW); outside the buffer = empty
-__device__ __forceinline__ void segment(uint64_t mine, int q, uint64_t cap, uint64_t* s0, uint64_t* m, bool* bad) {
-  const uint64_t a = __shfl(mine, q, 64), b = __shfl(mine, q + 1, 64);
-  *bad = b < a || b > cap;
-  *s0 = a;
-  *m = *bad ? 0 : b - a;
-}
+static_assert(K6_CAP == 64 && K6_CAP == GROUP_CAP, "the wave class holds one pair per lane, and every longer segment is the walk's long class");
 
 // The workgroup's table: keys[slots], then cnt[slots][4].  `mine` counts what this lane added where (the witness).
 struct Table {
@@ -133,86 +102,49 @@ __global__ void __launch_bounds__(256) k6_refstats(K6Args a) {
   }
   __syncthreads();
   const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const bool species = a.species_class != nullptr;
-  const int g = (int)(lane / LPR), sub = (int)(lane % LPR);
-  uint32_t n_matched = 0, n_unique = 0, n_empty = 0, n_single = 0, n_wave = 0, n_left = 0, n_bad = 0;  // lane 0 keeps the wave's counts
+  const ClassTables c{a.target_class, a.species_class, a.n_cols};
+  uint32_t n_matched = 0, n_unique = 0, n_empty = 0, n_single = 0, n_wave = 0, n_left = 0, n_bad = 0;  // the wave's counts over its rounds
   for (uint64_t r0 = ((uint64_t)blockIdx.x * 4 + wave) * RPW; r0 < a.n_reads; r0 += (uint64_t)gridDim.x * 4 * RPW) {  // wave-uniform
-    const uint64_t mine = a.offs[min(r0 + lane, (uint64_t)a.n_reads)];  // lanes 0..RPW hold offs[r0 + lane]
-    const uint64_t r = r0 + (uint64_t)g;
-    const bool live = r < a.n_reads;
-    uint64_t s0, m;
-    bool bad;
-    segment(mine, g, a.pair_cap, &s0, &m, &bad);
-    if (!live) m = 0, bad = false;
-    const int32_t qk = live ? a.nk[r] : 1;
+    const uint64_t mine = load_offsets(a.offs, r0, lane, a.n_reads);
+    const OwnRead own = own_read(mine, r0, lane, a.n_reads, a.pair_cap);
+    const uint64_t m = own.seg.m;
+    const int32_t qk = own.live ? a.nk[own.r] : 1;
     bool left = m > 0 && (qk > a.final_n || m > (uint64_t)K3_WG_CAP);
     const bool judged = m > 0 && !left;
-    // min / max of the classes: the lane group's strided loads and two butterfly steps (every lane takes part in the shuffles: the
-    // partners sub ^ 1, sub ^ 2 are lanes of the same group, and a group's lanes agree on `small`)
-    const bool small = judged && m <= GROUP_CAP;
-    MinMax v{0xffffffffu, 0u, 0xffffffffu, 0u};
-    if (small)
-      for (uint32_t i = (uint32_t)sub; i < (uint32_t)m; i += LPR) take(v, a, a.pairs[s0 + i]);
-    fold(v, 1);
-    fold(v, 2);
-    bool single = small && v.tmin == v.tmax;
-    // one target, up to GROUP_CAP pairs (by far the common case): the lane group counts its rows; the first pair is the first row
-    if (single) {
-      for (uint32_t i = (uint32_t)sub; i < (uint32_t)m; i += LPR) {
-        add_row(t, a, a.pairs[s0 + i], qk, i == 0, true);
-      }
-    }
-    // the long segments, one after the other, by the whole wave: one target = counted here, several = LEFT
-    uint64_t longs = __ballot(judged && !small && sub == 0);
-    while (longs) {  // wave-uniform
-      const int q = (__ffsll((long long)longs) - 1) / LPR;
-      longs &= longs - 1;
-      uint64_t t0, tm;
-      bool tb;
-      segment(mine, q, a.pair_cap, &t0, &tm, &tb);  // GROUP_CAP < tm <= K3_WG_CAP
-      MinMax w{0xffffffffu, 0u, 0xffffffffu, 0u};
-      for (uint64_t i = lane; i < tm; i += 64) take(w, a, a.pairs[t0 + i]);
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) fold(w, d);
-      const bool one = w.tmin == w.tmax;  // wave-uniform
-      if (one) {
-        const int32_t tq = __shfl(qk, q * LPR, 64);
-        for (uint64_t i = lane; i < tm; i += 64) {
-          add_row(t, a, a.pairs[t0 + i], tq, i == 0, true);
-        }
-      }
-      if (g == q) single = one, left = !one, v = w;
-    }
-    // several targets, up to K6_CAP pairs: one segment at a time by the whole wave, a pair per lane
-    uint64_t multi = __ballot(judged && !single && !left && sub == 0);
-    n_wave += (uint32_t)__popcll(multi);
-    while (multi) {  // wave-uniform
-      const int q = (__ffsll((long long)multi) - 1) / LPR;
-      multi &= multi - 1;
-      uint64_t t0, tm;
-      bool tb;
-      segment(mine, q, a.pair_cap, &t0, &tm, &tb);  // 2 <= tm <= K6_CAP
+    // a long segment (GROUP_CAP < tm <= K3_WG_CAP) of one target is counted while the wave has it at hand; of several, it is LEFT
+    const auto w = walk<true>(c, a.pairs, a.pair_cap, mine, lane, own, judged, [&](int q, uint64_t t0, uint64_t tm, const MinMax<true>& reduced) {
+      if (!reduced.one_target()) return;  // wave-uniform
       const int32_t tq = __shfl(qk, q * LPR, 64);
-      const bool uq = species && __shfl((int)v.smin, q * LPR, 64) == __shfl((int)v.smax, q * LPR, 64) && __shfl((int)v.smin, q * LPR, 64) != 0;
-      const bool has = lane < tm;
-      const kmcpg_pair p = has ? a.pairs[t0 + lane] : kmcpg_pair{0u, 0u};
-      const uint32_t cls = has ? (p.col < a.n_cols ? a.target_class[p.col] : 0xffffffffu) : 0u;
-      bool first = has;
-      for (uint32_t j = 0; j + 1 < (uint32_t)tm; j++) {  // wave-uniform
-        const uint32_t cj = (uint32_t)__shfl((int)cls, (int)j, 64);
-        if (lane > j && cls == cj) first = false;
-      }
+      for (uint64_t i = lane; i < tm; i += 64) add_row(t, a, a.pairs[t0 + i], tq, i == 0, true);
+    });
+    const bool single = judged && w.v.one_target();
+    if (judged && !single && m > K6_CAP) left = true;
+    // one target, up to GROUP_CAP pairs (by far the common case): the lane group counts its rows; the first pair is the first row
+    if (single && w.small)
+      for (uint32_t i = (uint32_t)own.sub; i < (uint32_t)m; i += LPR) add_row(t, a, a.pairs[own.seg.s0 + i], qk, i == 0, true);
+    // several targets, up to K6_CAP pairs: one segment at a time by the whole wave, a pair per lane
+    const bool by_wave = judged && !single && !left, unique = w.v.one_target() || w.v.one_species();  // (specific_rule.hpp)
+    uint64_t multi = __ballot(by_wave && own.sub == 0);
+    while (multi) {  // wave-uniform
+      const int q = pop_group(multi);
+      const Segment s = segment(mine, q, a.pair_cap);  // 2 <= s.m <= K6_CAP
+      const int32_t tq = __shfl(qk, q * LPR, 64);
+      const bool uq = __shfl((int)unique, q * LPR, 64) != 0;
+      const bool has = lane < s.m;
+      const kmcpg_pair p = has ? a.pairs[s.s0 + lane] : kmcpg_pair{0u, 0u};
+      const uint32_t cls = has ? class_of(c.target, c.n_cols, p.col, NO_CLASS) : 0u;
+      const bool first = first_of_class(cls, (uint32_t)s.m, lane);
       if (has) add_row(t, a, p, tq, first, uq);
     }
-    const bool lead = live && sub == 0;
-    if (lead) a.left[r] = left ? 1 : 0;
-    const bool counted = lead && m > 0 && !left;
-    n_matched += (uint32_t)__popcll(__ballot(counted));
-    n_unique += (uint32_t)__popcll(__ballot(counted && unique_of(v, species)));
-    n_empty += (uint32_t)__popcll(__ballot(lead && m == 0));
-    n_single += (uint32_t)__popcll(__ballot(lead && single));
-    n_left += (uint32_t)__popcll(__ballot(lead && left));
-    n_bad += (uint32_t)__popcll(__ballot(lead && bad));
+    if (own.lead) a.left[own.r] = left ? 1 : 0;
+    const bool counted = own.lead && m > 0 && !left;
+    n_matched += wave_count(counted);
+    n_unique += wave_count(counted && unique);
+    n_empty += wave_count(own.lead && m == 0);
+    n_single += wave_count(own.lead && single);
+    n_wave += wave_count(own.lead && by_wave);
+    n_left += wave_count(own.lead && left);
+    n_bad += wave_count(own.lead && own.seg.bad);
   }
   __syncthreads();
   // the table goes to global memory: one 64-bit add per non-zero counter
@@ -230,18 +162,16 @@ __global__ void __launch_bounds__(256) k6_refstats(K6Args a) {
     }
   }
   const uint32_t lds_adds = wave_sum(t.lds_adds), spilled = wave_sum(t.spilled), globals = wave_sum(flushed) + spilled;
-  if (lane == 0) {
-    if (n_matched) atomicAdd(&a.totals[0], (unsigned long long)n_matched);
-    if (n_unique) atomicAdd(&a.totals[1], (unsigned long long)n_unique);
-    if (n_empty) atomicAdd(&a.stats[K6_EMPTY], (unsigned long long)n_empty);
-    if (n_single) atomicAdd(&a.stats[K6_SINGLE], (unsigned long long)n_single);
-    if (n_wave) atomicAdd(&a.stats[K6_WAVE], (unsigned long long)n_wave);
-    if (n_left) atomicAdd(&a.stats[K6_LEFT], (unsigned long long)n_left);
-    if (lds_adds) atomicAdd(&a.stats[K6_LDS_ADDS], (unsigned long long)lds_adds);
-    if (globals) atomicAdd(&a.stats[K6_GLOBAL_ADDS], (unsigned long long)globals);
-    if (spilled) atomicAdd(&a.stats[K6_SPILLED], (unsigned long long)spilled);
-    if (n_bad) atomicAdd(&a.stats[K6_BAD], (unsigned long long)n_bad);
-  }
+  wave_add(&a.totals[0], n_matched, lane);
+  wave_add(&a.totals[1], n_unique, lane);
+  wave_add(&a.stats[K6_EMPTY], n_empty, lane);
+  wave_add(&a.stats[K6_SINGLE], n_single, lane);
+  wave_add(&a.stats[K6_WAVE], n_wave, lane);
+  wave_add(&a.stats[K6_LEFT], n_left, lane);
+  wave_add(&a.stats[K6_LDS_ADDS], lds_adds, lane);
+  wave_add(&a.stats[K6_GLOBAL_ADDS], globals, lane);
+  wave_add(&a.stats[K6_SPILLED], spilled, lane);
+  wave_add(&a.stats[K6_BAD], n_bad, lane);
 }
 
 }  // namespace
@@ -250,8 +180,7 @@ __global__ void __launch_bounds__(256) k6_refstats(K6Args a) {
 // rounds).  stats (K6_STATS words) must be zero on entry.  Returns the grid.
 unsigned launch_k6(const K6Args& a, unsigned max_wgs, hipStream_t st, K4Log* log) {
   if (a.n_reads == 0) return 0;
-  const uint64_t full = ((uint64_t)a.n_reads + 4 * RPW - 1) / (4 * RPW);
-  const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(full, max_wgs));
+  const unsigned grid = std::max(1u, std::min(walk_grid(a.n_reads), max_wgs));
   hipLaunchKernelGGL(k6_refstats, dim3(grid), dim3(256), (size_t)a.slots * 20, st, a);
   k4_note(log, KMCPG_K6_REFSTATS, grid, 256);
   return grid;

@@ -1,4 +1,6 @@
-// kernels.hpp — host-callable launchers of the HIP kernels in k1_kmers.hip (K1 entry; kernels in k1_reads.hip, k1_windows.hip, k1_seg.hip, k1_win_once.hip), k1_dedup.hip, k2_cobs.hip, support.hip and sort_huge.hip.
+// kernels.hpp — host-callable launchers of the HIP kernels in k1_kmers.hip (K1 entry; kernels in k1_reads.hip, k1_windows.hip, k1_seg.hip,
+// k1_win_once.hip), k1_dedup.hip, k2_cobs.hip, k3_finalize.hip (K3 and its scan), k4_specific.hip, k5_summary.hip, k6_refstats.hip (the
+// stages behind K3; their shared walk is seg_walk.hpp), density.hip, windows.hip, build_scatter.hip, support.hip and sort_huge.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 

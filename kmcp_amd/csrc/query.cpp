@@ -324,13 +324,6 @@ struct WsGuard {
   }
 };
 
-// a per-handle event of its own kind (COBS kernels one batch at a time; K3's scratch one user at a time)
-int chain_begin(hipEvent_t* ev, bool valid, hipStream_t st) {
-  if (!*ev) HIPCHK(hipEventCreateWithFlags(ev, hipEventDisableTiming));
-  if (valid) HIPCHK(hipStreamWaitEvent(st, *ev, 0));
-  return 0;
-}
-
 // The reference drops a column whose FPR(n, count) exceeds -f right where it counts it (util-db-search.go:7474-7478); here
 // that test runs on the host in float64, but the GPU can already leave out every count that cannot pass it: for each
 // NumKmers n <= kFprBoundMaxN the smallest count c with FPR(n, c) <= max_fpr (the very values kmcpg_finalize compares, so a
@@ -709,14 +702,8 @@ extern "C" int kmcpg_group_device(kmcpg_db* db, const kmcpg_hit* d_hits, const u
   const kmcpg_params p = params ? *params : default_params();
   if (int rcs = set_refuse_params(db, p)) return rcs;
   hipStream_t st = (hipStream_t)stream;
-  if (int rc0 = chain_begin(&db->fin_ev, db->fin_ev_valid, st)) return rc0;
-  struct FinGuard {  // as WsGuard: every way out leaves the event behind
-    kmcpg_db* db;
-    hipStream_t st;
-    ~FinGuard() {
-      if (db->fin_ev && hipEventRecord(db->fin_ev, st) == hipSuccess) db->fin_ev_valid = true;
-    }
-  } fing{db, st};
+  FinGuard fing{db, st};  // (engine.hpp; as WsGuard)
+  if (int rc0 = fing.wait()) return rc0;
   if (db->w_fin_cnt.ensure((size_t)n_reads + 2) || db->w_fin_sums.ensure((size_t)k3_scan_tiles_for(n_reads + 1) + 1)) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
   // counters of the reads + the word that counts hits naming a read / column that does not exist
   HIPCHK(hipMemsetAsync(db->w_fin_cnt.p, 0, ((size_t)n_reads + 2) * sizeof(uint32_t), st));

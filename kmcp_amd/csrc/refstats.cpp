@@ -16,14 +16,8 @@ static_assert(offsetof(kmcpg_col_stats, rows) == REFSTATS_ROWS * 8 && offsetof(k
 
 namespace {
 
-int refuse_handle(const kmcpg_db* db) {  // the handles K4 refuses (specific.cpp), for the same reason
-  const char* what = db->paged_passes > 0 ? "a paged handle (kmcpg_open_paged)"
-                     : !db->shards.empty() ? "a multi-device handle (kmcpg_open_devices)"
-                     : db->opts.shard_count > 1 ? "a handle with shard_count > 1"
-                                                : nullptr;
-  if (!what) return 0;
-  return kmcpg_fail(KMCPG_EUNSUPPORTED, "reference statistics are not supported on %s: a query's counts need its matches from every block", what);
-}
+// the handles K4 refuses (specific.cpp), for the same reason
+int refuse(const kmcpg_db* db) { return refuse_handle(db, "reference statistics", "a query's counts need its matches from every block"); }
 
 size_t counter_words(const kmcpg_db* db) { return db->h_rs_target.size() * REFSTATS_WORDS + 3; }  // ... then matched and unique reads and the skipped launches
 
@@ -43,7 +37,7 @@ extern "C" int kmcpg_set_refstats(kmcpg_db* db, const uint32_t* target_class, co
   if (!db) return kmcpg_fail(KMCPG_EINVAL, "null argument");
   const bool off = !target_class && !species_class && n_cols == 0;
   if (!off) {
-    if (int rc = refuse_handle(db)) return rc;
+    if (int rc = refuse(db)) return rc;
     KMCPG_NO_FILES_ONLY(db);
     if (!target_class) return kmcpg_fail(KMCPG_EINVAL, "target_class is needed (species_class alone decides nothing)");
     if (n_cols != db->col_meta.size()) return kmcpg_fail(KMCPG_EINVAL, "n_cols = %u, the handle has %zu columns", n_cols, db->col_meta.size());
@@ -131,13 +125,7 @@ int refstats_enqueue(kmcpg_db* db, const kmcpg_pair* d_pairs, const uint64_t* d_
   a.left = d_left;
   a.stats = db->d_rs_stats;
   db->rs_timed = db->profiling >= 1;
-  if (db->rs_timed) {
-    for (auto& ev : db->rs_ev)
-      if (!ev) HIPCHK(hipEventCreate(&ev));
-    HIPCHK(hipEventRecord(db->rs_ev[0], st));
-  }
-  db->rs_grid = launch_k6(a, db->rs_max_wgs, st, db->rs_timed ? &db->k6_log : nullptr);
-  if (db->rs_timed) HIPCHK(hipEventRecord(db->rs_ev[1], st));
+  if (int rc = timed_launches(db->rs_ev, db->rs_timed, st, [&] { db->rs_grid = launch_k6(a, db->rs_max_wgs, st, db->rs_timed ? &db->k6_log : nullptr); })) return rc;
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -147,7 +135,7 @@ extern "C" int kmcpg_refstats_device(kmcpg_db* db, const kmcpg_pair* d_pairs, co
                                      uint32_t n_reads, int32_t final_n, const uint64_t* d_n_hits, uint64_t hit_cap, uint8_t* d_left, void* stream) {
   if (!db || !d_read_offs || (n_reads && (!d_qkmers || !d_left)) || (pair_cap && !d_pairs)) return kmcpg_fail(KMCPG_EINVAL, "null argument");
   if (n_reads == 0xffffffffu) return kmcpg_fail(KMCPG_EINVAL, "too many reads");
-  if (int rc = refuse_handle(db)) return rc;
+  if (int rc = refuse(db)) return rc;
   return refstats_enqueue(db, d_pairs, d_read_offs, pair_cap, d_qkmers, n_reads, final_n, d_n_hits, hit_cap, d_left, (hipStream_t)stream);
 }
 
@@ -215,13 +203,6 @@ extern "C" int kmcpg_last_refstats(kmcpg_db* db, kmcpg_refstats_stats* out, kmcp
   out->bad_segments = s[K6_BAD];
   out->grid = db->rs_grid;
   out->slots = db->rs_slots;
-  if (db->rs_timed && db->rs_ev[1]) {
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, db->rs_ev[0], db->rs_ev[1]) == hipSuccess) out->k6_ms = ms;
-  }
-  const size_t have = db->profiling >= 1 ? db->k6_log.size() : 0;
-  const size_t m = std::min<size_t>(cap, have);
-  if (m) memcpy(launches, db->k6_log.data(), m * sizeof(kmcpg_k4_launch));
-  *n_launches = (uint32_t)have;
+  timed_launches_report(db, db->rs_ev, db->rs_timed, db->k6_log, &out->k6_ms, launches, cap, n_launches);
   return 0;
 }

@@ -14,21 +14,14 @@ namespace {
 constexpr size_t SPEC_STATS_BYTES = 64;  // K4_STATS 32-bit words, then at byte 32 the pairs in and out
 static_assert(K4_STATS * sizeof(uint32_t) <= 32, "the 64-bit words start at byte 32");
 
-int refuse_handle(const kmcpg_db* db) {
-  const char* what = db->paged_passes > 0 ? "a paged handle (kmcpg_open_paged)"
-                     : !db->shards.empty() ? "a multi-device handle (kmcpg_open_devices)"
-                     : db->opts.shard_count > 1 ? "a handle with shard_count > 1"
-                                                : nullptr;
-  if (!what) return 0;
-  return kmcpg_fail(KMCPG_EUNSUPPORTED, "species-specific queries are not supported on %s: a query's verdict needs its matches from every block", what);
-}
+int refuse(const kmcpg_db* db) { return refuse_handle(db, "species-specific queries", "a query's verdict needs its matches from every block"); }
 }  // namespace
 
 extern "C" int kmcpg_set_specific(kmcpg_db* db, const uint32_t* target_class, const uint32_t* species_class, uint32_t n_cols) {
   if (!db) return kmcpg_fail(KMCPG_EINVAL, "null argument");
   const bool off = !target_class && !species_class && n_cols == 0;
   if (!off) {
-    if (int rc = refuse_handle(db)) return rc;
+    if (int rc = refuse(db)) return rc;
     KMCPG_NO_FILES_ONLY(db);
     if (!target_class) return kmcpg_fail(KMCPG_EINVAL, "target_class is needed (species_class alone decides nothing)");
     if (n_cols != db->col_meta.size()) return kmcpg_fail(KMCPG_EINVAL, "n_cols = %u, the handle has %zu columns", n_cols, db->col_meta.size());
@@ -74,21 +67,13 @@ extern "C" int kmcpg_specific_device(kmcpg_db* db, const kmcpg_pair* d_pairs, co
     return kmcpg_fail(KMCPG_EINVAL, "null argument");
   if (out_cap < pair_cap) return kmcpg_fail(KMCPG_EINVAL, "out_cap (%llu) must be at least pair_cap (%llu)", (unsigned long long)out_cap, (unsigned long long)pair_cap);
   if (n_reads == 0xffffffffu) return kmcpg_fail(KMCPG_EINVAL, "too many reads");
-  if (int rc = refuse_handle(db)) return rc;
+  if (int rc = refuse(db)) return rc;
   std::lock_guard<std::mutex> g(db->mu);
   KMCPG_USE_DEVICE(db);
   if (!db->spec_on() || !db->d_spec_target) return kmcpg_fail(KMCPG_EINVAL, "the stage is off: call kmcpg_set_specific first");
   hipStream_t st = (hipStream_t)stream;
-  // the scratch has one user at a time: K3's chain (kmcpg_group_device)
-  if (!db->fin_ev) HIPCHK(hipEventCreateWithFlags(&db->fin_ev, hipEventDisableTiming));
-  if (db->fin_ev_valid) HIPCHK(hipStreamWaitEvent(st, db->fin_ev, 0));
-  struct FinGuard {  // every way out leaves the event behind
-    kmcpg_db* db;
-    hipStream_t st;
-    ~FinGuard() {
-      if (db->fin_ev && hipEventRecord(db->fin_ev, st) == hipSuccess) db->fin_ev_valid = true;
-    }
-  } fing{db, st};
+  FinGuard fing{db, st};  // the scratch has one user at a time: K3's chain (kmcpg_group_device)
+  if (int rc = fing.wait()) return rc;
   if (db->w_spec_cnt.ensure((size_t)n_reads + 2) || db->w_spec_sums.ensure((size_t)k3_scan_tiles_for(n_reads + 1) + 1)) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
   HIPCHK(hipMemsetAsync(db->d_spec_stats, 0, SPEC_STATS_BYTES, st));
   db->k4_log.clear();
@@ -116,13 +101,7 @@ extern "C" int kmcpg_specific_device(kmcpg_db* db, const kmcpg_pair* d_pairs, co
   a.out_cap = out_cap;
   a.stats = (uint32_t*)db->d_spec_stats;
   db->spec_timed = db->profiling >= 1;
-  if (db->spec_timed) {
-    for (auto& ev : db->spec_ev)
-      if (!ev) HIPCHK(hipEventCreate(&ev));
-    HIPCHK(hipEventRecord(db->spec_ev[0], st));
-  }
-  launch_k4(a, st, db->spec_timed ? &db->k4_log : nullptr);
-  if (db->spec_timed) HIPCHK(hipEventRecord(db->spec_ev[1], st));
+  if (int rc = timed_launches(db->spec_ev, db->spec_timed, st, [&] { launch_k4(a, st, db->spec_timed ? &db->k4_log : nullptr); })) return rc;
   // the witness's pairs in and out: the last offsets, kept where the caller's buffers need not outlive the call
   HIPCHK(hipMemcpyAsync(db->d_spec_stats + 4, d_read_offs + n_reads, sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
   HIPCHK(hipMemcpyAsync(db->d_spec_stats + 5, d_out_offs + n_reads, sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
@@ -152,14 +131,7 @@ extern "C" int kmcpg_last_specific(kmcpg_db* db, kmcpg_specific_stats* out, kmcp
   out->bad_segments = s[5];
   out->pairs_in = w[4];
   out->pairs_out = w[5];
-  if (db->spec_timed && db->spec_ev[1]) {
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, db->spec_ev[0], db->spec_ev[1]) == hipSuccess) out->k4_ms = ms;
-  }
-  const size_t have = db->profiling >= 1 ? db->k4_log.size() : 0;
-  const size_t m = std::min<size_t>(cap, have);
-  if (m) memcpy(launches, db->k4_log.data(), m * sizeof(kmcpg_k4_launch));
-  *n_launches = (uint32_t)have;
+  timed_launches_report(db, db->spec_ev, db->spec_timed, db->k4_log, &out->k4_ms, launches, cap, n_launches);
   return 0;
 }
 
@@ -173,21 +145,13 @@ extern "C" int kmcpg_summarize_device(kmcpg_db* db, const kmcpg_pair* d_pairs, c
     return kmcpg_fail(KMCPG_EINVAL, "null argument");
   if (left_cap < pair_cap) return kmcpg_fail(KMCPG_EINVAL, "left_cap (%llu) must be at least pair_cap (%llu)", (unsigned long long)left_cap, (unsigned long long)pair_cap);
   if (n == 0xffffffffu) return kmcpg_fail(KMCPG_EINVAL, "too many windows");
-  if (int rc = refuse_handle(db)) return rc;
+  if (int rc = refuse(db)) return rc;
   std::lock_guard<std::mutex> g(db->mu);
   KMCPG_USE_DEVICE(db);
   if (!db->spec_on() || !db->d_spec_target) return kmcpg_fail(KMCPG_EINVAL, "the stage is off: call kmcpg_set_specific first");
   hipStream_t st = (hipStream_t)stream;
-  // the scratch has one user at a time: K3's chain (kmcpg_group_device), K4 (kmcpg_specific_device)
-  if (!db->fin_ev) HIPCHK(hipEventCreateWithFlags(&db->fin_ev, hipEventDisableTiming));
-  if (db->fin_ev_valid) HIPCHK(hipStreamWaitEvent(st, db->fin_ev, 0));
-  struct FinGuard {  // every way out leaves the event behind
-    kmcpg_db* db;
-    hipStream_t st;
-    ~FinGuard() {
-      if (db->fin_ev && hipEventRecord(db->fin_ev, st) == hipSuccess) db->fin_ev_valid = true;
-    }
-  } fing{db, st};
+  FinGuard fing{db, st};  // the scratch has one user at a time: K3's chain (kmcpg_group_device), K4 (kmcpg_specific_device)
+  if (int rc = fing.wait()) return rc;
   if (db->w_spec_cnt.ensure((size_t)n + 2) || db->w_spec_sums.ensure((size_t)k3_scan_tiles_for(n + 1) + 1)) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
   if (!db->d_sum_stats) HIPCHK(hipMalloc((void**)&db->d_sum_stats, SPEC_STATS_BYTES));
   HIPCHK(hipMemsetAsync(db->d_sum_stats, 0, SPEC_STATS_BYTES, st));
@@ -216,13 +180,7 @@ extern "C" int kmcpg_summarize_device(kmcpg_db* db, const kmcpg_pair* d_pairs, c
   a.left_cap = left_cap;
   a.stats = (uint32_t*)db->d_sum_stats;
   db->sum_timed = db->profiling >= 1;
-  if (db->sum_timed) {
-    for (auto& ev : db->sum_ev)
-      if (!ev) HIPCHK(hipEventCreate(&ev));
-    HIPCHK(hipEventRecord(db->sum_ev[0], st));
-  }
-  launch_k5(a, st, db->sum_timed ? &db->k5_log : nullptr);
-  if (db->sum_timed) HIPCHK(hipEventRecord(db->sum_ev[1], st));
+  if (int rc = timed_launches(db->sum_ev, db->sum_timed, st, [&] { launch_k5(a, st, db->sum_timed ? &db->k5_log : nullptr); })) return rc;
   // the witness's LEFT pairs: the last offset, kept where the caller's buffers need not outlive the call
   HIPCHK(hipMemcpyAsync(db->d_sum_stats + 4, d_left_offs + n, sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
   HIPCHK(hipGetLastError());
@@ -258,13 +216,6 @@ extern "C" int kmcpg_last_summary(kmcpg_db* db, kmcpg_summary_stats* out, kmcpg_
     out->empty = s[3];
     out->left_pairs = w[4];
   }
-  if (db->sum_timed && db->sum_ev[1]) {
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, db->sum_ev[0], db->sum_ev[1]) == hipSuccess) out->k5_ms = ms;
-  }
-  const size_t have = db->profiling >= 1 ? db->k5_log.size() : 0;
-  const size_t m = std::min<size_t>(cap, have);
-  if (m) memcpy(launches, db->k5_log.data(), m * sizeof(kmcpg_k4_launch));
-  *n_launches = (uint32_t)have;
+  timed_launches_report(db, db->sum_ev, db->sum_timed, db->k5_log, &out->k5_ms, launches, cap, n_launches);
   return 0;
 }

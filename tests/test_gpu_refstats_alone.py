@@ -216,6 +216,27 @@ def test_segment_lengths(db, pattern, species):
         assert (want[12:18, 2].sum() > 1) == species
 
 
+# 16 reads = one wave: long segments (the whole wave reduces them — and counts the one-target ones — and hands the result back to the read's
+# lane group: the first, the last and inner groups among them), several-target segments the wave counts, one-target segments of a lane
+# group and empty reads, side by side
+ONE_WAVE = [("aba", 65), ("aba", 40), ("one", 3), ("distinct", 65), ("late", 5), ("one", 0), ("aba", 64), ("one", 130),
+            ("distinct", 2), ("late", 65), ("one", 1), ("one", 65), ("distinct", 63), ("one", 64), ("late", 4), ("one", 65)]
+
+
+@pytest.mark.parametrize("species", [True, False], ids=["species", "strain"])
+def test_long_wave_and_single_segments_in_one_wave_then_a_wave_of_one_read(db, species):
+    """17 reads: the wave above, and the batch's last read alone in a second wave beside 15 lane groups without a read — long (LEFT,
+    single), by the wave, single and empty in turn"""
+    rng = np.random.default_rng(17)
+    first = [PATTERNS[p](rng, m) for p, m in ONE_WAVE]
+    want = ["left", "wave", "single", "left", "wave", "empty", "wave", "single", "wave", "left", "single", "single", "wave", "single", "wave", "single"]
+    for (p, m), cls in ((("aba", 65), "left"), (("one", 65), "single"), (("aba", 40), "wave"), (("one", 3), "single"), (("one", 0), "empty")):
+        case = Case(first + [PATTERNS[p](rng, m)])
+        assert case.n == 17
+        sts, classes, _ = run(db, f"one wave and a read, the last one {m} pairs of '{p}'", [case], species=species)
+        assert classes[0] == want + [cls] and sts[0]["grid"] == 1
+
+
 @pytest.mark.parametrize("n_reads", [1, 15, 16, 17, 63, 64, 65])
 def test_read_counts(db, n_reads):
     run(db, f"{n_reads} reads", [mixed(n_reads, seed=n_reads)])

@@ -231,6 +231,27 @@ def test_read_counts(db, n_reads):
         run(db, f"{n_reads} reads, all empty", Case([np.zeros(0, dtype=np.uint32)] * n_reads))
 
 
+# 16 reads = one wave: long segments (the whole wave reduces them and hands the result back to the read's lane group — the first, the last
+# and inner groups among them), several-target and one-target segments of a lane group, and empty reads, side by side
+ONE_WAVE = [(65, "two"), (2, "species"), (1, "one"), (64, "two"), (130, "one"), (0, "one"), (33, "species"), (65, "species"),
+            (5, "two-no-species"), (64, "one"), (3, "no-species"), (65, "one"), (0, "two"), (40, "two"), (1, "no-species"), (65, "two")]
+
+
+@pytest.mark.parametrize("level", ["species", "strain"])
+def test_long_and_small_segments_in_one_wave_then_a_wave_of_one_read(db, level):
+    """17 reads: the wave above, and the batch's last read alone in a second wave beside 15 lane groups without a read — long (several
+    targets, one target), small (several targets, one target) and empty in turn"""
+    rng = np.random.default_rng(17)
+    first = [segment(rng, m, kind) for m, kind in ONE_WAVE]
+    for m, kind in ((65, "two"), (65, "one"), (40, "two"), (3, "one"), (0, "one")):
+        case = Case(first + [segment(rng, m, kind)])
+        assert case.n == 17
+        verdict, _, _, st = run(db, f"one wave and a read, the last one {m} pairs of '{kind}', {level}", case, level == "species")
+        assert st["wave_segments"] == 5 + (m > 64) and st["group_segments"] == 9 + (0 < m <= 64)
+        assert verdict[16] == (DROP if kind == "two" else KEEP)
+        assert list(verdict[[0, 4, 11, 15]]) == [DROP, KEEP, KEEP, DROP] and verdict[7] == (KEEP if level == "species" else DROP)
+
+
 MILLION = 256 * 4096 + 1  # 1 048 577 reads: 257 tiles of the scan, the second trip of k3_scan_sums
 
 _million = {}

@@ -173,6 +173,25 @@ def test_segment_lengths(db, pattern):
         assert [n for _, n, _ in ref][2:7] == [2, 4, 4, 4, 4]
 
 
+# 16 windows = one wave: long segments (the whole wave reduces them and hands the result back to the window's lane group — the first, the
+# last and inner groups among them), several-target segments the wave sums, one-target segments of a lane group and empty windows, side by side
+ONE_WAVE = [("aba", 65), ("aba", 40), ("one", 3), ("distinct", 65), ("late", 5), ("one", 0), ("aba", 64), ("one", 130),
+            ("distinct", 2), ("late", 65), ("one", 1), ("one", 65), ("distinct", 63), ("one", 64), ("late", 4), ("one", 65)]
+
+
+def test_long_wave_and_single_segments_in_one_wave_then_a_wave_of_one_window(db):
+    """17 windows: the wave above, and the batch's last window alone in a second wave beside 15 lane groups without a window — long
+    (LEFT, single), by the wave, single and empty in turn"""
+    rng = np.random.default_rng(17)
+    first = [PATTERNS[p](rng, m) for p, m in ONE_WAVE]
+    want = ["left", "wave", "single", "left", "wave", "empty", "wave", "single", "wave", "left", "single", "single", "wave", "single", "wave", "single"]
+    for (p, m), cls in ((("aba", 65), "left"), (("one", 65), "single"), (("aba", 40), "wave"), (("one", 3), "single"), (("one", 0), "empty")):
+        case = Case(first + [PATTERNS[p](rng, m)])
+        assert case.n == 17
+        ref = run(db, f"one wave and a window, the last one {m} pairs of '{p}'", case)
+        assert [c for c, _, _ in ref] == want + [cls]
+
+
 def test_a_single_target_of_any_length_stays_on_the_device(db):
     rng = np.random.default_rng(4)
     ref = run(db, "5 000 pairs of one target", Case([seg_one(rng, 5000), seg_one(rng, 1), seg_distinct(rng, 150)]))
