@@ -1,7 +1,8 @@
 // kmcp-refstats: which references are in the sample — host-side mirror of stage 1/4 of `kmcp profile` ("counting matches and unique
-// matches for filtering out low-confidence references", kmcp/cmd/profile.go:761-1099; row parser util-profile.go:94-182).  Host only, no GPU.
+// matches for filtering out low-confidence references", kmcp/cmd/profile.go:761-1099; row parser util-profile.go:94-182) and, with
+// --cooccur, of stage 2/4 ("counting ambiguous matches for correcting matches", profile.go:1117-1279).  Host only, no GPU.
 //
-//   kmcp-refstats [-o out.tsv[.gz]] [-f 0.01] [-t 0.55] [-n 0] [--keep-perfect-matches] [--keep-main-matches] [--max-qcov-gap 0.4]
+//   kmcp-refstats [-o out.tsv[.gz]] [--cooccur pairs.tsv[.gz]] [-f 0.01] [-t 0.55] [-n 0] [--keep-perfect-matches] [--keep-main-matches] [--max-qcov-gap 0.4]
 //                 [-m 3] [-p frac] [-H qcov] [--level species|strain|assembly] [-T map.tsv[,more.tsv]]... [-X taxdump/] [-i list.txt]
 //                 [a.tsv[.gz] ...]
 //
@@ -19,6 +20,11 @@
 //   # unique reads: U
 //   #ref chunks tLen reads ureads hicUreads chunksFrac verdict chunkReads chunkFirsts chunkUreads chunkHicUreads
 // one line per reference with at least one row, in ascending byte order of the name; the four per-chunk lists are comma-joined.
+// --cooccur FILE: a second pass over the inputs (stdin is refused) counts, for every pair of references that stage 1 kept (verdict ok),
+// the queries whose kept rows name both — the rule and the reference's quirks are kmcp_amd/csrc/cooccur_rule.hpp:
+//   # pairs: N
+//   #refA refB reads
+// one line per pair with refA < refB bytewise, in ascending order of (refA, refB).  The stage-1 output is what it is without the flag.
 #include <unistd.h>
 
 #include <algorithm>
@@ -28,6 +34,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "../kmcp_amd/csrc/cooccur_rule.hpp"
 #include "../kmcp_amd/csrc/refstats_rule.hpp"
 #include "../kmcp_amd/csrc/taxonomy.hpp"
 #include "tsv_in.hpp"
@@ -59,7 +66,9 @@ void usage() {
       "  -X, --taxdump string              Directory of NCBI taxonomy dump files: nodes.dmp, optional with merged.dmp and delnodes.dmp.\n"
       "      --level string                Level to estimate abundance at. available values: species, strain/assembly. (default \"species\")\n"
       "      --line-chunk-size int         Accepted for command-line compatibility. (default 5000)\n"
-      "  -i, --infile-list string          File of input files list (one file per line).\n",
+      "  -i, --infile-list string          File of input files list (one file per line).\n"
+      "      --cooccur string              Also count the reads shared by every pair of kept references (stage 2/4 of kmcp profile) into\n"
+      "                                    this file, supports a \".gz\" suffix. A second pass over the inputs: stdin is not supported.\n",
       stderr);
 }
 
@@ -84,12 +93,43 @@ bool parse_int(const char* p, size_t n, bool sign_ok, uint64_t* v, bool* neg) {
 struct Ref {
   uint32_t target_class, species_class;
   uint64_t chunks, tlen, base;  // its counters: 4 words per chunk from counters[4 * base]
+  bool ok = false;              // stage 1 kept it (set once every row is counted)
 };
+
+// a row cut at its first 12 tabs: field k = 1..12 (the 13th keeps the rest of the line)
+struct Fields {
+  const char* p;
+  size_t tab[13];
+  size_t get(int k, const char** fp) const {
+    *fp = k == 1 ? p : p + tab[k - 2] + 1;
+    return tab[k - 1] - (size_t)(*fp - p);
+  }
+};
+// a line of a search result through the tests every stage makes when it parses a row: false = not a row (blank, comment) or dropped by -t / -f
+bool parse_row(const char* p, size_t n, double min_qcov, double max_fpr, Fields* f, double* qcov) {
+  size_t len = n;  // without the end of line
+  if (len && p[len - 1] == '\n') len--;
+  if (len && p[len - 1] == '\r') len--;
+  if (len == 0 || p[0] == '#') return false;
+  f->p = p;
+  int nt = 0;
+  for (size_t i = 0; i < len && nt < 12; i++)
+    if (p[i] == '\t') f->tab[nt++] = i;
+  if (nt < 12) die("invalid kmcp search result format");
+  const char* fp;
+  double fpr = 0;
+  size_t fn = f->get(12, &fp);
+  if (!parse_float(fp, fn, qcov)) die("failed to parse qCov: %.*s", (int)fn, fp);
+  if (*qcov < min_qcov) return false;
+  fn = f->get(4, &fp);
+  if (!parse_float(fp, fn, &fpr)) die("failed to parse FPR: %.*s", (int)fn, fp);
+  return !(fpr > max_fpr);
+}
 
 }  // namespace
 
 int main(int argc, char** argv) {
-  std::string out_file = "-", level = "species", taxdump, infile_list;
+  std::string out_file = "-", level = "species", taxdump, infile_list, cooccur_file;
   std::vector<std::string> map_files, files;
   double max_fpr = 0.01, min_qcov = 0.55, flag_h = 0.75, flag_p = 0.8, max_gap = 0.4;
   bool given_h = false, given_p = false, keep_perfect = false, keep_main = false;
@@ -136,6 +176,7 @@ int main(int argc, char** argv) {
     else if (a == "--level") level = need(i);
     else if (a == "--line-chunk-size") chunk = integer("--line-chunk-size", need(i));
     else if (a == "-i" || a == "--infile-list") infile_list = need(i);
+    else if (a == "--cooccur") cooccur_file = need(i);
     else if (a == "-j" || a == "--threads" || a == "--log") need(i);  // accepted for command-line compatibility
     else if (a == "-q" || a == "--quiet") {
     } else if (a == "-h" || a == "--help") {
@@ -182,6 +223,13 @@ int main(int argc, char** argv) {
   if (files.empty()) files.push_back("-");
   for (const std::string& f : files)
     if (f != "-" && tsv_in::clean_path(f) == tsv_in::clean_path(out_file)) die("out file should not be one of the input file");
+  if (!cooccur_file.empty()) {  // before anything is read
+    for (const std::string& f : files) {
+      if (f == "-") die("flag --cooccur: stdin is not supported (the search results are read twice)");
+      if (tsv_in::clean_path(f) == tsv_in::clean_path(cooccur_file)) die("flag --cooccur: the file should not be one of the input file");
+    }
+    if (cooccur_file == "-" ? out_file == "-" : tsv_in::clean_path(cooccur_file) == tsv_in::clean_path(out_file)) die("flag --cooccur: the file must not be the out file (-o)");
+  }
 
   kmcpg::TaxidMap tmap;
   kmcpg::Taxonomy tax;
@@ -233,28 +281,13 @@ int main(int argc, char** argv) {
     const char* p = nullptr;
     size_t n = 0;
     while (in.next(&p, &n)) {
-      size_t len = n;  // without the end of line
-      if (len && p[len - 1] == '\n') len--;
-      if (len && p[len - 1] == '\r') len--;
-      if (len == 0 || p[0] == '#') continue;
-      size_t tab[13];
-      int nt = 0;
-      for (size_t i = 0; i < len && nt < 12; i++)
-        if (p[i] == '\t') tab[nt++] = i;
-      if (nt < 12) die("invalid kmcp search result format");
-      auto field = [&](int k, const char** fp) -> size_t {  // field k = 1..12 (the 13th keeps the rest of the line)
-        *fp = k == 1 ? p : p + tab[k - 2] + 1;
-        return tab[k - 1] - (size_t)(*fp - p);
-      };
+      Fields fl;
+      double qcov = 0;
+      if (!parse_row(p, n, min_qcov, max_fpr, &fl, &qcov)) continue;
+      const size_t* tab = fl.tab;
+      auto field = [&](int k, const char** fp) { return fl.get(k, fp); };
       const char* fp;
       size_t fn;
-      double fpr = 0, qcov = 0;
-      fn = field(12, &fp);
-      if (!parse_float(fp, fn, &qcov)) die("failed to parse qCov: %.*s", (int)fn, fp);
-      if (qcov < min_qcov) continue;
-      fn = field(4, &fp);
-      if (!parse_float(fp, fn, &fpr)) die("failed to parse FPR: %.*s", (int)fn, fp);
-      if (fpr > max_fpr) continue;
       uint64_t v[12] = {};
       bool neg[12] = {};
       static const struct {
@@ -279,6 +312,51 @@ int main(int argc, char** argv) {
       rows.push_back(kmcpg::RefstatsRow{r.target_class, r.species_class, r.base + v[7], qcov});
     }
     flush();
+  }
+
+  // the verdicts: what the output prints, and stage 2's set of kept references
+  for (auto& kv : refs) {
+    Ref& r = kv.second;
+    const uint64_t* w = counters.data() + r.base * kmcpg::REFSTATS_WORDS;
+    r.ok = kmcpg::refstats_rollup(r.chunks, min_frac, [&](uint64_t c) { return w + c * kmcpg::REFSTATS_WORDS; }).verdict == kmcpg::REFSTATS_OK;
+  }
+
+  // stage 2/4 (profile.go:1117-1279): the inputs once more; a query's targets are a set (chunks of one reference are one target)
+  std::unordered_map<uint64_t, uint64_t> shared;  // cooccur_key of two target classes -> queries
+  if (!cooccur_file.empty()) {
+    kmcpg::CooccurCut cut2;
+    cut2.cut = cut;
+    for (const std::string& file : files) {
+      RawLines in(file);
+      std::string query;  // the name of the previous row that was not skipped
+      bool any = false;
+      std::vector<uint32_t> cls;  // the current query's targets
+      auto flush = [&] {
+        kmcpg::cooccur_query_pairs(cls.data(), cls.size(), [&](uint64_t key) { shared[key]++; });
+        cls.clear();
+      };
+      const char* p = nullptr;
+      size_t n = 0;
+      while (in.next(&p, &n)) {
+        Fields fl;
+        double qcov = 0;
+        if (!parse_row(p, n, min_qcov, max_fpr, &fl, &qcov)) continue;
+        const char* fp;
+        const size_t fn = fl.get(6, &fp);
+        name.assign(fp, fn);
+        const auto it = refs.find(name);
+        const bool kept = it != refs.end() && it->second.ok;
+        const bool new_name = !any || query.size() != fl.tab[0] || memcmp(query.data(), p, fl.tab[0]) != 0;
+        bool opens = false;
+        const bool take = cut2.row(kept, new_name, qcov, &opens);
+        if (!kept) continue;
+        if (opens) flush();
+        query.assign(p, fl.tab[0]);
+        any = true;
+        if (take) cls.push_back(it->second.target_class);
+      }
+      flush();
+    }
   }
 
   Out out(out_file, -1);
@@ -306,5 +384,25 @@ int main(int argc, char** argv) {
     out.write(s);
   }
   out.close();
+
+  if (!cooccur_file.empty()) {
+    std::vector<const std::string*> name_of(refs.size());
+    for (const auto& kv : refs) name_of[kv.second.target_class] = &kv.first;
+    std::vector<std::pair<std::pair<const std::string*, const std::string*>, uint64_t>> rows;
+    for (const auto& kv : shared) {
+      const std::string *a = name_of[kmcpg::cooccur_key_a(kv.first)], *b = name_of[kmcpg::cooccur_key_b(kv.first)];
+      if (*b < *a) std::swap(a, b);
+      rows.push_back({{a, b}, kv.second});
+    }
+    std::sort(rows.begin(), rows.end(), [](const auto& x, const auto& y) { return *x.first.first != *y.first.first ? *x.first.first < *y.first.first : *x.first.second < *y.first.second; });
+    Out co(cooccur_file, -1);
+    co.write(line, (size_t)snprintf(line, sizeof line, "# pairs: %zu\n", rows.size()));
+    co.write("#refA\trefB\treads\n");
+    for (const auto& r : rows) {
+      s = *r.first.first + "\t" + *r.first.second + "\t" + std::to_string(r.second) + "\n";
+      co.write(s);
+    }
+    co.close();
+  }
   return 0;
 }

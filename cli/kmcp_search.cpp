@@ -93,6 +93,10 @@ struct Options {
   double ref_stats_h = 0.75, ref_stats_p = 0.8;
   bool ref_stats_h_given = false, ref_stats_p_given = false;
   const char* ref_stats_flag = nullptr;  // the first --ref-stats-* flag other than --ref-stats that was given
+  // --ref-stats-cooccur FILE [--ref-stats-cooccur-slots N]: stage 2/4 beside it — the reads shared by every pair of kept references; the
+  // file is what `kmcp-refstats -f 1 -t 0 ... --cooccur FILE` writes from this run's TSV (K7 of the library, kmcpg_set_cooccur)
+  std::string ref_stats_cooccur;
+  long long ref_stats_cooccur_slots = 0;  // the pair table's slots, a power of two; 0: the library's default
   std::vector<std::string> also_dbs;  // --also-db: further databases searched in the same pass, the output merged as kmcp-merge would
   bool gpus_given = false;
   int min_qlen = 30, min_kmers = 10, dedup = 256, top_scores = 0, threads = 0, device = 0, batch = 131072, gpus = 1, gpu_passes = -1;
@@ -144,6 +148,7 @@ static void usage() {
       "                             Not with -K, --try-se, -n, --sliding-* (except for --regions-bed), --gpus/--gpu-ids, --gpu-passes.\n"
       "           --ref-stats file [--ref-stats-mode int (3)] [--ref-stats-min-hic-ureads-qcov float] [--ref-stats-min-chunks-fraction float]\n"
       "                             [--ref-stats-level species|strain|assembly] [--taxid-map file(s) --taxdump dir]\n"
+      "                             [--ref-stats-cooccur file [--ref-stats-cooccur-slots int]]\n"
       "                             count, on the GPU while the search runs, what stage 1/4 of `kmcp profile` counts per reference (reads,\n"
       "                             uniquely matched reads, high-confidence ones, chunks covered) and judge which references are in the\n"
       "                             sample: the file is what `kmcp-refstats -f 1 -t 0 -m N --level L ...` writes from this command's\n"
@@ -190,7 +195,7 @@ static Options parse_args(int argc, char** argv) {
       {"gpu", 0, 1}, {"gpu-batch", 0, 1}, {"gpus", 0, 1}, {"gpu-ids", 0, 1}, {"gpu-passes", 0, 1}, {"parse-only", 0, 0}, {"help", 'h', 0}, {"version", 'V', 0},
       {"sliding-step", 0, 1}, {"sliding-window", 0, 1}, {"sliding-greedy", 0, 0}, {"also-db", 0, 1},
       {"specific-level", 0, 1}, {"taxid-map", 0, 1}, {"taxdump", 0, 1},
-      {"ref-stats", 0, 1}, {"ref-stats-mode", 0, 1}, {"ref-stats-min-hic-ureads-qcov", 0, 1}, {"ref-stats-min-chunks-fraction", 0, 1}, {"ref-stats-level", 0, 1},
+      {"ref-stats", 0, 1}, {"ref-stats-mode", 0, 1}, {"ref-stats-min-hic-ureads-qcov", 0, 1}, {"ref-stats-min-chunks-fraction", 0, 1}, {"ref-stats-level", 0, 1}, {"ref-stats-cooccur", 0, 1}, {"ref-stats-cooccur-slots", 0, 1},
       {"regions-bed", 0, 1}, {"regions-min-overlap", 0, 1}, {"regions-max-gap", 0, 1}, {"regions-ignore-type", 0, 0},
       {"regions-name-species", 0, 1}, {"regions-name-assembly", 0, 1}};
   auto regions_flag = [&](const char* flag) {
@@ -249,6 +254,8 @@ static Options parse_args(int argc, char** argv) {
     else if (name == "ref-stats-mode") { o.ref_stats_mode = to_i(name, v); if (!o.ref_stats_flag) o.ref_stats_flag = "--ref-stats-mode"; }
     else if (name == "ref-stats-min-hic-ureads-qcov") { o.ref_stats_h = to_f(name, v); o.ref_stats_h_given = true; if (!o.ref_stats_flag) o.ref_stats_flag = "--ref-stats-min-hic-ureads-qcov"; }
     else if (name == "ref-stats-min-chunks-fraction") { o.ref_stats_p = to_f(name, v); o.ref_stats_p_given = true; if (!o.ref_stats_flag) o.ref_stats_flag = "--ref-stats-min-chunks-fraction"; }
+    else if (name == "ref-stats-cooccur") { o.ref_stats_cooccur = v; if (!o.ref_stats_flag) o.ref_stats_flag = "--ref-stats-cooccur"; }
+    else if (name == "ref-stats-cooccur-slots") { o.ref_stats_cooccur_slots = to_i(name, v); if (!o.ref_stats_flag) o.ref_stats_flag = "--ref-stats-cooccur-slots"; }
     else if (name == "ref-stats-level") { o.ref_stats_level = v; for (char& c : o.ref_stats_level) c = (char)tolower((unsigned char)c); if (!o.ref_stats_flag) o.ref_stats_flag = "--ref-stats-level"; }
     else if (name == "specific-level") { o.specific_level = v; for (char& c : o.specific_level) c = (char)tolower((unsigned char)c); }
     else if (name == "taxdump") o.taxdump = v;
@@ -515,6 +522,13 @@ static int validate_flags(const Options& o, bool sliding) {
     if (o.taxid_maps.empty() && !o.taxdump.empty()) die("flag --taxid-map is needed when --taxdump given");
     if (lv == "species" && !both) die("TaxID mapping files (--taxid-map) and taxonomy dump files (--taxdump) are needed for --ref-stats-level species");
     if (o.ref_stats == o.out_file) die("flag --ref-stats: the statistics file must not be the search result's file");
+    if (o.ref_stats_cooccur.empty() && o.ref_stats_cooccur_slots != 0) die("flag --ref-stats-cooccur-slots is only used with --ref-stats-cooccur");
+    if (!o.ref_stats_cooccur.empty()) {
+      if (o.ref_stats_cooccur == o.out_file) die("flag --ref-stats-cooccur: the pairs' file must not be the search result's file");
+      if (o.ref_stats_cooccur == o.ref_stats) die("flag --ref-stats-cooccur: the pairs' file must not be the statistics file (--ref-stats)");
+      const long long n = o.ref_stats_cooccur_slots;
+      if (n < 0 || (n & (n - 1)) || n > (1ll << 30)) die("the value of --ref-stats-cooccur-slots (%lld) should be a power of two, at most 2^30", n);
+    }
   }
   // sliding windows: seqkit sliding has no meaning for pairs, whole files as queries or one ID for everything
   if (sliding) {
@@ -1042,7 +1056,17 @@ static void set_ref_stats(const Options& o, kmcpg_db* db, const std::vector<std:
 
 // ... and the file, once every batch has been waited for: kmcp-refstats' format (cli/kmcp_refstats.cpp), the references by name, each from
 // the counters of its columns (kmcp_amd/csrc/refstats_rule.hpp); returns the references written
-static uint64_t write_ref_stats(const Options& o, kmcpg_db* db, const std::vector<std::string>& target, uint64_t* reruns) {
+static void write_file(const std::string& path, const std::string& s) {
+  if (path.size() > 3 && path.compare(path.size() - 3, 3, ".gz") == 0) {
+    gzFile f = gzopen(path.c_str(), "wb");
+    if (!f || (!s.empty() && gzwrite(f, s.data(), (unsigned)s.size()) != (int)s.size()) || gzclose(f) != Z_OK) die("%s: write error", path.c_str());
+  } else {
+    FILE* f = path == "-" ? stdout : fopen(path.c_str(), "wb");
+    if (!f || fwrite(s.data(), 1, s.size(), f) != s.size() || (f == stdout ? fflush(f) : fclose(f)) != 0) die("%s: write error", path.c_str());
+  }
+}
+// kept: the references with the verdict ok (what stage 2 looks at)
+static uint64_t write_ref_stats(const Options& o, kmcpg_db* db, const std::vector<std::string>& target, uint64_t* reruns, std::set<std::string>* kept) {
   const uint32_t n_cols = (uint32_t)target.size();
   std::vector<kmcpg_col_stats> cols(n_cols);
   kmcpg_refstats_totals tot;
@@ -1081,6 +1105,7 @@ static uint64_t write_ref_stats(const Options& o, kmcpg_db* db, const std::vecto
     s.append(line, (size_t)snprintf(line, sizeof line, "\t%llu\t%llu\t%llu\t%llu\t%llu\t%.4f\t%s", (unsigned long long)r.chunks, (unsigned long long)r.tlen,
                                     (unsigned long long)t.reads, (unsigned long long)t.ureads, (unsigned long long)t.hic_ureads, t.chunks_frac,
                                     kmcpg::refstats_verdict_name(t.verdict)));
+    if (t.verdict == kmcpg::REFSTATS_OK) kept->insert(kv.first);
     for (int j = 0; j < kmcpg::REFSTATS_WORDS; j++)
       for (uint64_t c = 0; c < r.chunks; c++) {
         s.push_back(c ? ',' : '\t');
@@ -1088,15 +1113,44 @@ static uint64_t write_ref_stats(const Options& o, kmcpg_db* db, const std::vecto
       }
     s.push_back('\n');
   }
-  const std::string& path = o.ref_stats;
-  if (path.size() > 3 && path.compare(path.size() - 3, 3, ".gz") == 0) {
-    gzFile f = gzopen(path.c_str(), "wb");
-    if (!f || (!s.empty() && gzwrite(f, s.data(), (unsigned)s.size()) != (int)s.size()) || gzclose(f) != Z_OK) die("%s: write error", path.c_str());
-  } else {
-    FILE* f = path == "-" ? stdout : fopen(path.c_str(), "wb");
-    if (!f || fwrite(s.data(), 1, s.size(), f) != s.size() || (f == stdout ? fflush(f) : fclose(f)) != 0) die("%s: write error", path.c_str());
-  }
+  write_file(o.ref_stats, s);
   return refs.size();
+}
+
+// --ref-stats-cooccur: the library's stage — a class per printed target, whatever the level (a pair is a pair of references) ...
+static std::vector<std::string> set_cooccur(const Options& o, kmcpg_db* db, const std::vector<std::string>& target) {
+  std::vector<uint32_t> cls;
+  uint64_t unknown = 0;
+  std::string missing;
+  kmcpg::specific_classes(target, nullptr, nullptr, &cls, nullptr, &unknown, &missing);
+  std::vector<std::string> name_of;  // by class
+  for (size_t c = 0; c < cls.size(); c++) {
+    if (cls[c] >= name_of.size()) name_of.resize((size_t)cls[c] + 1);
+    name_of[cls[c]] = target[c];
+  }
+  if (kmcpg_set_cooccur(db, cls.data(), (uint32_t)cls.size(), (uint64_t)o.ref_stats_cooccur_slots) != 0) die("%s", kmcpg_last_error());
+  return name_of;
+}
+// ... and the file, once every batch has been waited for and the verdicts are known: kmcp-refstats --cooccur's format; every pair was
+// counted in the one pass, and the pairs of two kept references are written (with -f 1 -t 0 and no cuts that equals the two passes of the
+// TSV route: skipping a dropped target's rows only takes the target out of a query's set).  Returns the pairs written
+static uint64_t write_cooccur(const Options& o, kmcpg_db* db, const std::vector<std::string>& name_of, const std::set<std::string>& kept, kmcpg_cooccur_totals* tot) {
+  uint64_t n = 0;
+  if (kmcpg_cooccur_read(db, nullptr, 0, &n, tot) != 0) die("%s", kmcpg_last_error());
+  std::vector<kmcpg_cooccur_pair> pairs(n);
+  if (kmcpg_cooccur_read(db, pairs.data(), n, &n, tot) != 0) die("%s", kmcpg_last_error());
+  std::vector<std::pair<std::pair<const std::string*, const std::string*>, uint64_t>> rows;
+  for (const kmcpg_cooccur_pair& pr : pairs) {
+    const std::string *a = &name_of[pr.class_a], *b = &name_of[pr.class_b];
+    if (!kept.count(*a) || !kept.count(*b)) continue;
+    if (*b < *a) std::swap(a, b);
+    rows.push_back({{a, b}, pr.reads});
+  }
+  std::sort(rows.begin(), rows.end(), [](const auto& x, const auto& y) { return *x.first.first != *y.first.first ? *x.first.first < *y.first.first : *x.first.second < *y.first.second; });
+  std::string s = "# pairs: " + std::to_string(rows.size()) + "\n#refA\trefB\treads\n";
+  for (const auto& r : rows) s += *r.first.first + "\t" + *r.first.second + "\t" + std::to_string(r.second) + "\n";
+  write_file(o.ref_stats_cooccur, s);
+  return rows.size();
 }
 
 static kmcpg_params make_params(const Options& o, int sort_by, bool paired) {
@@ -1535,6 +1589,8 @@ int main(int argc, char** argv) {
   p.params = make_params(o, sort_by, paired);
   if (!o.specific_level.empty()) set_specific(o, p.db, p.target, taxonomy.get(), taxid_map.get());
   if (!o.ref_stats.empty()) set_ref_stats(o, p.db, p.target, taxonomy.get(), taxid_map.get());
+  std::vector<std::string> cooccur_names;
+  if (!o.ref_stats_cooccur.empty()) cooccur_names = set_cooccur(o, p.db, p.target);
 
   p.t_search = Clock::now();
   Out out(p.regions() ? o.regions_bed : o.out_file);
@@ -1572,10 +1628,18 @@ int main(int argc, char** argv) {
   }
   if (!o.ref_stats.empty()) {
     uint64_t reruns = 0;
-    const uint64_t n_refs = write_ref_stats(o, p.db, p.target, &reruns);
+    std::set<std::string> kept;
+    const uint64_t n_refs = write_ref_stats(o, p.db, p.target, &reruns, &kept);
     if (!o.quiet)
       info("reference statistics (mode %d, level %s): %llu references saved to: %s (%llu batches counted by their rerun after a hit-buffer overflow)", o.ref_stats_mode,
            ref_stats_species(o) ? "species" : "strain", (unsigned long long)n_refs, o.ref_stats.c_str(), (unsigned long long)reruns);
+    if (!o.ref_stats_cooccur.empty()) {
+      kmcpg_cooccur_totals tot;
+      const uint64_t n_pairs = write_cooccur(o, p.db, cooccur_names, kept, &tot);
+      if (!o.quiet)
+        info("shared reads of reference pairs: %llu pairs of kept references saved to: %s (%llu reads with several targets, %llu of them counted on the host, %llu for want of room in the table)",
+             (unsigned long long)n_pairs, o.ref_stats_cooccur.c_str(), (unsigned long long)tot.multi_reads, (unsigned long long)tot.host_reads, (unsigned long long)tot.left_full);
+    }
   }
   // Everything the user asked for is on disk.  Giving back pinned staging buffers, streams and a resident index one by one takes
   // ~0.1 s and the runtime's own exit handlers as long again (profiles/r06_cli_e2e.txt) — a short-lived process leaves that to the

@@ -496,6 +496,64 @@ int kmcpg_refstats_read(kmcpg_db* db, kmcpg_col_stats* out, uint32_t n_cols, kmc
 int kmcpg_refstats_reset(kmcpg_db* db);
 int kmcpg_last_refstats(kmcpg_db* db, kmcpg_refstats_stats* out, kmcpg_k4_launch* launches, uint32_t cap, uint32_t* n_launches);
 
+/* -- shared reads of reference pairs (K7, k7_cooccur.hip): what stage 2/4 of `kmcp profile` counts (kmcp/cmd/profile.go:1117-1279;
+ *    kmcp_amd/csrc/cooccur_rule.hpp states the rule), on K3's output while it is in device memory.  A pair is an unordered pair of printed
+ *    targets (target_class: chunks of one genome are one target, as for kmcpg_set_refstats); its count is the number of queries whose
+ *    final matches name both.  The stage does NOT filter: the result of every call is byte for byte what it is with the stage off.
+ *    kmcpg_set_cooccur uploads its own copy of the class table and allocates the zeroed pair table (open-addressed in device memory, 16
+ *    bytes per slot; table_slots must be a power of two up to 2^30, 0 = the default of 2^21 slots, 32 MiB); it is independent of
+ *    kmcpg_set_refstats and kmcpg_set_specific, and (NULL, 0, 0) switches it off and frees everything.  KMCPG_EUNSUPPORTED as for
+ *    kmcpg_set_refstats: paged, multi-device and sharded handles; while the stage is on, batches with try_se, top_n_scores != 0 or several
+ *    k-mer sizes with k == 0, and every window submit.
+ *    While the stage is on, every batch of kmcpg_submit / kmcpg_search_batch (and their _pairs / _packed forms) is counted: on the device
+ *    behind K3 — as the batch's last kernel, after K4 and K6 where those are on — for the reads whose matches are final there, by the
+ *    host half at wait time, into a host map, for the others (queries of more k-mers than the device's -f bound covers, segments above
+ *    4096 pairs, several targets among more than 64 pairs, reads whose pairs found no room in the table; KMCPG_COOCCUR_DEVICE=0 or
+ *    KMCPG_DEVICE_FINALIZE=0: every read) — its own -f test first, then the same rule.  A read is counted completely or not at all: a
+ *    full table never loses or half-counts one (it goes to the host half).  The table does not grow; size it with table_slots.  A batch
+ *    that is run again because its hit buffer overflowed is counted once.
+ *    kmcpg_cooccur_read waits for the device and merges the device slots with a count > 0 and the host map: n_pairs records sorted by
+ *    (class_a, class_b), class_a < class_b, the first `cap` of them in out_pairs (cap too small: *n_pairs says how many there are, and
+ *    the call can be repeated).  Valid once every ticket has been waited for.  KMCPG_EDEVICE if a batch failed after its reads had been
+ *    counted, or a kmcpg_search_batch call's pieces failed part of the way (call kmcpg_cooccur_reset).  totals may be NULL.
+ *    kmcpg_cooccur_device runs K7 alone on device pointers, as kmcpg_refstats_device runs K6: d_left[i] = 1 for the reads it does not
+ *    count (n_reads bytes).  d_n_hits may be NULL; otherwise the launch counts nothing when *d_n_hits > hit_cap.  max_wgs: 0 = the
+ *    handle's (two workgroups per CU), fewer to force grid-stride rounds.  Only enqueues on `stream`.
+ *    kmcpg_last_cooccur: the witness of the handle's last K7 launch (the call waits for the device to go idle; one set of witness words
+ *    per handle, zeroed by every launch: meaningful only with ONE batch in flight).  KMCPG_COOCCUR_SLOTS (read by kmcpg_set_cooccur):
+ *    slots of a workgroup's LDS table, a power of two up to 4096 (anything else is KMCPG_EINVAL), 0 = no LDS table; default 2048. */
+typedef struct {
+  uint32_t class_a, class_b;  /* class_a < class_b */
+  uint64_t reads;
+} kmcpg_cooccur_pair;
+typedef struct {
+  uint64_t multi_reads;              /* queries with several targets, counted by either half */
+  uint64_t device_adds, host_adds;   /* pair adds (one per read and pair) by the device and by the host half */
+  uint64_t left_full;                /* reads the device left to the host because their pairs found no room in the table */
+  uint64_t host_reads;               /* of multi_reads, counted by the host half */
+  uint64_t skipped_launches;         /* K7 launches that counted nothing because the batch's hit buffer had overflowed (the rerun counted) */
+  uint64_t table_slots, keys;        /* the table's size, and its keys (with any count) */
+  uint64_t rebuilds;                 /* always 0: the table does not grow */
+} kmcpg_cooccur_totals;
+enum { KMCPG_K7_COOCCUR = 48 };  /* kmcpg_k4_launch.kernel of K7's kernel */
+typedef struct {
+  uint64_t empty, single, wave, left;            /* reads by the class they took; the four add up to the reads */
+  uint64_t left_full;                            /* of left: no room in the table */
+  uint64_t pairs;                                /* pairs enumerated (of the reads counted) = lds_adds + the adds straight to global memory */
+  uint64_t lds_adds, global_adds, spilled_adds;  /* global_adds: table flushes and adds past the LDS table; spilled_adds: of those, past a FULL LDS table */
+  uint64_t claimed;                              /* keys claimed in the table in device memory */
+  uint64_t skipped;                              /* 1: the overflow guard skipped the launch */
+  uint64_t bad_segments;
+  uint32_t grid, slots;
+  double k7_ms;                                  /* HIP-event time of the kernel at profiling level >= 1; -1 otherwise */
+} kmcpg_cooccur_stats;
+int kmcpg_set_cooccur(kmcpg_db* db, const uint32_t* target_class, uint32_t n_cols, uint64_t table_slots);
+int kmcpg_cooccur_device(kmcpg_db* db, const kmcpg_pair* d_pairs, const uint64_t* d_read_offs, uint64_t pair_cap, const int32_t* d_qkmers,
+                         uint32_t n_reads, int32_t final_n, const uint64_t* d_n_hits, uint64_t hit_cap, uint8_t* d_left, uint32_t max_wgs, void* stream);
+int kmcpg_cooccur_read(kmcpg_db* db, kmcpg_cooccur_pair* out_pairs, uint64_t cap, uint64_t* n_pairs, kmcpg_cooccur_totals* totals);
+int kmcpg_cooccur_reset(kmcpg_db* db);
+int kmcpg_last_cooccur(kmcpg_db* db, kmcpg_cooccur_stats* out, kmcpg_k4_launch* launches, uint32_t cap, uint32_t* n_launches);
+
 /* -- benchmarking / full-size parity support (no counterpart in the reference) ------------------ */
 typedef struct {
   int32_t k;            /* 21 */

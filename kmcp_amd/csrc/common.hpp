@@ -280,5 +280,37 @@ struct K6Args {
   unsigned long long* stats;           // [K6_STATS], zero on entry
 };
 
+// K7 (k7_cooccur.hip): K3's segments -> the reads shared by every pair of targets, the counts of stage 2 of `kmcp profile` (cooccur_rule.hpp:
+// the key, the table's probe sequence, the two phases); the reads it cannot count exactly are LEFT to the host (a byte per read).
+constexpr uint32_t K7_CAP = 64;  // longest segment of several targets the device counts
+constexpr uint32_t K7_MAX_SLOTS = 4096, K7_DEFAULT_SLOTS = 2048;  // the workgroup's table in LDS: 12 bytes per slot
+constexpr uint64_t K7_DEFAULT_TABLE = 1ull << 21, K7_MAX_TABLE = 1ull << 30;  // the table in HBM: 16 bytes per slot
+// the witness: reads empty / single target / by the wave (counted) / LEFT, of those LEFT because the table was full; pairs enumerated (of
+// the counted reads), adds to LDS / to global memory (flushes and adds past the LDS table) / of those the ones past a full LDS table, keys
+// claimed in HBM, launches the overflow guard skipped, segments outside the buffer
+enum { K7_EMPTY = 0, K7_SINGLE, K7_WAVE, K7_LEFT, K7_LEFT_FULL, K7_PAIRS, K7_LDS_ADDS, K7_GLOBAL_ADDS, K7_SPILLED, K7_CLAIMED, K7_SKIPPED, K7_BAD, K7_STATS };
+// the totals that persist beside the table: reads with several targets counted here, their pairs, reads LEFT because the table was full,
+// launches the guard skipped
+enum { K7_T_MULTI = 0, K7_T_PAIRS, K7_T_LEFT_FULL, K7_T_SKIPPED, K7_TOTALS };
+struct K7Args {
+  const kmcpg_pair* pairs;             // K3's output
+  const uint64_t* offs;                // [n_reads + 1]
+  uint64_t pair_cap;                   // pairs there is room for behind `pairs`: a segment that ends behind it is treated as empty
+  const int32_t* nk;                   // NumKmers per read
+  uint32_t n_reads;
+  uint32_t n_cols;
+  int32_t final_n;                     // reads of more k-mers are LEFT (their pairs may still fall to -f on the host)
+  uint32_t slots;                      // LDS table slots per workgroup: a power of two up to K7_MAX_SLOTS, or 0 = every add goes to global memory
+  const uint32_t* target_class;        // [n_cols]
+  const unsigned long long* n_hits;    // device word or nullptr: the batch's hit counter ...
+  uint64_t hit_cap;                    // ... above this the batch will be run again: nothing is counted now
+  unsigned long long* keys;            // [table_slots] pair keys, 0 = empty (cooccur_rule.hpp)
+  unsigned long long* counts;          // [table_slots]
+  uint64_t table_slots;                // a power of two
+  unsigned long long* totals;          // [K7_TOTALS]
+  uint8_t* left;                       // out [n_reads]: 1 = LEFT to the host
+  unsigned long long* stats;           // [K7_STATS], zero on entry
+};
+
 
 }  // namespace kmcpg

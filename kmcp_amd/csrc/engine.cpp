@@ -839,6 +839,10 @@ extern "C" int kmcpg_close(kmcpg_db* db) {
   if (db->d_rs_species) (void)hipFree(db->d_rs_species);
   if (db->d_rs_counters) (void)hipFree(db->d_rs_counters);
   if (db->d_rs_stats) (void)hipFree(db->d_rs_stats);
+  for (void* q : {(void*)db->d_co_target, (void*)db->d_co_keys, (void*)db->d_co_counts, (void*)db->d_co_totals, (void*)db->d_co_stats})
+    if (q) (void)hipFree(q);
+  for (auto& ev : db->co_ev)
+    if (ev) (void)hipEventDestroy(ev);
   for (auto& ev : db->rs_ev)
     if (ev) (void)hipEventDestroy(ev);
   kmcpg::release_fpr_bounds(db);

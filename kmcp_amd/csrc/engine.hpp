@@ -13,6 +13,7 @@
 #include <memory>
 #include <mutex>
 #include <string>
+#include <unordered_map>
 #include <vector>
 
 #include "../../include/kmcp_gpu.h"
@@ -267,6 +268,28 @@ struct kmcpg_db {
   hipEvent_t rs_ev[2] = {};
   bool rs_timed = false;
   std::vector<kmcpg_k4_launch> k6_log;
+  // K7, the shared reads of reference pairs behind K3 (kmcpg_set_cooccur; k7_cooccur.hip, cooccur.cpp): a class table of its own, the
+  // open-addressed pair table in HBM (keys, counts: co_table slots each, a power of two), the totals that persist beside it, the witness
+  // words of the last launch, and the host half's map (key of cooccur_rule.hpp -> reads: the reads the device LEFT, and every read of a
+  // batch that did not go through K3; under co_mu)
+  uint32_t* d_co_target = nullptr;
+  std::vector<uint32_t> h_co_target;
+  bool cooccur_on() const { return !h_co_target.empty(); }
+  unsigned long long* d_co_keys = nullptr;    // [co_table]
+  unsigned long long* d_co_counts = nullptr;  // [co_table]
+  unsigned long long* d_co_totals = nullptr;  // [K7_TOTALS]
+  unsigned long long* d_co_stats = nullptr;   // [K7_STATS]
+  uint64_t co_table = 0;
+  uint32_t co_slots = 0;                      // KMCPG_COOCCUR_SLOTS, read when the stage is set
+  unsigned co_max_wgs = 0, co_grid = 0;
+  std::mutex co_mu;
+  std::unordered_map<uint64_t, uint64_t> h_co_pairs;
+  uint64_t h_co_multi = 0, h_co_adds = 0;
+  bool co_tainted = false;  // a batch failed after its reads were counted
+  bool co_ran = false;      // a K7 launch since the stage was set
+  hipEvent_t co_ev[2] = {};
+  bool co_timed = false;
+  std::vector<kmcpg_k4_launch> k7_log;
   std::vector<kmcpg::FprBoundTable> fpr_bounds;  // -f bound tables (query.cpp fpr_bound): one per (max_fpr, size), never rewritten
   hipEvent_t ev[16] = {};   // ring of 4 calls x (start, COBS start, COBS done, k-mers done)
   uint64_t ev_calls = 0;    // profiled calls so far
@@ -288,7 +311,7 @@ inline int set_refuse_entry(const kmcpg_db* db, const char* entry) {
   return kmcpg_fail(KMCPG_EUNSUPPORTED, "database set (%zu members): %s is not supported on a set handle", db->set_col_base.size(), entry);
 }
 
-// The stages behind K3 that need a query's matches from EVERY block (K4 / K5: specific.cpp, K6: refstats.cpp) refuse the handles that
+// The stages behind K3 that need a query's matches from EVERY block (K4 / K5: specific.cpp, K6: refstats.cpp, K7: cooccur.cpp) refuse the handles that
 // search the index in parts.  "<refused> are not supported on <the handle>: <why>"
 inline int refuse_handle(const kmcpg_db* db, const char* refused, const char* why) {
   const char* what = db->paged_passes > 0 ? "a paged handle (kmcpg_open_paged)"
@@ -372,6 +395,18 @@ inline int refstats_refuse_entry(const kmcpg_db* db, const char* entry) {
   return kmcpg_fail(KMCPG_EUNSUPPORTED, "reference statistics (kmcpg_set_refstats): %s is not supported while the stage is on", entry);
 }
 
+// The shared reads of reference pairs (kmcpg_set_cooccur): what K6 refuses, for the same reason
+inline int cooccur_refuse_params(const kmcpg_db* db, const kmcpg_params& p) {
+  if (!db->cooccur_on()) return 0;
+  const char* what = p.try_se ? "try_se" : (p.top_n_scores != 0 ? "top_n_scores != 0" : (p.k == 0 && db->ks_desc.size() > 1 ? "a database with several k-mer sizes searched with params->k == 0" : nullptr));
+  if (!what) return 0;
+  return kmcpg_fail(KMCPG_EUNSUPPORTED, "shared reads of reference pairs (kmcpg_set_cooccur): %s is not supported — switch the stage off, or count the results with kmcp-refstats --cooccur", what);
+}
+inline int cooccur_refuse_entry(const kmcpg_db* db, const char* entry) {
+  if (!db->cooccur_on()) return 0;
+  return kmcpg_fail(KMCPG_EUNSUPPORTED, "shared reads of reference pairs (kmcpg_set_cooccur): %s is not supported while the stage is on", entry);
+}
+
 inline kmcpg_params default_params() {
   kmcpg_params p{};
   p.min_qlen = 30;
@@ -447,6 +482,14 @@ void refstats_host_result(kmcpg_db* db, const kmcpg_result* out);
 // K6 behind K3 for a lane's batch (refstats.cpp): what kmcpg_refstats_device does, without the public entry's argument checks
 int refstats_enqueue(kmcpg_db* db, const kmcpg_pair* d_pairs, const uint64_t* d_read_offs, uint64_t pair_cap, const int32_t* d_qkmers, uint32_t n_reads,
                      int32_t final_n, const uint64_t* d_n_hits, uint64_t hit_cap, uint8_t* d_left, hipStream_t st);
+// The host half of K7 (cooccur.cpp), as K6's: the reads of a batch the device LEFT (left == nullptr: every read), from K3's pairs — the
+// host's own tests first, then the rule of cooccur_rule.hpp into the handle's host map; and every read of a finished result of records.
+int cooccur_host_batch(kmcpg_db* db, const kmcpg_pair* pairs, const uint64_t* read_offs, const int32_t* qkmers, uint32_t n_reads, const kmcpg_params& p,
+                       const uint8_t* left);
+void cooccur_host_result(kmcpg_db* db, const kmcpg_result* out);
+// K7 behind K3 for a lane's batch (cooccur.cpp): what kmcpg_cooccur_device does, without the public entry's argument checks (max_wgs 0: the handle's)
+int cooccur_enqueue(kmcpg_db* db, const kmcpg_pair* d_pairs, const uint64_t* d_read_offs, uint64_t pair_cap, const int32_t* d_qkmers, uint32_t n_reads,
+                    int32_t final_n, const uint64_t* d_n_hits, uint64_t hit_cap, uint8_t* d_left, unsigned max_wgs, hipStream_t st);
 // bound_n: what the kmcpg_query_device call(s) that produced the list actually did — every query of up to bound_n k-mers had the -f bound
 // applied on the device, whichever kernel form served it (0: no bound table in that call).  query_device_after reports the value of its
 // call; lane.cpp keeps it with the batch (Lane::bound_n) and hands it to the finalizer, which takes a compact segment as final only for

@@ -31,6 +31,7 @@
 #include "dbformat.hpp"
 #include "engine.hpp"
 #include "specific_rule.hpp"
+#include "cooccur_rule.hpp"
 #include "refstats_rule.hpp"
 #include "match_rule.hpp"
 #include "fpr.hpp"
@@ -758,6 +759,60 @@ void refstats_host_result(kmcpg_db* db, const kmcpg_result* out) {
   std::vector<RefstatsRow> rows;
   for (uint32_t r = 0; r < out->n_reads; r++)
     refstats_count_rows(db, o->matches.data() + o->offs[r], o->offs[(size_t)r + 1] - o->offs[r], o->qkmers[r], rows);
+}
+
+// ---- the host half of K7 (k7_cooccur.hip): cooccur_rule.hpp on the reads the device does not count
+namespace {
+// one query's final rows' targets (cls: scratch of the caller, n >= 1) -> the handle's host map
+void cooccur_count_targets(kmcpg_db* db, std::vector<uint32_t>& cls) {
+  if (cls.size() < 2) return;
+  std::lock_guard<std::mutex> g(db->co_mu);
+  uint64_t adds = 0;
+  const size_t m = cooccur_query_pairs(cls.data(), cls.size(), [&](uint64_t key) { db->h_co_pairs[key]++, adds++; });
+  if (m > 1) db->h_co_multi++;
+  db->h_co_adds += adds;
+}
+}  // namespace
+
+int cooccur_host_batch(kmcpg_db* db, const kmcpg_pair* pairs, const uint64_t* read_offs, const int32_t* qkmers, uint32_t n_reads, const kmcpg_params& p,
+                       const uint8_t* left) {
+  if (!db->cooccur_on()) return 0;
+  const size_t n_cols = db->col_meta.size();
+  const uint64_t n_pairs = read_offs[n_reads];
+  std::vector<uint32_t> cls;
+  FprRow row;
+  int row_n = -1;
+  const auto fpr_of = [&](int n2, int k) { return QueryFpr::value(*row, n2, k); };
+  for (uint32_t r = 0; r < n_reads; r++) {
+    if (left && !left[r]) continue;
+    const uint64_t s0 = read_offs[r], s1 = read_offs[r + 1];
+    if (s1 == s0) continue;
+    if (s1 < s0 || s1 > n_pairs) return kmcpg_fail(KMCPG_EINVAL, "grouped hit list: offsets out of range");
+    const int n = qkmers[r];
+    if (n > 0 && n != row_n) {
+      row_n = n;
+      row = db->fpr->ensure_row(n);
+    }
+    cls.clear();
+    for (uint64_t i = s0; i < s1; i++) {  // (a set of targets: the order of the rows does not matter)
+      if (pairs[i].col >= n_cols) return kmcpg_fail(KMCPG_EINVAL, "grouped hit list: columns out of range");
+      kmcpg_match mm;
+      if (match_accept(pairs[i].col, (int)pairs[i].count, n, db->col_meta[pairs[i].col], p, fpr_of, &mm)) cls.push_back(db->h_co_target[pairs[i].col]);
+    }
+    cooccur_count_targets(db, cls);
+  }
+  return 0;
+}
+
+void cooccur_host_result(kmcpg_db* db, const kmcpg_result* out) {
+  const ResultOwner* o = (const ResultOwner*)out->owner;
+  if (!o || !db->cooccur_on() || o->pairs_mode) return;
+  std::vector<uint32_t> cls;
+  for (uint32_t r = 0; r < out->n_reads; r++) {
+    cls.clear();
+    for (uint64_t i = o->offs[r]; i < o->offs[(size_t)r + 1]; i++) cls.push_back(db->h_co_target[o->matches[i].col]);
+    cooccur_count_targets(db, cls);
+  }
 }
 
 // counts in o->offs[1 ..] -> offsets, and the result's pointers

@@ -166,6 +166,7 @@ int finish_raw(kmcpg_ticket* t, kmcpg_result* out, bool as_pairs) {
   int rcf = kmcpg_finalize(t->db, hits, n_hits, t->n ? L0->h_qk.p : nullptr, t->n ? L0->h_ql.p : nullptr, t->n, &t->p, out);
   // the reference statistics without K3 in front of them (KMCPG_DEVICE_FINALIZE=0): every read, from the finished (unfiltered) records
   if (rcf == 0 && t->db->refstats_on()) refstats_host_result(t->db, out);
+  if (rcf == 0 && t->db->cooccur_on()) cooccur_host_result(t->db, out);  // ... and the shared reads of reference pairs likewise
   // the species-specific stage without K3 in front of it (KMCPG_DEVICE_FINALIZE=0): the rule on the finished records
   if (rcf == 0 && t->db->spec_on()) specific_filter_result(t->db, out);
   return rcf;
@@ -455,6 +456,7 @@ int submit_handle(kmcpg_db* db, const kmcpg_params* params, kmcpg_params* p) {
   if (p->min_matched < 1) return kmcpg_fail(KMCPG_EINVAL, "min_matched must be >= 1");
   if (int rcs = specific_refuse_params(db, *p)) return rcs;
   if (int rcs = refstats_refuse_params(db, *p)) return rcs;
+  if (int rcs = cooccur_refuse_params(db, *p)) return rcs;
   return set_refuse_params(db, *p);
 }
 
@@ -608,6 +610,7 @@ static int search_batch_impl(kmcpg_db* db, const HostBatch& in, const kmcpg_para
     if (int rcs = set_refuse_params(db, pp)) return rcs;
     if (int rcs = specific_refuse_params(db, pp)) return rcs;
     if (int rcs = refstats_refuse_params(db, pp)) return rcs;
+    if (int rcs = cooccur_refuse_params(db, pp)) return rcs;
     if (pp.min_matched >= 1 && in.offs[0] == 0 && (!in.offs2 || in.offs2[0] == 0)) rc = search_batch_pieces(db, in, pp, as_pairs, out, &took);
   }
   if (took && rc == 0) return 0;
@@ -616,6 +619,10 @@ static int search_batch_impl(kmcpg_db* db, const HostBatch& in, const kmcpg_para
     // hold those reads twice (kmcpg_refstats_read refuses until kmcpg_refstats_reset)
     std::lock_guard<std::mutex> g(db->rs_mu);
     db->rs_tainted = true;
+  }
+  if (took && db->cooccur_on()) {  // ... and so would K7's table (kmcpg_cooccur_read refuses until kmcpg_cooccur_reset)
+    std::lock_guard<std::mutex> g(db->co_mu);
+    db->co_tainted = true;
   }
   if (took) memset(out, 0, sizeof *out);
   if (!took || rc == KMCPG_ENOMEM) {

@@ -297,7 +297,7 @@ int enqueue_query(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p, c
     rc = kmcpg_group_device(db, L->d_hits.p, L->d_cnt.p, L->d_hits.cap, L->d_qk.p, L->n, &p, L->d_pairs.p, L->d_roffs.p, st);
     if (rc) return rc;
     L->spec = db->spec_on();
-    L->rs = false;  // (a lane keeps its fields from batch to batch: the summary path below returns before K6's turn)
+    L->rs = L->co = false;  // (a lane keeps its fields from batch to batch: the summary path below returns before K6's and K7's turn)
     // (a batch K5 summarises needs K3's last two words only: the pairs it kept, and its count of bad hits)
     const size_t skip = L->summarized() ? L->n : 0;
     HIPCHK(hipMemcpyAsync(L->h_roffs.p + skip, L->d_roffs.p + skip, ((size_t)L->n + 2 - skip) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
@@ -327,6 +327,9 @@ int enqueue_query(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p, c
       HIPCHK(hipMemcpyAsync(L->h_verd.p, L->d_verd.p, (size_t)L->n, hipMemcpyDeviceToHost, st));
     }
     L->rs = db->refstats_on();
+    L->co = db->cooccur_on();
+    // (K7's buffers before K6 runs: K6 must stay the last step BEFORE any counting that can fail for want of memory — see below)
+    if (L->co && (L->d_left7.ensure(L->n) || L->h_left7.ensure(L->n) || (L->spec && L->h_roffs3.ensure((size_t)L->n + 1)))) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
     if (L->rs) {
       // K6 on K3's output, which K4 leaves where it is (it compacts into d_hits).  The LAST step that can fail for want of memory: a batch
       // that is enqueued again after KMCPG_ENOMEM has not been counted yet.  One whose hit buffer overflowed is not counted either (the
@@ -339,7 +342,17 @@ int enqueue_query(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p, c
       HIPCHK(hipMemcpyAsync(L->h_left.p, L->d_left.p, (size_t)L->n, hipMemcpyDeviceToHost, st));
       if (L->spec) HIPCHK(hipMemcpyAsync(L->h_roffs3.p, L->d_roffs.p, ((size_t)L->n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     }
-  } else L->spec = L->rs = false;
+    if (L->co) {
+      // K7 on K3's output, as K6 and behind it: the batch's last kernel; it allocates nothing (its buffers were made above), so a batch
+      // that is enqueued again after KMCPG_ENOMEM has been counted by neither.  KMCPG_COOCCUR_DEVICE=0: every read goes to the host half
+      const char* e = getenv("KMCPG_COOCCUR_DEVICE");
+      const int32_t final_n = e && atoi(e) == 0 ? -1 : std::min<int32_t>(L->bound_n, kFprBoundAlways);
+      rc = cooccur_enqueue(db, L->d_pairs.p, L->d_roffs.p, L->d_hits.cap, L->d_qk.p, L->n, final_n, L->d_cnt.p, L->d_hits.cap, L->d_left7.p, 0, st);
+      if (rc) return rc;
+      HIPCHK(hipMemcpyAsync(L->h_left7.p, L->d_left7.p, (size_t)L->n, hipMemcpyDeviceToHost, st));
+      if (L->spec && !L->rs) HIPCHK(hipMemcpyAsync(L->h_roffs3.p, L->d_roffs.p, ((size_t)L->n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    }
+  } else L->spec = L->rs = L->co = false;
   return 0;
 }
 
@@ -461,18 +474,21 @@ int enqueue(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p, bool ge
 }
 
 namespace {
-int refstats_collect(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p, bool fetched) {
+// the host half of K6 (k7 = false) or K7 for a finished batch: the reads its kernel LEFT, from K3's pairs
+int left_collect(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p, bool fetched, bool k7) {
+  const uint8_t* left = k7 ? L->h_left7.p : L->h_left.p;
+  const auto host_batch = k7 ? cooccur_host_batch : refstats_host_batch;
   bool any = false;
-  for (uint32_t r = 0; r < L->n && !any; r++) any = L->h_left.p[r] != 0;
+  for (uint32_t r = 0; r < L->n && !any; r++) any = left[r] != 0;
   if (!any) return 0;
-  if (!L->spec && fetched) return refstats_host_batch(db, L->h_pairs.p, L->h_roffs.p, L->h_qk.p, L->n, p, L->h_left.p);
+  if (!L->spec && fetched) return host_batch(db, L->h_pairs.p, L->h_roffs.p, L->h_qk.p, L->n, p, left);
   const uint64_t* offs = L->spec ? L->h_roffs3.p : L->h_roffs.p;
   std::vector<kmcpg_pair, NoInitAlloc<kmcpg_pair>> k3(offs[L->n]);
   if (!k3.empty()) {
     HIPCHK(hipMemcpyAsync(k3.data(), L->d_pairs.p, k3.size() * sizeof(kmcpg_pair), hipMemcpyDeviceToHost, A->copy_stream));
     HIPCHK(hipStreamSynchronize(A->copy_stream));
   }
-  return refstats_host_batch(db, k3.data(), offs, L->h_qk.p, L->n, p, L->h_left.p);
+  return host_batch(db, k3.data(), offs, L->h_qk.p, L->n, p, left);
 }
 }  // namespace
 
@@ -480,14 +496,20 @@ int collect(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p, uint64_
   *n_hits = 0;
   if (L->n == 0) return 0;
   KMCPG_USE_DEVICE(db);
-  struct Taint {  // a batch that fails from here on may have been counted by K6 already, and a caller may search its reads again
+  struct Taint {  // a batch that fails from here on may have been counted by K6 or K7 already, and a caller may search its reads again
     kmcpg_db* db;
     const Lane* L;
     bool ok = false;
     ~Taint() {
-      if (ok || !L->rs || !L->grouped || !db->refstats_on() || L->h_cnt.p[0] > L->d_hits.cap) return;  // (an overflowing attempt was not counted: the kernel's guard)
-      std::lock_guard<std::mutex> g(db->rs_mu);
-      db->rs_tainted = true;
+      if (ok || !L->grouped || L->h_cnt.p[0] > L->d_hits.cap) return;  // (an overflowing attempt was not counted: the kernel's guard)
+      if (L->rs && db->refstats_on()) {
+        std::lock_guard<std::mutex> g(db->rs_mu);
+        db->rs_tainted = true;
+      }
+      if (L->co && db->cooccur_on()) {
+        std::lock_guard<std::mutex> g(db->co_mu);
+        db->co_tainted = true;
+      }
     }
   } taint{db, L};
   HIPCHK(hipEventSynchronize(L->done));
@@ -532,7 +554,11 @@ int collect(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p, uint64_
   }
   if (L->rs && L->grouped && db->refstats_on()) {
     // the host half of K6: the reads the device LEFT, from K3's pairs — which are the lane's result itself, or, behind K4, still in d_pairs
-    int rc = refstats_collect(db, A, L, p, fetch);
+    int rc = left_collect(db, A, L, p, fetch, false);
+    if (rc) return rc;
+  }
+  if (L->co && L->grouped && db->cooccur_on()) {  // ... and of K7
+    int rc = left_collect(db, A, L, p, fetch, true);
     if (rc) return rc;
   }
   // a batch large enough to say something about the data (one genome with 5 000 matches does not)

@@ -83,6 +83,10 @@ struct Lane {
   PinBuf<uint8_t> h_left;
   PinBuf<uint64_t> h_roffs3;
   bool rs = false;  // this batch went through K6
+  // K7 (the shared reads of reference pairs, when the handle has them on): the same, with LEFT bytes of its own
+  DevBuf<uint8_t> d_left7;
+  PinBuf<uint8_t> h_left7;
+  bool co = false;  // this batch went through K7
   bool spec = false;  // this batch went through K4: h_roffs / h_pairs hold ITS output, h_verd the verdicts
   // 2-bit packed upload (stage): the batch's bases as codes + the runs of foreign bytes instead of h_seqs; unpacked on the device
   PinBuf<uint8_t> h_pack;

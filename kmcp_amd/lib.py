@@ -29,6 +29,7 @@ EXPORTS = [
     "kmcpg_set_specific", "kmcpg_specific_device", "kmcpg_last_specific",
     "kmcpg_summarize_device", "kmcpg_last_summary", "kmcpg_submit_windows_summary", "kmcpg_wait_summaries", "kmcpg_result_summaries_free",
     "kmcpg_set_refstats", "kmcpg_refstats_device", "kmcpg_refstats_read", "kmcpg_refstats_reset", "kmcpg_last_refstats",
+    "kmcpg_set_cooccur", "kmcpg_cooccur_device", "kmcpg_cooccur_read", "kmcpg_cooccur_reset", "kmcpg_last_cooccur",
     "kmcpg_sketch_genomes_to", "kmcpg_builder_open", "kmcpg_builder_close", "kmcpg_builder_add_cols", "kmcpg_builder_plan",
     "kmcpg_builder_col_place", "kmcpg_builder_block_info", "kmcpg_builder_begin_round", "kmcpg_builder_scatter_device",
     "kmcpg_builder_end_round", "kmcpg_builder_finish", "kmcpg_builder_info",
@@ -264,6 +265,25 @@ class RefstatsStats(C.Structure):
                 ("grid", C.c_uint32), ("slots", C.c_uint32), ("k6_ms", C.c_double)]
 
 
+COOCCUR_DTYPE = np.dtype([("class_a", "<u4"), ("class_b", "<u4"), ("reads", "<u8")])  # kmcpg_cooccur_pair
+K7_COOCCUR = 48  # KMCPG_K7_COOCCUR: kmcpg_k4_launch.kernel of K7's kernel
+
+
+class CooccurTotals(C.Structure):
+    """kmcpg_cooccur_totals"""
+    _fields_ = [("multi_reads", C.c_uint64), ("device_adds", C.c_uint64), ("host_adds", C.c_uint64), ("left_full", C.c_uint64),
+                ("host_reads", C.c_uint64), ("skipped_launches", C.c_uint64), ("table_slots", C.c_uint64), ("keys", C.c_uint64),
+                ("rebuilds", C.c_uint64)]
+
+
+class CooccurStats(C.Structure):
+    """kmcpg_cooccur_stats: the witness of the last K7 launch"""
+    _fields_ = [("empty", C.c_uint64), ("single", C.c_uint64), ("wave", C.c_uint64), ("left", C.c_uint64), ("left_full", C.c_uint64),
+                ("pairs", C.c_uint64), ("lds_adds", C.c_uint64), ("global_adds", C.c_uint64), ("spilled_adds", C.c_uint64),
+                ("claimed", C.c_uint64), ("skipped", C.c_uint64), ("bad_segments", C.c_uint64), ("grid", C.c_uint32), ("slots", C.c_uint32),
+                ("k7_ms", C.c_double)]
+
+
 class ResultSummaries(C.Structure):
     """kmcpg_result_summaries"""
     _fields_ = [("n_windows", C.c_uint32), ("reserved", C.c_uint32), ("qlen", C.POINTER(C.c_int32)), ("qkmers", C.POINTER(C.c_int32)),
@@ -447,6 +467,11 @@ def load():
     L.kmcpg_refstats_read.argtypes = [vp, vp, C.c_uint32, C.POINTER(RefstatsTotals)]
     L.kmcpg_refstats_reset.argtypes = [vp]
     L.kmcpg_last_refstats.argtypes = [vp, C.POINTER(RefstatsStats), C.POINTER(K4Launch), C.c_uint32, C.POINTER(C.c_uint32)]
+    L.kmcpg_set_cooccur.argtypes = [vp, vp, C.c_uint32, C.c_uint64]
+    L.kmcpg_cooccur_device.argtypes = [vp, vp, vp, C.c_uint64, vp, C.c_uint32, C.c_int32, vp, C.c_uint64, vp, C.c_uint32, vp]
+    L.kmcpg_cooccur_read.argtypes = [vp, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(CooccurTotals)]
+    L.kmcpg_cooccur_reset.argtypes = [vp]
+    L.kmcpg_last_cooccur.argtypes = [vp, C.POINTER(CooccurStats), C.POINTER(K4Launch), C.c_uint32, C.POINTER(C.c_uint32)]
     L.kmcpg_sketch_genomes_to.argtypes = [vp, vp, vp, C.c_uint32, C.POINTER(SplitSpec), SKETCH_SINK, vp]
     u32p = C.POINTER(C.c_uint32)
     L.kmcpg_builder_open.argtypes = [C.POINTER(BuilderCfg), C.c_int32, C.POINTER(vp)]
@@ -1262,6 +1287,41 @@ class Database:
         _check(load().kmcpg_last_refstats(self._h, C.byref(st), buf, n.value, C.byref(n)))
         self.last_k6_ms = float(st.k6_ms)  # HIP-event time of the kernel (profiling level >= 1), else -1
         return {f: int(getattr(st, f)) for f, _ in RefstatsStats._fields_ if f != "k6_ms"}, [buf[i] for i in range(n.value)]
+
+    # ---- shared reads of reference pairs: K7 behind K3 -----------------------------------------------------------
+    def set_cooccur(self, target_class=None, table_slots=0):
+        """kmcpg_set_cooccur: one uint32 per global column; table_slots a power of two (0 = the default); no argument = off."""
+        if target_class is None:
+            _check(load().kmcpg_set_cooccur(self._h, None, 0, 0))
+            return
+        t = np.ascontiguousarray(target_class, dtype=np.uint32)
+        _check(load().kmcpg_set_cooccur(self._h, t.ctypes.data, len(t), int(table_slots)))
+
+    def cooccur_device(self, d_pairs, d_read_offs, pair_cap, d_qkmers, n_reads, final_n, d_left, d_n_hits=None, hit_cap=0, max_wgs=0, stream=None):
+        """kmcpg_cooccur_device on device pointers: K3's pairs and offsets -> the handle's pair table and a LEFT byte per read."""
+        _check(load().kmcpg_cooccur_device(self._h, d_pairs, d_read_offs, pair_cap, d_qkmers, n_reads, final_n, d_n_hits, hit_cap, d_left, max_wgs, stream))
+
+    def cooccur_read(self):
+        """kmcpg_cooccur_read: (COOCCUR_DTYPE [n_pairs] sorted by (class_a, class_b), dict of the totals) — device table and host map merged"""
+        tot = CooccurTotals()
+        n = C.c_uint64(0)
+        _check(load().kmcpg_cooccur_read(self._h, None, 0, C.byref(n), C.byref(tot)))
+        out = np.zeros(n.value, dtype=COOCCUR_DTYPE)
+        _check(load().kmcpg_cooccur_read(self._h, out.ctypes.data if n.value else None, n.value, C.byref(n), C.byref(tot)))
+        return out[:n.value], {f: int(getattr(tot, f)) for f, _ in CooccurTotals._fields_}
+
+    def cooccur_reset(self):
+        _check(load().kmcpg_cooccur_reset(self._h))
+
+    def last_cooccur(self):
+        """kmcpg_last_cooccur: (dict of the counters, [K4Launch] of the last K7 launch — empty below profiling level 1)"""
+        st = CooccurStats()
+        n = C.c_uint32(0)
+        _check(load().kmcpg_last_cooccur(self._h, C.byref(st), None, 0, C.byref(n)))
+        buf = (K4Launch * max(1, n.value))()
+        _check(load().kmcpg_last_cooccur(self._h, C.byref(st), buf, n.value, C.byref(n)))
+        self.last_k7_ms = float(st.k7_ms)  # HIP-event time of the kernel (profiling level >= 1), else -1
+        return {f: int(getattr(st, f)) for f, _ in CooccurStats._fields_ if f != "k7_ms"}, [buf[i] for i in range(n.value)]
 
     # ---- window summaries for region merging: K5 behind K4 ------------------------------------------------------
     def summarize_device(self, d_pairs, d_offs, pair_cap, d_verdicts, d_qkmers, n, d_out, d_left_pairs, left_cap, d_left_offs, stream=None):
