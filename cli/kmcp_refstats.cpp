@@ -4,6 +4,7 @@
 //
 //   kmcp-refstats [-o out.tsv[.gz]] [--cooccur pairs.tsv[.gz]] [-f 0.01] [-t 0.55] [-n 0] [--keep-perfect-matches] [--keep-main-matches] [--max-qcov-gap 0.4]
 //                 [-m 3] [-p frac] [-H qcov] [--level species|strain|assembly] [-T map.tsv[,more.tsv]]... [-X taxdump/] [-i list.txt]
+//                 [--recount recount.tsv[.gz]] [-r n] [-u n] [-U n] [-P prop] [-d stdev] [-D 0.05] [-R 0.05] [--no-amb-corr] [--norm-abund mean|min|max]
 //                 [a.tsv[.gz] ...]
 //
 // Semantics restated from the reference (the counting rule, the verdict and the presets are kmcp_amd/csrc/refstats_rule.hpp):
@@ -15,6 +16,9 @@
 //   * a reference's chunks and tLen are those of its first row; at --level species a target without a TaxId is fatal;
 //   * -m picks H and p (mode 0 also --keep-main-matches); -H / -p override the preset only when given; the VALUE of -H (0.75 when not
 //     given) must lie in [-t, 1], as in the reference, whatever the mode.
+//   * --recount FILE: stage 3/4 ("recounting matches and unique matches", profile.go:1282-1888) after stages 1 and 2 — the rule, the
+//     reference's quirk and our tie order are kmcp_amd/csrc/recount_rule.hpp, the file's format is cli/recount_format.hpp; -r -u -U -P -d
+//     come from -m and are overridden only when given, -D -R --no-amb-corr --norm-abund are the reference's.
 // The reference prints none of this (it goes on to stages 2-4); the output format is this tool's:
 //   # matched reads: N
 //   # unique reads: U
@@ -35,8 +39,10 @@
 #include <vector>
 
 #include "../kmcp_amd/csrc/cooccur_rule.hpp"
+#include "../kmcp_amd/csrc/recount_rule.hpp"
 #include "../kmcp_amd/csrc/refstats_rule.hpp"
 #include "../kmcp_amd/csrc/taxonomy.hpp"
+#include "recount_format.hpp"
 #include "tsv_in.hpp"
 #include "tsv_out.hpp"
 
@@ -68,7 +74,18 @@ void usage() {
       "      --line-chunk-size int         Accepted for command-line compatibility. (default 5000)\n"
       "  -i, --infile-list string          File of input files list (one file per line).\n"
       "      --cooccur string              Also count the reads shared by every pair of kept references (stage 2/4 of kmcp profile) into\n"
-      "                                    this file, supports a \".gz\" suffix. A second pass over the inputs: stdin is not supported.\n",
+      "                                    this file, supports a \".gz\" suffix. A second pass over the inputs: stdin is not supported.\n"
+      "      --recount string              Also recount the reads with ambiguity correction and judge the references again (stage 3/4 of\n"
+      "                                    kmcp profile) into this file, supports a \".gz\" suffix. Stdin is not supported.\n"
+      "  -r, --min-chunks-reads int        Minimum number of reads for a reference chunk. (default 50)\n"
+      "  -u, --min-uniq-reads int          Minimum number of uniquely matched reads for a reference. (default 20)\n"
+      "  -U, --min-hic-ureads int          Minimum number of high-confidence uniquely matched reads for a reference. (default 5)\n"
+      "  -P, --min-hic-ureads-prop float   Minimum proportion of high-confidence uniquely matched reads. (default 0.1)\n"
+      "  -d, --max-chunks-depth-stdev float  Maximum standard deviation of relative depths of all chunks. (default 2)\n"
+      "  -D, --min-dreads-prop float       Minimum proportion of distinct reads, for determing the right reference for ambiguous reads. (default 0.05)\n"
+      "  -R, --max-mismatch-err float      Maximum error rate of a read being matched to a wrong reference. (default 0.05)\n"
+      "      --no-amb-corr                 Do not correct ambiguous reads.\n"
+      "      --norm-abund string           Method for normalizing abundance of a reference by the mean/min/max abundance in all chunks. (default \"mean\")\n",
       stderr);
 }
 
@@ -94,6 +111,7 @@ struct Ref {
   uint32_t target_class, species_class;
   uint64_t chunks, tlen, base;  // its counters: 4 words per chunk from counters[4 * base]
   bool ok = false;              // stage 1 kept it (set once every row is counted)
+  uint64_t reads = 0, ureads = 0;  // stage 1's sums (what stage 3 compares)
 };
 
 // a row cut at its first 12 tabs: field k = 1..12 (the 13th keeps the rest of the line)
@@ -129,7 +147,10 @@ bool parse_row(const char* p, size_t n, double min_qcov, double max_fpr, Fields*
 }  // namespace
 
 int main(int argc, char** argv) {
-  std::string out_file = "-", level = "species", taxdump, infile_list, cooccur_file;
+  std::string out_file = "-", level = "species", taxdump, infile_list, cooccur_file, recount_file, norm_abund = "mean";
+  long flag_r = 50, flag_u = 20, flag_U = 5;
+  double flag_P = 0.1, flag_d = 2, flag_D = 0.05, flag_R = 0.05;
+  bool given_r = false, given_u = false, given_U = false, given_P = false, given_d = false, no_amb_corr = false;
   std::vector<std::string> map_files, files;
   double max_fpr = 0.01, min_qcov = 0.55, flag_h = 0.75, flag_p = 0.8, max_gap = 0.4;
   bool given_h = false, given_p = false, keep_perfect = false, keep_main = false;
@@ -177,6 +198,16 @@ int main(int argc, char** argv) {
     else if (a == "--line-chunk-size") chunk = integer("--line-chunk-size", need(i));
     else if (a == "-i" || a == "--infile-list") infile_list = need(i);
     else if (a == "--cooccur") cooccur_file = need(i);
+    else if (a == "--recount") recount_file = need(i);
+    else if (a == "-r" || a == "--min-chunks-reads") flag_r = integer("-r, --min-chunks-reads", need(i)), given_r = true;
+    else if (a == "-u" || a == "--min-uniq-reads") flag_u = integer("-u, --min-uniq-reads", need(i)), given_u = true;
+    else if (a == "-U" || a == "--min-hic-ureads") flag_U = integer("-U, --min-hic-ureads", need(i)), given_U = true;
+    else if (a == "-P" || a == "--min-hic-ureads-prop") flag_P = num("-P, --min-hic-ureads-prop", need(i)), given_P = true;
+    else if (a == "-d" || a == "--max-chunks-depth-stdev") flag_d = num("-d, --max-chunks-depth-stdev", need(i)), given_d = true;
+    else if (a == "-D" || a == "--min-dreads-prop") flag_D = num("-D, --min-dreads-prop", need(i));
+    else if (a == "-R" || a == "--max-mismatch-err") flag_R = num("-R, --max-mismatch-err", need(i));
+    else if (a == "--no-amb-corr") no_amb_corr = true;
+    else if (a == "--norm-abund") norm_abund = need(i);
     else if (a == "-j" || a == "--threads" || a == "--log") need(i);  // accepted for command-line compatibility
     else if (a == "-q" || a == "--quiet") {
     } else if (a == "-h" || a == "--help") {
@@ -195,7 +226,26 @@ int main(int argc, char** argv) {
   if (flag_p > 1) die("the value of -p/--min-chunks-fraction (%f) should be in range of [0, 1]", flag_p);
   if (flag_h <= 0) die("value of flag --min-hic-ureads-qcov should be greater than 0");
   if (flag_h > 1 || flag_h < min_qcov) die("the value of -H/--min-hic-ureads-qcov (%f) should be in range of [<-t/--min-query-cov>, 1]", flag_h);
+  if (flag_r <= 0) die("value of flag --min-chunks-reads should be greater than 0");
+  if (flag_d <= 0) die("value of flag --max-chunks-depth-stdev should be greater than 0");
+  if (flag_u <= 0) die("value of flag --min-uniq-reads should be greater than 0");
+  if (flag_U <= 0) die("value of flag --min-hic-ureads should be greater than 0");
+  if (flag_P <= 0) die("value of flag --min-hic-ureads-prop should be greater than 0");
+  if (flag_P > 1) die("the value of -P/--min-hic-ureads-prop (%f) should be in range of (0, 1]", flag_P);
+  if (flag_D <= 0) die("value of flag --min-dreads-prop should be greater than 0");
+  if (flag_D > 1) die("the value of -D/--min-dreads-prop (%f) should be in range of (0, 1]", flag_D);
+  if (flag_R <= 0) die("value of flag --max-mismatch-err should be greater than 0");
+  if (flag_R >= 1) die("the value of -R/--max-mismatch-err (%f) should be in range of (0, 1)", flag_R);
+  for (char& c : norm_abund) c = (char)tolower((unsigned char)c);
+  if (norm_abund != "mean" && norm_abund != "min" && norm_abund != "max") die("invalid value of --norm-abund: %s. available: mean, min, max", norm_abund.c_str());
   kmcpg::RefstatsMode preset = kmcpg::refstats_mode((int)mode);
+  kmcpg::RecountThresholds th;
+  th.min_chunks_reads = given_r ? (uint64_t)flag_r : preset.min_chunks_reads;
+  th.min_uniq_reads = given_u ? (uint64_t)flag_u : preset.min_uniq_reads;
+  th.min_hic_ureads = given_U ? (uint64_t)flag_U : preset.min_hic_ureads;
+  th.min_hic_ureads_prop = given_P ? flag_P : preset.min_hic_ureads_prop;
+  th.max_depth_stdev = given_d ? flag_d : preset.max_chunks_depth_stdev;
+  th.norm = norm_abund == "mean" ? kmcpg::RECOUNT_NORM_MEAN : norm_abund == "min" ? kmcpg::RECOUNT_NORM_MIN : kmcpg::RECOUNT_NORM_MAX;
   const double H = given_h ? flag_h : preset.hic_min_qcov, min_frac = given_p ? flag_p : preset.min_chunks_fraction;
   keep_main = keep_main || preset.keep_main;
   for (char& c : level) c = (char)tolower((unsigned char)c);
@@ -230,6 +280,17 @@ int main(int argc, char** argv) {
     }
     if (cooccur_file == "-" ? out_file == "-" : tsv_in::clean_path(cooccur_file) == tsv_in::clean_path(out_file)) die("flag --cooccur: the file must not be the out file (-o)");
   }
+
+  if (!recount_file.empty()) {  // before anything is read
+    for (const std::string& f : files) {
+      if (f == "-") die("flag --recount: stdin is not supported (the search results are read three times)");
+      if (tsv_in::clean_path(f) == tsv_in::clean_path(recount_file)) die("flag --recount: the file should not be one of the input file");
+    }
+    if (recount_file == "-" ? out_file == "-" : tsv_in::clean_path(recount_file) == tsv_in::clean_path(out_file)) die("flag --recount: the file must not be the out file (-o)");
+    if (!cooccur_file.empty() && (recount_file == "-" ? cooccur_file == "-" : tsv_in::clean_path(recount_file) == tsv_in::clean_path(cooccur_file)))
+      die("flag --recount: the file must not be the --cooccur file");
+  }
+  th.min_chunks_fraction = min_frac;
 
   kmcpg::TaxidMap tmap;
   kmcpg::Taxonomy tax;
@@ -318,12 +379,13 @@ int main(int argc, char** argv) {
   for (auto& kv : refs) {
     Ref& r = kv.second;
     const uint64_t* w = counters.data() + r.base * kmcpg::REFSTATS_WORDS;
-    r.ok = kmcpg::refstats_rollup(r.chunks, min_frac, [&](uint64_t c) { return w + c * kmcpg::REFSTATS_WORDS; }).verdict == kmcpg::REFSTATS_OK;
+    const kmcpg::RefstatsRef t = kmcpg::refstats_rollup(r.chunks, min_frac, [&](uint64_t c) { return w + c * kmcpg::REFSTATS_WORDS; });
+    r.ok = t.verdict == kmcpg::REFSTATS_OK, r.reads = t.reads, r.ureads = t.ureads;
   }
 
   // stage 2/4 (profile.go:1117-1279): the inputs once more; a query's targets are a set (chunks of one reference are one target)
   std::unordered_map<uint64_t, uint64_t> shared;  // cooccur_key of two target classes -> queries
-  if (!cooccur_file.empty()) {
+  if (!cooccur_file.empty() || !recount_file.empty()) {
     kmcpg::CooccurCut cut2;
     cut2.cut = cut;
     for (const std::string& file : files) {
@@ -359,6 +421,68 @@ int main(int argc, char** argv) {
     }
   }
 
+  // stage 3/4 (profile.go:1282-1888): the inputs a third time; the kept rows are stage 2's, the rest is recount_rule.hpp
+  std::vector<uint64_t> recounted;  // RECOUNT_WORDS per column, laid out as `counters`
+  uint64_t n_recounted = 0, n_unique3 = 0, n_corrected = 0;
+  if (!recount_file.empty()) {
+    recounted.assign(counters.size() / kmcpg::REFSTATS_WORDS * kmcpg::RECOUNT_WORDS, 0);
+    std::vector<kmcpg::RecountClass> classes(refs.size());
+    for (const auto& kv : refs) classes[kv.second.target_class] = kmcpg::RecountClass{kv.second.ok ? 1u : 0u, kv.second.reads, kv.second.ureads};
+    kmcpg::RecountParams rp;
+    rp.one_minus_d = 1 - flag_D, rp.r_err = flag_R, rp.hic_min_qcov = H, rp.no_amb_corr = no_amb_corr, rp.level_species = level_species;
+    kmcpg::CooccurCut cut3;
+    cut3.cut = cut;
+    for (const std::string& file : files) {
+      RawLines in(file);
+      std::string query;  // the name of the previous row that was not skipped
+      bool any = false;
+      std::vector<kmcpg::RecountRow> rows;  // the current query's kept rows
+      auto flush = [&] {
+        if (rows.empty()) return;
+        bool lost = false;
+        const size_t ns = kmcpg::recount_query(
+            rows.data(), rows.size(), classes.data(), rp,
+            [&](uint32_t a, uint32_t b) {
+              const auto it = shared.find(kmcpg::cooccur_key(a, b));
+              return it == shared.end() ? (uint64_t)0 : it->second;
+            },
+            [&](uint64_t col, int w, uint64_t n) { recounted[col * kmcpg::RECOUNT_WORDS + w] += n; }, &lost);
+        n_recounted++;
+        if (ns == 1) n_unique3++;
+        if (lost) n_corrected++;
+        rows.clear();
+      };
+      const char* p = nullptr;
+      size_t n = 0;
+      while (in.next(&p, &n)) {
+        Fields fl;
+        double qcov = 0;
+        if (!parse_row(p, n, min_qcov, max_fpr, &fl, &qcov)) continue;
+        const char* fp;
+        size_t fn = fl.get(6, &fp);
+        name.assign(fp, fn);
+        const auto it = refs.find(name);
+        const bool kept = it != refs.end() && it->second.ok;
+        const bool new_name = !any || query.size() != fl.tab[0] || memcmp(query.data(), p, fl.tab[0]) != 0;
+        bool opens = false;
+        const bool take = cut3.row(kept, new_name, qcov, &opens);
+        if (!kept) continue;
+        if (opens) flush();
+        query.assign(p, fl.tab[0]);
+        any = true;
+        if (!take) continue;
+        uint64_t qlen = 0, chunk_idx = 0;  // (both parsed and range-checked by stage 1: a kept target's rows all passed it)
+        bool neg = false;
+        fn = fl.get(2, &fp);
+        if (!parse_int(fp, fn, true, &qlen, &neg) || neg) qlen = 0;
+        fn = fl.get(7, &fp);
+        if (!parse_int(fp, fn, true, &chunk_idx, &neg) || neg || chunk_idx >= it->second.chunks) die("chunkIdx of %s is outside its chunks", name.c_str());
+        rows.push_back(kmcpg::RecountRow{it->second.target_class, it->second.species_class, it->second.base + chunk_idx, qcov, qlen});
+      }
+      flush();
+    }
+  }
+
   Out out(out_file, -1);
   char line[256];
   out.write(line, (size_t)snprintf(line, sizeof line, "# matched reads: %llu\n# unique reads: %llu\n", (unsigned long long)matched, (unsigned long long)unique));
@@ -384,6 +508,14 @@ int main(int argc, char** argv) {
     out.write(s);
   }
   out.close();
+
+  if (!recount_file.empty()) {
+    std::vector<recount_format::Ref> list;
+    for (const auto& kv : refs) list.push_back(recount_format::Ref{&kv.first, kv.second.chunks, kv.second.tlen, recounted.data() + kv.second.base * kmcpg::RECOUNT_WORDS});
+    Out rc(recount_file, -1);
+    recount_format::write(rc, list, n_recounted, n_unique3, n_corrected, th);
+    rc.close();
+  }
 
   if (!cooccur_file.empty()) {
     std::vector<const std::string*> name_of(refs.size());

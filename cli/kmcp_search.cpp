@@ -97,6 +97,14 @@ struct Options {
   // file is what `kmcp-refstats -f 1 -t 0 ... --cooccur FILE` writes from this run's TSV (K7 of the library, kmcpg_set_cooccur)
   std::string ref_stats_cooccur;
   long long ref_stats_cooccur_slots = 0;  // the pair table's slots, a power of two; 0: the library's default
+  // --ref-stats-recount FILE [--ref-stats-no-amb-corr] [--ref-stats-min-dreads-prop D] [--ref-stats-max-mismatch-err R]
+  // [--ref-stats-recount-log-mb N]: stage 3/4 behind the two — the recount with ambiguity correction; the file is what
+  // kmcp-refstats --recount writes from the search result
+  std::string ref_stats_recount;
+  bool ref_stats_no_amb_corr = false;
+  double ref_stats_d = 0.05, ref_stats_r = 0.05;
+  long long ref_stats_recount_log_mb = -1;  // the read log in device memory; -1: the library's default
+  const char* recount_flag = nullptr;       // the first of the four optional flags that was given
   std::vector<std::string> also_dbs;  // --also-db: further databases searched in the same pass, the output merged as kmcp-merge would
   bool gpus_given = false;
   int min_qlen = 30, min_kmers = 10, dedup = 256, top_scores = 0, threads = 0, device = 0, batch = 131072, gpus = 1, gpu_passes = -1;
@@ -149,12 +157,17 @@ static void usage() {
       "           --ref-stats file [--ref-stats-mode int (3)] [--ref-stats-min-hic-ureads-qcov float] [--ref-stats-min-chunks-fraction float]\n"
       "                             [--ref-stats-level species|strain|assembly] [--taxid-map file(s) --taxdump dir]\n"
       "                             [--ref-stats-cooccur file [--ref-stats-cooccur-slots int]]\n"
+      "                             [--ref-stats-recount file [--ref-stats-no-amb-corr] [--ref-stats-min-dreads-prop float (0.05)]\n"
+      "                              [--ref-stats-max-mismatch-err float (0.05)] [--ref-stats-recount-log-mb int]]\n"
       "                             count, on the GPU while the search runs, what stage 1/4 of `kmcp profile` counts per reference (reads,\n"
       "                             uniquely matched reads, high-confidence ones, chunks covered) and judge which references are in the\n"
       "                             sample: the file is what `kmcp-refstats -f 1 -t 0 -m N --level L ...` writes from this command's\n"
       "                             unfiltered output, which is written as before.  Modes 1-5 are kmcp profile's presets (mode 0 cuts\n"
       "                             rows: use kmcp-refstats).  The level defaults to species with --taxid-map and --taxdump, else strain.\n"
       "                             Not with what --specific-level refuses.\n"
+      "                             --ref-stats-recount (with --ref-stats and --ref-stats-cooccur): stage 3/4 as well — the reads recounted\n"
+      "                             with ambiguity correction and the references judged with the mode's thresholds; the file is what\n"
+      "                             `kmcp-refstats ... --recount` writes from this command's output.\n"
       "           --parse-only (read the inputs and print records / bases / checksum per file; no database, no GPU)\n"
       "           --regions-bed file [--regions-min-overlap int (1)] [--regions-max-gap int (0)] [--regions-ignore-type]\n"
       "                             [--regions-name-species string] [--regions-name-assembly string]\n"
@@ -196,6 +209,7 @@ static Options parse_args(int argc, char** argv) {
       {"sliding-step", 0, 1}, {"sliding-window", 0, 1}, {"sliding-greedy", 0, 0}, {"also-db", 0, 1},
       {"specific-level", 0, 1}, {"taxid-map", 0, 1}, {"taxdump", 0, 1},
       {"ref-stats", 0, 1}, {"ref-stats-mode", 0, 1}, {"ref-stats-min-hic-ureads-qcov", 0, 1}, {"ref-stats-min-chunks-fraction", 0, 1}, {"ref-stats-level", 0, 1}, {"ref-stats-cooccur", 0, 1}, {"ref-stats-cooccur-slots", 0, 1},
+      {"ref-stats-recount", 0, 1}, {"ref-stats-no-amb-corr", 0, 0}, {"ref-stats-min-dreads-prop", 0, 1}, {"ref-stats-max-mismatch-err", 0, 1}, {"ref-stats-recount-log-mb", 0, 1},
       {"regions-bed", 0, 1}, {"regions-min-overlap", 0, 1}, {"regions-max-gap", 0, 1}, {"regions-ignore-type", 0, 0},
       {"regions-name-species", 0, 1}, {"regions-name-assembly", 0, 1}};
   auto regions_flag = [&](const char* flag) {
@@ -255,6 +269,11 @@ static Options parse_args(int argc, char** argv) {
     else if (name == "ref-stats-min-hic-ureads-qcov") { o.ref_stats_h = to_f(name, v); o.ref_stats_h_given = true; if (!o.ref_stats_flag) o.ref_stats_flag = "--ref-stats-min-hic-ureads-qcov"; }
     else if (name == "ref-stats-min-chunks-fraction") { o.ref_stats_p = to_f(name, v); o.ref_stats_p_given = true; if (!o.ref_stats_flag) o.ref_stats_flag = "--ref-stats-min-chunks-fraction"; }
     else if (name == "ref-stats-cooccur") { o.ref_stats_cooccur = v; if (!o.ref_stats_flag) o.ref_stats_flag = "--ref-stats-cooccur"; }
+    else if (name == "ref-stats-recount") { o.ref_stats_recount = v; if (!o.ref_stats_flag) o.ref_stats_flag = "--ref-stats-recount"; }
+    else if (name == "ref-stats-no-amb-corr") { o.ref_stats_no_amb_corr = true; if (!o.recount_flag) o.recount_flag = "--ref-stats-no-amb-corr"; }
+    else if (name == "ref-stats-min-dreads-prop") { o.ref_stats_d = to_f(name, v); if (!o.recount_flag) o.recount_flag = "--ref-stats-min-dreads-prop"; }
+    else if (name == "ref-stats-max-mismatch-err") { o.ref_stats_r = to_f(name, v); if (!o.recount_flag) o.recount_flag = "--ref-stats-max-mismatch-err"; }
+    else if (name == "ref-stats-recount-log-mb") { o.ref_stats_recount_log_mb = to_i(name, v); if (o.ref_stats_recount_log_mb < 0) o.ref_stats_recount_log_mb = 0; if (!o.recount_flag) o.recount_flag = "--ref-stats-recount-log-mb"; }
     else if (name == "ref-stats-cooccur-slots") { o.ref_stats_cooccur_slots = to_i(name, v); if (!o.ref_stats_flag) o.ref_stats_flag = "--ref-stats-cooccur-slots"; }
     else if (name == "ref-stats-level") { o.ref_stats_level = v; for (char& c : o.ref_stats_level) c = (char)tolower((unsigned char)c); if (!o.ref_stats_flag) o.ref_stats_flag = "--ref-stats-level"; }
     else if (name == "specific-level") { o.specific_level = v; for (char& c : o.specific_level) c = (char)tolower((unsigned char)c); }
@@ -326,6 +345,7 @@ static Options parse_args(int argc, char** argv) {
 #include "../kmcp_amd/csrc/taxonomy.hpp"
 #include "../kmcp_amd/csrc/regions_rule.hpp"
 #include "../kmcp_amd/csrc/refstats_rule.hpp"
+#include "recount_format.hpp"
 #include "search_batch.hpp"
 #include "row_format.hpp"
 
@@ -505,6 +525,9 @@ static int validate_flags(const Options& o, bool sliding) {
   }
   // --ref-stats: the same refusals as --specific-level, for the same reason (what is counted must be every query's final matches, counted
   // once); mode 0 cuts rows of a query, which only the TSV route can do
+  if (o.ref_stats_recount.empty() && o.recount_flag) die("flag %s is only used with --ref-stats-recount", o.recount_flag);
+  if (!o.ref_stats_recount.empty() && (o.ref_stats.empty() || o.ref_stats_cooccur.empty()))
+    die("flag --ref-stats-recount is only used with --ref-stats and --ref-stats-cooccur (stage 3 starts from the tables of stages 1 and 2)");
   if (o.ref_stats.empty() && o.ref_stats_flag) die("flag %s is only used with --ref-stats", o.ref_stats_flag);
   if (!o.ref_stats.empty()) {
     const char* bad = o.keep_unmatched ? "-K/--keep-unmatched" : o.try_se ? "--try-se" : o.top_scores != 0 ? "-n/--keep-top-scores"
@@ -528,6 +551,14 @@ static int validate_flags(const Options& o, bool sliding) {
       if (o.ref_stats_cooccur == o.ref_stats) die("flag --ref-stats-cooccur: the pairs' file must not be the statistics file (--ref-stats)");
       const long long n = o.ref_stats_cooccur_slots;
       if (n < 0 || (n & (n - 1)) || n > (1ll << 30)) die("the value of --ref-stats-cooccur-slots (%lld) should be a power of two, at most 2^30", n);
+    }
+    if (!o.ref_stats_recount.empty()) {
+      if (o.ref_stats_recount == o.out_file) die("flag --ref-stats-recount: the file must not be the search result's file");
+      if (o.ref_stats_recount == o.ref_stats) die("flag --ref-stats-recount: the file must not be the statistics file (--ref-stats)");
+      if (o.ref_stats_recount == o.ref_stats_cooccur) die("flag --ref-stats-recount: the file must not be the pairs' file (--ref-stats-cooccur)");
+      if (o.ref_stats_recount_log_mb == 0 || o.ref_stats_recount_log_mb > 4096) die("the value of --ref-stats-recount-log-mb (%lld) should be in range of [1, 4096]", o.ref_stats_recount_log_mb);
+      if (!(o.ref_stats_d > 0) || o.ref_stats_d > 1) die("the value of --ref-stats-min-dreads-prop (%f) should be in range of (0, 1]", o.ref_stats_d);
+      if (!(o.ref_stats_r > 0) || !(o.ref_stats_r < 1)) die("the value of --ref-stats-max-mismatch-err (%f) should be in range of (0, 1)", o.ref_stats_r);
     }
   }
   // sliding windows: seqkit sliding has no meaning for pairs, whole files as queries or one ID for everything
@@ -1065,8 +1096,14 @@ static void write_file(const std::string& path, const std::string& s) {
     if (!f || fwrite(s.data(), 1, s.size(), f) != s.size() || (f == stdout ? fflush(f) : fclose(f)) != 0) die("%s: write error", path.c_str());
   }
 }
-// kept: the references with the verdict ok (what stage 2 looks at)
-static uint64_t write_ref_stats(const Options& o, kmcpg_db* db, const std::vector<std::string>& target, uint64_t* reruns, std::set<std::string>* kept) {
+// what stage 1 leaves of a reference for stage 3
+struct Stage1Ref {
+  uint64_t chunks, tlen, reads, ureads;
+  bool ok;
+};
+// kept: the references with the verdict ok (what stage 2 looks at); stage1: every reference with rows
+static uint64_t write_ref_stats(const Options& o, kmcpg_db* db, const std::vector<std::string>& target, uint64_t* reruns, std::set<std::string>* kept,
+                                std::map<std::string, Stage1Ref>* stage1) {
   const uint32_t n_cols = (uint32_t)target.size();
   std::vector<kmcpg_col_stats> cols(n_cols);
   kmcpg_refstats_totals tot;
@@ -1106,6 +1143,7 @@ static uint64_t write_ref_stats(const Options& o, kmcpg_db* db, const std::vecto
                                     (unsigned long long)t.reads, (unsigned long long)t.ureads, (unsigned long long)t.hic_ureads, t.chunks_frac,
                                     kmcpg::refstats_verdict_name(t.verdict)));
     if (t.verdict == kmcpg::REFSTATS_OK) kept->insert(kv.first);
+    (*stage1)[kv.first] = Stage1Ref{r.chunks, r.tlen, t.reads, t.ureads, t.verdict == kmcpg::REFSTATS_OK};
     for (int j = 0; j < kmcpg::REFSTATS_WORDS; j++)
       for (uint64_t c = 0; c < r.chunks; c++) {
         s.push_back(c ? ',' : '\t');
@@ -1151,6 +1189,66 @@ static uint64_t write_cooccur(const Options& o, kmcpg_db* db, const std::vector<
   for (const auto& r : rows) s += *r.first.first + "\t" + *r.first.second + "\t" + std::to_string(r.second) + "\n";
   write_file(o.ref_stats_cooccur, s);
   return rows.size();
+}
+
+// --ref-stats-recount: the library's stage — the classes of --ref-stats-cooccur (a class per printed target) and the species of --ref-stats ...
+static std::vector<uint32_t> set_recount(const Options& o, kmcpg_db* db, const std::vector<std::string>& target, const kmcpg::Taxonomy* tax, const kmcpg::TaxidMap* map) {
+  const bool species = ref_stats_species(o);
+  std::vector<uint32_t> cls, cls2, sp;
+  uint64_t unknown = 0;
+  std::string missing;
+  kmcpg::specific_classes(target, nullptr, nullptr, &cls, nullptr, &unknown, &missing);
+  if (species && !kmcpg::specific_classes(target, map, tax, &cls2, &sp, &unknown, &missing)) die("unknown taxid for %s, please check taxid mapping file(s)", missing.c_str());
+  const double H = o.ref_stats_h_given ? o.ref_stats_h : kmcpg::refstats_mode(o.ref_stats_mode).hic_min_qcov;
+  const uint64_t log_bytes = o.ref_stats_recount_log_mb < 0 ? 0 : (uint64_t)o.ref_stats_recount_log_mb << 20;
+  if (kmcpg_set_recount(db, cls.data(), species ? sp.data() : nullptr, (uint32_t)cls.size(), H, log_bytes) != 0) die("%s", kmcpg_last_error());
+  return cls;
+}
+// ... and the file, once stage 1 is rolled up and the pair table is read: the logs are replayed with both, and the references are written
+// by the formatter kmcp-refstats --recount uses.  All pairs go in: the rows of a reference stage 1 dropped are skipped at replay, so its
+// pairs are never asked for — with no row cut that equals the TSV route's skip
+static void write_recount(const Options& o, kmcpg_db* db, const std::vector<std::string>& target, const std::vector<uint32_t>& cls,
+                          const std::map<std::string, Stage1Ref>& stage1, kmcpg_recount_totals* tot) {
+  uint32_t n_classes = 0;
+  for (uint32_t c : cls) n_classes = std::max(n_classes, c + 1);
+  std::vector<kmcpg_recount_class> classes(n_classes);
+  for (size_t c = 0; c < cls.size(); c++) {
+    const auto it = stage1.find(target[c]);
+    classes[cls[c]] = it == stage1.end() ? kmcpg_recount_class{0, 0, 0, 0} : kmcpg_recount_class{it->second.ok ? 1u : 0u, 0, it->second.reads, it->second.ureads};
+  }
+  uint64_t n = 0;
+  if (kmcpg_cooccur_read(db, nullptr, 0, &n, nullptr) != 0) die("%s", kmcpg_last_error());
+  std::vector<kmcpg_cooccur_pair> pairs(n);
+  if (kmcpg_cooccur_read(db, pairs.data(), n, &n, nullptr) != 0) die("%s", kmcpg_last_error());
+  kmcpg_recount_params rp{1 - o.ref_stats_d, o.ref_stats_r, o.ref_stats_no_amb_corr ? 1u : 0u, ref_stats_species(o) ? 1u : 0u};
+  if (kmcpg_recount_run(db, classes.data(), n_classes, pairs.data(), n, &rp) != 0) die("%s", kmcpg_last_error());
+  const uint32_t n_cols = (uint32_t)target.size();
+  std::vector<kmcpg_recount_col> cols(n_cols);
+  if (kmcpg_recount_read(db, cols.data(), n_cols, tot) != 0) die("%s", kmcpg_last_error());
+  std::map<std::string, std::vector<uint64_t>> counters;  // per listed reference: RECOUNT_WORDS per chunk
+  for (uint32_t c = 0; c < n_cols; c++) {
+    if (!cols[c].match && !cols[c].uniq && !cols[c].hic && !cols[c].bases) continue;
+    const auto it = stage1.find(target[c]);
+    if (it == stage1.end()) die("--ref-stats-recount: %s was recounted but has no row in stage 1", target[c].c_str());
+    uint32_t tidx = 0;
+    kmcpg_col_info(db, c, nullptr, &tidx, nullptr, nullptr);
+    const uint64_t chunk = (uint16_t)tidx;
+    if (chunk >= it->second.chunks) die("--ref-stats-recount: chunk %llu of %s is outside its %llu chunks", (unsigned long long)chunk, target[c].c_str(), (unsigned long long)it->second.chunks);
+    std::vector<uint64_t>& w = counters[target[c]];
+    if (w.empty()) w.assign((size_t)it->second.chunks * kmcpg::RECOUNT_WORDS, 0);
+    const uint64_t v[kmcpg::RECOUNT_WORDS] = {cols[c].match, cols[c].uniq, cols[c].hic, cols[c].bases};
+    for (int j = 0; j < kmcpg::RECOUNT_WORDS; j++) w[chunk * kmcpg::RECOUNT_WORDS + j] += v[j];
+  }
+  std::vector<recount_format::Ref> list;
+  for (const auto& kv : counters) list.push_back(recount_format::Ref{&kv.first, stage1.at(kv.first).chunks, stage1.at(kv.first).tlen, kv.second.data()});
+  const kmcpg::RefstatsMode preset = kmcpg::refstats_mode(o.ref_stats_mode);
+  kmcpg::RecountThresholds th;
+  th.min_chunks_reads = preset.min_chunks_reads, th.min_uniq_reads = preset.min_uniq_reads, th.min_hic_ureads = preset.min_hic_ureads;
+  th.min_hic_ureads_prop = preset.min_hic_ureads_prop, th.max_depth_stdev = preset.max_chunks_depth_stdev;
+  th.min_chunks_fraction = o.ref_stats_p_given ? o.ref_stats_p : preset.min_chunks_fraction;
+  tsv_out::Out out(o.ref_stats_recount, -1);
+  recount_format::write(out, list, tot->recounted_reads, tot->unique_reads, tot->corrected_reads, th);
+  out.close();
 }
 
 static kmcpg_params make_params(const Options& o, int sort_by, bool paired) {
@@ -1591,6 +1689,8 @@ int main(int argc, char** argv) {
   if (!o.ref_stats.empty()) set_ref_stats(o, p.db, p.target, taxonomy.get(), taxid_map.get());
   std::vector<std::string> cooccur_names;
   if (!o.ref_stats_cooccur.empty()) cooccur_names = set_cooccur(o, p.db, p.target);
+  std::vector<uint32_t> recount_classes;
+  if (!o.ref_stats_recount.empty()) recount_classes = set_recount(o, p.db, p.target, taxonomy.get(), taxid_map.get());
 
   p.t_search = Clock::now();
   Out out(p.regions() ? o.regions_bed : o.out_file);
@@ -1629,7 +1729,8 @@ int main(int argc, char** argv) {
   if (!o.ref_stats.empty()) {
     uint64_t reruns = 0;
     std::set<std::string> kept;
-    const uint64_t n_refs = write_ref_stats(o, p.db, p.target, &reruns, &kept);
+    std::map<std::string, Stage1Ref> stage1;
+    const uint64_t n_refs = write_ref_stats(o, p.db, p.target, &reruns, &kept, &stage1);
     if (!o.quiet)
       info("reference statistics (mode %d, level %s): %llu references saved to: %s (%llu batches counted by their rerun after a hit-buffer overflow)", o.ref_stats_mode,
            ref_stats_species(o) ? "species" : "strain", (unsigned long long)n_refs, o.ref_stats.c_str(), (unsigned long long)reruns);
@@ -1639,6 +1740,14 @@ int main(int argc, char** argv) {
       if (!o.quiet)
         info("shared reads of reference pairs: %llu pairs of kept references saved to: %s (%llu reads with several targets, %llu of them counted on the host, %llu for want of room in the table)",
              (unsigned long long)n_pairs, o.ref_stats_cooccur.c_str(), (unsigned long long)tot.multi_reads, (unsigned long long)tot.host_reads, (unsigned long long)tot.left_full);
+    }
+    if (!o.ref_stats_recount.empty()) {
+      kmcpg_recount_totals tot;
+      write_recount(o, p.db, p.target, recount_classes, stage1, &tot);
+      // (one line of its own, whatever -q says: the tests read it)
+      fprintf(stderr, "%llu reads recounted, %llu of them replayed (%llu on the host, %llu for want of log room), %llu corrected\n", (unsigned long long)tot.recounted_reads,
+              (unsigned long long)(tot.recounted_reads - tot.single_reads), (unsigned long long)tot.host_reads, (unsigned long long)tot.left_full,
+              (unsigned long long)tot.corrected_reads);
     }
   }
   // Everything the user asked for is on disk.  Giving back pinned staging buffers, streams and a resident index one by one takes

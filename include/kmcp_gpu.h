@@ -554,6 +554,79 @@ int kmcpg_cooccur_read(kmcpg_db* db, kmcpg_cooccur_pair* out_pairs, uint64_t cap
 int kmcpg_cooccur_reset(kmcpg_db* db);
 int kmcpg_last_cooccur(kmcpg_db* db, kmcpg_cooccur_stats* out, kmcpg_k4_launch* launches, uint32_t cap, uint32_t* n_launches);
 
+/* -- recount with ambiguity correction (K8, k8_recount.hip): stage 3/4 of `kmcp profile` (kmcp/cmd/profile.go:1282-1888;
+ *    kmcp_amd/csrc/recount_rule.hpp states the rule: the order of a read's targets, the elimination loop in bit masks, the integer shares).
+ *    Every global column has four counters IN UNITS: match, uniq, hic (units of 1 / 720720 read) and bases (units of 2^-16 base).  Stage 3
+ *    needs the final verdicts of stage 1 and the final pair list of stage 2, so it runs in two steps: while the stage is on, every batch is
+ *    LOGGED behind K3 (k8_log: reads with one target are counted at once, reads with several targets among up to 64 pairs are appended to
+ *    a read log in device memory, the others — more k-mers than the device's -f bound covers, more than 4096 pairs, several targets among
+ *    more than 64 pairs, no room in the log — are appended by the host half at wait time, after its own -f test, to a log in host memory);
+ *    after the last ticket was waited for, kmcpg_recount_run REPLAYS both logs (k8_replay on the device, the same rule on the host).
+ *    The stage does NOT filter: the result of every call is byte for byte what it is with the stage off.
+ *    kmcpg_set_recount uploads its own copies of the class tables (species_class NULL: strain / assembly level) and allocates the zeroed
+ *    counters and the read log: log_bytes of device memory, fixed until the stage is set again (64 bytes .. 4 GiB; 0 = the default of
+ *    256 MiB; a read with m pairs takes 8 * (m + 3) bytes).  A read is logged completely or not at all; the log does not grow.  It is
+ *    independent of kmcpg_set_refstats, kmcpg_set_cooccur and kmcpg_set_specific; (NULL, NULL, 0, 0, 0) switches it off and frees
+ *    everything.  KMCPG_EUNSUPPORTED as for kmcpg_set_refstats: paged, multi-device and sharded handles; while the stage is on, batches with
+ *    try_se, top_n_scores != 0 or several k-mer sizes with k == 0, and every window submit.  A batch that is run again because its hit
+ *    buffer overflowed is logged once.
+ *    kmcpg_recount_log_device runs k8_log alone on device pointers, as kmcpg_cooccur_device runs K7, with d_qlen (one int32 per read)
+ *    beside d_qkmers: d_left[i] = 1 for the reads it neither counts nor logs.  Only enqueues on `stream`.
+ *    kmcpg_recount_run: classes[c] = {kept: stage 1's verdict of target class c is ok; reads, ureads: its stage-1 sums}, for every class
+ *    of target_class; pairs = what kmcpg_cooccur_read returns (sorted by (class_a, class_b), class_a < class_b; anything else is
+ *    KMCPG_EINVAL) — a pair that is not listed shares 0 reads.  params: one_minus_d = 1 - --min-dreads-prop, r_err = --max-mismatch-err,
+ *    no_amb_corr, level_species.  It waits for the device, zeroes the replay counters and replays: the logs are kept, so the call can be
+ *    repeated with other classes, pairs or params without a new search.  KMCPG_EDEVICE if a batch failed after it had been logged (call
+ *    kmcpg_recount_reset and search again).
+ *    kmcpg_recount_read: single-target reads of kept classes + device replay + host replay, n_cols records; valid after kmcpg_recount_run.
+ *    kmcpg_last_recount: the witness of the handle's last k8_log launch and of the last replay (the call waits for the device to go idle;
+ *    the words of k8_log are zeroed by every launch: meaningful only with ONE batch in flight).  KMCPG_RECOUNT_SLOTS (read by
+ *    kmcpg_set_recount): slots of a workgroup's LDS table, a power of two up to 1024 (anything else is KMCPG_EINVAL), 0 = no table;
+ *    default 1024.  KMCPG_RECOUNT_LOG_BYTES (read by kmcpg_set_recount): the log's size, whatever log_bytes says (the same range).
+ *    KMCPG_RECOUNT_DEVICE=0 sends every read to the host half. */
+typedef struct {
+  uint64_t match, uniq, hic, bases;  /* units: 720720 per read, 65536 per base */
+} kmcpg_recount_col;
+typedef struct {
+  uint32_t kept, reserved;
+  uint64_t reads, ureads;
+} kmcpg_recount_class;
+typedef struct {
+  double one_minus_d, r_err;
+  uint32_t no_amb_corr, level_species;
+} kmcpg_recount_params;
+typedef struct {
+  uint64_t recounted_reads, unique_reads, corrected_reads;  /* reads with a kept target; that ended with one target; that lost a target */
+  uint64_t single_reads;                                    /* of recounted_reads, counted by k8_log at once */
+  uint64_t replayed_reads, host_reads;                      /* reads replayed from the logs (with or without a kept target); of those, from the host log */
+  uint64_t left_full;                                       /* reads the device left to the host for want of log room */
+  uint64_t skipped_launches;                                /* k8_log launches that did nothing because the batch's hit buffer had overflowed */
+  uint64_t log_bytes, log_bytes_used, logged_reads;         /* the device log */
+} kmcpg_recount_totals;
+enum { KMCPG_K8_LOG = 64, KMCPG_K8_REPLAY = 65 };  /* kmcpg_k4_launch.kernel of K8's kernels */
+typedef struct {
+  uint64_t empty, single, logged, left;          /* k8_log: reads by the class they took; the four add up to the reads */
+  uint64_t left_full;                            /* of left: no room in the log */
+  uint64_t lds_adds, global_adds, spilled_adds;  /* spilled_adds is part of global_adds */
+  uint64_t skipped;                              /* 1: the overflow guard skipped the launch */
+  uint64_t bad_segments;
+  uint64_t log_bytes_used;                       /* the device log after the launch (the call waits) */
+  uint64_t replay_reads, replay_recounted, replay_corrected, replay_unique;  /* k8_replay: reads; with a kept target; that lost one; that ended unique */
+  uint64_t replay_lookups;                       /* binary searches in the pair list */
+  uint64_t replay_lds_adds, replay_global_adds, replay_spilled_adds;
+  uint32_t grid, slots, replay_grid, reserved;
+  double log_ms, replay_ms;                      /* HIP-event times at profiling level >= 1; -1 otherwise */
+} kmcpg_recount_stats;
+int kmcpg_set_recount(kmcpg_db* db, const uint32_t* target_class, const uint32_t* species_class, uint32_t n_cols, double hic_min_qcov, uint64_t log_bytes);
+int kmcpg_recount_log_device(kmcpg_db* db, const kmcpg_pair* d_pairs, const uint64_t* d_read_offs, uint64_t pair_cap, const int32_t* d_qkmers,
+                             const int32_t* d_qlen, uint32_t n_reads, int32_t final_n, const uint64_t* d_n_hits, uint64_t hit_cap, uint8_t* d_left,
+                             uint32_t max_wgs, void* stream);
+int kmcpg_recount_run(kmcpg_db* db, const kmcpg_recount_class* classes, uint32_t n_classes, const kmcpg_cooccur_pair* pairs, uint64_t n_pairs,
+                      const kmcpg_recount_params* params);
+int kmcpg_recount_read(kmcpg_db* db, kmcpg_recount_col* out_cols, uint32_t n_cols, kmcpg_recount_totals* totals);
+int kmcpg_recount_reset(kmcpg_db* db);
+int kmcpg_last_recount(kmcpg_db* db, kmcpg_recount_stats* out, kmcpg_k4_launch* launches, uint32_t cap, uint32_t* n_launches);
+
 /* -- benchmarking / full-size parity support (no counterpart in the reference) ------------------ */
 typedef struct {
   int32_t k;            /* 21 */

@@ -312,5 +312,67 @@ struct K7Args {
   unsigned long long* stats;           // [K7_STATS], zero on entry
 };
 
+// K8 (k8_recount.hip): stage 3 of `kmcp profile` (recount_rule.hpp) in two kernels.  k8_log, behind K3: single-target reads are counted at
+// once (four 64-bit counters per column, in units), reads with several targets among up to K8_CAP pairs are appended to the READ LOG; the
+// others are LEFT to the host (a byte per read).  k8_replay, after the last batch: the ambiguity correction and the shares of every logged
+// read, with stage 1's verdicts and stage 2's pair list.
+//
+// The read log: `cap` 64-bit words.  Records grow from the front — word 0: pairs m | NumKmers << 32, word 1: qLen, then the m pairs as K3
+// left them (col | count << 32) —, the index from the back: the record of logged read k starts at word log[cap - 1 - k].  Two words hold both
+// fill levels each (K8_STATE_*): what was asked for (fetch-add; it may run past the end) and what was taken (atomic max of the ends of the
+// allocations that fit).
+constexpr uint32_t K8_CAP = 64;  // longest segment of several targets the device logs
+constexpr uint32_t K8_MAX_SLOTS = 1024, K8_DEFAULT_SLOTS = 1024, K8_PROBES = 8;  // the workgroup's table in LDS: 36 bytes per slot (64-bit counters)
+constexpr uint64_t K8_DEFAULT_LOG_BYTES = 256ull << 20, K8_MIN_LOG_BYTES = 64, K8_MAX_LOG_BYTES = 4ull << 30;
+constexpr int K8_STATE_WORD_BITS = 36;  // state = logged reads << 36 | record words used (4 GiB: 2^29 words, fewer than 2^28 reads)
+// the witness of k8_log: reads empty / single target / logged / LEFT, of those LEFT for want of log room; adds to LDS / to global memory
+// (flushes and spills) / of those the spills; launches the overflow guard skipped, segments outside the buffer
+enum { K8_EMPTY = 0, K8_SINGLE, K8_LOGGED, K8_LEFT, K8_LEFT_FULL, K8_LDS_ADDS, K8_GLOBAL_ADDS, K8_SPILLED, K8_SKIPPED, K8_BAD, K8_STATS };
+// ... and of k8_replay: reads replayed, of those with a kept target / that lost a target / that ended with one target; pair lookups, adds
+enum { K8_R_READS = 0, K8_R_RECOUNTED, K8_R_CORRECTED, K8_R_UNIQUE, K8_R_LOOKUPS, K8_R_LDS_ADDS, K8_R_GLOBAL_ADDS, K8_R_SPILLED, K8_R_STATS };
+// the totals that persist beside the log: single-target reads counted, reads LEFT for want of log room, launches the guard skipped
+enum { K8_T_SINGLE = 0, K8_T_LEFT_FULL, K8_T_SKIPPED, K8_TOTALS };
+struct K8LogArgs {
+  const kmcpg_pair* pairs;             // K3's output, in print order
+  const uint64_t* offs;                // [n_reads + 1]
+  uint64_t pair_cap;                   // pairs there is room for behind `pairs`: a segment that ends behind it is treated as empty
+  const int32_t* nk;                   // NumKmers per read
+  const int32_t* qlen;                 // qLen per read
+  uint32_t n_reads;
+  uint32_t n_cols;
+  int32_t final_n;                     // reads of more k-mers are LEFT (their pairs may still fall to -f on the host)
+  uint32_t slots;                      // table slots per workgroup: a power of two up to K8_MAX_SLOTS, or 0 = every add goes to global memory
+  const uint32_t* target_class;        // [n_cols]
+  double hic_min_qcov;                 // H
+  const unsigned long long* n_hits;    // device word or nullptr: the batch's hit counter ...
+  uint64_t hit_cap;                    // ... above this the batch will be run again: nothing is counted or logged now
+  unsigned long long* counters;        // [4 * n_cols]: match, uniq, hic, bases of column c at 4 * c (recount_rule.hpp), the single-target reads'
+  unsigned long long* log;             // [log_cap] the read log
+  uint64_t log_cap;                    // words
+  unsigned long long* log_state;       // the reserve word ...
+  unsigned long long* log_commit;      // ... and the commit word
+  unsigned long long* totals;          // [K8_TOTALS]
+  uint8_t* left;                       // out [n_reads]: 1 = LEFT to the host
+  unsigned long long* stats;           // [K8_STATS], zero on entry
+};
+struct RecountClass;
+struct K8ReplayArgs {
+  const unsigned long long* log;       // the read log ...
+  uint64_t log_cap;
+  uint64_t n_logged;                   // ... and its reads
+  uint32_t n_cols, n_classes;
+  uint32_t slots;
+  const uint32_t* target_class;        // [n_cols]
+  const uint32_t* species_class;       // [n_cols] or nullptr: strain / assembly level
+  const RecountClass* classes;         // [n_classes] stage 1's verdict and sums (recount_rule.hpp)
+  const unsigned long long* keys;      // [n_pairs] stage 2's pairs, cooccur_key ascending ...
+  const unsigned long long* counts;    // ... and their reads
+  uint64_t n_pairs;
+  double one_minus_d, r_err, hic_min_qcov;
+  uint32_t no_amb_corr, level_species;
+  unsigned long long* counters;        // [4 * n_cols] the replay's counters, zero on entry
+  unsigned long long* stats;           // [K8_R_STATS], zero on entry
+};
+
 
 }  // namespace kmcpg

@@ -290,6 +290,33 @@ struct kmcpg_db {
   hipEvent_t co_ev[2] = {};
   bool co_timed = false;
   std::vector<kmcpg_k4_launch> k7_log;
+  // K8, the recount with ambiguity correction (kmcpg_set_recount; k8_recount.hip, recount.cpp): class tables of its own, H, the counters of
+  // the single-target reads and of the last replay (4 words per column each), the read log in HBM with its state word, the totals that
+  // persist beside it, the witness words of the last k8_log launch and of the last replay; and the host half's log — the reads the device
+  // LEFT, and every read of a batch that did not go through K3 — in the device log's record form (common.hpp: K8LogArgs), its index
+  // beside it (under rc_mu)
+  uint32_t* d_rc_target = nullptr;
+  uint32_t* d_rc_species = nullptr;
+  std::vector<uint32_t> h_rc_target, h_rc_species;  // species empty: strain level
+  bool recount_on() const { return !h_rc_target.empty(); }
+  double rc_hic = 0;
+  unsigned long long* d_rc_counters = nullptr;  // [4 * n_cols] single-target reads
+  unsigned long long* d_rc_replay = nullptr;    // [4 * n_cols] the last replay
+  unsigned long long* d_rc_log = nullptr;       // [rc_log_cap]
+  unsigned long long* d_rc_words = nullptr;     // the log's state word, then K8_TOTALS, K8_STATS and K8_R_STATS words
+  uint64_t rc_log_cap = 0;                      // words
+  uint32_t rc_slots = 0;                        // KMCPG_RECOUNT_SLOTS, read when the stage is set
+  unsigned rc_max_wgs = 0, rc_grid = 0, rc_replay_grid = 0;
+  std::mutex rc_mu;
+  std::vector<uint64_t> h_rc_log, h_rc_index;
+  std::vector<uint64_t> h_rc_replay;            // [4 * n_cols] the last replay of the host log
+  std::vector<uint8_t> rc_kept;                 // per column: its class was kept in the last kmcpg_recount_run
+  uint64_t rc_run_totals[4] = {};               // of the last run: recounted / unique / corrected reads of both replays, reads replayed by the device
+  bool rc_tainted = false;  // a batch failed after its reads were logged
+  bool rc_ran = false, rc_replayed = false;  // a k8_log launch / a kmcpg_recount_run since the stage was set
+  hipEvent_t rc_ev[2] = {}, rc_rev[2] = {};
+  bool rc_timed = false, rc_rtimed = false;
+  std::vector<kmcpg_k4_launch> k8_log, k8_rlog;
   std::vector<kmcpg::FprBoundTable> fpr_bounds;  // -f bound tables (query.cpp fpr_bound): one per (max_fpr, size), never rewritten
   hipEvent_t ev[16] = {};   // ring of 4 calls x (start, COBS start, COBS done, k-mers done)
   uint64_t ev_calls = 0;    // profiled calls so far
@@ -407,6 +434,18 @@ inline int cooccur_refuse_entry(const kmcpg_db* db, const char* entry) {
   return kmcpg_fail(KMCPG_EUNSUPPORTED, "shared reads of reference pairs (kmcpg_set_cooccur): %s is not supported while the stage is on", entry);
 }
 
+// The recount with ambiguity correction (kmcpg_set_recount): what K6 refuses, for the same reason
+inline int recount_refuse_params(const kmcpg_db* db, const kmcpg_params& p) {
+  if (!db->recount_on()) return 0;
+  const char* what = p.try_se ? "try_se" : (p.top_n_scores != 0 ? "top_n_scores != 0" : (p.k == 0 && db->ks_desc.size() > 1 ? "a database with several k-mer sizes searched with params->k == 0" : nullptr));
+  if (!what) return 0;
+  return kmcpg_fail(KMCPG_EUNSUPPORTED, "recount with ambiguity correction (kmcpg_set_recount): %s is not supported — switch the stage off, or recount the results with kmcp-refstats --recount", what);
+}
+inline int recount_refuse_entry(const kmcpg_db* db, const char* entry) {
+  if (!db->recount_on()) return 0;
+  return kmcpg_fail(KMCPG_EUNSUPPORTED, "recount with ambiguity correction (kmcpg_set_recount): %s is not supported while the stage is on", entry);
+}
+
 inline kmcpg_params default_params() {
   kmcpg_params p{};
   p.min_qlen = 30;
@@ -487,6 +526,14 @@ int refstats_enqueue(kmcpg_db* db, const kmcpg_pair* d_pairs, const uint64_t* d_
 int cooccur_host_batch(kmcpg_db* db, const kmcpg_pair* pairs, const uint64_t* read_offs, const int32_t* qkmers, uint32_t n_reads, const kmcpg_params& p,
                        const uint8_t* left);
 void cooccur_host_result(kmcpg_db* db, const kmcpg_result* out);
+// The host half of K8 (finalize.cpp), as K7's: the reads of a batch the device LEFT (left == nullptr: every read), from K3's pairs — the
+// host's own tests first, then the surviving rows, in final order, into the handle's host log; and every read of a finished result of records.
+int recount_host_batch(kmcpg_db* db, const kmcpg_pair* pairs, const uint64_t* read_offs, const int32_t* qkmers, const int32_t* qlen, uint32_t n_reads,
+                       const kmcpg_params& p, const uint8_t* left);
+void recount_host_result(kmcpg_db* db, const kmcpg_result* out);
+// k8_log behind K3 for a lane's batch (recount.cpp): what kmcpg_recount_log_device does, without the public entry's argument checks
+int recount_enqueue(kmcpg_db* db, const kmcpg_pair* d_pairs, const uint64_t* d_read_offs, uint64_t pair_cap, const int32_t* d_qkmers, const int32_t* d_qlen,
+                    uint32_t n_reads, int32_t final_n, const uint64_t* d_n_hits, uint64_t hit_cap, uint8_t* d_left, unsigned max_wgs, hipStream_t st);
 // K7 behind K3 for a lane's batch (cooccur.cpp): what kmcpg_cooccur_device does, without the public entry's argument checks (max_wgs 0: the handle's)
 int cooccur_enqueue(kmcpg_db* db, const kmcpg_pair* d_pairs, const uint64_t* d_read_offs, uint64_t pair_cap, const int32_t* d_qkmers, uint32_t n_reads,
                     int32_t final_n, const uint64_t* d_n_hits, uint64_t hit_cap, uint8_t* d_left, unsigned max_wgs, hipStream_t st);

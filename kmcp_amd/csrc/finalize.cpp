@@ -815,6 +815,61 @@ void cooccur_host_result(kmcpg_db* db, const kmcpg_result* out) {
   }
 }
 
+// ---- the host half of K8 (k8_recount.hip): the reads the device neither counts nor logs go into the handle's host log, in the device
+// log's record form — their FINAL rows in final order; kmcpg_recount_run replays them with recount_rule.hpp (recount.cpp)
+namespace {
+// one query's final rows (n >= 1) -> the handle's host log
+void recount_log_rows(kmcpg_db* db, const kmcpg_match* m, uint64_t n, int32_t qkmers, int32_t qlen) {
+  if (n == 0) return;
+  std::lock_guard<std::mutex> g(db->rc_mu);
+  db->h_rc_index.push_back(db->h_rc_log.size());
+  db->h_rc_log.push_back((uint64_t)(uint32_t)n | ((uint64_t)(uint32_t)qkmers << 32));
+  db->h_rc_log.push_back((uint64_t)std::max(qlen, 0));
+  for (uint64_t i = 0; i < n; i++) db->h_rc_log.push_back((uint64_t)m[i].col | ((uint64_t)(uint32_t)m[i].mkmers << 32));
+}
+}  // namespace
+
+int recount_host_batch(kmcpg_db* db, const kmcpg_pair* pairs, const uint64_t* read_offs, const int32_t* qkmers, const int32_t* qlen, uint32_t n_reads,
+                       const kmcpg_params& p, const uint8_t* left) {
+  if (!db->recount_on()) return 0;
+  const size_t n_cols = db->col_meta.size();
+  const uint64_t n_pairs = read_offs[n_reads];
+  std::vector<kmcpg_match> tmp;
+  FprRow row;
+  int row_n = -1;
+  const auto fpr_of = [&](int n2, int k) { return QueryFpr::value(*row, n2, k); };
+  for (uint32_t r = 0; r < n_reads; r++) {
+    if (left && !left[r]) continue;
+    const uint64_t s0 = read_offs[r], s1 = read_offs[r + 1];
+    if (s1 == s0) continue;
+    if (s1 < s0 || s1 > n_pairs) return kmcpg_fail(KMCPG_EINVAL, "grouped hit list: offsets out of range");
+    if (s1 - s0 >= (1ull << 32)) return kmcpg_fail(KMCPG_EINVAL, "grouped hit list: a read with 2^32 matches or more");
+    const int n = qkmers[r];
+    if (n > 0 && n != row_n) {
+      row_n = n;
+      row = db->fpr->ensure_row(n);
+    }
+    tmp.clear();
+    for (uint64_t i = s0; i < s1; i++) {
+      if (pairs[i].col >= n_cols) return kmcpg_fail(KMCPG_EINVAL, "grouped hit list: columns out of range");
+      kmcpg_match mm;
+      if (match_accept(pairs[i].col, (int)pairs[i].count, n, db->col_meta[pairs[i].col], p, fpr_of, &mm)) tmp.push_back(mm);
+    }
+    if (s1 - s0 > (uint64_t)K3_WG_CAP && !tmp.empty()) {  // K3 leaves these unordered: the host's order, as finalize_grouped_into gives them
+      sort_matches(tmp.data(), tmp.data() + tmp.size(), p);
+      if (db->is_set()) set_order_records(db, tmp.data(), tmp.size(), p.sort_by);
+    }
+    recount_log_rows(db, tmp.data(), tmp.size(), n, qlen[r]);
+  }
+  return 0;
+}
+
+void recount_host_result(kmcpg_db* db, const kmcpg_result* out) {
+  const ResultOwner* o = (const ResultOwner*)out->owner;
+  if (!o || !db->recount_on() || o->pairs_mode) return;
+  for (uint32_t r = 0; r < out->n_reads; r++) recount_log_rows(db, o->matches.data() + o->offs[r], o->offs[(size_t)r + 1] - o->offs[r], o->qkmers[r], o->qlen[r]);
+}
+
 // counts in o->offs[1 ..] -> offsets, and the result's pointers
 void result_publish(ResultOwner* o, uint32_t n_reads, int k_used, kmcpg_result* out) {
   o->offs[0] = 0;

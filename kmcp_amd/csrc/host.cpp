@@ -167,6 +167,7 @@ int finish_raw(kmcpg_ticket* t, kmcpg_result* out, bool as_pairs) {
   // the reference statistics without K3 in front of them (KMCPG_DEVICE_FINALIZE=0): every read, from the finished (unfiltered) records
   if (rcf == 0 && t->db->refstats_on()) refstats_host_result(t->db, out);
   if (rcf == 0 && t->db->cooccur_on()) cooccur_host_result(t->db, out);  // ... and the shared reads of reference pairs likewise
+  if (rcf == 0 && t->db->recount_on()) recount_host_result(t->db, out);  // ... and the recount's host log
   // the species-specific stage without K3 in front of it (KMCPG_DEVICE_FINALIZE=0): the rule on the finished records
   if (rcf == 0 && t->db->spec_on()) specific_filter_result(t->db, out);
   return rcf;
@@ -457,6 +458,7 @@ int submit_handle(kmcpg_db* db, const kmcpg_params* params, kmcpg_params* p) {
   if (int rcs = specific_refuse_params(db, *p)) return rcs;
   if (int rcs = refstats_refuse_params(db, *p)) return rcs;
   if (int rcs = cooccur_refuse_params(db, *p)) return rcs;
+  if (int rcs = recount_refuse_params(db, *p)) return rcs;
   return set_refuse_params(db, *p);
 }
 
@@ -611,6 +613,7 @@ static int search_batch_impl(kmcpg_db* db, const HostBatch& in, const kmcpg_para
     if (int rcs = specific_refuse_params(db, pp)) return rcs;
     if (int rcs = refstats_refuse_params(db, pp)) return rcs;
     if (int rcs = cooccur_refuse_params(db, pp)) return rcs;
+    if (int rcs = recount_refuse_params(db, pp)) return rcs;
     if (pp.min_matched >= 1 && in.offs[0] == 0 && (!in.offs2 || in.offs2[0] == 0)) rc = search_batch_pieces(db, in, pp, as_pairs, out, &took);
   }
   if (took && rc == 0) return 0;
@@ -623,6 +626,10 @@ static int search_batch_impl(kmcpg_db* db, const HostBatch& in, const kmcpg_para
   if (took && db->cooccur_on()) {  // ... and so would K7's table (kmcpg_cooccur_read refuses until kmcpg_cooccur_reset)
     std::lock_guard<std::mutex> g(db->co_mu);
     db->co_tainted = true;
+  }
+  if (took && db->recount_on()) {  // ... and K8's logs (kmcpg_recount_run refuses until kmcpg_recount_reset)
+    std::lock_guard<std::mutex> g(db->rc_mu);
+    db->rc_tainted = true;
   }
   if (took) memset(out, 0, sizeof *out);
   if (!took || rc == KMCPG_ENOMEM) {

@@ -297,7 +297,7 @@ int enqueue_query(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p, c
     rc = kmcpg_group_device(db, L->d_hits.p, L->d_cnt.p, L->d_hits.cap, L->d_qk.p, L->n, &p, L->d_pairs.p, L->d_roffs.p, st);
     if (rc) return rc;
     L->spec = db->spec_on();
-    L->rs = L->co = false;  // (a lane keeps its fields from batch to batch: the summary path below returns before K6's and K7's turn)
+    L->rs = L->co = L->rc8 = false;  // (a lane keeps its fields from batch to batch: the summary path below returns before K6's and K7's turn)
     // (a batch K5 summarises needs K3's last two words only: the pairs it kept, and its count of bad hits)
     const size_t skip = L->summarized() ? L->n : 0;
     HIPCHK(hipMemcpyAsync(L->h_roffs.p + skip, L->d_roffs.p + skip, ((size_t)L->n + 2 - skip) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
@@ -328,6 +328,8 @@ int enqueue_query(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p, c
     }
     L->rs = db->refstats_on();
     L->co = db->cooccur_on();
+    L->rc8 = db->recount_on();
+    if (L->rc8 && (L->d_left8.ensure(L->n) || L->h_left8.ensure(L->n) || (L->spec && L->h_roffs3.ensure((size_t)L->n + 1)))) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
     // (K7's buffers before K6 runs: K6 must stay the last step BEFORE any counting that can fail for want of memory — see below)
     if (L->co && (L->d_left7.ensure(L->n) || L->h_left7.ensure(L->n) || (L->spec && L->h_roffs3.ensure((size_t)L->n + 1)))) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
     if (L->rs) {
@@ -352,7 +354,17 @@ int enqueue_query(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p, c
       HIPCHK(hipMemcpyAsync(L->h_left7.p, L->d_left7.p, (size_t)L->n, hipMemcpyDeviceToHost, st));
       if (L->spec && !L->rs) HIPCHK(hipMemcpyAsync(L->h_roffs3.p, L->d_roffs.p, ((size_t)L->n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     }
-  } else L->spec = L->rs = L->co = false;
+    if (L->rc8) {
+      // K8's log kernel on K3's output, as K6 and K7 and behind them: it allocates nothing (its buffers were made above) and takes the
+      // reads' lengths from where the k-mer stage wrote them.  KMCPG_RECOUNT_DEVICE=0: every read goes to the host half
+      const char* e = getenv("KMCPG_RECOUNT_DEVICE");
+      const int32_t final_n = e && atoi(e) == 0 ? -1 : std::min<int32_t>(L->bound_n, kFprBoundAlways);
+      rc = recount_enqueue(db, L->d_pairs.p, L->d_roffs.p, L->d_hits.cap, L->d_qk.p, L->d_ql.p, L->n, final_n, L->d_cnt.p, L->d_hits.cap, L->d_left8.p, 0, st);
+      if (rc) return rc;
+      HIPCHK(hipMemcpyAsync(L->h_left8.p, L->d_left8.p, (size_t)L->n, hipMemcpyDeviceToHost, st));
+      if (L->spec && !L->rs && !L->co) HIPCHK(hipMemcpyAsync(L->h_roffs3.p, L->d_roffs.p, ((size_t)L->n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    }
+  } else L->spec = L->rs = L->co = L->rc8 = false;
   return 0;
 }
 
@@ -474,10 +486,12 @@ int enqueue(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p, bool ge
 }
 
 namespace {
-// the host half of K6 (k7 = false) or K7 for a finished batch: the reads its kernel LEFT, from K3's pairs
-int left_collect(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p, bool fetched, bool k7) {
-  const uint8_t* left = k7 ? L->h_left7.p : L->h_left.p;
-  const auto host_batch = k7 ? cooccur_host_batch : refstats_host_batch;
+// the host half of K6 (stage 6), K7 (7) or K8 (8) for a finished batch: the reads its kernel LEFT, from K3's pairs
+int left_collect(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p, bool fetched, int stage) {
+  const uint8_t* left = stage == 8 ? L->h_left8.p : stage == 7 ? L->h_left7.p : L->h_left.p;
+  const auto host_batch = [&](kmcpg_db* d, const kmcpg_pair* pairs, const uint64_t* offs, const int32_t* qk, uint32_t n, const kmcpg_params& pp, const uint8_t* lf) {
+    return stage == 8 ? recount_host_batch(d, pairs, offs, qk, L->h_ql.p, n, pp, lf) : stage == 7 ? cooccur_host_batch(d, pairs, offs, qk, n, pp, lf) : refstats_host_batch(d, pairs, offs, qk, n, pp, lf);
+  };
   bool any = false;
   for (uint32_t r = 0; r < L->n && !any; r++) any = left[r] != 0;
   if (!any) return 0;
@@ -509,6 +523,10 @@ int collect(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p, uint64_
       if (L->co && db->cooccur_on()) {
         std::lock_guard<std::mutex> g(db->co_mu);
         db->co_tainted = true;
+      }
+      if (L->rc8 && db->recount_on()) {
+        std::lock_guard<std::mutex> g(db->rc_mu);
+        db->rc_tainted = true;
       }
     }
   } taint{db, L};
@@ -554,11 +572,15 @@ int collect(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p, uint64_
   }
   if (L->rs && L->grouped && db->refstats_on()) {
     // the host half of K6: the reads the device LEFT, from K3's pairs — which are the lane's result itself, or, behind K4, still in d_pairs
-    int rc = left_collect(db, A, L, p, fetch, false);
+    int rc = left_collect(db, A, L, p, fetch, 6);
     if (rc) return rc;
   }
   if (L->co && L->grouped && db->cooccur_on()) {  // ... and of K7
-    int rc = left_collect(db, A, L, p, fetch, true);
+    int rc = left_collect(db, A, L, p, fetch, 7);
+    if (rc) return rc;
+  }
+  if (L->rc8 && L->grouped && db->recount_on()) {  // ... and of K8
+    int rc = left_collect(db, A, L, p, fetch, 8);
     if (rc) return rc;
   }
   // a batch large enough to say something about the data (one genome with 5 000 matches does not)

@@ -87,6 +87,9 @@ struct Lane {
   DevBuf<uint8_t> d_left7;
   PinBuf<uint8_t> h_left7;
   bool co = false;  // this batch went through K7
+  DevBuf<uint8_t> d_left8;
+  PinBuf<uint8_t> h_left8;
+  bool rc8 = false;  // this batch went through K8's log kernel
   bool spec = false;  // this batch went through K4: h_roffs / h_pairs hold ITS output, h_verd the verdicts
   // 2-bit packed upload (stage): the batch's bases as codes + the runs of foreign bytes instead of h_seqs; unpacked on the device
   PinBuf<uint8_t> h_pack;

@@ -24,14 +24,19 @@ namespace kmcpg {
 
 constexpr int REFSTATS_ROWS = 0, REFSTATS_FIRSTS = 1, REFSTATS_UREADS = 2, REFSTATS_HIC = 3, REFSTATS_WORDS = 4;
 
-// --mode 0..5: H = --min-hic-ureads-qcov, p = --min-chunks-fraction, and whether --keep-main-matches is on
+// --mode 0..5: H = --min-hic-ureads-qcov, p = --min-chunks-fraction, and whether --keep-main-matches is on; then what only stage 3 asks
+// (recount_rule.hpp): r = --min-chunks-reads, u = --min-uniq-reads, U = --min-hic-ureads, P = --min-hic-ureads-prop,
+// d = --max-chunks-depth-stdev (mode 3: the flags' defaults)
 struct RefstatsMode {
   double hic_min_qcov, min_chunks_fraction;
   bool keep_main;
+  uint64_t min_chunks_reads, min_uniq_reads, min_hic_ureads;
+  double min_hic_ureads_prop, max_chunks_depth_stdev;
 };
 constexpr int REFSTATS_MODES = 6, REFSTATS_DEFAULT_MODE = 3;
 inline RefstatsMode refstats_mode(int mode) {
-  constexpr RefstatsMode t[REFSTATS_MODES] = {{0.7, 0.2, true}, {0.7, 0.6, false}, {0.7, 0.7, false}, {0.75, 0.8, false}, {0.8, 1.0, false}, {0.8, 1.0, false}};
+  constexpr RefstatsMode t[REFSTATS_MODES] = {{0.7, 0.2, true, 1, 1, 1, 0.01, 10},    {0.7, 0.6, false, 5, 2, 1, 0.1, 2},    {0.7, 0.7, false, 10, 5, 2, 0.2, 2},
+                                               {0.75, 0.8, false, 50, 20, 5, 0.1, 2}, {0.8, 1.0, false, 100, 50, 10, 0.1, 2}, {0.8, 1.0, false, 100, 50, 10, 0.15, 1.5}};
   return t[mode];
 }
 

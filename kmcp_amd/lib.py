@@ -30,6 +30,7 @@ EXPORTS = [
     "kmcpg_summarize_device", "kmcpg_last_summary", "kmcpg_submit_windows_summary", "kmcpg_wait_summaries", "kmcpg_result_summaries_free",
     "kmcpg_set_refstats", "kmcpg_refstats_device", "kmcpg_refstats_read", "kmcpg_refstats_reset", "kmcpg_last_refstats",
     "kmcpg_set_cooccur", "kmcpg_cooccur_device", "kmcpg_cooccur_read", "kmcpg_cooccur_reset", "kmcpg_last_cooccur",
+    "kmcpg_set_recount", "kmcpg_recount_log_device", "kmcpg_recount_run", "kmcpg_recount_read", "kmcpg_recount_reset", "kmcpg_last_recount",
     "kmcpg_sketch_genomes_to", "kmcpg_builder_open", "kmcpg_builder_close", "kmcpg_builder_add_cols", "kmcpg_builder_plan",
     "kmcpg_builder_col_place", "kmcpg_builder_block_info", "kmcpg_builder_begin_round", "kmcpg_builder_scatter_device",
     "kmcpg_builder_end_round", "kmcpg_builder_finish", "kmcpg_builder_info",
@@ -284,6 +285,34 @@ class CooccurStats(C.Structure):
                 ("k7_ms", C.c_double)]
 
 
+RECOUNT_DTYPE = np.dtype([("match", "<u8"), ("uniq", "<u8"), ("hic", "<u8"), ("bases", "<u8")])  # kmcpg_recount_col, in units
+RECOUNT_CLASS_DTYPE = np.dtype([("kept", "<u4"), ("reserved", "<u4"), ("reads", "<u8"), ("ureads", "<u8")])  # kmcpg_recount_class
+RECOUNT_UNIT, RECOUNT_BASE_UNIT = 720720, 65536  # recount_rule.hpp: units per read, per base
+K8_LOG, K8_REPLAY = 64, 65  # KMCPG_K8_LOG, KMCPG_K8_REPLAY: kmcpg_k4_launch.kernel of K8's kernels
+
+
+class RecountParams(C.Structure):
+    """kmcpg_recount_params"""
+    _fields_ = [("one_minus_d", C.c_double), ("r_err", C.c_double), ("no_amb_corr", C.c_uint32), ("level_species", C.c_uint32)]
+
+
+class RecountTotals(C.Structure):
+    """kmcpg_recount_totals"""
+    _fields_ = [("recounted_reads", C.c_uint64), ("unique_reads", C.c_uint64), ("corrected_reads", C.c_uint64), ("single_reads", C.c_uint64),
+                ("replayed_reads", C.c_uint64), ("host_reads", C.c_uint64), ("left_full", C.c_uint64), ("skipped_launches", C.c_uint64),
+                ("log_bytes", C.c_uint64), ("log_bytes_used", C.c_uint64), ("logged_reads", C.c_uint64)]
+
+
+class RecountStats(C.Structure):
+    """kmcpg_recount_stats: the witness of the last k8_log launch and of the last replay"""
+    _fields_ = [("empty", C.c_uint64), ("single", C.c_uint64), ("logged", C.c_uint64), ("left", C.c_uint64), ("left_full", C.c_uint64),
+                ("lds_adds", C.c_uint64), ("global_adds", C.c_uint64), ("spilled_adds", C.c_uint64), ("skipped", C.c_uint64),
+                ("bad_segments", C.c_uint64), ("log_bytes_used", C.c_uint64), ("replay_reads", C.c_uint64), ("replay_recounted", C.c_uint64),
+                ("replay_corrected", C.c_uint64), ("replay_unique", C.c_uint64), ("replay_lookups", C.c_uint64), ("replay_lds_adds", C.c_uint64),
+                ("replay_global_adds", C.c_uint64), ("replay_spilled_adds", C.c_uint64), ("grid", C.c_uint32), ("slots", C.c_uint32),
+                ("replay_grid", C.c_uint32), ("reserved", C.c_uint32), ("log_ms", C.c_double), ("replay_ms", C.c_double)]
+
+
 class ResultSummaries(C.Structure):
     """kmcpg_result_summaries"""
     _fields_ = [("n_windows", C.c_uint32), ("reserved", C.c_uint32), ("qlen", C.POINTER(C.c_int32)), ("qkmers", C.POINTER(C.c_int32)),
@@ -472,6 +501,12 @@ def load():
     L.kmcpg_cooccur_read.argtypes = [vp, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(CooccurTotals)]
     L.kmcpg_cooccur_reset.argtypes = [vp]
     L.kmcpg_last_cooccur.argtypes = [vp, C.POINTER(CooccurStats), C.POINTER(K4Launch), C.c_uint32, C.POINTER(C.c_uint32)]
+    L.kmcpg_set_recount.argtypes = [vp, vp, vp, C.c_uint32, C.c_double, C.c_uint64]
+    L.kmcpg_recount_log_device.argtypes = [vp, vp, vp, C.c_uint64, vp, vp, C.c_uint32, C.c_int32, vp, C.c_uint64, vp, C.c_uint32, vp]
+    L.kmcpg_recount_run.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint64, C.POINTER(RecountParams)]
+    L.kmcpg_recount_read.argtypes = [vp, vp, C.c_uint32, C.POINTER(RecountTotals)]
+    L.kmcpg_recount_reset.argtypes = [vp]
+    L.kmcpg_last_recount.argtypes = [vp, C.POINTER(RecountStats), C.POINTER(K4Launch), C.c_uint32, C.POINTER(C.c_uint32)]
     L.kmcpg_sketch_genomes_to.argtypes = [vp, vp, vp, C.c_uint32, C.POINTER(SplitSpec), SKETCH_SINK, vp]
     u32p = C.POINTER(C.c_uint32)
     L.kmcpg_builder_open.argtypes = [C.POINTER(BuilderCfg), C.c_int32, C.POINTER(vp)]
@@ -1322,6 +1357,54 @@ class Database:
         _check(load().kmcpg_last_cooccur(self._h, C.byref(st), buf, n.value, C.byref(n)))
         self.last_k7_ms = float(st.k7_ms)  # HIP-event time of the kernel (profiling level >= 1), else -1
         return {f: int(getattr(st, f)) for f, _ in CooccurStats._fields_ if f != "k7_ms"}, [buf[i] for i in range(n.value)]
+
+    # ---- recount with ambiguity correction: K8, a log kernel behind K3 and a replay after the last batch ---------
+    def set_recount(self, target_class=None, species_class=None, hic_min_qcov=0.75, log_bytes=0):
+        """kmcpg_set_recount: one uint32 per global column each (species_class None: strain / assembly level); log_bytes: the read log in
+        device memory (0 = the default); no argument = off."""
+        if target_class is None:
+            _check(load().kmcpg_set_recount(self._h, None, None, 0, 0.0, 0))
+            self._n_recount_cols = 0
+            return
+        t = np.ascontiguousarray(target_class, dtype=np.uint32)
+        s = None if species_class is None else np.ascontiguousarray(species_class, dtype=np.uint32)
+        if s is not None and len(s) != len(t):
+            raise ValueError("target_class and species_class differ in length")
+        _check(load().kmcpg_set_recount(self._h, t.ctypes.data, None if s is None else s.ctypes.data, len(t), float(hic_min_qcov), int(log_bytes)))
+        self._n_recount_cols = len(t)
+
+    def recount_log_device(self, d_pairs, d_read_offs, pair_cap, d_qkmers, d_qlen, n_reads, final_n, d_left, d_n_hits=None, hit_cap=0, max_wgs=0, stream=None):
+        """kmcpg_recount_log_device on device pointers: K3's pairs and offsets -> the single-target counters, the read log and a LEFT byte per read."""
+        _check(load().kmcpg_recount_log_device(self._h, d_pairs, d_read_offs, pair_cap, d_qkmers, d_qlen, n_reads, final_n, d_n_hits, hit_cap, d_left, max_wgs, stream))
+
+    def recount_run(self, classes, pairs, min_dreads_prop=0.05, max_mismatch_err=0.05, no_amb_corr=False, level_species=True):
+        """kmcpg_recount_run: classes RECOUNT_CLASS_DTYPE [n_classes] (kept, reads, ureads of stage 1), pairs COOCCUR_DTYPE as cooccur_read
+        returns them; replays the logs (they are kept: the call can be repeated with other arguments)."""
+        c = np.ascontiguousarray(classes, dtype=RECOUNT_CLASS_DTYPE)
+        p = np.ascontiguousarray(pairs, dtype=COOCCUR_DTYPE)
+        par = RecountParams(1 - float(min_dreads_prop), float(max_mismatch_err), int(bool(no_amb_corr)), int(bool(level_species)))
+        _check(load().kmcpg_recount_run(self._h, c.ctypes.data if len(c) else None, len(c), p.ctypes.data if len(p) else None, len(p), C.byref(par)))
+
+    def recount_read(self):
+        """kmcpg_recount_read: (RECOUNT_DTYPE [n_cols] in units, dict of the totals) — single-target reads + device replay + host replay"""
+        n = getattr(self, "_n_recount_cols", 0)
+        out = np.zeros(n, dtype=RECOUNT_DTYPE)
+        tot = RecountTotals()
+        _check(load().kmcpg_recount_read(self._h, out.ctypes.data if n else None, n, C.byref(tot)))
+        return out, {f: int(getattr(tot, f)) for f, _ in RecountTotals._fields_}
+
+    def recount_reset(self):
+        _check(load().kmcpg_recount_reset(self._h))
+
+    def last_recount(self):
+        """kmcpg_last_recount: (dict of the counters, [K4Launch] of the last k8_log launch and the last replay — empty below profiling level 1)"""
+        st = RecountStats()
+        n = C.c_uint32(0)
+        _check(load().kmcpg_last_recount(self._h, C.byref(st), None, 0, C.byref(n)))
+        buf = (K4Launch * max(1, n.value))()
+        _check(load().kmcpg_last_recount(self._h, C.byref(st), buf, n.value, C.byref(n)))
+        self.last_k8_log_ms, self.last_k8_replay_ms = float(st.log_ms), float(st.replay_ms)
+        return {f: int(getattr(st, f)) for f, _ in RecountStats._fields_ if f not in ("log_ms", "replay_ms", "reserved")}, [buf[i] for i in range(n.value)]
 
     # ---- window summaries for region merging: K5 behind K4 ------------------------------------------------------
     def summarize_device(self, d_pairs, d_offs, pair_cap, d_verdicts, d_qkmers, n, d_out, d_left_pairs, left_cap, d_left_offs, stream=None):
