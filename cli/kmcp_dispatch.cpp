@@ -6,7 +6,7 @@
 //   kmcp [persistent flags] utils index-density | ref-info ...
 //                                       -> kmcp-inspect (index inspection on the GPU; kmcp/cmd/index-density.go, ref-info.go)
 //   kmcp [persistent flags] utils ref-stats ...
-//                                       -> kmcp-refstats (stage 1/4 of kmcp profile on a search result and, with --cooccur FILE, stage 2/4, with --recount FILE, stage 3/4;
+//                                       -> kmcp-refstats (stage 1/4 of kmcp profile on a search result and, with --cooccur FILE, stage 2/4, with --recount FILE, stage 3/4, with --profile FILE, stage 4/4: the abundances by EM;
 //                                          a spelling of this build)
 //   kmcp <any other command> ...        -> the reference binary named by $KMCP_REFERENCE_BIN, or the next `kmcp` on PATH that
 //                                          is not this file (compute / index / profile / the other utils are out of scope of this build,
@@ -114,7 +114,8 @@ int main(int argc, char** argv) {
           "  kmcp utils ref-info -d <db> [flags]             k-mers and false-positive rate of every reference chunk (kmcp-inspect)\n"
           "  kmcp utils ref-stats [flags] <search results>   reads, unique reads and covered chunks per reference; with --cooccur FILE the\n"
           "                                                  reads shared by every pair of kept references, with --recount FILE the\n"
-          "                                                  reads recounted with ambiguity correction (kmcp-refstats)\n\n"
+          "                                                  reads recounted with ambiguity correction, with --profile FILE the\n"
+          "                                                  table of references with abundances estimated by EM (kmcp-refstats)\n\n"
           "Every other kmcp command (compute, index, profile, the other utils, ...) is handed to the reference binary:\n"
           "$KMCP_REFERENCE_BIN, or the next `kmcp` on PATH.\n", help ? stdout : stderr);
     return help ? 0 : 255;

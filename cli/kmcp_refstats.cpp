@@ -5,6 +5,7 @@
 //   kmcp-refstats [-o out.tsv[.gz]] [--cooccur pairs.tsv[.gz]] [-f 0.01] [-t 0.55] [-n 0] [--keep-perfect-matches] [--keep-main-matches] [--max-qcov-gap 0.4]
 //                 [-m 3] [-p frac] [-H qcov] [--level species|strain|assembly] [-T map.tsv[,more.tsv]]... [-X taxdump/] [-i list.txt]
 //                 [--recount recount.tsv[.gz]] [-r n] [-u n] [-U n] [-P prop] [-d stdev] [-D 0.05] [-R 0.05] [--no-amb-corr] [--norm-abund mean|min|max]
+//                 [--profile profile.tsv[.gz]] [-I 10] [--abund-pct-threshold 0.01] [-F 0]
 //                 [a.tsv[.gz] ...]
 //
 // Semantics restated from the reference (the counting rule, the verdict and the presets are kmcp_amd/csrc/refstats_rule.hpp):
@@ -19,6 +20,12 @@
 //   * --recount FILE: stage 3/4 ("recounting matches and unique matches", profile.go:1282-1888) after stages 1 and 2 — the rule, the
 //     reference's quirk and our tie order are kmcp_amd/csrc/recount_rule.hpp, the file's format is cli/recount_format.hpp; -r -u -U -P -d
 //     come from -m and are overridden only when given, -D -R --no-amb-corr --norm-abund are the reference's.
+//   * --profile FILE: stage 4/4 ("estimating abundance using EM algorithm", profile.go:1907-2570, its end :2786-2853) after stages 1-3,
+//     whether or not their files are asked for — the rule, the loop and our tie orders are kmcp_amd/csrc/em_rule.hpp, the table's format
+//     is cli/profile_format.hpp; -I --abund-pct-threshold -F are the reference's.  The rows are kept in memory after stage 3 (about 56 bytes
+//     per row of a reference stage 3 judged ok, and the distinct query names of one input at a time) and every
+//     pass applies the row cuts after the skip of the rows outside ITS whitelist, as profile.go:2039-2226 does.  -m 0 is refused: its
+//     final order rests on the score column, which this tool does not compute.
 // The reference prints none of this (it goes on to stages 2-4); the output format is this tool's:
 //   # matched reads: N
 //   # unique reads: U
@@ -42,6 +49,8 @@
 #include "../kmcp_amd/csrc/recount_rule.hpp"
 #include "../kmcp_amd/csrc/refstats_rule.hpp"
 #include "../kmcp_amd/csrc/taxonomy.hpp"
+#include "../kmcp_amd/csrc/em_rule.hpp"
+#include "profile_format.hpp"
 #include "recount_format.hpp"
 #include "tsv_in.hpp"
 #include "tsv_out.hpp"
@@ -85,7 +94,13 @@ void usage() {
       "  -D, --min-dreads-prop float       Minimum proportion of distinct reads, for determing the right reference for ambiguous reads. (default 0.05)\n"
       "  -R, --max-mismatch-err float      Maximum error rate of a read being matched to a wrong reference. (default 0.05)\n"
       "      --no-amb-corr                 Do not correct ambiguous reads.\n"
-      "      --norm-abund string           Method for normalizing abundance of a reference by the mean/min/max abundance in all chunks. (default \"mean\")\n",
+      "      --norm-abund string           Method for normalizing abundance of a reference by the mean/min/max abundance in all chunks. (default \"mean\")\n"
+      "      --profile string              Also estimate the abundances by EM (stage 4/4 of kmcp profile) and write the table of references\n"
+      "                                    into this file, supports a \".gz\" suffix. Stdin and -m 0 are not supported.\n"
+      "                                    The rows of the references stage 3 keeps stay in memory for the passes: about 56 bytes per row.\n"
+      "  -I, --abund-max-iters int         Maximum iteration of abundance estimation. (default 10)\n"
+      "      --abund-pct-threshold float   If the percentage change of the predominant target is smaller than this threshold, stop the iteration. (default 0.01)\n"
+      "  -F, --filter-low-pct float        Filter out predictions with the smallest relative abundances summing up X%. Range: [0,100). (default 0)\n",
       stderr);
 }
 
@@ -147,7 +162,9 @@ bool parse_row(const char* p, size_t n, double min_qcov, double max_fpr, Fields*
 }  // namespace
 
 int main(int argc, char** argv) {
-  std::string out_file = "-", level = "species", taxdump, infile_list, cooccur_file, recount_file, norm_abund = "mean";
+  std::string out_file = "-", level = "species", taxdump, infile_list, cooccur_file, recount_file, norm_abund = "mean", profile_file;
+  long max_iters = 10;
+  double pct_threshold = 0.01, filter_low_pct = 0;
   long flag_r = 50, flag_u = 20, flag_U = 5;
   double flag_P = 0.1, flag_d = 2, flag_D = 0.05, flag_R = 0.05;
   bool given_r = false, given_u = false, given_U = false, given_P = false, given_d = false, no_amb_corr = false;
@@ -208,6 +225,10 @@ int main(int argc, char** argv) {
     else if (a == "-R" || a == "--max-mismatch-err") flag_R = num("-R, --max-mismatch-err", need(i));
     else if (a == "--no-amb-corr") no_amb_corr = true;
     else if (a == "--norm-abund") norm_abund = need(i);
+    else if (a == "--profile") profile_file = need(i);
+    else if (a == "-I" || a == "--abund-max-iters") max_iters = integer("-I, --abund-max-iters", need(i));
+    else if (a == "--abund-pct-threshold") pct_threshold = num("--abund-pct-threshold", need(i));
+    else if (a == "-F" || a == "--filter-low-pct") filter_low_pct = num("-F, --filter-low-pct", need(i));
     else if (a == "-j" || a == "--threads" || a == "--log") need(i);  // accepted for command-line compatibility
     else if (a == "-q" || a == "--quiet") {
     } else if (a == "-h" || a == "--help") {
@@ -236,6 +257,10 @@ int main(int argc, char** argv) {
   if (flag_D > 1) die("the value of -D/--min-dreads-prop (%f) should be in range of (0, 1]", flag_D);
   if (flag_R <= 0) die("value of flag --max-mismatch-err should be greater than 0");
   if (flag_R >= 1) die("the value of -R/--max-mismatch-err (%f) should be in range of (0, 1)", flag_R);
+  if (max_iters <= 0) die("value of flag --abund-max-iters should be greater than 0");
+  if (pct_threshold <= 0) die("value of flag --abund-pct-threshold should be greater than 0");
+  if (filter_low_pct < 0 || filter_low_pct >= 100) die("the value of -F/--filter-low-pct (%f) should be in range of [0, 100)", filter_low_pct);
+  if (!profile_file.empty() && mode == 0) die("flag --profile: -m 0 is not supported (its final order rests on the score column)");
   for (char& c : norm_abund) c = (char)tolower((unsigned char)c);
   if (norm_abund != "mean" && norm_abund != "min" && norm_abund != "max") die("invalid value of --norm-abund: %s. available: mean, min, max", norm_abund.c_str());
   kmcpg::RefstatsMode preset = kmcpg::refstats_mode((int)mode);
@@ -290,6 +315,17 @@ int main(int argc, char** argv) {
     if (!cooccur_file.empty() && (recount_file == "-" ? cooccur_file == "-" : tsv_in::clean_path(recount_file) == tsv_in::clean_path(cooccur_file)))
       die("flag --recount: the file must not be the --cooccur file");
   }
+  if (!profile_file.empty()) {  // before anything is read
+    for (const std::string& f : files) {
+      if (f == "-") die("flag --profile: stdin is not supported (the search results are read four times)");
+      if (tsv_in::clean_path(f) == tsv_in::clean_path(profile_file)) die("flag --profile: the file should not be one of the input file");
+    }
+    const auto same = [&](const std::string& other) { return profile_file == "-" ? other == "-" : tsv_in::clean_path(profile_file) == tsv_in::clean_path(other); };
+    if (same(out_file)) die("flag --profile: the file must not be the out file (-o)");
+    if (!cooccur_file.empty() && same(cooccur_file)) die("flag --profile: the file must not be the --cooccur file");
+    if (!recount_file.empty() && same(recount_file)) die("flag --profile: the file must not be the --recount file");
+  }
+  const bool stage3 = !recount_file.empty() || !profile_file.empty();
   th.min_chunks_fraction = min_frac;
 
   kmcpg::TaxidMap tmap;
@@ -385,7 +421,7 @@ int main(int argc, char** argv) {
 
   // stage 2/4 (profile.go:1117-1279): the inputs once more; a query's targets are a set (chunks of one reference are one target)
   std::unordered_map<uint64_t, uint64_t> shared;  // cooccur_key of two target classes -> queries
-  if (!cooccur_file.empty() || !recount_file.empty()) {
+  if (!cooccur_file.empty() || stage3) {
     kmcpg::CooccurCut cut2;
     cut2.cut = cut;
     for (const std::string& file : files) {
@@ -424,7 +460,7 @@ int main(int argc, char** argv) {
   // stage 3/4 (profile.go:1282-1888): the inputs a third time; the kept rows are stage 2's, the rest is recount_rule.hpp
   std::vector<uint64_t> recounted;  // RECOUNT_WORDS per column, laid out as `counters`
   uint64_t n_recounted = 0, n_unique3 = 0, n_corrected = 0;
-  if (!recount_file.empty()) {
+  if (stage3) {
     recounted.assign(counters.size() / kmcpg::REFSTATS_WORDS * kmcpg::RECOUNT_WORDS, 0);
     std::vector<kmcpg::RecountClass> classes(refs.size());
     for (const auto& kv : refs) classes[kv.second.target_class] = kmcpg::RecountClass{kv.second.ok ? 1u : 0u, kv.second.reads, kv.second.ureads};
@@ -483,6 +519,122 @@ int main(int argc, char** argv) {
     }
   }
 
+  // stage 4/4 (profile.go:1907-2570): the rows of the references stage 3 lists as ok, kept in memory; a pass is em_rule.hpp over them
+  std::vector<kmcpg::EmClass> em_classes;
+  kmcpg::EmResult em_res;
+  std::vector<uint32_t> em_order;
+  if (!profile_file.empty()) {
+    const size_t n_cols = counters.size() / kmcpg::REFSTATS_WORDS;
+    em_classes.resize(refs.size());
+    std::vector<uint8_t> est(refs.size(), 0);
+    std::vector<double> cov(refs.size(), 0.0);
+    for (const auto& kv : refs) {
+      const Ref& r = kv.second;
+      kmcpg::EmClass& c = em_classes[r.target_class];
+      c.name = kv.first, c.tlen = r.tlen;
+      for (uint64_t k = 0; k < r.chunks; k++) c.columns.push_back(r.base + k);
+      const uint64_t* w = recounted.data() + r.base * kmcpg::RECOUNT_WORDS;
+      const kmcpg::RecountRef t = kmcpg::recount_rollup(r.chunks, r.tlen, th, [&](uint64_t k) { return w + k * kmcpg::RECOUNT_WORDS; });
+      est[r.target_class] = kmcpg::em_start(t, &cov[r.target_class]) ? 1 : 0;
+    }
+    // the log: every row of a reference on the first whitelist that passed -t / -f, with the name of its query (per file) and whether the
+    // rows of its run of equal query names — all of them, whatever their reference — name ONE target (em_rule.hpp: such a read is
+    // counted by K8's single rule)
+    struct LogRow {
+      kmcpg::RecountRow row;
+      uint32_t file, query;
+      bool run_single;
+    };
+    std::vector<LogRow> log;
+    {
+      std::unordered_map<std::string, uint32_t> query_ids;
+      std::string qname, first_target;
+      for (size_t fi = 0; fi < files.size(); fi++) {
+        RawLines in(files[fi]);
+        query_ids.clear();
+        std::string run;  // the query name of the previous row that passed -t / -f
+        bool any = false, single = true;
+        size_t run_from = log.size();
+        auto end_run = [&] {
+          for (size_t i = run_from; i < log.size(); i++) log[i].run_single = single;
+          run_from = log.size(), single = true;
+        };
+        const char* p = nullptr;
+        size_t n = 0;
+        while (in.next(&p, &n)) {
+          Fields fl;
+          double qcov = 0;
+          if (!parse_row(p, n, min_qcov, max_fpr, &fl, &qcov)) continue;
+          const char* fp;
+          size_t fn = fl.get(6, &fp);
+          name.assign(fp, fn);
+          if (!any || run.size() != fl.tab[0] || memcmp(run.data(), p, fl.tab[0]) != 0) {
+            end_run();
+            run.assign(p, fl.tab[0]), any = true, first_target = name;
+          } else if (name != first_target) single = false;
+          const auto it = refs.find(name);
+          if (it == refs.end() || !est[it->second.target_class]) continue;
+          uint64_t qlen = 0, chunk_idx = 0;
+          bool neg = false;
+          fn = fl.get(2, &fp);
+          if (!parse_int(fp, fn, true, &qlen, &neg) || neg) qlen = 0;
+          fn = fl.get(7, &fp);
+          if (!parse_int(fp, fn, true, &chunk_idx, &neg) || neg || chunk_idx >= it->second.chunks) die("chunkIdx of %s is outside its chunks", name.c_str());
+          const uint32_t q = query_ids.emplace(run, (uint32_t)query_ids.size()).first->second;
+          log.push_back(LogRow{kmcpg::RecountRow{it->second.target_class, it->second.species_class, it->second.base + chunk_idx, qcov, qlen}, (uint32_t)fi, q, false});
+        }
+        end_run();
+      }
+    }
+    kmcpg::EmParams ep;
+    ep.th = th, ep.max_iters = (int)std::min<long>(max_iters, INT32_MAX - 1), ep.pct_threshold = pct_threshold;
+    const auto pass = [&](const std::vector<uint8_t>& e, const std::vector<double>& cv, std::vector<kmcpg::EmChunk>* cols, uint64_t* assigned) {
+      cols->assign(n_cols, kmcpg::EmChunk());
+      *assigned = 0;
+      kmcpg::CooccurCut cut4;
+      cut4.cut = cut;
+      std::vector<kmcpg::RecountRow> rows;
+      bool single = true, any = false;
+      uint32_t file = 0, query = 0;
+      auto flush = [&] {
+        if (rows.empty()) return;
+        (*assigned)++;
+        if (single) {  // one target in the whole table: K8's single rule, in its units
+          const uint64_t m = rows.size();
+          for (size_t i = 0; i < rows.size(); i++) {
+            kmcpg::EmChunk& w = (*cols)[rows[i].column];
+            const uint64_t u = i == 0 ? kmcpg::EM_UNIT : 0;
+            w.match += kmcpg::em_single_share(m, i == 0), w.uniq += u, w.hic += rows[i].qcov >= H ? u : 0;
+            w.single_bases += kmcpg::recount_bases(rows[i].qlen, 1, m);
+          }
+        } else {
+          kmcpg::em_query(rows.data(), rows.size(), cv.data(), H, level_species, [&](uint64_t col, int w, uint64_t x) {
+            kmcpg::EmChunk& c = (*cols)[col];
+            (w == kmcpg::EM_MATCH ? c.match : w == kmcpg::EM_UNIQ ? c.uniq : w == kmcpg::EM_HIC ? c.hic : w == kmcpg::EM_BASES_LO ? c.bases_lo : c.bases_hi) += x;
+          });
+        }
+        rows.clear();
+      };
+      for (const LogRow& l : log) {
+        const bool kept = e[l.row.target_class] != 0;
+        const bool new_name = !any || l.file != file || l.query != query;
+        if (any && l.file != file) flush(), any = false, cut4 = kmcpg::CooccurCut{cut};  // (a file ends its last query)
+        bool opens = false;
+        const bool take = cut4.row(kept, new_name, l.row.qcov, &opens);
+        if (!kept) continue;
+        if (opens) flush(), single = true;
+        file = l.file, query = l.query, any = true;
+        if (!take) continue;
+        single = single && l.run_single;
+        rows.push_back(l.row);
+      }
+      flush();
+      return 0;
+    };
+    if (kmcpg::em_run(em_classes, est, cov, ep, pass, &em_res) != 0) die("the EM loop failed");
+    em_order = kmcpg::em_finish(em_classes, filter_low_pct, &em_res);
+  }
+
   Out out(out_file, -1);
   char line[256];
   out.write(line, (size_t)snprintf(line, sizeof line, "# matched reads: %llu\n# unique reads: %llu\n", (unsigned long long)matched, (unsigned long long)unique));
@@ -515,6 +667,12 @@ int main(int argc, char** argv) {
     Out rc(recount_file, -1);
     recount_format::write(rc, list, n_recounted, n_unique3, n_corrected, th);
     rc.close();
+  }
+
+  if (!profile_file.empty()) {
+    Out pf(profile_file, -1);
+    profile_format::write(pf, em_classes, em_res, em_order);
+    pf.close();
   }
 
   if (!cooccur_file.empty()) {

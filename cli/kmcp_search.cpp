@@ -105,6 +105,12 @@ struct Options {
   double ref_stats_d = 0.05, ref_stats_r = 0.05;
   long long ref_stats_recount_log_mb = -1;  // the read log in device memory; -1: the library's default
   const char* recount_flag = nullptr;       // the first of the four optional flags that was given
+  // --ref-stats-profile FILE [--ref-stats-abund-max-iters I] [--ref-stats-abund-pct-threshold X] [--ref-stats-filter-low-pct F]: stage 4/4
+  // behind the three — the abundances by EM over the logs stage 3 keeps; the file is what kmcp-refstats --profile writes from the search result
+  std::string ref_stats_profile;
+  long long ref_stats_iters = 10;
+  double ref_stats_pct = 0.01, ref_stats_filter = 0;
+  const char* profile_flag = nullptr;       // the first of the three optional flags that was given
   std::vector<std::string> also_dbs;  // --also-db: further databases searched in the same pass, the output merged as kmcp-merge would
   bool gpus_given = false;
   int min_qlen = 30, min_kmers = 10, dedup = 256, top_scores = 0, threads = 0, device = 0, batch = 131072, gpus = 1, gpu_passes = -1;
@@ -158,7 +164,9 @@ static void usage() {
       "                             [--ref-stats-level species|strain|assembly] [--taxid-map file(s) --taxdump dir]\n"
       "                             [--ref-stats-cooccur file [--ref-stats-cooccur-slots int]]\n"
       "                             [--ref-stats-recount file [--ref-stats-no-amb-corr] [--ref-stats-min-dreads-prop float (0.05)]\n"
-      "                              [--ref-stats-max-mismatch-err float (0.05)] [--ref-stats-recount-log-mb int]]\n"
+      "                              [--ref-stats-max-mismatch-err float (0.05)] [--ref-stats-recount-log-mb int]\n"
+      "                              [--ref-stats-profile file [--ref-stats-abund-max-iters int (10)] [--ref-stats-abund-pct-threshold float (0.01)]\n"
+      "                               [--ref-stats-filter-low-pct float (0)]]]\n"
       "                             count, on the GPU while the search runs, what stage 1/4 of `kmcp profile` counts per reference (reads,\n"
       "                             uniquely matched reads, high-confidence ones, chunks covered) and judge which references are in the\n"
       "                             sample: the file is what `kmcp-refstats -f 1 -t 0 -m N --level L ...` writes from this command's\n"
@@ -168,6 +176,8 @@ static void usage() {
       "                             --ref-stats-recount (with --ref-stats and --ref-stats-cooccur): stage 3/4 as well — the reads recounted\n"
       "                             with ambiguity correction and the references judged with the mode's thresholds; the file is what\n"
       "                             `kmcp-refstats ... --recount` writes from this command's output.\n"
+      "                             --ref-stats-profile (with --ref-stats-recount): stage 4/4 as well — the abundances estimated by EM on the\n"
+      "                             GPU, one pass per iteration over the reads stage 3 kept; the table `kmcp-refstats ... --profile` writes.\n"
       "           --parse-only (read the inputs and print records / bases / checksum per file; no database, no GPU)\n"
       "           --regions-bed file [--regions-min-overlap int (1)] [--regions-max-gap int (0)] [--regions-ignore-type]\n"
       "                             [--regions-name-species string] [--regions-name-assembly string]\n"
@@ -210,6 +220,7 @@ static Options parse_args(int argc, char** argv) {
       {"specific-level", 0, 1}, {"taxid-map", 0, 1}, {"taxdump", 0, 1},
       {"ref-stats", 0, 1}, {"ref-stats-mode", 0, 1}, {"ref-stats-min-hic-ureads-qcov", 0, 1}, {"ref-stats-min-chunks-fraction", 0, 1}, {"ref-stats-level", 0, 1}, {"ref-stats-cooccur", 0, 1}, {"ref-stats-cooccur-slots", 0, 1},
       {"ref-stats-recount", 0, 1}, {"ref-stats-no-amb-corr", 0, 0}, {"ref-stats-min-dreads-prop", 0, 1}, {"ref-stats-max-mismatch-err", 0, 1}, {"ref-stats-recount-log-mb", 0, 1},
+      {"ref-stats-profile", 0, 1}, {"ref-stats-abund-max-iters", 0, 1}, {"ref-stats-abund-pct-threshold", 0, 1}, {"ref-stats-filter-low-pct", 0, 1},
       {"regions-bed", 0, 1}, {"regions-min-overlap", 0, 1}, {"regions-max-gap", 0, 1}, {"regions-ignore-type", 0, 0},
       {"regions-name-species", 0, 1}, {"regions-name-assembly", 0, 1}};
   auto regions_flag = [&](const char* flag) {
@@ -274,6 +285,10 @@ static Options parse_args(int argc, char** argv) {
     else if (name == "ref-stats-min-dreads-prop") { o.ref_stats_d = to_f(name, v); if (!o.recount_flag) o.recount_flag = "--ref-stats-min-dreads-prop"; }
     else if (name == "ref-stats-max-mismatch-err") { o.ref_stats_r = to_f(name, v); if (!o.recount_flag) o.recount_flag = "--ref-stats-max-mismatch-err"; }
     else if (name == "ref-stats-recount-log-mb") { o.ref_stats_recount_log_mb = to_i(name, v); if (o.ref_stats_recount_log_mb < 0) o.ref_stats_recount_log_mb = 0; if (!o.recount_flag) o.recount_flag = "--ref-stats-recount-log-mb"; }
+    else if (name == "ref-stats-profile") o.ref_stats_profile = v;
+    else if (name == "ref-stats-abund-max-iters") { o.ref_stats_iters = to_i(name, v); if (!o.profile_flag) o.profile_flag = "--ref-stats-abund-max-iters"; }
+    else if (name == "ref-stats-abund-pct-threshold") { o.ref_stats_pct = to_f(name, v); if (!o.profile_flag) o.profile_flag = "--ref-stats-abund-pct-threshold"; }
+    else if (name == "ref-stats-filter-low-pct") { o.ref_stats_filter = to_f(name, v); if (!o.profile_flag) o.profile_flag = "--ref-stats-filter-low-pct"; }
     else if (name == "ref-stats-cooccur-slots") { o.ref_stats_cooccur_slots = to_i(name, v); if (!o.ref_stats_flag) o.ref_stats_flag = "--ref-stats-cooccur-slots"; }
     else if (name == "ref-stats-level") { o.ref_stats_level = v; for (char& c : o.ref_stats_level) c = (char)tolower((unsigned char)c); if (!o.ref_stats_flag) o.ref_stats_flag = "--ref-stats-level"; }
     else if (name == "specific-level") { o.specific_level = v; for (char& c : o.specific_level) c = (char)tolower((unsigned char)c); }
@@ -346,6 +361,7 @@ static Options parse_args(int argc, char** argv) {
 #include "../kmcp_amd/csrc/regions_rule.hpp"
 #include "../kmcp_amd/csrc/refstats_rule.hpp"
 #include "recount_format.hpp"
+#include "profile_format.hpp"
 #include "search_batch.hpp"
 #include "row_format.hpp"
 
@@ -525,6 +541,9 @@ static int validate_flags(const Options& o, bool sliding) {
   }
   // --ref-stats: the same refusals as --specific-level, for the same reason (what is counted must be every query's final matches, counted
   // once); mode 0 cuts rows of a query, which only the TSV route can do
+  if (o.ref_stats_profile.empty() && o.profile_flag) die("flag %s is only used with --ref-stats-profile", o.profile_flag);
+  if (!o.ref_stats_profile.empty() && o.ref_stats_recount.empty())
+    die("flag --ref-stats-profile is only used with --ref-stats-recount (stage 4 starts from the references stage 3 lists and from the reads it kept)");
   if (o.ref_stats_recount.empty() && o.recount_flag) die("flag %s is only used with --ref-stats-recount", o.recount_flag);
   if (!o.ref_stats_recount.empty() && (o.ref_stats.empty() || o.ref_stats_cooccur.empty()))
     die("flag --ref-stats-recount is only used with --ref-stats and --ref-stats-cooccur (stage 3 starts from the tables of stages 1 and 2)");
@@ -559,6 +578,15 @@ static int validate_flags(const Options& o, bool sliding) {
       if (o.ref_stats_recount_log_mb == 0 || o.ref_stats_recount_log_mb > 4096) die("the value of --ref-stats-recount-log-mb (%lld) should be in range of [1, 4096]", o.ref_stats_recount_log_mb);
       if (!(o.ref_stats_d > 0) || o.ref_stats_d > 1) die("the value of --ref-stats-min-dreads-prop (%f) should be in range of (0, 1]", o.ref_stats_d);
       if (!(o.ref_stats_r > 0) || !(o.ref_stats_r < 1)) die("the value of --ref-stats-max-mismatch-err (%f) should be in range of (0, 1)", o.ref_stats_r);
+    }
+    if (!o.ref_stats_profile.empty()) {
+      if (o.ref_stats_profile == o.out_file) die("flag --ref-stats-profile: the file must not be the search result's file");
+      if (o.ref_stats_profile == o.ref_stats) die("flag --ref-stats-profile: the file must not be the statistics file (--ref-stats)");
+      if (o.ref_stats_profile == o.ref_stats_cooccur) die("flag --ref-stats-profile: the file must not be the pairs' file (--ref-stats-cooccur)");
+      if (o.ref_stats_profile == o.ref_stats_recount) die("flag --ref-stats-profile: the file must not be the recount's file (--ref-stats-recount)");
+      if (o.ref_stats_iters <= 0 || o.ref_stats_iters > 1000000) die("the value of --ref-stats-abund-max-iters (%lld) should be in range of [1, 1000000]", o.ref_stats_iters);
+      if (!(o.ref_stats_pct > 0)) die("the value of --ref-stats-abund-pct-threshold (%f) should be greater than 0", o.ref_stats_pct);
+      if (!(o.ref_stats_filter >= 0) || !(o.ref_stats_filter < 100)) die("the value of --ref-stats-filter-low-pct (%f) should be in range of [0, 100)", o.ref_stats_filter);
     }
   }
   // sliding windows: seqkit sliding has no meaning for pairs, whole files as queries or one ID for everything
@@ -1207,8 +1235,9 @@ static std::vector<uint32_t> set_recount(const Options& o, kmcpg_db* db, const s
 // ... and the file, once stage 1 is rolled up and the pair table is read: the logs are replayed with both, and the references are written
 // by the formatter kmcp-refstats --recount uses.  All pairs go in: the rows of a reference stage 1 dropped are skipped at replay, so its
 // pairs are never asked for — with no row cut that equals the TSV route's skip
+typedef std::map<std::string, std::vector<uint64_t>> RecountCounters;  // per listed reference: RECOUNT_WORDS per chunk
 static void write_recount(const Options& o, kmcpg_db* db, const std::vector<std::string>& target, const std::vector<uint32_t>& cls,
-                          const std::map<std::string, Stage1Ref>& stage1, kmcpg_recount_totals* tot) {
+                          const std::map<std::string, Stage1Ref>& stage1, kmcpg_recount_totals* tot, RecountCounters* listed, kmcpg::RecountThresholds* thresholds) {
   uint32_t n_classes = 0;
   for (uint32_t c : cls) n_classes = std::max(n_classes, c + 1);
   std::vector<kmcpg_recount_class> classes(n_classes);
@@ -1225,7 +1254,7 @@ static void write_recount(const Options& o, kmcpg_db* db, const std::vector<std:
   const uint32_t n_cols = (uint32_t)target.size();
   std::vector<kmcpg_recount_col> cols(n_cols);
   if (kmcpg_recount_read(db, cols.data(), n_cols, tot) != 0) die("%s", kmcpg_last_error());
-  std::map<std::string, std::vector<uint64_t>> counters;  // per listed reference: RECOUNT_WORDS per chunk
+  RecountCounters& counters = *listed;
   for (uint32_t c = 0; c < n_cols; c++) {
     if (!cols[c].match && !cols[c].uniq && !cols[c].hic && !cols[c].bases) continue;
     const auto it = stage1.find(target[c]);
@@ -1248,6 +1277,63 @@ static void write_recount(const Options& o, kmcpg_db* db, const std::vector<std:
   th.min_chunks_fraction = o.ref_stats_p_given ? o.ref_stats_p : preset.min_chunks_fraction;
   tsv_out::Out out(o.ref_stats_recount, -1);
   recount_format::write(out, list, tot->recounted_reads, tot->unique_reads, tot->corrected_reads, th);
+  out.close();
+  *thresholds = th;
+}
+
+// --ref-stats-profile: stage 4/4 — em_run (kmcp_amd/csrc/em_rule.hpp) with kmcpg_em_pass as the pass, from the references stage 3 lists
+// (`listed`: their stage-3 counters) to the table kmcp-refstats --profile writes.  A reference's chunk is the sum of its columns of that
+// chunk, as in the files of the earlier stages
+static void write_profile(const Options& o, kmcpg_db* db, const std::vector<std::string>& target, const std::vector<uint32_t>& cls,
+                          const std::map<std::string, Stage1Ref>& stage1, const RecountCounters& listed, const kmcpg::RecountThresholds& th, kmcpg::EmResult* res,
+                          kmcpg_em_totals* tot) {
+  const uint32_t n_cols = (uint32_t)target.size();
+  uint32_t n_classes = 0;
+  for (uint32_t c : cls) n_classes = std::max(n_classes, c + 1);
+  std::vector<kmcpg::EmClass> classes(n_classes);
+  std::vector<uint8_t> est(n_classes, 0);
+  std::vector<double> cov(n_classes, 0.0);
+  std::vector<uint64_t> chunk_of(n_cols, UINT64_MAX);  // a column's place in the chunk table: its reference's first chunk + its own
+  uint64_t n_chunks = 0;
+  for (uint32_t c = 0; c < n_cols; c++) {
+    const auto it = listed.find(target[c]);
+    if (it == listed.end()) continue;
+    const Stage1Ref& s1 = stage1.at(target[c]);
+    kmcpg::EmClass& k = classes[cls[c]];
+    if (k.columns.empty()) {
+      k.name = target[c], k.tlen = s1.tlen;
+      for (uint64_t i = 0; i < s1.chunks; i++) k.columns.push_back(n_chunks++);
+      const uint64_t* w = it->second.data();
+      est[cls[c]] = kmcpg::em_start(kmcpg::recount_rollup(s1.chunks, s1.tlen, th, [&](uint64_t i) { return w + i * kmcpg::RECOUNT_WORDS; }), &cov[cls[c]]) ? 1 : 0;
+    }
+    uint32_t tidx = 0;
+    kmcpg_col_info(db, c, nullptr, &tidx, nullptr, nullptr);
+    if ((uint16_t)tidx < s1.chunks) chunk_of[c] = k.columns[(uint16_t)tidx];
+  }
+  std::vector<kmcpg_em_class> pass_classes(n_classes);
+  std::vector<kmcpg_em_col> cols(n_cols);
+  const uint32_t level_species = ref_stats_species(o) ? 1u : 0u;
+  const auto pass = [&](const std::vector<uint8_t>& e, const std::vector<double>& cv, std::vector<kmcpg::EmChunk>* chunks, uint64_t* assigned) {
+    for (uint32_t k = 0; k < n_classes; k++) pass_classes[k] = kmcpg_em_class{e[k] ? 1u : 0u, 0, cv[k]};
+    if (kmcpg_em_pass(db, pass_classes.data(), n_classes, level_species) != 0) return -1;
+    if (kmcpg_em_read(db, cols.data(), n_cols, tot) != 0) return -1;
+    chunks->assign(n_chunks, kmcpg::EmChunk());
+    for (uint32_t c = 0; c < n_cols; c++) {
+      if (chunk_of[c] == UINT64_MAX) continue;
+      kmcpg::EmChunk& w = (*chunks)[chunk_of[c]];
+      w.match += cols[c].match, w.uniq += cols[c].uniq, w.hic += cols[c].hic;
+      w.single_bases += cols[c].single_bases, w.bases_lo += cols[c].bases_lo, w.bases_hi += cols[c].bases_hi;
+    }
+    *assigned = tot->assigned_reads;
+    return 0;
+  };
+  kmcpg::EmParams ep;
+  ep.th = th, ep.max_iters = (int)o.ref_stats_iters, ep.pct_threshold = o.ref_stats_pct;
+  memset(tot, 0, sizeof *tot);
+  if (kmcpg::em_run(classes, est, cov, ep, pass, res) != 0) die("%s", kmcpg_last_error());
+  const std::vector<uint32_t> order = kmcpg::em_finish(classes, o.ref_stats_filter, res);
+  tsv_out::Out out(o.ref_stats_profile, -1);
+  profile_format::write(out, classes, *res, order);
   out.close();
 }
 
@@ -1743,11 +1829,21 @@ int main(int argc, char** argv) {
     }
     if (!o.ref_stats_recount.empty()) {
       kmcpg_recount_totals tot;
-      write_recount(o, p.db, p.target, recount_classes, stage1, &tot);
+      RecountCounters listed;
+      kmcpg::RecountThresholds th;
+      write_recount(o, p.db, p.target, recount_classes, stage1, &tot, &listed, &th);
       // (one line of its own, whatever -q says: the tests read it)
       fprintf(stderr, "%llu reads recounted, %llu of them replayed (%llu on the host, %llu for want of log room), %llu corrected\n", (unsigned long long)tot.recounted_reads,
               (unsigned long long)(tot.recounted_reads - tot.single_reads), (unsigned long long)tot.host_reads, (unsigned long long)tot.left_full,
               (unsigned long long)tot.corrected_reads);
+      if (!o.ref_stats_profile.empty()) {
+        kmcpg::EmResult res;
+        kmcpg_em_totals et;
+        write_profile(o, p.db, p.target, recount_classes, stage1, listed, th, &res, &et);
+        // (one line of its own, whatever -q says: the tests read it)
+        fprintf(stderr, "%d EM passes (%s), %llu reads assigned in the last, %llu of them split (%llu from the host log)\n", res.passes, res.converged ? "converged" : "not converged",
+                (unsigned long long)et.assigned_reads, (unsigned long long)et.split_reads, (unsigned long long)et.host_reads);
+      }
     }
   }
   // Everything the user asked for is on disk.  Giving back pinned staging buffers, streams and a resident index one by one takes

@@ -627,6 +627,47 @@ int kmcpg_recount_read(kmcpg_db* db, kmcpg_recount_col* out_cols, uint32_t n_col
 int kmcpg_recount_reset(kmcpg_db* db);
 int kmcpg_last_recount(kmcpg_db* db, kmcpg_recount_stats* out, kmcpg_k4_launch* launches, uint32_t cap, uint32_t* n_launches);
 
+/* -- abundance estimation by EM (K9, k9_em.hip): one PASS of stage 4/4 of `kmcp profile` (kmcp/cmd/profile.go:1907-2570;
+ *    kmcp_amd/csrc/em_rule.hpp states the rule: the integer shares of a read over its estimated targets, the two-word bases, the roll-up
+ *    and the loop).  A pass works on what the recount stage keeps: the read log in device memory, the host log and the single-target
+ *    counters; nothing is searched again.  Units: 2 952 069 120 (= 720720 << 12) per read; bases_lo / bases_hi hold the low 32 bits and the
+ *    rest of exact products qlen * share, in units of 1 / 2 952 069 120 base: bases = (bases_hi * 2^32 + bases_lo) / 2 952 069 120.
+ *    kmcpg_em_pass: classes[c] = {est: class c is in this pass's whitelist; coverage: its current coverage}, for every class of the
+ *    recount stage's target_class.  KMCPG_EINVAL with the recount stage off, and for an estimated class whose coverage is not finite and
+ *    > 0; KMCPG_EDEVICE after a tainted batch, as kmcpg_recount_run.  It waits for the device, zeroes its own pass counters (allocated on
+ *    first use, freed with the recount stage), runs k9_em over the device log and the same rule over the host log.  It does not touch
+ *    what kmcpg_recount_run / kmcpg_recount_read work on, and can be repeated with other classes without a new search.
+ *    kmcpg_em_read: per column, the single-target reads' counters if the column's class is estimated (match, uniq, hic << 12; their bases
+ *    apart, in units of 2^-16 base) plus both halves of the pass; valid after kmcpg_em_pass.
+ *    kmcpg_last_em: the witness of the last k9_em launch (the call waits for the device to go idle).
+ *    KMCPG_EM_SLOTS (read by kmcpg_em_pass): slots of a workgroup's LDS table, a power of two up to 1024 (anything else is KMCPG_EINVAL),
+ *    0 = no table, every add is a global atomic; default 0.  The grid is bounded as K8's (KMCPG_RECOUNT_WGS). */
+typedef struct {
+  uint32_t est, reserved;
+  double coverage;
+} kmcpg_em_class;
+typedef struct {
+  uint64_t match, uniq, hic;    /* units of 1 / 2 952 069 120 read, single-target reads included */
+  uint64_t single_bases;        /* the single-target reads' bases, units of 2^-16 base */
+  uint64_t bases_lo, bases_hi;  /* the pass's bases, see above */
+} kmcpg_em_col;
+typedef struct {
+  uint64_t assigned_reads;  /* reads with at least one estimated target */
+  uint64_t unique_reads;    /* of those, with exactly one */
+  uint64_t split_reads;     /* ... with several: shared out by coverage */
+  uint64_t host_reads;      /* of assigned_reads, from the host log */
+} kmcpg_em_totals;
+enum { KMCPG_K9_EM = 66 };  /* kmcpg_k4_launch.kernel of K9 */
+typedef struct {
+  uint64_t reads, none, one, split;              /* k9_em: logged reads; with no / one / several estimated targets */
+  uint64_t lds_adds, global_adds, spilled_adds;  /* spilled_adds is part of global_adds */
+  uint32_t grid, slots;
+  double em_ms;                                  /* HIP-event time at profiling level >= 1; -1 otherwise */
+} kmcpg_em_stats;
+int kmcpg_em_pass(kmcpg_db* db, const kmcpg_em_class* classes, uint32_t n_classes, uint32_t level_species);
+int kmcpg_em_read(kmcpg_db* db, kmcpg_em_col* out_cols, uint32_t n_cols, kmcpg_em_totals* totals);
+int kmcpg_last_em(kmcpg_db* db, kmcpg_em_stats* out, kmcpg_k4_launch* launches, uint32_t cap, uint32_t* n_launches);
+
 /* -- benchmarking / full-size parity support (no counterpart in the reference) ------------------ */
 typedef struct {
   int32_t k;            /* 21 */

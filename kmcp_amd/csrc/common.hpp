@@ -374,5 +374,28 @@ struct K8ReplayArgs {
   unsigned long long* stats;           // [K8_R_STATS], zero on entry
 };
 
+// K9 (k9_em.hip): one pass of stage 4 of `kmcp profile` (em_rule.hpp) over K8's read log: every logged read is shared out over its
+// estimated targets in proportion to their coverage; five 64-bit counters per column (match, uniq, hic, bases_lo, bases_hi).
+// The workgroup's table in LDS: 44 bytes per slot (five 64-bit counters and the key), 1024 slots = 44 KiB — two workgroups per CU take
+// 88 KiB of the CU's 160 KiB.  The default is 0, plain global atomics: the table gained nothing on either sample of tools/bench_em.py
+// (0.371 against 0.317 ms and 0.334 against 0.329 ms per pass)
+constexpr uint32_t K9_MAX_SLOTS = 1024, K9_DEFAULT_SLOTS = 0, K9_PROBES = 8;
+// the witness: logged reads, of those with no / one / several estimated targets; adds to LDS / to global memory (flushes and spills) / of
+// those the spills
+enum { K9_READS = 0, K9_NONE, K9_ONE, K9_SPLIT, K9_LDS_ADDS, K9_GLOBAL_ADDS, K9_SPILLED, K9_STATS };
+struct K9Args {
+  const unsigned long long* log;       // the read log (K8LogArgs) ...
+  uint64_t log_cap;
+  uint64_t n_logged;                   // ... and its reads
+  uint32_t n_cols, n_classes;
+  uint32_t slots;                      // table slots per workgroup: a power of two up to K9_MAX_SLOTS, or 0 = every add goes to global memory
+  uint32_t level_species;
+  const uint32_t* target_class;        // [n_cols]
+  const uint32_t* species_class;       // [n_cols] or nullptr: strain / assembly level
+  const kmcpg_em_class* classes;       // [n_classes] the pass's whitelist and coverages
+  double hic_min_qcov;
+  unsigned long long* counters;        // [5 * n_cols] the pass's counters, zero on entry
+  unsigned long long* stats;           // [K9_STATS], zero on entry
+};
 
 }  // namespace kmcpg

@@ -847,8 +847,9 @@ extern "C" int kmcpg_close(kmcpg_db* db) {
     if (ev) (void)hipEventDestroy(ev);
   for (void* q : {(void*)db->d_rc_target, (void*)db->d_rc_species, (void*)db->d_rc_counters, (void*)db->d_rc_replay, (void*)db->d_rc_log, (void*)db->d_rc_words})
     if (q) (void)hipFree(q);
-  for (hipEvent_t ev : {db->rc_ev[0], db->rc_ev[1], db->rc_rev[0], db->rc_rev[1]})
+  for (hipEvent_t ev : {db->rc_ev[0], db->rc_ev[1], db->rc_rev[0], db->rc_rev[1], db->em_ev[0], db->em_ev[1]})
     if (ev) (void)hipEventDestroy(ev);
+  kmcpg::em_release(db);
   kmcpg::release_fpr_bounds(db);
   kmcpg::async_release(db);
   if (db->k1_stream) (void)hipStreamDestroy(db->k1_stream);

@@ -317,6 +317,20 @@ struct kmcpg_db {
   hipEvent_t rc_ev[2] = {}, rc_rev[2] = {};
   bool rc_timed = false, rc_rtimed = false;
   std::vector<kmcpg_k4_launch> k8_log, k8_rlog;
+  // K9, an EM pass over K8's logs (kmcpg_em_pass; k9_em.hip, em.cpp): the pass counters of both halves (five words per column), the pass's
+  // classes on the device, the witness words; allocated on first use, freed with the recount stage
+  unsigned long long* d_em_counters = nullptr;  // [5 * n_cols]
+  unsigned long long* d_em_words = nullptr;     // [K9_STATS]
+  kmcpg_em_class* d_em_classes = nullptr;       // [em_classes_cap]
+  uint32_t em_classes_cap = 0, em_slots = 0;
+  std::vector<uint64_t> h_em_pass;              // [5 * n_cols] the last pass over the host log ...
+  std::vector<uint64_t> h_em_single;            // ... [4 * n_cols] its single-target reads of estimated classes, in K8's units
+  std::vector<uint8_t> em_est;                  // per column: its class was estimated in the last pass
+  uint64_t em_totals[4] = {};                   // of the last pass: reads with one / several targets on the device, then on the host
+  bool em_ran = false, em_timed = false;
+  unsigned em_grid = 0;
+  hipEvent_t em_ev[2] = {};
+  std::vector<kmcpg_k4_launch> k9_log;
   std::vector<kmcpg::FprBoundTable> fpr_bounds;  // -f bound tables (query.cpp fpr_bound): one per (max_fpr, size), never rewritten
   hipEvent_t ev[16] = {};   // ring of 4 calls x (start, COBS start, COBS done, k-mers done)
   uint64_t ev_calls = 0;    // profiled calls so far
@@ -531,6 +545,11 @@ void cooccur_host_result(kmcpg_db* db, const kmcpg_result* out);
 int recount_host_batch(kmcpg_db* db, const kmcpg_pair* pairs, const uint64_t* read_offs, const int32_t* qkmers, const int32_t* qlen, uint32_t n_reads,
                        const kmcpg_params& p, const uint8_t* left);
 void recount_host_result(kmcpg_db* db, const kmcpg_result* out);
+// kmcpg_db::d_rc_words: the log's reserve word, its commit word (what the log holds: logged reads << K8_STATE_WORD_BITS | record words),
+// then the totals and the two sets of witness words.  recount.cpp lays them out; em.cpp reads the commit word
+constexpr size_t RC_COMMIT = 1, RC_TOTALS = 2, RC_STATS = RC_TOTALS + K8_TOTALS, RC_RSTATS = RC_STATS + K8_STATS, RC_WORDS = RC_RSTATS + K8_R_STATS;
+// K9's buffers and state go with the recount stage (em.cpp); the caller holds db->mu and the device is idle
+void em_release(kmcpg_db* db);
 // k8_log behind K3 for a lane's batch (recount.cpp): what kmcpg_recount_log_device does, without the public entry's argument checks
 int recount_enqueue(kmcpg_db* db, const kmcpg_pair* d_pairs, const uint64_t* d_read_offs, uint64_t pair_cap, const int32_t* d_qkmers, const int32_t* d_qlen,
                     uint32_t n_reads, int32_t final_n, const uint64_t* d_n_hits, uint64_t hit_cap, uint8_t* d_left, unsigned max_wgs, hipStream_t st);

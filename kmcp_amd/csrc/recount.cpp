@@ -37,10 +37,10 @@ void free_device(kmcpg_db* db) {
     if (q) (void)hipFree(q);
   db->d_rc_target = db->d_rc_species = nullptr;
   db->d_rc_counters = db->d_rc_replay = db->d_rc_log = db->d_rc_words = nullptr;
+  em_release(db);
 }
 
-// d_rc_words: the log's reserve word, its commit word (what the log holds), then the totals and the two sets of witness words
-constexpr size_t RC_COMMIT = 1, RC_TOTALS = 2, RC_STATS = RC_TOTALS + K8_TOTALS, RC_RSTATS = RC_STATS + K8_STATS, RC_WORDS = RC_RSTATS + K8_R_STATS;
+// d_rc_words (engine.hpp: RC_COMMIT .. RC_WORDS)
 unsigned long long* totals_of(kmcpg_db* db) { return db->d_rc_words + RC_TOTALS; }
 unsigned long long* stats_of(kmcpg_db* db) { return db->d_rc_words + RC_STATS; }
 unsigned long long* rstats_of(kmcpg_db* db) { return db->d_rc_words + RC_RSTATS; }
@@ -362,6 +362,7 @@ extern "C" int kmcpg_recount_reset(kmcpg_db* db) {
   db->h_rc_replay.clear();
   db->rc_kept.clear();
   db->rc_tainted = db->rc_replayed = false;
+  db->em_ran = false;  // (a pass over the logs that went)
   return 0;
 }
 

@@ -31,6 +31,7 @@ EXPORTS = [
     "kmcpg_set_refstats", "kmcpg_refstats_device", "kmcpg_refstats_read", "kmcpg_refstats_reset", "kmcpg_last_refstats",
     "kmcpg_set_cooccur", "kmcpg_cooccur_device", "kmcpg_cooccur_read", "kmcpg_cooccur_reset", "kmcpg_last_cooccur",
     "kmcpg_set_recount", "kmcpg_recount_log_device", "kmcpg_recount_run", "kmcpg_recount_read", "kmcpg_recount_reset", "kmcpg_last_recount",
+    "kmcpg_em_pass", "kmcpg_em_read", "kmcpg_last_em",
     "kmcpg_sketch_genomes_to", "kmcpg_builder_open", "kmcpg_builder_close", "kmcpg_builder_add_cols", "kmcpg_builder_plan",
     "kmcpg_builder_col_place", "kmcpg_builder_block_info", "kmcpg_builder_begin_round", "kmcpg_builder_scatter_device",
     "kmcpg_builder_end_round", "kmcpg_builder_finish", "kmcpg_builder_info",
@@ -313,6 +314,23 @@ class RecountStats(C.Structure):
                 ("replay_grid", C.c_uint32), ("reserved", C.c_uint32), ("log_ms", C.c_double), ("replay_ms", C.c_double)]
 
 
+EM_COL_DTYPE = np.dtype([("match", "<u8"), ("uniq", "<u8"), ("hic", "<u8"), ("single_bases", "<u8"), ("bases_lo", "<u8"), ("bases_hi", "<u8")])  # kmcpg_em_col
+EM_CLASS_DTYPE = np.dtype([("est", "<u4"), ("reserved", "<u4"), ("coverage", "<f8")])  # kmcpg_em_class
+EM_UNIT = RECOUNT_UNIT << 12  # em_rule.hpp: units per read of an EM pass
+K9_EM = 66  # KMCPG_K9_EM: kmcpg_k4_launch.kernel of K9
+
+
+class EmTotals(C.Structure):
+    """kmcpg_em_totals"""
+    _fields_ = [("assigned_reads", C.c_uint64), ("unique_reads", C.c_uint64), ("split_reads", C.c_uint64), ("host_reads", C.c_uint64)]
+
+
+class EmStats(C.Structure):
+    """kmcpg_em_stats: the witness of the last k9_em launch"""
+    _fields_ = [("reads", C.c_uint64), ("none", C.c_uint64), ("one", C.c_uint64), ("split", C.c_uint64), ("lds_adds", C.c_uint64),
+                ("global_adds", C.c_uint64), ("spilled_adds", C.c_uint64), ("grid", C.c_uint32), ("slots", C.c_uint32), ("em_ms", C.c_double)]
+
+
 class ResultSummaries(C.Structure):
     """kmcpg_result_summaries"""
     _fields_ = [("n_windows", C.c_uint32), ("reserved", C.c_uint32), ("qlen", C.POINTER(C.c_int32)), ("qkmers", C.POINTER(C.c_int32)),
@@ -507,6 +525,9 @@ def load():
     L.kmcpg_recount_read.argtypes = [vp, vp, C.c_uint32, C.POINTER(RecountTotals)]
     L.kmcpg_recount_reset.argtypes = [vp]
     L.kmcpg_last_recount.argtypes = [vp, C.POINTER(RecountStats), C.POINTER(K4Launch), C.c_uint32, C.POINTER(C.c_uint32)]
+    L.kmcpg_em_pass.argtypes = [vp, vp, C.c_uint32, C.c_uint32]
+    L.kmcpg_em_read.argtypes = [vp, vp, C.c_uint32, C.POINTER(EmTotals)]
+    L.kmcpg_last_em.argtypes = [vp, C.POINTER(EmStats), C.POINTER(K4Launch), C.c_uint32, C.POINTER(C.c_uint32)]
     L.kmcpg_sketch_genomes_to.argtypes = [vp, vp, vp, C.c_uint32, C.POINTER(SplitSpec), SKETCH_SINK, vp]
     u32p = C.POINTER(C.c_uint32)
     L.kmcpg_builder_open.argtypes = [C.POINTER(BuilderCfg), C.c_int32, C.POINTER(vp)]
@@ -1405,6 +1426,31 @@ class Database:
         _check(load().kmcpg_last_recount(self._h, C.byref(st), buf, n.value, C.byref(n)))
         self.last_k8_log_ms, self.last_k8_replay_ms = float(st.log_ms), float(st.replay_ms)
         return {f: int(getattr(st, f)) for f, _ in RecountStats._fields_ if f not in ("log_ms", "replay_ms", "reserved")}, [buf[i] for i in range(n.value)]
+
+    # ---- abundance estimation by EM: K9, a pass over the logs the recount stage keeps ------------------------------
+    def em_pass(self, classes, level_species=True):
+        """kmcpg_em_pass: classes EM_CLASS_DTYPE [n_classes] (est, coverage); one pass over the device log and the host log (they are kept:
+        the call can be repeated with other classes)."""
+        c = np.ascontiguousarray(classes, dtype=EM_CLASS_DTYPE)
+        _check(load().kmcpg_em_pass(self._h, c.ctypes.data if len(c) else None, len(c), int(bool(level_species))))
+
+    def em_read(self):
+        """kmcpg_em_read: (EM_COL_DTYPE [n_cols], dict of the totals) — single-target reads of estimated classes + both halves of the pass"""
+        n = getattr(self, "_n_recount_cols", 0)
+        out = np.zeros(n, dtype=EM_COL_DTYPE)
+        tot = EmTotals()
+        _check(load().kmcpg_em_read(self._h, out.ctypes.data if n else None, n, C.byref(tot)))
+        return out, {f: int(getattr(tot, f)) for f, _ in EmTotals._fields_}
+
+    def last_em(self):
+        """kmcpg_last_em: (dict of the counters, [K4Launch] of the last k9_em launch — empty below profiling level 1)"""
+        st = EmStats()
+        n = C.c_uint32(0)
+        _check(load().kmcpg_last_em(self._h, C.byref(st), None, 0, C.byref(n)))
+        buf = (K4Launch * max(1, n.value))()
+        _check(load().kmcpg_last_em(self._h, C.byref(st), buf, n.value, C.byref(n)))
+        self.last_k9_ms = float(st.em_ms)
+        return {f: int(getattr(st, f)) for f, _ in EmStats._fields_ if f != "em_ms"}, [buf[i] for i in range(n.value)]
 
     # ---- window summaries for region merging: K5 behind K4 ------------------------------------------------------
     def summarize_device(self, d_pairs, d_offs, pair_cap, d_verdicts, d_qkmers, n, d_out, d_left_pairs, left_cap, d_left_offs, stream=None):
