@@ -668,6 +668,18 @@ int kmcpg_em_pass(kmcpg_db* db, const kmcpg_em_class* classes, uint32_t n_classe
 int kmcpg_em_read(kmcpg_db* db, kmcpg_em_col* out_cols, uint32_t n_cols, kmcpg_em_totals* totals);
 int kmcpg_last_em(kmcpg_db* db, kmcpg_em_stats* out, kmcpg_k4_launch* launches, uint32_t cap, uint32_t* n_launches);
 
+/* -- the host half of the counting stages (K6, K7, K8) alone: what kmcpg_wait does for the reads of a batch their kernels LEFT, on a list
+ *    the caller brings, in K3's hand-over form (pairs grouped by read, segments up to 4096 pairs in final order; read_offs: n_reads + 1
+ *    words).  The host's own tests run first (params, -f among them), a longer segment is put in final order here, and each read's final
+ *    rows go to the host state of the stages that are on — the counters kmcpg_refstats_read adds, the map kmcpg_cooccur_read merges, the
+ *    log kmcpg_recount_run replays.  left_refstats / left_cooccur / left_recount: a byte per read, != 0 = the stage takes the read; NULL =
+ *    every read; ignored for a stage that is off.  Needs no GPU (a metadata-only handle will do).  With every stage off: 0, nothing
+ *    changes.  KMCPG_EINVAL: read_offs[0] != 0, offsets that run backwards or past read_offs[n_reads], a column the handle does not have
+ *    (reads in front of the bad one have been counted: reset the stages). */
+int kmcpg_count_left_reads(kmcpg_db* db, const kmcpg_pair* pairs, const uint64_t* read_offs, const int32_t* qkmers, const int32_t* qlen,
+                           uint32_t n_reads, const kmcpg_params* params, const uint8_t* left_refstats, const uint8_t* left_cooccur,
+                           const uint8_t* left_recount);
+
 /* -- benchmarking / full-size parity support (no counterpart in the reference) ------------------ */
 typedef struct {
   int32_t k;            /* 21 */

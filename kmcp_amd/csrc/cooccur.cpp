@@ -1,6 +1,6 @@
 // cooccur.cpp — the host side of K7 (k7_cooccur.hip): the class table and the pair table on the handle, the stage alone, the merge of the
 // device's table and the host half's map, the witness.  The host half itself (the reads the device LEFT) is beside the other users of the
-// match rule, in finalize.cpp (cooccur_host_batch, cooccur_host_result).
+// match rule, in finalize.cpp (left_reads_host, the one walk of all the counting stages, and counting_host_result).
 #include <cstring>
 
 #include "cooccur_rule.hpp"

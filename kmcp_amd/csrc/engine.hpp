@@ -410,11 +410,16 @@ inline void timed_launches_report(const kmcpg_db* db, const hipEvent_t (&ev)[2],
   *n_launches = (uint32_t)have;
 }
 
+// What a stage that judges or counts a query's FINAL matches, once, refuses while it is on (K4 and the counting stages): the parameter
+// that would make it see something else, or nullptr
+// (the smaller-k retry of a database with several k-mer sizes looks for reads without matches, and a dropped read is not one)
+inline const char* final_matches_refused(const kmcpg_db* db, const kmcpg_params& p) {
+  return p.try_se ? "try_se" : (p.top_n_scores != 0 ? "top_n_scores != 0" : (p.k == 0 && db->ks_desc.size() > 1 ? "a database with several k-mer sizes searched with params->k == 0" : nullptr));
+}
+
 // The species-specific stage (kmcpg_set_specific): what would judge something else than a query's final matches is refused while it is on
 inline int specific_refuse_params(const kmcpg_db* db, const kmcpg_params& p) {
-  if (!db->spec_on()) return 0;
-  // (the smaller-k retry of a database with several k-mer sizes looks for reads without matches, and a dropped read is not one)
-  const char* what = p.try_se ? "try_se" : (p.top_n_scores != 0 ? "top_n_scores != 0" : (p.k == 0 && db->ks_desc.size() > 1 ? "a database with several k-mer sizes searched with params->k == 0" : nullptr));
+  const char* what = db->spec_on() ? final_matches_refused(db, p) : nullptr;
   if (!what) return 0;
   return kmcpg_fail(KMCPG_EUNSUPPORTED, "species-specific queries (kmcpg_set_specific): %s is not supported — switch the stage off, or filter the results with kmcp-filter", what);
 }
@@ -423,41 +428,50 @@ inline int specific_refuse_entry(const kmcpg_db* db, const char* entry) {
   return kmcpg_fail(KMCPG_EUNSUPPORTED, "species-specific queries (kmcpg_set_specific): %s is not supported while the stage is on", entry);
 }
 
-// The reference statistics (kmcpg_set_refstats): the same refusals as the species-specific stage, for the same reason — what is counted
-// must be a query's final matches, counted once
-inline int refstats_refuse_params(const kmcpg_db* db, const kmcpg_params& p) {
-  if (!db->refstats_on()) return 0;
-  const char* what = p.try_se ? "try_se" : (p.top_n_scores != 0 ? "top_n_scores != 0" : (p.k == 0 && db->ks_desc.size() > 1 ? "a database with several k-mer sizes searched with params->k == 0" : nullptr));
-  if (!what) return 0;
-  return kmcpg_fail(KMCPG_EUNSUPPORTED, "reference statistics (kmcpg_set_refstats): %s is not supported — switch the stage off, or count the results with kmcp-refstats", what);
+// The COUNTING STAGES: K6 (the reference statistics), K7 (the shared reads of reference pairs) and K8 (the recount's log).  Each counts a
+// query's final matches behind K3 — a kernel that marks the reads it LEFT, the host half for those (finalize.cpp left_reads_host) — into state
+// on the handle that its *_read entry adds up.  What hangs them into a batch is stated once, over this table: the lane (lane.cpp), the
+// refusals, the taint rule.
+enum CountingStage { K6, K7, K8, N_COUNTING };
+struct CountingStageDesc {
+  bool (kmcpg_db::*on)() const;
+  std::mutex kmcpg_db::*mu;
+  bool kmcpg_db::*tainted;                  // under mu: a batch failed after its reads were counted; the stage's read-outs refuse until its reset
+  const char *title, *setter, *instead;     // the words of its refusals
+  const char* device_knob;                  // = 0 in the environment: the kernel leaves every read to the host half
+};
+inline const CountingStageDesc kCountingStages[N_COUNTING] = {
+    {&kmcpg_db::refstats_on, &kmcpg_db::rs_mu, &kmcpg_db::rs_tainted, "reference statistics", "kmcpg_set_refstats", "count the results with kmcp-refstats", "KMCPG_REFSTATS_DEVICE"},
+    {&kmcpg_db::cooccur_on, &kmcpg_db::co_mu, &kmcpg_db::co_tainted, "shared reads of reference pairs", "kmcpg_set_cooccur", "count the results with kmcp-refstats --cooccur", "KMCPG_COOCCUR_DEVICE"},
+    {&kmcpg_db::recount_on, &kmcpg_db::rc_mu, &kmcpg_db::rc_tainted, "recount with ambiguity correction", "kmcpg_set_recount", "recount the results with kmcp-refstats --recount", "KMCPG_RECOUNT_DEVICE"},
+};
+inline bool counting_on(const kmcpg_db* db, int s) { return (db->*kCountingStages[s].on)(); }
+inline unsigned counting_mask(const kmcpg_db* db) {  // bit s: stage s is on
+  unsigned m = 0;
+  for (int s = 0; s < N_COUNTING; s++) m |= (unsigned)counting_on(db, s) << s;
+  return m;
 }
-inline int refstats_refuse_entry(const kmcpg_db* db, const char* entry) {
-  if (!db->refstats_on()) return 0;
-  return kmcpg_fail(KMCPG_EUNSUPPORTED, "reference statistics (kmcpg_set_refstats): %s is not supported while the stage is on", entry);
+// The same refusals as the species-specific stage, for the same reason — what is counted must be a query's final matches, counted once
+inline int counting_refuse_params(const kmcpg_db* db, const kmcpg_params& p) {
+  const char* what = final_matches_refused(db, p);
+  for (int s = 0; what && s < N_COUNTING; s++)
+    if (const CountingStageDesc& d = kCountingStages[s]; counting_on(db, s))
+      return kmcpg_fail(KMCPG_EUNSUPPORTED, "%s (%s): %s is not supported — switch the stage off, or %s", d.title, d.setter, what, d.instead);
+  return 0;
 }
-
-// The shared reads of reference pairs (kmcpg_set_cooccur): what K6 refuses, for the same reason
-inline int cooccur_refuse_params(const kmcpg_db* db, const kmcpg_params& p) {
-  if (!db->cooccur_on()) return 0;
-  const char* what = p.try_se ? "try_se" : (p.top_n_scores != 0 ? "top_n_scores != 0" : (p.k == 0 && db->ks_desc.size() > 1 ? "a database with several k-mer sizes searched with params->k == 0" : nullptr));
-  if (!what) return 0;
-  return kmcpg_fail(KMCPG_EUNSUPPORTED, "shared reads of reference pairs (kmcpg_set_cooccur): %s is not supported — switch the stage off, or count the results with kmcp-refstats --cooccur", what);
+inline int counting_refuse_entry(const kmcpg_db* db, const char* entry) {
+  for (int s = 0; s < N_COUNTING; s++)
+    if (const CountingStageDesc& d = kCountingStages[s]; counting_on(db, s))
+      return kmcpg_fail(KMCPG_EUNSUPPORTED, "%s (%s): %s is not supported while the stage is on", d.title, d.setter, entry);
+  return 0;
 }
-inline int cooccur_refuse_entry(const kmcpg_db* db, const char* entry) {
-  if (!db->cooccur_on()) return 0;
-  return kmcpg_fail(KMCPG_EUNSUPPORTED, "shared reads of reference pairs (kmcpg_set_cooccur): %s is not supported while the stage is on", entry);
-}
-
-// The recount with ambiguity correction (kmcpg_set_recount): what K6 refuses, for the same reason
-inline int recount_refuse_params(const kmcpg_db* db, const kmcpg_params& p) {
-  if (!db->recount_on()) return 0;
-  const char* what = p.try_se ? "try_se" : (p.top_n_scores != 0 ? "top_n_scores != 0" : (p.k == 0 && db->ks_desc.size() > 1 ? "a database with several k-mer sizes searched with params->k == 0" : nullptr));
-  if (!what) return 0;
-  return kmcpg_fail(KMCPG_EUNSUPPORTED, "recount with ambiguity correction (kmcpg_set_recount): %s is not supported — switch the stage off, or recount the results with kmcp-refstats --recount", what);
-}
-inline int recount_refuse_entry(const kmcpg_db* db, const char* entry) {
-  if (!db->recount_on()) return 0;
-  return kmcpg_fail(KMCPG_EUNSUPPORTED, "recount with ambiguity correction (kmcpg_set_recount): %s is not supported while the stage is on", entry);
+// A batch failed after the stages in `mask` may have counted its reads, and a caller may search them again
+inline void counting_taint(kmcpg_db* db, unsigned mask) {
+  for (int s = 0; s < N_COUNTING; s++)
+    if ((mask >> s & 1) && counting_on(db, s)) {
+      std::lock_guard<std::mutex> g(db->*kCountingStages[s].mu);
+      db->*kCountingStages[s].tainted = true;
+    }
 }
 
 inline kmcpg_params default_params() {
@@ -526,25 +540,17 @@ int finalize_grouped_trusted(const kmcpg_db* db, const kmcpg_pair* pairs, const 
 // the filters above left of it, with the handle's tables; KEEP and DROP were settled on the device.
 // specific_filter_result: the same rule on every read of a finished result of Match records (the paths without K3)
 void specific_filter_result(const kmcpg_db* db, kmcpg_result* out);
-// The host half of K6 (refstats.cpp).  refstats_host_batch: the reads of a batch the device LEFT (left == nullptr: every read), from K3's
-// pairs — the host's own tests (-f among them) first, the host's order for segments above K3_WG_CAP, then the rule of refstats_rule.hpp,
-// added to the handle's host counters.  refstats_host_result: every read of a finished result of Match records (the paths without K3).
-int refstats_host_batch(kmcpg_db* db, const kmcpg_pair* pairs, const uint64_t* read_offs, const int32_t* qkmers, uint32_t n_reads, const kmcpg_params& p,
-                        const uint8_t* left);
-void refstats_host_result(kmcpg_db* db, const kmcpg_result* out);
+// The host half of the counting stages (finalize.cpp), for the reads of a batch their kernels LEFT: K3's pairs (n_reads + 1 offsets), the
+// host's own tests (-f among them) first, the host's order for segments above K3_WG_CAP, then each read's final rows to the stages of `mask`
+// that took it — left[s][r] != 0, or left[s] == nullptr: every read — by refstats_rule.hpp into the host counters (K6), by cooccur_rule.hpp
+// into the host map (K7), in final order into the host log (K8).  counting_host_result: every read of a finished result of Match records
+// (the paths without K3), for the stages that are on.
+int left_reads_host(kmcpg_db* db, const kmcpg_pair* pairs, const uint64_t* read_offs, const int32_t* qkmers, const int32_t* qlen, uint32_t n_reads,
+                    const kmcpg_params& p, unsigned mask, const uint8_t* const left[N_COUNTING]);
+void counting_host_result(kmcpg_db* db, const kmcpg_result* out);
 // K6 behind K3 for a lane's batch (refstats.cpp): what kmcpg_refstats_device does, without the public entry's argument checks
 int refstats_enqueue(kmcpg_db* db, const kmcpg_pair* d_pairs, const uint64_t* d_read_offs, uint64_t pair_cap, const int32_t* d_qkmers, uint32_t n_reads,
                      int32_t final_n, const uint64_t* d_n_hits, uint64_t hit_cap, uint8_t* d_left, hipStream_t st);
-// The host half of K7 (cooccur.cpp), as K6's: the reads of a batch the device LEFT (left == nullptr: every read), from K3's pairs — the
-// host's own tests first, then the rule of cooccur_rule.hpp into the handle's host map; and every read of a finished result of records.
-int cooccur_host_batch(kmcpg_db* db, const kmcpg_pair* pairs, const uint64_t* read_offs, const int32_t* qkmers, uint32_t n_reads, const kmcpg_params& p,
-                       const uint8_t* left);
-void cooccur_host_result(kmcpg_db* db, const kmcpg_result* out);
-// The host half of K8 (finalize.cpp), as K7's: the reads of a batch the device LEFT (left == nullptr: every read), from K3's pairs — the
-// host's own tests first, then the surviving rows, in final order, into the handle's host log; and every read of a finished result of records.
-int recount_host_batch(kmcpg_db* db, const kmcpg_pair* pairs, const uint64_t* read_offs, const int32_t* qkmers, const int32_t* qlen, uint32_t n_reads,
-                       const kmcpg_params& p, const uint8_t* left);
-void recount_host_result(kmcpg_db* db, const kmcpg_result* out);
 // kmcpg_db::d_rc_words: the log's reserve word, its commit word (what the log holds: logged reads << K8_STATE_WORD_BITS | record words),
 // then the totals and the two sets of witness words.  recount.cpp lays them out; em.cpp reads the commit word
 constexpr size_t RC_COMMIT = 1, RC_TOTALS = 2, RC_STATS = RC_TOTALS + K8_TOTALS, RC_RSTATS = RC_STATS + K8_STATS, RC_WORDS = RC_RSTATS + K8_R_STATS;

@@ -701,7 +701,9 @@ void specific_filter_result(const kmcpg_db* db, kmcpg_result* out) {
   out->matches = o->matches.data();
 }
 
-// ---- the host half of K6 (k6_refstats.hip): refstats_rule.hpp on the reads the device does not count
+// ---- the host half of the counting stages (engine.hpp: K6 k6_refstats.hip, K7 k7_cooccur.hip, K8 k8_recount.hip): the reads their kernels
+// do not count.  One query's final rows go to refstats_rule.hpp (K6), as a set of targets to cooccur_rule.hpp (K7), and in final order into
+// the handle's host log, in the device log's record form — kmcpg_recount_run replays it with recount_rule.hpp (K8; recount.cpp)
 namespace {
 // one query's final rows -> the handle's host counters (rows: scratch of the caller)
 void refstats_count_rows(kmcpg_db* db, const kmcpg_match* m, uint64_t n, int32_t qkmers, std::vector<RefstatsRow>& rows) {
@@ -716,54 +718,8 @@ void refstats_count_rows(kmcpg_db* db, const kmcpg_match* m, uint64_t n, int32_t
   db->h_rs_matched++;
   if (unique) db->h_rs_unique++;
 }
-}  // namespace
 
-int refstats_host_batch(kmcpg_db* db, const kmcpg_pair* pairs, const uint64_t* read_offs, const int32_t* qkmers, uint32_t n_reads, const kmcpg_params& p,
-                        const uint8_t* left) {
-  if (!db->refstats_on()) return 0;
-  const size_t n_cols = db->col_meta.size();
-  const uint64_t n_pairs = read_offs[n_reads];
-  std::vector<kmcpg_match> tmp;
-  std::vector<RefstatsRow> rows;
-  FprRow row;
-  int row_n = -1;
-  const auto fpr_of = [&](int n2, int k) { return QueryFpr::value(*row, n2, k); };
-  for (uint32_t r = 0; r < n_reads; r++) {
-    if (left && !left[r]) continue;
-    const uint64_t s0 = read_offs[r], s1 = read_offs[r + 1];
-    if (s1 == s0) continue;
-    if (s1 < s0 || s1 > n_pairs) return kmcpg_fail(KMCPG_EINVAL, "grouped hit list: offsets out of range");
-    const int n = qkmers[r];
-    if (n > 0 && n != row_n) {
-      row_n = n;
-      row = db->fpr->ensure_row(n);
-    }
-    tmp.clear();
-    for (uint64_t i = s0; i < s1; i++) {
-      if (pairs[i].col >= n_cols) return kmcpg_fail(KMCPG_EINVAL, "grouped hit list: columns out of range");
-      kmcpg_match mm;
-      if (match_accept(pairs[i].col, (int)pairs[i].count, n, db->col_meta[pairs[i].col], p, fpr_of, &mm)) tmp.push_back(mm);
-    }
-    if (s1 - s0 > (uint64_t)K3_WG_CAP && !tmp.empty()) {  // K3 leaves these unordered: the host's order, as finalize_grouped_into gives them
-      sort_matches(tmp.data(), tmp.data() + tmp.size(), p);
-      if (db->is_set()) set_order_records(db, tmp.data(), tmp.size(), p.sort_by);
-    }
-    refstats_count_rows(db, tmp.data(), tmp.size(), n, rows);
-  }
-  return 0;
-}
-
-void refstats_host_result(kmcpg_db* db, const kmcpg_result* out) {
-  const ResultOwner* o = (const ResultOwner*)out->owner;
-  if (!o || !db->refstats_on() || o->pairs_mode) return;
-  std::vector<RefstatsRow> rows;
-  for (uint32_t r = 0; r < out->n_reads; r++)
-    refstats_count_rows(db, o->matches.data() + o->offs[r], o->offs[(size_t)r + 1] - o->offs[r], o->qkmers[r], rows);
-}
-
-// ---- the host half of K7 (k7_cooccur.hip): cooccur_rule.hpp on the reads the device does not count
-namespace {
-// one query's final rows' targets (cls: scratch of the caller, n >= 1) -> the handle's host map
+// one query's final rows' targets (cls: scratch of the caller) -> the handle's host map
 void cooccur_count_targets(kmcpg_db* db, std::vector<uint32_t>& cls) {
   if (cls.size() < 2) return;
   std::lock_guard<std::mutex> g(db->co_mu);
@@ -772,53 +728,8 @@ void cooccur_count_targets(kmcpg_db* db, std::vector<uint32_t>& cls) {
   if (m > 1) db->h_co_multi++;
   db->h_co_adds += adds;
 }
-}  // namespace
 
-int cooccur_host_batch(kmcpg_db* db, const kmcpg_pair* pairs, const uint64_t* read_offs, const int32_t* qkmers, uint32_t n_reads, const kmcpg_params& p,
-                       const uint8_t* left) {
-  if (!db->cooccur_on()) return 0;
-  const size_t n_cols = db->col_meta.size();
-  const uint64_t n_pairs = read_offs[n_reads];
-  std::vector<uint32_t> cls;
-  FprRow row;
-  int row_n = -1;
-  const auto fpr_of = [&](int n2, int k) { return QueryFpr::value(*row, n2, k); };
-  for (uint32_t r = 0; r < n_reads; r++) {
-    if (left && !left[r]) continue;
-    const uint64_t s0 = read_offs[r], s1 = read_offs[r + 1];
-    if (s1 == s0) continue;
-    if (s1 < s0 || s1 > n_pairs) return kmcpg_fail(KMCPG_EINVAL, "grouped hit list: offsets out of range");
-    const int n = qkmers[r];
-    if (n > 0 && n != row_n) {
-      row_n = n;
-      row = db->fpr->ensure_row(n);
-    }
-    cls.clear();
-    for (uint64_t i = s0; i < s1; i++) {  // (a set of targets: the order of the rows does not matter)
-      if (pairs[i].col >= n_cols) return kmcpg_fail(KMCPG_EINVAL, "grouped hit list: columns out of range");
-      kmcpg_match mm;
-      if (match_accept(pairs[i].col, (int)pairs[i].count, n, db->col_meta[pairs[i].col], p, fpr_of, &mm)) cls.push_back(db->h_co_target[pairs[i].col]);
-    }
-    cooccur_count_targets(db, cls);
-  }
-  return 0;
-}
-
-void cooccur_host_result(kmcpg_db* db, const kmcpg_result* out) {
-  const ResultOwner* o = (const ResultOwner*)out->owner;
-  if (!o || !db->cooccur_on() || o->pairs_mode) return;
-  std::vector<uint32_t> cls;
-  for (uint32_t r = 0; r < out->n_reads; r++) {
-    cls.clear();
-    for (uint64_t i = o->offs[r]; i < o->offs[(size_t)r + 1]; i++) cls.push_back(db->h_co_target[o->matches[i].col]);
-    cooccur_count_targets(db, cls);
-  }
-}
-
-// ---- the host half of K8 (k8_recount.hip): the reads the device neither counts nor logs go into the handle's host log, in the device
-// log's record form — their FINAL rows in final order; kmcpg_recount_run replays them with recount_rule.hpp (recount.cpp)
-namespace {
-// one query's final rows (n >= 1) -> the handle's host log
+// one query's final rows -> the handle's host log
 void recount_log_rows(kmcpg_db* db, const kmcpg_match* m, uint64_t n, int32_t qkmers, int32_t qlen) {
   if (n == 0) return;
   std::lock_guard<std::mutex> g(db->rc_mu);
@@ -827,23 +738,44 @@ void recount_log_rows(kmcpg_db* db, const kmcpg_match* m, uint64_t n, int32_t qk
   db->h_rc_log.push_back((uint64_t)std::max(qlen, 0));
   for (uint64_t i = 0; i < n; i++) db->h_rc_log.push_back((uint64_t)m[i].col | ((uint64_t)(uint32_t)m[i].mkmers << 32));
 }
+
+// one query's final rows, in final order, to the stages of `take`
+struct CountingScratch {
+  std::vector<RefstatsRow> rows;
+  std::vector<uint32_t> cls;
+};
+void counting_hand_over(kmcpg_db* db, unsigned take, const kmcpg_match* m, uint64_t n, int32_t qkmers, int32_t qlen, CountingScratch& sc) {
+  if (take >> K6 & 1) refstats_count_rows(db, m, n, qkmers, sc.rows);
+  if (take >> K7 & 1) {
+    sc.cls.clear();
+    for (uint64_t i = 0; i < n; i++) sc.cls.push_back(db->h_co_target[m[i].col]);
+    cooccur_count_targets(db, sc.cls);
+  }
+  if (take >> K8 & 1) recount_log_rows(db, m, n, qkmers, qlen);
+}
 }  // namespace
 
-int recount_host_batch(kmcpg_db* db, const kmcpg_pair* pairs, const uint64_t* read_offs, const int32_t* qkmers, const int32_t* qlen, uint32_t n_reads,
-                       const kmcpg_params& p, const uint8_t* left) {
-  if (!db->recount_on()) return 0;
+// A list that is refused half way (it never is, on K3's output) leaves every stage of the batch with the reads before the bad one — the
+// caller's failing collect() taints all the stages that ran, so nothing of it can be read until the stage's reset
+int left_reads_host(kmcpg_db* db, const kmcpg_pair* pairs, const uint64_t* read_offs, const int32_t* qkmers, const int32_t* qlen, uint32_t n_reads,
+                    const kmcpg_params& p, unsigned mask, const uint8_t* const left[N_COUNTING]) {
+  mask &= counting_mask(db);
+  if (!mask) return 0;
   const size_t n_cols = db->col_meta.size();
   const uint64_t n_pairs = read_offs[n_reads];
   std::vector<kmcpg_match> tmp;
+  CountingScratch sc;
   FprRow row;
   int row_n = -1;
   const auto fpr_of = [&](int n2, int k) { return QueryFpr::value(*row, n2, k); };
   for (uint32_t r = 0; r < n_reads; r++) {
-    if (left && !left[r]) continue;
+    unsigned take = 0;
+    for (int s = 0; s < N_COUNTING; s++)
+      if ((mask >> s & 1) && (!left[s] || left[s][r])) take |= 1u << s;
     const uint64_t s0 = read_offs[r], s1 = read_offs[r + 1];
-    if (s1 == s0) continue;
+    if (!take || s1 == s0) continue;
     if (s1 < s0 || s1 > n_pairs) return kmcpg_fail(KMCPG_EINVAL, "grouped hit list: offsets out of range");
-    if (s1 - s0 >= (1ull << 32)) return kmcpg_fail(KMCPG_EINVAL, "grouped hit list: a read with 2^32 matches or more");
+    if ((take >> K8 & 1) && s1 - s0 >= (1ull << 32)) return kmcpg_fail(KMCPG_EINVAL, "grouped hit list: a read with 2^32 matches or more");
     const int n = qkmers[r];
     if (n > 0 && n != row_n) {
       row_n = n;
@@ -855,19 +787,23 @@ int recount_host_batch(kmcpg_db* db, const kmcpg_pair* pairs, const uint64_t* re
       kmcpg_match mm;
       if (match_accept(pairs[i].col, (int)pairs[i].count, n, db->col_meta[pairs[i].col], p, fpr_of, &mm)) tmp.push_back(mm);
     }
-    if (s1 - s0 > (uint64_t)K3_WG_CAP && !tmp.empty()) {  // K3 leaves these unordered: the host's order, as finalize_grouped_into gives them
+    // K3 leaves these unordered: the host's order, as finalize_grouped_into gives them (K7 takes a set of targets: it needs no order)
+    if (s1 - s0 > (uint64_t)K3_WG_CAP && !tmp.empty() && (take & (1u << K6 | 1u << K8))) {
       sort_matches(tmp.data(), tmp.data() + tmp.size(), p);
       if (db->is_set()) set_order_records(db, tmp.data(), tmp.size(), p.sort_by);
     }
-    recount_log_rows(db, tmp.data(), tmp.size(), n, qlen[r]);
+    counting_hand_over(db, take, tmp.data(), tmp.size(), n, (take >> K8 & 1) ? qlen[r] : 0, sc);
   }
   return 0;
 }
 
-void recount_host_result(kmcpg_db* db, const kmcpg_result* out) {
+void counting_host_result(kmcpg_db* db, const kmcpg_result* out) {
   const ResultOwner* o = (const ResultOwner*)out->owner;
-  if (!o || !db->recount_on() || o->pairs_mode) return;
-  for (uint32_t r = 0; r < out->n_reads; r++) recount_log_rows(db, o->matches.data() + o->offs[r], o->offs[(size_t)r + 1] - o->offs[r], o->qkmers[r], o->qlen[r]);
+  const unsigned mask = counting_mask(db);
+  if (!o || !mask || o->pairs_mode) return;
+  CountingScratch sc;
+  for (uint32_t r = 0; r < out->n_reads; r++)
+    counting_hand_over(db, mask, o->matches.data() + o->offs[r], o->offs[(size_t)r + 1] - o->offs[r], o->qkmers[r], o->qlen[r], sc);
 }
 
 // counts in o->offs[1 ..] -> offsets, and the result's pointers
@@ -917,6 +853,15 @@ extern "C" int kmcpg_finalize_grouped(const kmcpg_db* db, const kmcpg_pair* pair
   if (int rc = finalize_grouped_into(db, pairs, read_offs, qkmers, qlen, n_reads, p, o.get(), 0, 0, &kept)) return rc;
   result_publish(o.release(), n_reads, p.k > 0 ? p.k : db->info.k, out);
   return 0;
+}
+
+extern "C" int kmcpg_count_left_reads(kmcpg_db* db, const kmcpg_pair* pairs, const uint64_t* read_offs, const int32_t* qkmers, const int32_t* qlen,
+                                      uint32_t n_reads, const kmcpg_params* params, const uint8_t* left_refstats, const uint8_t* left_cooccur,
+                                      const uint8_t* left_recount) {
+  if (!db || !read_offs || (n_reads && (!qkmers || !qlen)) || (read_offs[n_reads] && !pairs)) return kmcpg_fail(KMCPG_EINVAL, "null argument");
+  if (read_offs[0] != 0) return kmcpg_fail(KMCPG_EINVAL, "read_offs[0] must be 0");
+  const uint8_t* const left[N_COUNTING] = {left_refstats, left_cooccur, left_recount};
+  return left_reads_host(db, pairs, read_offs, qkmers, qlen, n_reads, params ? *params : default_params(), counting_mask(db), left);
 }
 
 // a result that holds records (a path that does not collect pairs natively: retries, host-merged lists, paged handles) -> pairs

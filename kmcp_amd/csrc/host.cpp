@@ -164,10 +164,8 @@ int finish_raw(kmcpg_ticket* t, kmcpg_result* out, bool as_pairs) {
   }
   Lane* L0 = t->parts[0].lane;  // every shard generates the same k-mers
   int rcf = kmcpg_finalize(t->db, hits, n_hits, t->n ? L0->h_qk.p : nullptr, t->n ? L0->h_ql.p : nullptr, t->n, &t->p, out);
-  // the reference statistics without K3 in front of them (KMCPG_DEVICE_FINALIZE=0): every read, from the finished (unfiltered) records
-  if (rcf == 0 && t->db->refstats_on()) refstats_host_result(t->db, out);
-  if (rcf == 0 && t->db->cooccur_on()) cooccur_host_result(t->db, out);  // ... and the shared reads of reference pairs likewise
-  if (rcf == 0 && t->db->recount_on()) recount_host_result(t->db, out);  // ... and the recount's host log
+  // the counting stages without K3 in front of them (KMCPG_DEVICE_FINALIZE=0): every read, from the finished (unfiltered) records
+  if (rcf == 0) counting_host_result(t->db, out);
   // the species-specific stage without K3 in front of it (KMCPG_DEVICE_FINALIZE=0): the rule on the finished records
   if (rcf == 0 && t->db->spec_on()) specific_filter_result(t->db, out);
   return rcf;
@@ -456,9 +454,7 @@ int submit_handle(kmcpg_db* db, const kmcpg_params* params, kmcpg_params* p) {
   *p = params ? *params : default_params();
   if (p->min_matched < 1) return kmcpg_fail(KMCPG_EINVAL, "min_matched must be >= 1");
   if (int rcs = specific_refuse_params(db, *p)) return rcs;
-  if (int rcs = refstats_refuse_params(db, *p)) return rcs;
-  if (int rcs = cooccur_refuse_params(db, *p)) return rcs;
-  if (int rcs = recount_refuse_params(db, *p)) return rcs;
+  if (int rcs = counting_refuse_params(db, *p)) return rcs;
   return set_refuse_params(db, *p);
 }
 
@@ -611,26 +607,13 @@ static int search_batch_impl(kmcpg_db* db, const HostBatch& in, const kmcpg_para
     const kmcpg_params pp = params ? *params : default_params();
     if (int rcs = set_refuse_params(db, pp)) return rcs;
     if (int rcs = specific_refuse_params(db, pp)) return rcs;
-    if (int rcs = refstats_refuse_params(db, pp)) return rcs;
-    if (int rcs = cooccur_refuse_params(db, pp)) return rcs;
-    if (int rcs = recount_refuse_params(db, pp)) return rcs;
+    if (int rcs = counting_refuse_params(db, pp)) return rcs;
     if (pp.min_matched >= 1 && in.offs[0] == 0 && (!in.offs2 || in.offs2[0] == 0)) rc = search_batch_pieces(db, in, pp, as_pairs, out, &took);
   }
   if (took && rc == 0) return 0;
-  if (took && db->refstats_on()) {
-    // K6 has counted the pieces that were enqueued before one of them failed, and the batch is searched again below: the counters would
-    // hold those reads twice (kmcpg_refstats_read refuses until kmcpg_refstats_reset)
-    std::lock_guard<std::mutex> g(db->rs_mu);
-    db->rs_tainted = true;
-  }
-  if (took && db->cooccur_on()) {  // ... and so would K7's table (kmcpg_cooccur_read refuses until kmcpg_cooccur_reset)
-    std::lock_guard<std::mutex> g(db->co_mu);
-    db->co_tainted = true;
-  }
-  if (took && db->recount_on()) {  // ... and K8's logs (kmcpg_recount_run refuses until kmcpg_recount_reset)
-    std::lock_guard<std::mutex> g(db->rc_mu);
-    db->rc_tainted = true;
-  }
+  // the counting stages have counted the pieces that were enqueued before one of them failed, and the batch is searched again below: they
+  // would hold those reads twice (their read-outs refuse until the stage's reset)
+  if (took) counting_taint(db, counting_mask(db));
   if (took) memset(out, 0, sizeof *out);
   if (!took || rc == KMCPG_ENOMEM) {
     rc = submit_checked(db, in, params, true, &t);

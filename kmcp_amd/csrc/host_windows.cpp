@@ -224,9 +224,7 @@ extern "C" int kmcpg_submit_windows(kmcpg_db* db, const uint8_t* seqs, const uin
   *out = nullptr;
   if (int rc = set_refuse_entry(db, "kmcpg_submit_windows")) return rc;
   if (int rc = specific_refuse_entry(db, "kmcpg_submit_windows")) return rc;
-  if (int rc = refstats_refuse_entry(db, "kmcpg_submit_windows")) return rc;
-  if (int rc = cooccur_refuse_entry(db, "kmcpg_submit_windows")) return rc;
-  if (int rc = recount_refuse_entry(db, "kmcpg_submit_windows")) return rc;
+  if (int rc = counting_refuse_entry(db, "kmcpg_submit_windows")) return rc;
   kmcpg_params p;
   if (int rc = submit_handle(db, params, &p)) return rc;
   if (int rc = window_args(offs, n_reads, spec)) return rc;
@@ -239,9 +237,7 @@ extern "C" int kmcpg_submit_packed_windows(kmcpg_db* db, const uint8_t* codes, c
   *out = nullptr;
   if (int rc = set_refuse_entry(db, "kmcpg_submit_packed_windows")) return rc;
   if (int rc = specific_refuse_entry(db, "kmcpg_submit_packed_windows")) return rc;
-  if (int rc = refstats_refuse_entry(db, "kmcpg_submit_packed_windows")) return rc;
-  if (int rc = cooccur_refuse_entry(db, "kmcpg_submit_packed_windows")) return rc;
-  if (int rc = recount_refuse_entry(db, "kmcpg_submit_packed_windows")) return rc;
+  if (int rc = counting_refuse_entry(db, "kmcpg_submit_packed_windows")) return rc;
   kmcpg_params p;
   if (int rc = submit_handle(db, params, &p)) return rc;
   if (int rc = window_args(offs, n_reads, spec)) return rc;
@@ -266,9 +262,7 @@ extern "C" int kmcpg_submit_windows_summary(kmcpg_db* db, const uint8_t* seqs, c
   if (!db || !out || (n_reads && (!seqs || !offs))) return kmcpg_fail(KMCPG_EINVAL, "null argument");
   *out = nullptr;
   if (int rc = set_refuse_entry(db, "kmcpg_submit_windows_summary")) return rc;
-  if (int rc = refstats_refuse_entry(db, "kmcpg_submit_windows_summary")) return rc;
-  if (int rc = cooccur_refuse_entry(db, "kmcpg_submit_windows_summary")) return rc;
-  if (int rc = recount_refuse_entry(db, "kmcpg_submit_windows_summary")) return rc;
+  if (int rc = counting_refuse_entry(db, "kmcpg_submit_windows_summary")) return rc;
   if (!db->spec_on()) return kmcpg_fail(KMCPG_EINVAL, "kmcpg_submit_windows_summary: the species-specific stage is off: call kmcpg_set_specific first");
   kmcpg_params p;
   if (int rc = submit_handle(db, params, &p)) return rc;

@@ -297,7 +297,7 @@ int enqueue_query(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p, c
     rc = kmcpg_group_device(db, L->d_hits.p, L->d_cnt.p, L->d_hits.cap, L->d_qk.p, L->n, &p, L->d_pairs.p, L->d_roffs.p, st);
     if (rc) return rc;
     L->spec = db->spec_on();
-    L->rs = L->co = L->rc8 = false;  // (a lane keeps its fields from batch to batch: the summary path below returns before K6's and K7's turn)
+    L->counted = 0;  // (a lane keeps its fields from batch to batch: the summary path below returns before the counting stages' turn)
     // (a batch K5 summarises needs K3's last two words only: the pairs it kept, and its count of bad hits)
     const size_t skip = L->summarized() ? L->n : 0;
     HIPCHK(hipMemcpyAsync(L->h_roffs.p + skip, L->d_roffs.p + skip, ((size_t)L->n + 2 - skip) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
@@ -326,45 +326,28 @@ int enqueue_query(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p, c
       HIPCHK(hipMemcpyAsync(L->h_roffs.p, L->d_soffs4.p, ((size_t)L->n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
       HIPCHK(hipMemcpyAsync(L->h_verd.p, L->d_verd.p, (size_t)L->n, hipMemcpyDeviceToHost, st));
     }
-    L->rs = db->refstats_on();
-    L->co = db->cooccur_on();
-    L->rc8 = db->recount_on();
-    if (L->rc8 && (L->d_left8.ensure(L->n) || L->h_left8.ensure(L->n) || (L->spec && L->h_roffs3.ensure((size_t)L->n + 1)))) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
-    // (K7's buffers before K6 runs: K6 must stay the last step BEFORE any counting that can fail for want of memory — see below)
-    if (L->co && (L->d_left7.ensure(L->n) || L->h_left7.ensure(L->n) || (L->spec && L->h_roffs3.ensure((size_t)L->n + 1)))) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
-    if (L->rs) {
-      // K6 on K3's output, which K4 leaves where it is (it compacts into d_hits).  The LAST step that can fail for want of memory: a batch
-      // that is enqueued again after KMCPG_ENOMEM has not been counted yet.  One whose hit buffer overflowed is not counted either (the
-      // kernel looks at the hit counter itself): collect() runs it again.  KMCPG_REFSTATS_DEVICE=0: every read goes to the host half
-      if (L->d_left.ensure(L->n) || L->h_left.ensure(L->n) || (L->spec && L->h_roffs3.ensure((size_t)L->n + 1))) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
-      const char* e = getenv("KMCPG_REFSTATS_DEVICE");
+    // The counting stages (engine.hpp) on K3's output, which K4 leaves where it is (it compacts into d_hits), in the order K6, K7, K8: the
+    // batch's last kernels.  Every buffer first — the kernels allocate nothing, so nothing that can fail for want of memory happens once the
+    // first of them is on the stream: a batch that is enqueued again after KMCPG_ENOMEM has been counted by none.  One whose hit buffer
+    // overflowed is not counted either (the kernels look at the hit counter themselves): collect() runs it again.
+    L->counted = counting_mask(db);
+    for (int s = 0; s < N_COUNTING; s++)
+      if ((L->counted >> s & 1) && (L->d_left[s].ensure(L->n) || L->h_left[s].ensure(L->n))) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
+    if (L->counted && L->spec && L->h_roffs3.ensure((size_t)L->n + 1)) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
+    for (int s = 0; s < N_COUNTING; s++) {
+      if (!(L->counted >> s & 1)) continue;
+      const char* e = getenv(kCountingStages[s].device_knob);  // KMCPG_*_DEVICE=0: every read goes to the host half
       const int32_t final_n = e && atoi(e) == 0 ? -1 : std::min<int32_t>(L->bound_n, kFprBoundAlways);
-      rc = refstats_enqueue(db, L->d_pairs.p, L->d_roffs.p, L->d_hits.cap, L->d_qk.p, L->n, final_n, L->d_cnt.p, L->d_hits.cap, L->d_left.p, st);
+      uint8_t* d_left = L->d_left[s].p;
+      // (K8 takes the reads' lengths from where the k-mer stage wrote them)
+      rc = s == K6   ? refstats_enqueue(db, L->d_pairs.p, L->d_roffs.p, L->d_hits.cap, L->d_qk.p, L->n, final_n, L->d_cnt.p, L->d_hits.cap, d_left, st)
+           : s == K7 ? cooccur_enqueue(db, L->d_pairs.p, L->d_roffs.p, L->d_hits.cap, L->d_qk.p, L->n, final_n, L->d_cnt.p, L->d_hits.cap, d_left, 0, st)
+                     : recount_enqueue(db, L->d_pairs.p, L->d_roffs.p, L->d_hits.cap, L->d_qk.p, L->d_ql.p, L->n, final_n, L->d_cnt.p, L->d_hits.cap, d_left, 0, st);
       if (rc) return rc;
-      HIPCHK(hipMemcpyAsync(L->h_left.p, L->d_left.p, (size_t)L->n, hipMemcpyDeviceToHost, st));
-      if (L->spec) HIPCHK(hipMemcpyAsync(L->h_roffs3.p, L->d_roffs.p, ((size_t)L->n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+      HIPCHK(hipMemcpyAsync(L->h_left[s].p, d_left, (size_t)L->n, hipMemcpyDeviceToHost, st));
     }
-    if (L->co) {
-      // K7 on K3's output, as K6 and behind it: the batch's last kernel; it allocates nothing (its buffers were made above), so a batch
-      // that is enqueued again after KMCPG_ENOMEM has been counted by neither.  KMCPG_COOCCUR_DEVICE=0: every read goes to the host half
-      const char* e = getenv("KMCPG_COOCCUR_DEVICE");
-      const int32_t final_n = e && atoi(e) == 0 ? -1 : std::min<int32_t>(L->bound_n, kFprBoundAlways);
-      rc = cooccur_enqueue(db, L->d_pairs.p, L->d_roffs.p, L->d_hits.cap, L->d_qk.p, L->n, final_n, L->d_cnt.p, L->d_hits.cap, L->d_left7.p, 0, st);
-      if (rc) return rc;
-      HIPCHK(hipMemcpyAsync(L->h_left7.p, L->d_left7.p, (size_t)L->n, hipMemcpyDeviceToHost, st));
-      if (L->spec && !L->rs) HIPCHK(hipMemcpyAsync(L->h_roffs3.p, L->d_roffs.p, ((size_t)L->n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    }
-    if (L->rc8) {
-      // K8's log kernel on K3's output, as K6 and K7 and behind them: it allocates nothing (its buffers were made above) and takes the
-      // reads' lengths from where the k-mer stage wrote them.  KMCPG_RECOUNT_DEVICE=0: every read goes to the host half
-      const char* e = getenv("KMCPG_RECOUNT_DEVICE");
-      const int32_t final_n = e && atoi(e) == 0 ? -1 : std::min<int32_t>(L->bound_n, kFprBoundAlways);
-      rc = recount_enqueue(db, L->d_pairs.p, L->d_roffs.p, L->d_hits.cap, L->d_qk.p, L->d_ql.p, L->n, final_n, L->d_cnt.p, L->d_hits.cap, L->d_left8.p, 0, st);
-      if (rc) return rc;
-      HIPCHK(hipMemcpyAsync(L->h_left8.p, L->d_left8.p, (size_t)L->n, hipMemcpyDeviceToHost, st));
-      if (L->spec && !L->rs && !L->co) HIPCHK(hipMemcpyAsync(L->h_roffs3.p, L->d_roffs.p, ((size_t)L->n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    }
-  } else L->spec = L->rs = L->co = L->rc8 = false;
+    if (L->counted && L->spec) HIPCHK(hipMemcpyAsync(L->h_roffs3.p, L->d_roffs.p, ((size_t)L->n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  } else L->spec = false, L->counted = 0;
   return 0;
 }
 
@@ -486,23 +469,30 @@ int enqueue(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p, bool ge
 }
 
 namespace {
-// the host half of K6 (stage 6), K7 (7) or K8 (8) for a finished batch: the reads its kernel LEFT, from K3's pairs
-int left_collect(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p, bool fetched, int stage) {
-  const uint8_t* left = stage == 8 ? L->h_left8.p : stage == 7 ? L->h_left7.p : L->h_left.p;
-  const auto host_batch = [&](kmcpg_db* d, const kmcpg_pair* pairs, const uint64_t* offs, const int32_t* qk, uint32_t n, const kmcpg_params& pp, const uint8_t* lf) {
-    return stage == 8 ? recount_host_batch(d, pairs, offs, qk, L->h_ql.p, n, pp, lf) : stage == 7 ? cooccur_host_batch(d, pairs, offs, qk, n, pp, lf) : refstats_host_batch(d, pairs, offs, qk, n, pp, lf);
-  };
+// the host half of the counting stages for a finished batch: the reads their kernels LEFT, from K3's pairs — which are the lane's result
+// itself, or, behind K4 or where the caller did not fetch them, still in d_pairs: one download for all the stages, and none if no read was LEFT
+int left_collect(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p, bool fetched) {
+  const unsigned mask = L->counted & counting_mask(db);
+  const uint8_t* left[N_COUNTING] = {};
   bool any = false;
-  for (uint32_t r = 0; r < L->n && !any; r++) any = left[r] != 0;
-  if (!any) return 0;
-  if (!L->spec && fetched) return host_batch(db, L->h_pairs.p, L->h_roffs.p, L->h_qk.p, L->n, p, left);
-  const uint64_t* offs = L->spec ? L->h_roffs3.p : L->h_roffs.p;
-  std::vector<kmcpg_pair, NoInitAlloc<kmcpg_pair>> k3(offs[L->n]);
-  if (!k3.empty()) {
-    HIPCHK(hipMemcpyAsync(k3.data(), L->d_pairs.p, k3.size() * sizeof(kmcpg_pair), hipMemcpyDeviceToHost, A->copy_stream));
-    HIPCHK(hipStreamSynchronize(A->copy_stream));
+  for (int s = 0; s < N_COUNTING; s++) {
+    if (!(mask >> s & 1)) continue;
+    left[s] = L->h_left[s].p;
+    for (uint32_t r = 0; r < L->n && !any; r++) any = left[s][r] != 0;
   }
-  return host_batch(db, k3.data(), offs, L->h_qk.p, L->n, p, left);
+  if (!any) return 0;
+  const kmcpg_pair* pairs = L->h_pairs.p;
+  const uint64_t* offs = L->spec ? L->h_roffs3.p : L->h_roffs.p;
+  std::vector<kmcpg_pair, NoInitAlloc<kmcpg_pair>> k3;
+  if (L->spec || !fetched) {
+    k3.resize(offs[L->n]);
+    if (!k3.empty()) {
+      HIPCHK(hipMemcpyAsync(k3.data(), L->d_pairs.p, k3.size() * sizeof(kmcpg_pair), hipMemcpyDeviceToHost, A->copy_stream));
+      HIPCHK(hipStreamSynchronize(A->copy_stream));
+    }
+    pairs = k3.data();
+  }
+  return left_reads_host(db, pairs, offs, L->h_qk.p, L->h_ql.p, L->n, p, mask, left);
 }
 }  // namespace
 
@@ -510,24 +500,13 @@ int collect(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p, uint64_
   *n_hits = 0;
   if (L->n == 0) return 0;
   KMCPG_USE_DEVICE(db);
-  struct Taint {  // a batch that fails from here on may have been counted by K6 or K7 already, and a caller may search its reads again
+  struct Taint {  // a batch that fails from here on may have been counted by the counting stages already, and a caller may search its reads again
     kmcpg_db* db;
     const Lane* L;
     bool ok = false;
     ~Taint() {
-      if (ok || !L->grouped || L->h_cnt.p[0] > L->d_hits.cap) return;  // (an overflowing attempt was not counted: the kernel's guard)
-      if (L->rs && db->refstats_on()) {
-        std::lock_guard<std::mutex> g(db->rs_mu);
-        db->rs_tainted = true;
-      }
-      if (L->co && db->cooccur_on()) {
-        std::lock_guard<std::mutex> g(db->co_mu);
-        db->co_tainted = true;
-      }
-      if (L->rc8 && db->recount_on()) {
-        std::lock_guard<std::mutex> g(db->rc_mu);
-        db->rc_tainted = true;
-      }
+      if (ok || !L->grouped || L->h_cnt.p[0] > L->d_hits.cap) return;  // (an overflowing attempt was not counted: the kernels' guard)
+      counting_taint(db, L->counted);
     }
   } taint{db, L};
   HIPCHK(hipEventSynchronize(L->done));
@@ -570,17 +549,8 @@ int collect(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p, uint64_
     HIPCHK(hipStreamSynchronize(A->copy_stream));
     L->copied = cnt;
   }
-  if (L->rs && L->grouped && db->refstats_on()) {
-    // the host half of K6: the reads the device LEFT, from K3's pairs — which are the lane's result itself, or, behind K4, still in d_pairs
-    int rc = left_collect(db, A, L, p, fetch, 6);
-    if (rc) return rc;
-  }
-  if (L->co && L->grouped && db->cooccur_on()) {  // ... and of K7
-    int rc = left_collect(db, A, L, p, fetch, 7);
-    if (rc) return rc;
-  }
-  if (L->rc8 && L->grouped && db->recount_on()) {  // ... and of K8
-    int rc = left_collect(db, A, L, p, fetch, 8);
+  if (L->counted && L->grouped) {
+    int rc = left_collect(db, A, L, p, fetch);
     if (rc) return rc;
   }
   // a batch large enough to say something about the data (one genome with 5 000 matches does not)

@@ -77,19 +77,12 @@ struct Lane {
   PinBuf<kmcpg_window_summary> h_sum;
   DevBuf<uint64_t> d_loffs;
   bool summarized() const { return summary && grouped && spec; }  // K5 ran: h_sum is the result
-  // K6 (the reference statistics, when the handle has them on): a byte per read — 1 = LEFT to the host half, which counts it from K3's pairs
-  // at collect time; with K4 on as well, K3's own offsets come down beside K4's (h_roffs3) and K3's pairs only if a read was LEFT
-  DevBuf<uint8_t> d_left;
-  PinBuf<uint8_t> h_left;
+  // The counting stages (K6, K7, K8: engine.hpp), each when the handle has it on: a byte per read — 1 = LEFT to the host half, which counts
+  // it from K3's pairs at collect time; with K4 on as well, K3's own offsets come down beside K4's (h_roffs3) and K3's pairs only if a read was LEFT
+  DevBuf<uint8_t> d_left[N_COUNTING];
+  PinBuf<uint8_t> h_left[N_COUNTING];
   PinBuf<uint64_t> h_roffs3;
-  bool rs = false;  // this batch went through K6
-  // K7 (the shared reads of reference pairs, when the handle has them on): the same, with LEFT bytes of its own
-  DevBuf<uint8_t> d_left7;
-  PinBuf<uint8_t> h_left7;
-  bool co = false;  // this batch went through K7
-  DevBuf<uint8_t> d_left8;
-  PinBuf<uint8_t> h_left8;
-  bool rc8 = false;  // this batch went through K8's log kernel
+  unsigned counted = 0;  // bit s: this batch went through counting stage s
   bool spec = false;  // this batch went through K4: h_roffs / h_pairs hold ITS output, h_verd the verdicts
   // 2-bit packed upload (stage): the batch's bases as codes + the runs of foreign bytes instead of h_seqs; unpacked on the device
   PinBuf<uint8_t> h_pack;
@@ -129,7 +122,9 @@ struct Lane {
     d_pairs.release(); d_roffs.release(); h_pairs.release(); h_roffs.release();
     d_soffs4.release(); d_verd.release(); h_verd.release();
     d_sum.release(); h_sum.release(); d_loffs.release();
-    d_left.release(); h_left.release(); h_roffs3.release();
+    for (auto& b : d_left) b.release();
+    for (auto& b : h_left) b.release();
+    h_roffs3.release();
     h_pack.release(); h_exc.release(); d_pack.release(); d_exc.release();
     h_wmeta.release(); d_soffs.release(); d_wmeta.release(); d_wsrc.release();
     if (done) (void)hipEventDestroy(done);

@@ -1,6 +1,7 @@
 // recount.cpp — the host side of K8 (k8_recount.hip): the class tables, the counters and the read log on the handle, k8_log alone, the
 // replay of both logs (k8_replay on the device's, recount_rule.hpp on the host's), the read-out, the witness.  What fills the host log
-// (the reads the device LEFT) is beside the other users of the match rule, in finalize.cpp (recount_host_batch, recount_host_result).
+// (the reads the device LEFT) is beside the other users of the match rule, in finalize.cpp (left_reads_host, the one walk of all the counting
+// stages, and counting_host_result).
 #include <cstring>
 
 #include "engine.hpp"

@@ -1,6 +1,6 @@
 // refstats.cpp — the host side of K6 (k6_refstats.hip): the tables and counters on the handle, the stage alone, the sum of the device's and
 // the host half's counters, the witness.  The host half itself (the reads the device LEFT) is beside the other users of the match rule, in
-// finalize.cpp (refstats_host_batch, refstats_host_result).
+// finalize.cpp (left_reads_host, the one walk of all the counting stages, and counting_host_result).
 #include <cstring>
 
 #include "engine.hpp"

@@ -31,7 +31,7 @@ EXPORTS = [
     "kmcpg_set_refstats", "kmcpg_refstats_device", "kmcpg_refstats_read", "kmcpg_refstats_reset", "kmcpg_last_refstats",
     "kmcpg_set_cooccur", "kmcpg_cooccur_device", "kmcpg_cooccur_read", "kmcpg_cooccur_reset", "kmcpg_last_cooccur",
     "kmcpg_set_recount", "kmcpg_recount_log_device", "kmcpg_recount_run", "kmcpg_recount_read", "kmcpg_recount_reset", "kmcpg_last_recount",
-    "kmcpg_em_pass", "kmcpg_em_read", "kmcpg_last_em",
+    "kmcpg_em_pass", "kmcpg_em_read", "kmcpg_last_em", "kmcpg_count_left_reads",
     "kmcpg_sketch_genomes_to", "kmcpg_builder_open", "kmcpg_builder_close", "kmcpg_builder_add_cols", "kmcpg_builder_plan",
     "kmcpg_builder_col_place", "kmcpg_builder_block_info", "kmcpg_builder_begin_round", "kmcpg_builder_scatter_device",
     "kmcpg_builder_end_round", "kmcpg_builder_finish", "kmcpg_builder_info",
@@ -528,6 +528,7 @@ def load():
     L.kmcpg_em_pass.argtypes = [vp, vp, C.c_uint32, C.c_uint32]
     L.kmcpg_em_read.argtypes = [vp, vp, C.c_uint32, C.POINTER(EmTotals)]
     L.kmcpg_last_em.argtypes = [vp, C.POINTER(EmStats), C.POINTER(K4Launch), C.c_uint32, C.POINTER(C.c_uint32)]
+    L.kmcpg_count_left_reads.argtypes = [vp, vp, vp, vp, vp, C.c_uint32, C.POINTER(Params), vp, vp, vp]
     L.kmcpg_sketch_genomes_to.argtypes = [vp, vp, vp, C.c_uint32, C.POINTER(SplitSpec), SKETCH_SINK, vp]
     u32p = C.POINTER(C.c_uint32)
     L.kmcpg_builder_open.argtypes = [C.POINTER(BuilderCfg), C.c_int32, C.POINTER(vp)]
@@ -1506,6 +1507,21 @@ class Database:
             load().kmcpg_result_free(C.byref(r))
             return m
         return _copy_result(r)
+
+    def count_left_reads(self, pairs, read_offs, qkmers, qlen, params=None, left_refstats=None, left_cooccur=None, left_recount=None):
+        """kmcpg_count_left_reads: the host half of the counting stages (K6, K7, K8) on a grouped list — pairs uint32 [m, 2] (or PAIR_DTYPE
+        [m]), read_offs uint64 [n + 1] — into the handle's host state; left_*: a byte per read (non-zero = the stage takes it), None = every read."""
+        p = params or default_params()
+        pairs = np.ascontiguousarray(pairs)
+        read_offs = np.ascontiguousarray(read_offs, dtype=np.uint64)
+        qkmers = np.ascontiguousarray(qkmers, dtype=np.int32)
+        qlen = np.ascontiguousarray(qlen, dtype=np.int32)
+        n = len(qkmers)
+        assert pairs.dtype.itemsize in (4, 8) and len(read_offs) == n + 1 and len(qlen) == n
+        left = [None if l is None else np.ascontiguousarray(l, dtype=np.uint8) for l in (left_refstats, left_cooccur, left_recount)]
+        assert all(l is None or len(l) == n for l in left)
+        _check(load().kmcpg_count_left_reads(self._h, pairs.ctypes.data, read_offs.ctypes.data, qkmers.ctypes.data, qlen.ctypes.data, n, C.byref(p),
+                                             *[None if l is None else l.ctypes.data for l in left]))
 
     # ---- bench / parity support -----------------------------------------------------------------------
     def read_row_range(self, block, first_row, out):
