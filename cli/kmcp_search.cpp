@@ -23,6 +23,7 @@
 #include <deque>
 #include <functional>
 #include <map>
+#include <optional>
 #include <memory>
 #include <mutex>
 #include <set>
@@ -108,6 +109,9 @@ struct Options {
   // --ref-stats-profile FILE [--ref-stats-abund-max-iters I] [--ref-stats-abund-pct-threshold X] [--ref-stats-filter-low-pct F]: stage 4/4
   // behind the three — the abundances by EM over the logs stage 3 keeps; the file is what kmcp-refstats --profile writes from the search result
   std::string ref_stats_profile;
+  // --ref-stats-only: the same files, and no search result — the batches go through kmcpg_submit_stats / kmcpg_wait_stats, no match leaves
+  // the GPU but those of the reads the counting stages left to the host
+  bool ref_stats_only = false;
   long long ref_stats_iters = 10;
   double ref_stats_pct = 0.01, ref_stats_filter = 0;
   const char* profile_flag = nullptr;       // the first of the three optional flags that was given
@@ -166,7 +170,7 @@ static void usage() {
       "                             [--ref-stats-recount file [--ref-stats-no-amb-corr] [--ref-stats-min-dreads-prop float (0.05)]\n"
       "                              [--ref-stats-max-mismatch-err float (0.05)] [--ref-stats-recount-log-mb int]\n"
       "                              [--ref-stats-profile file [--ref-stats-abund-max-iters int (10)] [--ref-stats-abund-pct-threshold float (0.01)]\n"
-      "                               [--ref-stats-filter-low-pct float (0)]]]\n"
+      "                               [--ref-stats-filter-low-pct float (0)]]] [--ref-stats-only]\n"
       "                             count, on the GPU while the search runs, what stage 1/4 of `kmcp profile` counts per reference (reads,\n"
       "                             uniquely matched reads, high-confidence ones, chunks covered) and judge which references are in the\n"
       "                             sample: the file is what `kmcp-refstats -f 1 -t 0 -m N --level L ...` writes from this command's\n"
@@ -178,6 +182,9 @@ static void usage() {
       "                             `kmcp-refstats ... --recount` writes from this command's output.\n"
       "                             --ref-stats-profile (with --ref-stats-recount): stage 4/4 as well — the abundances estimated by EM on the\n"
       "                             GPU, one pass per iteration over the reads stage 3 kept; the table `kmcp-refstats ... --profile` writes.\n"
+      "                             --ref-stats-only: write the --ref-stats* files and NO search result — byte for byte the files of the\n"
+      "                             same command without it, but no match leaves the GPU except those of the reads its counting kernels\n"
+      "                             leave to the host, and no row is formatted.  Not with -o, --specific-level, --regions-bed, --also-db, -g.\n"
       "           --parse-only (read the inputs and print records / bases / checksum per file; no database, no GPU)\n"
       "           --regions-bed file [--regions-min-overlap int (1)] [--regions-max-gap int (0)] [--regions-ignore-type]\n"
       "                             [--regions-name-species string] [--regions-name-assembly string]\n"
@@ -220,7 +227,7 @@ static Options parse_args(int argc, char** argv) {
       {"specific-level", 0, 1}, {"taxid-map", 0, 1}, {"taxdump", 0, 1},
       {"ref-stats", 0, 1}, {"ref-stats-mode", 0, 1}, {"ref-stats-min-hic-ureads-qcov", 0, 1}, {"ref-stats-min-chunks-fraction", 0, 1}, {"ref-stats-level", 0, 1}, {"ref-stats-cooccur", 0, 1}, {"ref-stats-cooccur-slots", 0, 1},
       {"ref-stats-recount", 0, 1}, {"ref-stats-no-amb-corr", 0, 0}, {"ref-stats-min-dreads-prop", 0, 1}, {"ref-stats-max-mismatch-err", 0, 1}, {"ref-stats-recount-log-mb", 0, 1},
-      {"ref-stats-profile", 0, 1}, {"ref-stats-abund-max-iters", 0, 1}, {"ref-stats-abund-pct-threshold", 0, 1}, {"ref-stats-filter-low-pct", 0, 1},
+      {"ref-stats-only", 0, 0}, {"ref-stats-profile", 0, 1}, {"ref-stats-abund-max-iters", 0, 1}, {"ref-stats-abund-pct-threshold", 0, 1}, {"ref-stats-filter-low-pct", 0, 1},
       {"regions-bed", 0, 1}, {"regions-min-overlap", 0, 1}, {"regions-max-gap", 0, 1}, {"regions-ignore-type", 0, 0},
       {"regions-name-species", 0, 1}, {"regions-name-assembly", 0, 1}};
   auto regions_flag = [&](const char* flag) {
@@ -286,6 +293,7 @@ static Options parse_args(int argc, char** argv) {
     else if (name == "ref-stats-max-mismatch-err") { o.ref_stats_r = to_f(name, v); if (!o.recount_flag) o.recount_flag = "--ref-stats-max-mismatch-err"; }
     else if (name == "ref-stats-recount-log-mb") { o.ref_stats_recount_log_mb = to_i(name, v); if (o.ref_stats_recount_log_mb < 0) o.ref_stats_recount_log_mb = 0; if (!o.recount_flag) o.recount_flag = "--ref-stats-recount-log-mb"; }
     else if (name == "ref-stats-profile") o.ref_stats_profile = v;
+    else if (name == "ref-stats-only") o.ref_stats_only = true;
     else if (name == "ref-stats-abund-max-iters") { o.ref_stats_iters = to_i(name, v); if (!o.profile_flag) o.profile_flag = "--ref-stats-abund-max-iters"; }
     else if (name == "ref-stats-abund-pct-threshold") { o.ref_stats_pct = to_f(name, v); if (!o.profile_flag) o.profile_flag = "--ref-stats-abund-pct-threshold"; }
     else if (name == "ref-stats-filter-low-pct") { o.ref_stats_filter = to_f(name, v); if (!o.profile_flag) o.profile_flag = "--ref-stats-filter-low-pct"; }
@@ -548,10 +556,16 @@ static int validate_flags(const Options& o, bool sliding) {
   if (!o.ref_stats_recount.empty() && (o.ref_stats.empty() || o.ref_stats_cooccur.empty()))
     die("flag --ref-stats-recount is only used with --ref-stats and --ref-stats-cooccur (stage 3 starts from the tables of stages 1 and 2)");
   if (o.ref_stats.empty() && o.ref_stats_flag) die("flag %s is only used with --ref-stats", o.ref_stats_flag);
+  if (o.ref_stats.empty() && o.ref_stats_only) die("flag --ref-stats-only is only used with --ref-stats");
   if (!o.ref_stats.empty()) {
     const char* bad = o.keep_unmatched ? "-K/--keep-unmatched" : o.try_se ? "--try-se" : o.top_scores != 0 ? "-n/--keep-top-scores"
                       : sliding ? "--sliding-step/--sliding-window/--sliding-greedy" : o.gpus_given ? "--gpus/--gpu-ids" : o.gpu_passes >= 0 ? "--gpu-passes" : nullptr;
     if (bad) die("flag %s cannot be combined with --ref-stats", bad);
+    if (o.ref_stats_only) {  // no search result: nothing that writes one, filters one, or merges several
+      const char* clash = o.out_file_given ? "-o/--out-file" : !o.specific_level.empty() ? "--specific-level" : !o.regions_bed.empty() ? "--regions-bed"
+                          : !o.also_dbs.empty() ? "--also-db" : o.whole_file ? "-g/--query-whole-file" : nullptr;
+      if (clash) die("flag %s cannot be combined with --ref-stats-only: no search result is written, the reads are only counted", clash);
+    }
     if (o.ref_stats_mode < 0 || o.ref_stats_mode >= kmcpg::REFSTATS_MODES) die("invalid profiling mode: %d", o.ref_stats_mode);
     if (o.ref_stats_mode == 0)
       die("flag --ref-stats-mode 0 is not supported: its main-match cut (--keep-main-matches) drops rows of a query before they are counted; run kmcp-refstats -m 0 on the search result");
@@ -775,6 +789,7 @@ struct Pipeline {
   const Options& o;  // (main goes on writing o.batch and o.gpu_ids while it opens the database: no thread reads those two)
   const bool paired, sliding;
   bool regions() const { return !o.regions_bed.empty(); }
+  bool stats_only() const { return o.ref_stats_only; }
   const kmcpg_window_spec wspec;
   // set by main after the database open and before the searchers start; the reader never looks at them
   kmcpg_db* db = nullptr;
@@ -798,6 +813,7 @@ struct Pipeline {
   std::atomic<int> live{0};                 // searchers still running
   // the writer loop alone (the main thread), read by print_summary and the trailer after it
   uint64_t total = 0, matched = 0;
+  kmcpg_result_stats stats{};  // --ref-stats-only: the tickets' sums
   int fmt_threads = 0;
   double t_fmt = 0;                                       // formatting + writing, all of an iteration
   double t_fmt_busy = 0;                                  // summed over the formatter threads: time inside the parts
@@ -1408,8 +1424,27 @@ struct Searcher {
       die("%s", kmcpg_last_error());
   }
 
+  // --ref-stats-only, a batch the ticket route could not take for memory: the one-call form counts it all the same (and halves it if it
+  // must); what came to the host is then its whole result
+  void search_sync_stats(Batch& bb) {
+    static std::atomic<bool> said{false};
+    if (!said.exchange(true))
+      warn("--ref-stats-only: a batch did not fit the statistics-only route (%s); it is counted through the route that brings all its matches to the host, "
+           "which the summary line counts as left to the host", kmcpg_last_error());
+    search_sync(bb);
+    const kmcpg_result_pairs& r = bb.res;
+    kmcpg_result_stats& st = bb.stats;
+    st = kmcpg_result_stats{};
+    st.n_reads = r.n_reads;
+    for (uint32_t i = 0; i < r.n_reads; i++) st.matched_reads += r.match_offs[i + 1] > r.match_offs[i] ? 1 : 0;
+    st.kept_pairs = r.n_reads ? r.match_offs[r.n_reads] : 0;
+    st.left_reads = st.matched_reads, st.left_pairs = st.kept_pairs;  // (all of them came to the host)
+    st.bytes_d2h = st.kept_pairs * sizeof(kmcpg_pair) + st.n_reads * (sizeof(uint64_t) + 2 * sizeof(int32_t));
+    kmcpg_result_pairs_free(&bb.res);
+  }
+
   void publish(std::unique_ptr<Batch> bb) {
-    if (!p.o.quiet) {  // order-independent checksum of the (query, column, mKmers) tuples: the same on 1, 2, 4, 8 GPUs
+    if (!p.o.quiet && !p.stats_only()) {  // order-independent checksum of the (query, column, mKmers) tuples: the same on 1, 2, 4, 8 GPUs
       const kmcpg_result_pairs& r = bb->res;
       for (uint32_t i = 0; i < r.n_reads; i++)
         for (uint64_t j = r.match_offs[i]; j < r.match_offs[i + 1]; j++)
@@ -1424,8 +1459,10 @@ struct Searcher {
     std::unique_ptr<Batch> bb = std::move(fl.front().second);
     fl.pop_front();
     const auto t0 = Clock::now();
-    const int rc = p.regions() ? kmcpg_wait_summaries(t, &bb->sres) : kmcpg_wait_pairs(t, &bb->res);
-    if (rc == KMCPG_ENOMEM && !p.regions()) search_sync(*bb);  // (kmcpg_wait consumed the ticket; the batch's buffers are still ours)
+    const int rc = p.stats_only() ? kmcpg_wait_stats(t, &bb->stats) : p.regions() ? kmcpg_wait_summaries(t, &bb->sres) : kmcpg_wait_pairs(t, &bb->res);
+    // (a statistics-only batch may have been counted by the time its wait runs out of memory: searching it again would count it twice)
+    if (rc != 0 && p.stats_only()) die("--ref-stats-only: %s", kmcpg_last_error());
+    else if (rc == KMCPG_ENOMEM && !p.regions()) search_sync(*bb);  // (kmcpg_wait consumed the ticket; the batch's buffers are still ours)
     else if (rc != 0) die("%s", kmcpg_last_error());
     my_gpu += seconds_since(t0);
     publish(std::move(bb));
@@ -1433,6 +1470,8 @@ struct Searcher {
 
   // the asynchronous form that takes the batch as the reader left it: the records' windows, packed codes, or text
   int submit(Batch& b, kmcpg_ticket** t) {
+    if (p.stats_only())  // (reads as text, single or paired: validate_flags refused the rest)
+      return kmcpg_submit_stats(p.db, b.seqs.data(), b.offs.data(), b.paired ? b.seqs2.data() : nullptr, b.paired ? b.offs2.data() : nullptr, (uint32_t)b.size(), &p.params, t);
     if (b.windows && p.regions()) return kmcpg_submit_windows_summary(p.db, b.seqs.data(), b.offs.data(), (uint32_t)(b.offs.size() - 1), &p.wspec, &p.params, t);
     if (b.windows) return kmcpg_submit_windows(p.db, b.seqs.data(), b.offs.data(), (uint32_t)(b.offs.size() - 1), &p.wspec, &p.params, t);
     if (b.packed) return kmcpg_submit_packed(p.db, b.codes.data(), b.offs.data(), b.exc.data(), b.n_exc, (uint32_t)b.size(), &p.params, t);
@@ -1465,12 +1504,14 @@ struct Searcher {
         }
         // The lanes are all the other searcher's.  The one place where windows and reads differ: a batch of reads goes to the one-call form
         // below; windows have none that takes them as they are (it would mean cutting their text), so they wait for a lane to come back.
-        if (!b->windows) break;
+        // (a statistics-only batch waits as well: the one-call form would bring all its matches down)
+        if (!b->windows && !p.stats_only()) break;
         std::this_thread::sleep_for(std::chrono::microseconds(200));
       }
       if (rc == KMCPG_ENOMEM && p.regions()) die("%s", kmcpg_last_error());  // (summaries have no one-call form)
       if (rc == KMCPG_EBUSY || rc == KMCPG_ENOMEM) {  // no lane / a batch that must be halved: the one-call form
-        search_sync(*b);
+        if (p.stats_only()) search_sync_stats(*b);
+        else search_sync(*b);
         my_gpu += seconds_since(t0);
         publish(std::move(b));
         continue;
@@ -1684,6 +1725,22 @@ static void write_regions(Pipeline& p, Out& out, kmcpg::RegionMerger& merger) {
   out.write(bed);
 }
 
+// --ref-stats-only: nothing to format, nothing to write — the batches' counts are added up and their buffers go back to the reader
+static void drain_stats(Pipeline& p) {
+  std::unique_ptr<Batch> b;
+  while (p.q_out.pop(&b)) {
+    const kmcpg_result_stats& s = b->stats;
+    p.stats.n_reads += s.n_reads, p.stats.matched_reads += s.matched_reads, p.stats.kept_pairs += s.kept_pairs;
+    p.stats.left_reads += s.left_reads, p.stats.left_pairs += s.left_pairs, p.stats.bytes_d2h += s.bytes_d2h;
+    p.total += s.n_reads;
+    recycle(*b);
+    if (!p.o.quiet) {
+      double min = seconds_since(p.t_search) / 60.0;
+      fprintf(stderr, "processed queries: %llu, speed: %.3f million queries per minute\r", (unsigned long long)p.total, p.total / 1e6 / min);
+    }
+  }
+}
+
 // ---- the end of a run
 static void print_summary(const Pipeline& p) {
   fprintf(stderr, "\n");
@@ -1779,8 +1836,9 @@ int main(int argc, char** argv) {
   if (!o.ref_stats_recount.empty()) recount_classes = set_recount(o, p.db, p.target, taxonomy.get(), taxid_map.get());
 
   p.t_search = Clock::now();
-  Out out(p.regions() ? o.regions_bed : o.out_file);
-  if (!o.no_header && !p.regions()) out.write("#query\tqLen\tqKmers\tFPR\thits\ttarget\tchunkIdx\tchunks\ttLen\tkSize\tmKmers\tqCov\ttCov\tjacc\tqueryIdx\n");
+  std::optional<Out> out_file;  // (--ref-stats-only: no search result, no file)
+  if (!p.stats_only()) out_file.emplace(p.regions() ? o.regions_bed : o.out_file);
+  if (!o.no_header && !p.regions() && !p.stats_only()) out_file->write("#query\tqLen\tqKmers\tFPR\thits\ttarget\tchunkIdx\tchunks\ttLen\tkSize\tmKmers\tqCov\ttCov\tjacc\tqueryIdx\n");
   open_gate(p, dbi.k);
 
   const int n_search = p.paged_passes > 1 ? 1 : 2;  // (see Searcher)
@@ -1796,21 +1854,30 @@ int main(int argc, char** argv) {
   region_params.name_species = o.regions_name_species;
   region_params.name_assembly = o.regions_name_assembly;
   kmcpg::RegionMerger merger(region_params);
-  if (p.regions()) write_regions(p, out, merger);
-  else write_results(p, out);
+  if (p.stats_only()) drain_stats(p);
+  else if (p.regions()) write_regions(p, *out_file, merger);
+  else write_results(p, *out_file);
   reader.join();
   for (auto& t : searchers) t.join();
 
-  if (p.regions()) {
+  if (p.stats_only()) {
+    if (!o.quiet) {
+      fprintf(stderr, "\n");
+      info("done searching (%.3f s in the GPU library, %.3f s waiting for the reader; no search result is written)", p.t_gpu, p.t_read_wait);
+    }
+    // (one line of its own, whatever -q says: the tests read it)
+    fprintf(stderr, "%llu reads searched, %llu matched; %llu reads (%llu pairs) left to the host, %llu bytes from the device\n", (unsigned long long)p.stats.n_reads,
+            (unsigned long long)p.stats.matched_reads, (unsigned long long)p.stats.left_reads, (unsigned long long)p.stats.left_pairs, (unsigned long long)p.stats.bytes_d2h);
+  } else if (p.regions()) {
     if (!o.quiet) {
       fprintf(stderr, "\n");
       info("specific regions: %llu windows, %llu with a summary (species- or assembly-specific), %llu regions saved to: %s", (unsigned long long)p.total,
            (unsigned long long)p.matched, (unsigned long long)merger.n_regions, o.regions_bed.c_str());
     }
-    out.close();
+    out_file->close();
   } else {
     if (!o.quiet) print_summary(p);
-    write_trailer(p, out);
+    write_trailer(p, *out_file);
   }
   if (!o.ref_stats.empty()) {
     uint64_t reruns = 0;

@@ -680,6 +680,54 @@ int kmcpg_count_left_reads(kmcpg_db* db, const kmcpg_pair* pairs, const uint64_t
                            uint32_t n_reads, const kmcpg_params* params, const uint8_t* left_refstats, const uint8_t* left_cooccur,
                            const uint8_t* left_recount);
 
+/* -- statistics-only search (K10, k10_left.hip): reads in, the counting stages' state on the handle out — no matches come to the host
+ *    and nothing is there to be written.  kmcpg_submit_stats takes kmcpg_submit's arguments on a handle with at least one counting stage
+ *    on (kmcpg_set_refstats, kmcpg_set_cooccur, kmcpg_set_recount; KMCPG_EINVAL with none) and runs K10 as the batch's last kernels: the
+ *    bytes the stages wrote for the reads they LEFT become one mask byte per read (bit 0: K6, bit 1: K7, bit 2: K8), and the segments of
+ *    those reads, and only those, are compacted into the batch's dead hit buffer.  Per ticket the two hit counters, K3's last two words,
+ *    qlen / qkmers (4 + 4 bytes per read), the mask bytes and the witness words leave the GPU, and — only if a read was LEFT — the
+ *    n_reads + 1 offsets of the compacted segments and 8 bytes per LEFT pair: bytes_d2h <= 9 n + 256 without a LEFT read,
+ *    <= 17 n + 256 + 8 left_pairs with one.  kmcpg_wait_stats does for the batch what kmcpg_wait does (a batch whose hit buffer overflowed
+ *    runs again and is counted once; a batch that fails after it was counted taints the stages) and hands the compacted pairs to the
+ *    host half; what kmcpg_refstats_read, kmcpg_cooccur_read, kmcpg_recount_run / _read and kmcpg_em_pass / _read report afterwards is
+ *    byte for byte what they report after kmcpg_submit + kmcpg_wait of the same reads.
+ *    KMCPG_EINVAL with the species-specific stage on (K4 filters an output this ticket does not have); KMCPG_EUNSUPPORTED on database
+ *    sets, on paged / multi-device / sharded handles, with KMCPG_DEVICE_FINALIZE=0, and for the parameters the stages refuse (try_se,
+ *    top_n_scores != 0, several k-mer sizes with k == 0).  The ticket is consumed by kmcpg_wait_stats ONLY: kmcpg_wait, kmcpg_wait_pairs
+ *    and kmcpg_wait_summaries refuse it (KMCPG_EINVAL, the ticket stays valid), and kmcpg_wait_stats refuses every other ticket.
+ *    kmcpg_left_compact_device runs K10 alone on device pointers: K3's output (d_pairs, d_read_offs: n_reads + 1 words, at most pair_cap
+ *    pairs), the three stages' bytes (NULL: the stage is not looked at), the overflow guard of the counting kernels (d_n_hits NULL: none;
+ *    *d_n_hits > hit_cap: d_mask, d_left_pairs and d_left_offs keep what they held) -> d_mask[n_reads], the LEFT reads' pairs in
+ *    d_left_pairs[d_left_offs[i] .. d_left_offs[i + 1]) in their order (d_left_offs: n_reads + 1 words; left_cap >= pair_cap).  It needs
+ *    no stage on.  Only enqueues on `stream`.
+ *    kmcpg_last_stats: the witness of the handle's last K10 launch (the call waits for the device to go idle) or, after
+ *    kmcpg_wait_stats, of that ticket; at profiling level >= 1 the HIP-event time of the handle's last K10 launch and one record per
+ *    kernel launched (the scan's records carry KMCPG_K4_SCAN_*). */
+enum { KMCPG_K10_MASK = 67, KMCPG_K10_COMPACT = 68, KMCPG_K10_OFFS = 69 };  /* kmcpg_k4_launch.kernel of K10's own kernels */
+typedef struct {
+  uint64_t n_reads;
+  uint64_t matched_reads;  /* reads with at least one pair in K3's output */
+  uint64_t kept_pairs;     /* K3's total */
+  uint64_t left_reads;     /* reads a counting stage left to the host half */
+  uint64_t left_pairs;     /* their pairs: all that came to the host of the batch's matches */
+  uint64_t bytes_d2h;      /* bytes that came from the device for the ticket */
+} kmcpg_result_stats;
+typedef struct {
+  uint64_t n_reads, matched_reads, kept_pairs, left_reads, left_pairs;  /* n_reads and kept_pairs: 0 after kmcpg_left_compact_device */
+  uint64_t bytes_d2h;      /* 0 after kmcpg_left_compact_device */
+  uint64_t bad_segments;   /* segments that did not lie inside pair_cap (treated as empty; must be 0) */
+  uint64_t skipped;        /* 1: the overflow guard skipped the launch */
+  double k10_ms;           /* HIP-event time of the stage's kernels at profiling level >= 1; -1 otherwise */
+} kmcpg_stats_ticket_stats;
+int kmcpg_left_compact_device(kmcpg_db* db, const kmcpg_pair* d_pairs, const uint64_t* d_read_offs, uint64_t pair_cap, uint32_t n_reads,
+                              const uint8_t* d_left_refstats, const uint8_t* d_left_cooccur, const uint8_t* d_left_recount,
+                              const uint64_t* d_n_hits, uint64_t hit_cap, uint8_t* d_mask, kmcpg_pair* d_left_pairs, uint64_t left_cap,
+                              uint64_t* d_left_offs, void* stream);
+int kmcpg_submit_stats(kmcpg_db* db, const uint8_t* seqs, const uint64_t* offs, const uint8_t* seqs2, const uint64_t* offs2, uint32_t n_reads,
+                       const kmcpg_params* params, kmcpg_ticket** out);
+int kmcpg_wait_stats(kmcpg_ticket* ticket, kmcpg_result_stats* out);
+int kmcpg_last_stats(kmcpg_db* db, kmcpg_stats_ticket_stats* out, kmcpg_k4_launch* launches, uint32_t cap, uint32_t* n_launches);
+
 /* -- benchmarking / full-size parity support (no counterpart in the reference) ------------------ */
 typedef struct {
   int32_t k;            /* 21 */

@@ -253,6 +253,23 @@ struct K5Args {
   uint32_t* stats;               // [K5_STATS], zero on entry
 };
 
+// K10 (k10_left.hip): the bytes the counting stages (K6, K7, K8) wrote for the reads they LEFT -> one mask byte per read (bit s: stage s
+// left it) and the length of every LEFT read's segment in K3's output; the scan and k4_compact behind it bring those segments together.
+// The witness: reads with at least one pair, LEFT reads, their pairs, segments outside the buffer, launches the overflow guard skipped
+enum { K10_MATCHED = 0, K10_LEFT, K10_LEFT_PAIRS, K10_BAD, K10_SKIPPED, K10_STATS };
+constexpr int K10_STAGES = 3;  // K6, K7, K8 in the order of engine.hpp
+struct K10Args {
+  const uint64_t* offs;                // K3's offsets [n_reads + 1]
+  uint64_t pair_cap;                   // pairs there is room for in K3's output: a segment that ends behind it is treated as empty
+  uint32_t n_reads;
+  const uint8_t* left[K10_STAGES];     // [n_reads] each, or nullptr: the stage is not looked at
+  const unsigned long long* n_hits;    // device word or nullptr: the batch's hit counter ...
+  uint64_t hit_cap;                    // ... above this the batch will be run again: nothing is written now
+  uint8_t* mask;                       // out [n_reads]
+  uint32_t* cnt;                       // [n_reads + 1] scratch: the LEFT lengths (all 0 where the guard skipped the launch)
+  unsigned long long* stats;           // [K10_STATS], zero on entry
+};
+
 // K6 (k6_refstats.hip): K3's segments -> four counters per column, the counts of stage 1 of `kmcp profile` (refstats_rule.hpp); the reads
 // it cannot count exactly are LEFT to the host (a byte per read).
 constexpr uint32_t K6_CAP = 64;  // longest segment of several targets the device counts

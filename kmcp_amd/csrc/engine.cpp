@@ -850,6 +850,10 @@ extern "C" int kmcpg_close(kmcpg_db* db) {
   for (hipEvent_t ev : {db->rc_ev[0], db->rc_ev[1], db->rc_rev[0], db->rc_rev[1], db->em_ev[0], db->em_ev[1]})
     if (ev) (void)hipEventDestroy(ev);
   kmcpg::em_release(db);
+  db->w_left_offs.release();
+  if (db->d_left_stats) (void)hipFree(db->d_left_stats);
+  for (auto& ev : db->left_ev)
+    if (ev) (void)hipEventDestroy(ev);
   kmcpg::release_fpr_bounds(db);
   kmcpg::async_release(db);
   if (db->k1_stream) (void)hipStreamDestroy(db->k1_stream);

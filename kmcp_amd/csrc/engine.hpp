@@ -331,6 +331,17 @@ struct kmcpg_db {
   unsigned em_grid = 0;
   hipEvent_t em_ev[2] = {};
   std::vector<kmcpg_k4_launch> k9_log;
+  // K10, the LEFT reads' pairs compacted behind the counting stages (kmcpg_submit_stats, kmcpg_left_compact_device; k10_left.hip,
+  // stats.cpp): the scan's offsets before they are published, the witness words of the last launch that did not bring its own, and what
+  // that launch noted; cnt and sums are K4's scratch (one user at a time: fin_ev).  All of it allocated on first use
+  kmcpg::DevBuf<uint64_t> w_left_offs;
+  unsigned long long* d_left_stats = nullptr;  // [K10_STATS]
+  bool left_ran = false, left_timed = false;
+  hipEvent_t left_ev[2] = {};
+  std::vector<kmcpg_k4_launch> k10_log;
+  // ... or, after kmcpg_wait_stats, what that ticket's batch came to
+  bool left_from_ticket = false;
+  kmcpg_stats_ticket_stats left_ticket{};
   std::vector<kmcpg::FprBoundTable> fpr_bounds;  // -f bound tables (query.cpp fpr_bound): one per (max_fpr, size), never rewritten
   hipEvent_t ev[16] = {};   // ring of 4 calls x (start, COBS start, COBS done, k-mers done)
   uint64_t ev_calls = 0;    // profiled calls so far
@@ -562,6 +573,14 @@ int recount_enqueue(kmcpg_db* db, const kmcpg_pair* d_pairs, const uint64_t* d_r
 // K7 behind K3 for a lane's batch (cooccur.cpp): what kmcpg_cooccur_device does, without the public entry's argument checks (max_wgs 0: the handle's)
 int cooccur_enqueue(kmcpg_db* db, const kmcpg_pair* d_pairs, const uint64_t* d_read_offs, uint64_t pair_cap, const int32_t* d_qkmers, uint32_t n_reads,
                     int32_t final_n, const uint64_t* d_n_hits, uint64_t hit_cap, uint8_t* d_left, unsigned max_wgs, hipStream_t st);
+// K10 behind the counting stages for a lane's batch (stats.cpp).  left_compact_reserve: the handle's scratch for n_reads reads — called
+// before the counting kernels are enqueued, so that nothing behind them fails for want of memory.  left_compact_enqueue: what
+// kmcpg_left_compact_device does, without the public entry's argument checks; d_stats = K10_STATS witness words of the caller's (a lane's:
+// batches in flight keep theirs apart), zeroed here, or nullptr: the handle's
+int left_compact_reserve(kmcpg_db* db, uint32_t n_reads);
+int left_compact_enqueue(kmcpg_db* db, const kmcpg_pair* d_pairs, const uint64_t* d_read_offs, uint64_t pair_cap, uint32_t n_reads, const uint8_t* const d_left[N_COUNTING],
+                         const uint64_t* d_n_hits, uint64_t hit_cap, uint8_t* d_mask, kmcpg_pair* d_left_pairs, uint64_t left_cap, uint64_t* d_left_offs,
+                         unsigned long long* d_stats, hipStream_t st);
 // bound_n: what the kmcpg_query_device call(s) that produced the list actually did — every query of up to bound_n k-mers had the -f bound
 // applied on the device, whichever kernel form served it (0: no bound table in that call).  query_device_after reports the value of its
 // call; lane.cpp keeps it with the batch (Lane::bound_n) and hands it to the finalizer, which takes a compact segment as final only for

@@ -23,13 +23,14 @@
 
 namespace kmcpg {
 
-int submit_impl(kmcpg_db* db, const HostBatch& b, const kmcpg_params& p, bool retry, bool block, kmcpg_ticket** out, const PackedIn* packed, bool summary) {
+int submit_impl(kmcpg_db* db, const HostBatch& b, const kmcpg_params& p, bool retry, bool block, kmcpg_ticket** out, const PackedIn* packed, bool summary, bool stats) {
   std::unique_ptr<kmcpg_ticket> t(new kmcpg_ticket());
   t->db = db;
   t->n = b.n;
   t->paired = b.seqs2 != nullptr;
   t->p = p;
   t->summary = summary;
+  t->stats = stats;
   if (db->paged_passes > 0) {
     int rc = search_paged(db, b, p, t.get());
     if (rc) return rc;
@@ -59,7 +60,7 @@ int submit_impl(kmcpg_db* db, const HostBatch& b, const kmcpg_params& p, bool re
   auto one = [&](size_t i) {
     auto& pt = t->parts[i];
     rcs[i] = packed ? stage_packed(pt.lane, *packed, b) : stage(pt.lane, b, can_pack);
-    if (rcs[i] == 0) pt.lane->summary = summary;
+    if (rcs[i] == 0) pt.lane->summary = summary, pt.lane->stats = stats;
     if (rcs[i] == 0) rcs[i] = enqueue(pt.shard, pt.shard->async, pt.lane, p);
     if (rcs[i]) errs[i] = kmcpg_err_ref();
   };
@@ -482,6 +483,7 @@ extern "C" int kmcpg_wait(kmcpg_ticket* t, kmcpg_result* out) {
     return kmcpg_fail(KMCPG_EINVAL, "null argument");
   }
   if (t->summary) return kmcpg_fail(KMCPG_EINVAL, "kmcpg_wait: a ticket of kmcpg_submit_windows_summary is consumed by kmcpg_wait_summaries (the ticket is still valid)");
+  if (t->stats) return kmcpg_fail(KMCPG_EINVAL, "kmcpg_wait: a ticket of kmcpg_submit_stats is consumed by kmcpg_wait_stats (the ticket is still valid)");
   return wait_impl(t, out, false);
 }
 
@@ -684,11 +686,67 @@ extern "C" int kmcpg_wait_pairs(kmcpg_ticket* t, kmcpg_result_pairs* out) {
     return kmcpg_fail(KMCPG_EINVAL, "null argument");
   }
   if (t->summary) return kmcpg_fail(KMCPG_EINVAL, "kmcpg_wait_pairs: a ticket of kmcpg_submit_windows_summary is consumed by kmcpg_wait_summaries (the ticket is still valid)");
+  if (t->stats) return kmcpg_fail(KMCPG_EINVAL, "kmcpg_wait_pairs: a ticket of kmcpg_submit_stats is consumed by kmcpg_wait_stats (the ticket is still valid)");
   memset(out, 0, sizeof *out);
   const bool native = !may_retry(t->db, t->p, t->paired);
   kmcpg_result r{};
   if (int rc = wait_impl(t, &r, native)) return rc;
   return publish_pairs(&r, out);
+}
+
+// ---- statistics-only search: the batch goes through the counting stages and K10 (lane.cpp), and nothing of its matches comes to the host
+//      but the pairs of the reads the stages LEFT
+extern "C" int kmcpg_submit_stats(kmcpg_db* db, const uint8_t* seqs, const uint64_t* offs, const uint8_t* seqs2, const uint64_t* offs2, uint32_t n_reads,
+                                  const kmcpg_params* params, kmcpg_ticket** out) {
+  const HostBatch b{seqs, offs, seqs2, offs2, n_reads};
+  if (!db || !out || (b.n && (!b.seqs || !b.offs))) return kmcpg_fail(KMCPG_EINVAL, "null argument");
+  *out = nullptr;
+  if ((b.seqs2 == nullptr) != (b.offs2 == nullptr)) return kmcpg_fail(KMCPG_EINVAL, "seqs2 and offs2 must be given together");
+  if (!counting_mask(db)) return kmcpg_fail(KMCPG_EINVAL, "kmcpg_submit_stats: no counting stage is on: call kmcpg_set_refstats, kmcpg_set_cooccur or kmcpg_set_recount first");
+  if (db->spec_on())
+    return kmcpg_fail(KMCPG_EINVAL, "kmcpg_submit_stats: the species-specific stage (kmcpg_set_specific) is on — it filters a result this ticket does not have; switch it off");
+  if (int rc = set_refuse_entry(db, "kmcpg_submit_stats")) return rc;
+  if (int rc = refuse_handle(db, "statistics-only searches (kmcpg_submit_stats)", "the counting stages need a query's matches from every block")) return rc;
+  kmcpg_params p;
+  if (int rc = submit_handle(db, params, &p)) return rc;
+  AsyncState* A = nullptr;
+  if (int rc = async_state(db, &A)) return rc;
+  if (!A->device_finalize || A->hits_stay_on_device)
+    return kmcpg_fail(KMCPG_EUNSUPPORTED, "kmcpg_submit_stats needs K3 on the device (KMCPG_DEVICE_FINALIZE=0 is set): use kmcpg_submit and kmcpg_wait");
+  return submit_impl(db, b, p, false, false, out, nullptr, false, true);
+}
+
+extern "C" int kmcpg_wait_stats(kmcpg_ticket* t, kmcpg_result_stats* out) {
+  if (!t || !out) {
+    if (t) drop_ticket(t);
+    return kmcpg_fail(KMCPG_EINVAL, "null argument");
+  }
+  if (!t->stats) return kmcpg_fail(KMCPG_EINVAL, "kmcpg_wait_stats: the ticket is not one of kmcpg_submit_stats (it is still valid)");
+  memset(out, 0, sizeof *out);
+  kmcpg_db* db = t->db;
+  int rc = 0;
+  kmcpg_stats_ticket_stats st{};
+  st.k10_ms = -1;
+  if (t->n) {
+    auto& pt = t->parts[0];
+    Lane* L = pt.lane;
+    uint64_t n_hits = 0;
+    rc = collect(pt.shard, pt.shard->async, L, t->p, &n_hits, false);
+    if (rc == 0 && !L->stats_only()) rc = kmcpg_fail(KMCPG_EDEVICE, "internal: a statistics-only batch did not go through K10");
+    if (rc == 0 && L->h_roffs.p[(size_t)t->n + 1] != 0)
+      rc = kmcpg_fail(KMCPG_EINVAL, "%llu hit(s) named a read or column that does not exist", (unsigned long long)L->h_roffs.p[(size_t)t->n + 1]);
+    if (rc == 0) st = L->left_res;
+  }
+  if (rc == 0) {
+    out->n_reads = st.n_reads, out->matched_reads = st.matched_reads, out->kept_pairs = st.kept_pairs;
+    out->left_reads = st.left_reads, out->left_pairs = st.left_pairs, out->bytes_d2h = st.bytes_d2h;
+    std::lock_guard<std::mutex> g(db->mu);
+    db->left_ticket = st;
+    db->left_from_ticket = true;
+    db->left_ran = true;
+  }
+  drop_after(t, rc);
+  return rc;
 }
 
 // How many bases a batch may hold on this handle so that its workspace fits beside the resident index: K1/K1d take up to 24 B

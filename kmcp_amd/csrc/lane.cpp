@@ -168,7 +168,7 @@ bool pack_wanted(uint64_t total_bases, uint32_t n) {
 int lane_begin(Lane* L, const HostBatch& b) {
   L->up_reads = L->n = b.n;
   L->up_bases = L->tb1 = L->tb2 = 0;
-  L->packed = L->win = L->summary = false;
+  L->packed = L->win = L->summary = L->stats = false;
   L->n_exc = 0;
   L->ext_pack = nullptr;
   L->paired = b.seqs2 != nullptr;
@@ -298,8 +298,9 @@ int enqueue_query(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p, c
     if (rc) return rc;
     L->spec = db->spec_on();
     L->counted = 0;  // (a lane keeps its fields from batch to batch: the summary path below returns before the counting stages' turn)
-    // (a batch K5 summarises needs K3's last two words only: the pairs it kept, and its count of bad hits)
-    const size_t skip = L->summarized() ? L->n : 0;
+    // (a batch K5 summarises, and one searched for statistics only, needs K3's last two words only: the pairs it kept, and its count of bad hits)
+    const bool stats_only = L->stats && counting_mask(db) != 0;
+    const size_t skip = L->summarized() || stats_only ? L->n : 0;
     HIPCHK(hipMemcpyAsync(L->h_roffs.p + skip, L->d_roffs.p + skip, ((size_t)L->n + 2 - skip) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     L->d_final = L->d_pairs.p;
     if (L->spec) {  // K4 right behind K3: only the surviving reads' matches leave the GPU
@@ -334,6 +335,11 @@ int enqueue_query(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p, c
     for (int s = 0; s < N_COUNTING; s++)
       if ((L->counted >> s & 1) && (L->d_left[s].ensure(L->n) || L->h_left[s].ensure(L->n))) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
     if (L->counted && L->spec && L->h_roffs3.ensure((size_t)L->n + 1)) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
+    if (stats_only) {
+      if (L->d_mask.ensure(L->n) || L->h_mask.ensure(L->n) || L->d_loffs.ensure((size_t)L->n + 1) || L->d_lstats.ensure(K10_STATS) || L->h_lstats.ensure(K10_STATS))
+        return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
+      if (int rc2 = left_compact_reserve(db, L->n)) return rc2;
+    }
     for (int s = 0; s < N_COUNTING; s++) {
       if (!(L->counted >> s & 1)) continue;
       const char* e = getenv(kCountingStages[s].device_knob);  // KMCPG_*_DEVICE=0: every read goes to the host half
@@ -344,7 +350,19 @@ int enqueue_query(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p, c
            : s == K7 ? cooccur_enqueue(db, L->d_pairs.p, L->d_roffs.p, L->d_hits.cap, L->d_qk.p, L->n, final_n, L->d_cnt.p, L->d_hits.cap, d_left, 0, st)
                      : recount_enqueue(db, L->d_pairs.p, L->d_roffs.p, L->d_hits.cap, L->d_qk.p, L->d_ql.p, L->n, final_n, L->d_cnt.p, L->d_hits.cap, d_left, 0, st);
       if (rc) return rc;
-      HIPCHK(hipMemcpyAsync(L->h_left[s].p, d_left, (size_t)L->n, hipMemcpyDeviceToHost, st));
+      if (!stats_only) HIPCHK(hipMemcpyAsync(L->h_left[s].p, d_left, (size_t)L->n, hipMemcpyDeviceToHost, st));
+    }
+    if (stats_only) {
+      // K10 right behind the counting stages: one mask byte per read leaves the GPU instead of the stages' bytes; the pairs of the reads LEFT
+      // to the host go into d_hits — dead once K3 has grouped it, and room for d_hits.cap pairs and more — and come down on demand (collect)
+      const uint8_t* left[N_COUNTING];
+      for (int s = 0; s < N_COUNTING; s++) left[s] = (L->counted >> s & 1) ? L->d_left[s].p : nullptr;
+      kmcpg_pair* out = (kmcpg_pair*)L->d_hits.p;
+      rc = left_compact_enqueue(db, L->d_pairs.p, L->d_roffs.p, L->d_hits.cap, L->n, left, L->d_cnt.p, L->d_hits.cap, L->d_mask.p, out, L->d_hits.cap, L->d_loffs.p, L->d_lstats.p, st);
+      if (rc) return rc;
+      HIPCHK(hipMemcpyAsync(L->h_mask.p, L->d_mask.p, (size_t)L->n, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipMemcpyAsync(L->h_lstats.p, L->d_lstats.p, K10_STATS * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+      L->d_final = out;
     }
     if (L->counted && L->spec) HIPCHK(hipMemcpyAsync(L->h_roffs3.p, L->d_roffs.p, ((size_t)L->n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
   } else L->spec = false, L->counted = 0;
@@ -392,7 +410,8 @@ int enqueue(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p, bool ge
   }
   // K3 only where this handle holds the whole database: the lists of shards (several GPUs, passes of a paged handle) are merged first
   L->grouped = A->device_finalize && !A->hits_stay_on_device && db->opts.shard_count == 1;
-  if (L->h_cnt.ensure(2) || L->h_qk.ensure(n) || L->h_ql.ensure(n) || (L->grouped ? L->h_pairs.ensure(first) : L->h_hits.ensure(first)))
+  // (a batch searched for statistics only brings no pairs down but those of the reads LEFT to the host: collect sizes h_pairs for them)
+  if (L->h_cnt.ensure(2) || L->h_qk.ensure(n) || L->h_ql.ensure(n) || (L->grouped ? (!L->stats && L->h_pairs.ensure(first)) : L->h_hits.ensure(first)))
     return kmcpg_fail(KMCPG_ENOMEM, "hipHostMalloc failed");
   // the reads go up on a stream of their own (150 MB per million reads: 4 ms of PCIe that would otherwise sit between the
   // kernels of consecutive batches); the lane's device buffers are idle, its previous batch was waited for
@@ -448,7 +467,7 @@ int enqueue(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p, bool ge
   HIPCHK(hipMemcpyAsync(L->h_ql.p, L->d_ql.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
   L->copied = A->hits_stay_on_device ? 0 : std::min<uint64_t>(first, L->d_hits.cap);
   L->eager_aside = false;
-  if (L->summarized()) L->copied = 0;  // no eager copy of pairs: what the host needs of them (the LEFT windows') it asks for by itself
+  if (L->summarized() || L->stats_only()) L->copied = 0;  // no eager copy of pairs: what the host needs of them (the LEFT windows', the LEFT reads') it asks for by itself
   if (L->copied && L->grouped && !generous_eager) {
     // a small copy (<= 32 pairs per read), in stream order before the lane's completion event (same-box A/B: on a stream of its own it
     // cost the pipelined submit / wait path 8 %)
@@ -493,6 +512,46 @@ int left_collect(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p, bo
     pairs = k3.data();
   }
   return left_reads_host(db, pairs, offs, L->h_qk.p, L->h_ql.p, L->n, p, mask, left);
+}
+
+// ... of a batch searched for statistics only (Lane::stats_only): the mask bytes and the witness words are here; if a read was LEFT, K10's
+// offsets and the pairs it compacted come down now — nothing else of the batch's matches ever does — and the mask is split into the
+// per-stage bytes the host half takes.  Reads that were not LEFT have empty segments there.  Fills L->left_res
+int stats_collect(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p) {
+  const uint32_t n = L->n;
+  const unsigned long long* w = L->h_lstats.p;
+  kmcpg_stats_ticket_stats& r = L->left_res;
+  r = kmcpg_stats_ticket_stats{};
+  r.k10_ms = -1;
+  r.n_reads = n;
+  r.matched_reads = w[K10_MATCHED];
+  r.kept_pairs = L->h_roffs.p[n];
+  r.left_reads = w[K10_LEFT];
+  r.left_pairs = w[K10_LEFT_PAIRS];
+  r.bad_segments = w[K10_BAD];
+  r.skipped = w[K10_SKIPPED];
+  // the two hit counters, K3's last two words, the witness words, qkmers / qlen and the mask
+  r.bytes_d2h = 4 * sizeof(uint64_t) + K10_STATS * sizeof(unsigned long long) + (uint64_t)n * (2 * sizeof(int32_t) + 1);
+  if (r.skipped || r.left_pairs > r.kept_pairs || r.left_pairs > L->d_hits.cap)
+    return kmcpg_fail(KMCPG_EDEVICE, "internal: K10 left %llu pairs of %llu (skipped: %llu)", (unsigned long long)r.left_pairs, (unsigned long long)r.kept_pairs,
+                      (unsigned long long)r.skipped);
+  if (r.left_reads == 0) return 0;
+  if (L->h_loffs.ensure((size_t)n + 1) || L->h_pairs.ensure(r.left_pairs + 1)) return kmcpg_fail(KMCPG_ENOMEM, "hipHostMalloc failed");
+  HIPCHK(hipMemcpyAsync(L->h_loffs.p, L->d_loffs.p, ((size_t)n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, A->copy_stream));
+  if (r.left_pairs) HIPCHK(hipMemcpyAsync(L->h_pairs.p, L->d_final, r.left_pairs * sizeof(kmcpg_pair), hipMemcpyDeviceToHost, A->copy_stream));
+  HIPCHK(hipStreamSynchronize(A->copy_stream));
+  r.bytes_d2h += ((uint64_t)n + 1) * sizeof(uint64_t) + r.left_pairs * sizeof(kmcpg_pair);
+  if (L->h_loffs.p[n] != r.left_pairs) return kmcpg_fail(KMCPG_EDEVICE, "internal: K10 compacted %llu pairs, counted %llu", (unsigned long long)L->h_loffs.p[n], (unsigned long long)r.left_pairs);
+  const unsigned mask = L->counted & counting_mask(db);
+  std::vector<uint8_t> bytes[N_COUNTING];
+  const uint8_t* left[N_COUNTING] = {};
+  for (int s = 0; s < N_COUNTING; s++) {
+    if (!(mask >> s & 1)) continue;
+    bytes[s].resize(n);
+    for (uint32_t i = 0; i < n; i++) bytes[s][i] = L->h_mask.p[i] >> s & 1;
+    left[s] = bytes[s].data();
+  }
+  return left_reads_host(db, L->h_pairs.p, L->h_loffs.p, L->h_qk.p, L->h_ql.p, n, p, mask, left);
 }
 }  // namespace
 
@@ -550,7 +609,7 @@ int collect(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p, uint64_
     L->copied = cnt;
   }
   if (L->counted && L->grouped) {
-    int rc = left_collect(db, A, L, p, fetch);
+    int rc = L->stats_only() ? stats_collect(db, A, L, p) : left_collect(db, A, L, p, fetch);
     if (rc) return rc;
   }
   // a batch large enough to say something about the data (one genome with 5 000 matches does not)

@@ -83,6 +83,17 @@ struct Lane {
   PinBuf<uint8_t> h_left[N_COUNTING];
   PinBuf<uint64_t> h_roffs3;
   unsigned counted = 0;  // bit s: this batch went through counting stage s
+  // K10 (statistics-only batches, kmcpg_submit_stats): behind the counting stages the bytes of d_left become one mask byte per read and the
+  // LEFT reads' segments are compacted into d_hits (= d_final; offsets in d_loffs) — dead once K3 has grouped it; the mask and the lane's own
+  // witness words come down with the batch, the offsets and the pairs on demand (collect); of K3's offsets only the last two words do
+  bool stats = false;  // the caller asked for statistics only (set after lane_begin, before enqueue)
+  DevBuf<uint8_t> d_mask;
+  PinBuf<uint8_t> h_mask;
+  DevBuf<unsigned long long> d_lstats;
+  PinBuf<unsigned long long> h_lstats;
+  PinBuf<uint64_t> h_loffs;
+  bool stats_only() const { return stats && grouped && counted != 0; }  // K10 ran: left_res is the result (after collect)
+  kmcpg_stats_ticket_stats left_res{};
   bool spec = false;  // this batch went through K4: h_roffs / h_pairs hold ITS output, h_verd the verdicts
   // 2-bit packed upload (stage): the batch's bases as codes + the runs of foreign bytes instead of h_seqs; unpacked on the device
   PinBuf<uint8_t> h_pack;
@@ -125,6 +136,7 @@ struct Lane {
     for (auto& b : d_left) b.release();
     for (auto& b : h_left) b.release();
     h_roffs3.release();
+    d_mask.release(); h_mask.release(); d_lstats.release(); h_lstats.release(); h_loffs.release();
     h_pack.release(); h_exc.release(); d_pack.release(); d_exc.release();
     h_wmeta.release(); d_soffs.release(); d_wmeta.release(); d_wsrc.release();
     if (done) (void)hipEventDestroy(done);
@@ -218,6 +230,8 @@ struct kmcpg_ticket {
   // summaries in piece_sum[i]
   bool summary = false;
   std::vector<kmcpg::SummaryPart> piece_sum;
+  // kmcpg_submit_stats: the ticket is consumed by kmcpg_wait_stats only
+  bool stats = false;
 };
 
 namespace kmcpg {
@@ -268,7 +282,7 @@ void drop_ticket(kmcpg_ticket* t, bool failed = false);
 // the submit family works on a handle that holds the whole database and can reach a GPU; *p = the caller's params or the defaults
 int submit_handle(kmcpg_db* db, const kmcpg_params* params, kmcpg_params* p);
 int submit_impl(kmcpg_db* db, const HostBatch& b, const kmcpg_params& p, bool retry, bool block, kmcpg_ticket** out, const PackedIn* packed = nullptr,
-                bool summary = false);
+                bool summary = false, bool stats = false);
 // kmcpg_wait / kmcpg_wait_pairs: the ticket's result, as_pairs = in the compact form where the path it took collects that natively; gives the ticket back
 int wait_impl(kmcpg_ticket* t, kmcpg_result* out, bool as_pairs);
 // kmcpg_wait_summaries: the summaries of a ticket of kmcpg_submit_windows_summary (one batch or its pieces); gives the ticket back

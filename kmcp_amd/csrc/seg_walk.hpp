@@ -1,5 +1,5 @@
 // seg_walk.hpp — the walk over K3's (column, count) segments that the stages behind K3 share: K4 (k4_specific.hip), K5 (k5_summary.hip),
-// K6 (k6_refstats.hip).  Device code, and nothing stage-specific: what a stage does with a segment's reduced classes is its own.
+// K6 (k6_refstats.hip), K10 (k10_left.hip).  Device code, and nothing stage-specific: what a stage does with a segment's reduced classes is its own.
 //
 // One wave takes RPW = 16 consecutive reads (as k3_sort_wave): lanes 0..16 load the offsets with one coalesced load, and the LPR = 4 lanes
 // of lane group g work for read r0 + g.  A segment of up to GROUP_CAP = 64 pairs is reduced by its lane group (strided loads, two
@@ -163,6 +163,12 @@ __device__ __forceinline__ uint32_t wave_count(bool p) { return (uint32_t)__popc
 template <class Word>
 __device__ __forceinline__ void wave_add(Word* word, uint32_t n, uint32_t lane) {
   if (lane == 0 && n) atomicAdd(word, (Word)n);
+}
+// ... and the sum of a 64-bit value over the wave's lanes (every lane takes part and gets the sum; a lane without a share holds 0)
+__device__ __forceinline__ uint64_t wave_sum64(uint64_t v) {
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) v += __shfl_xor(v, d, 64);
+  return v;
 }
 
 }  // namespace kmcpg

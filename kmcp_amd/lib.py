@@ -32,6 +32,7 @@ EXPORTS = [
     "kmcpg_set_cooccur", "kmcpg_cooccur_device", "kmcpg_cooccur_read", "kmcpg_cooccur_reset", "kmcpg_last_cooccur",
     "kmcpg_set_recount", "kmcpg_recount_log_device", "kmcpg_recount_run", "kmcpg_recount_read", "kmcpg_recount_reset", "kmcpg_last_recount",
     "kmcpg_em_pass", "kmcpg_em_read", "kmcpg_last_em", "kmcpg_count_left_reads",
+    "kmcpg_left_compact_device", "kmcpg_submit_stats", "kmcpg_wait_stats", "kmcpg_last_stats",
     "kmcpg_sketch_genomes_to", "kmcpg_builder_open", "kmcpg_builder_close", "kmcpg_builder_add_cols", "kmcpg_builder_plan",
     "kmcpg_builder_col_place", "kmcpg_builder_block_info", "kmcpg_builder_begin_round", "kmcpg_builder_scatter_device",
     "kmcpg_builder_end_round", "kmcpg_builder_finish", "kmcpg_builder_info",
@@ -249,6 +250,21 @@ class SummaryStats(C.Structure):
     """kmcpg_summary_stats: the witness of the last K5 launch, or of the last ticket of wait_summaries"""
     _fields_ = [("single", C.c_uint64), ("wave", C.c_uint64), ("left", C.c_uint64), ("empty", C.c_uint64), ("left_pairs", C.c_uint64),
                 ("bytes_d2h", C.c_uint64), ("bad_segments", C.c_uint64), ("k5_ms", C.c_double)]
+
+
+K10_MASK, K10_COMPACT, K10_OFFS = 67, 68, 69  # KMCPG_K10_*: kmcpg_k4_launch.kernel of K10's own kernels
+
+
+class StatsResult(C.Structure):
+    """kmcpg_result_stats: what a statistics-only ticket came to (plain values, nothing to free)"""
+    _fields_ = [("n_reads", C.c_uint64), ("matched_reads", C.c_uint64), ("kept_pairs", C.c_uint64), ("left_reads", C.c_uint64),
+                ("left_pairs", C.c_uint64), ("bytes_d2h", C.c_uint64)]
+
+
+class StatsTicketStats(C.Structure):
+    """kmcpg_stats_ticket_stats: the witness of the last K10 launch, or of the last ticket of wait_stats"""
+    _fields_ = [("n_reads", C.c_uint64), ("matched_reads", C.c_uint64), ("kept_pairs", C.c_uint64), ("left_reads", C.c_uint64),
+                ("left_pairs", C.c_uint64), ("bytes_d2h", C.c_uint64), ("bad_segments", C.c_uint64), ("skipped", C.c_uint64), ("k10_ms", C.c_double)]
 
 
 COL_STATS_DTYPE = np.dtype([("rows", "<u8"), ("firsts", "<u8"), ("ureads", "<u8"), ("hic_ureads", "<u8")])  # kmcpg_col_stats
@@ -529,6 +545,10 @@ def load():
     L.kmcpg_em_read.argtypes = [vp, vp, C.c_uint32, C.POINTER(EmTotals)]
     L.kmcpg_last_em.argtypes = [vp, C.POINTER(EmStats), C.POINTER(K4Launch), C.c_uint32, C.POINTER(C.c_uint32)]
     L.kmcpg_count_left_reads.argtypes = [vp, vp, vp, vp, vp, C.c_uint32, C.POINTER(Params), vp, vp, vp]
+    L.kmcpg_left_compact_device.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp, vp, vp, C.c_uint64, vp, vp, C.c_uint64, vp, vp]
+    L.kmcpg_submit_stats.argtypes = [vp, vp, vp, vp, vp, C.c_uint32, C.POINTER(Params), C.POINTER(vp)]
+    L.kmcpg_wait_stats.argtypes = [vp, C.POINTER(StatsResult)]
+    L.kmcpg_last_stats.argtypes = [vp, C.POINTER(StatsTicketStats), C.POINTER(K4Launch), C.c_uint32, C.POINTER(C.c_uint32)]
     L.kmcpg_sketch_genomes_to.argtypes = [vp, vp, vp, C.c_uint32, C.POINTER(SplitSpec), SKETCH_SINK, vp]
     u32p = C.POINTER(C.c_uint32)
     L.kmcpg_builder_open.argtypes = [C.POINTER(BuilderCfg), C.c_int32, C.POINTER(vp)]
@@ -1522,6 +1542,47 @@ class Database:
         assert all(l is None or len(l) == n for l in left)
         _check(load().kmcpg_count_left_reads(self._h, pairs.ctypes.data, read_offs.ctypes.data, qkmers.ctypes.data, qlen.ctypes.data, n, C.byref(p),
                                              *[None if l is None else l.ctypes.data for l in left]))
+
+    # ---- statistics-only search: the counting stages and K10, no matches to the host ----------------------------
+    def submit_stats(self, seqs, offs, seqs2=None, offs2=None, params=None):
+        """kmcpg_submit_stats: submit's arguments on a handle with a counting stage on; the ticket is consumed by wait_stats only"""
+        p = params or default_params()
+        t = C.c_void_p()
+        n = len(offs) - 1
+        _check(load().kmcpg_submit_stats(self._h, seqs.ctypes.data, offs.ctypes.data, seqs2.ctypes.data if seqs2 is not None else None,
+                                         offs2.ctypes.data if offs2 is not None else None, n, C.byref(p), C.byref(t)))
+        return t
+
+    def wait_stats(self, ticket):
+        """kmcpg_wait_stats: dict of n_reads, matched_reads, kept_pairs, left_reads, left_pairs, bytes_d2h"""
+        r = StatsResult()
+        _check(load().kmcpg_wait_stats(ticket, C.byref(r)))
+        return {f: int(getattr(r, f)) for f, _ in StatsResult._fields_}
+
+    def search_stats(self, reads, reads2=None, params=None):
+        """`reads` (list of bytes) through submit_stats / wait_stats: the counting stages' state on the handle is the result"""
+        seqs, offs = pack_reads(reads)
+        s2 = o2 = None
+        if reads2 is not None:
+            s2, o2 = pack_reads(reads2)
+        return self.wait_stats(self.submit_stats(seqs, offs, s2, o2, params))
+
+    def left_compact_device(self, d_pairs, d_read_offs, pair_cap, n, d_left_refstats, d_left_cooccur, d_left_recount, d_n_hits, hit_cap, d_mask,
+                            d_left_pairs, left_cap, d_left_offs, stream=None):
+        """kmcpg_left_compact_device on device pointers: the stages' LEFT bytes (None: the stage is not looked at) -> one mask byte per read,
+        the pairs of the LEFT reads compacted behind d_left_pairs with their offsets (n + 1 words)."""
+        _check(load().kmcpg_left_compact_device(self._h, d_pairs, d_read_offs, pair_cap, n, d_left_refstats, d_left_cooccur, d_left_recount, d_n_hits, hit_cap,
+                                                d_mask, d_left_pairs, left_cap, d_left_offs, stream))
+
+    def last_stats(self):
+        """kmcpg_last_stats: (dict of the counters, [K4Launch] of the last K10 launch — empty below profiling level 1)"""
+        st = StatsTicketStats()
+        n = C.c_uint32(0)
+        _check(load().kmcpg_last_stats(self._h, C.byref(st), None, 0, C.byref(n)))
+        buf = (K4Launch * max(1, n.value))()
+        _check(load().kmcpg_last_stats(self._h, C.byref(st), buf, n.value, C.byref(n)))
+        self.last_k10_ms = float(st.k10_ms)  # HIP-event time of the stage's kernels (profiling level >= 1), else -1
+        return {f: int(getattr(st, f)) for f, _ in StatsTicketStats._fields_ if f != "k10_ms"}, [buf[i] for i in range(n.value)]
 
     # ---- bench / parity support -----------------------------------------------------------------------
     def read_row_range(self, block, first_row, out):
