@@ -5,7 +5,7 @@
 //   kmcp-refstats [-o out.tsv[.gz]] [--cooccur pairs.tsv[.gz]] [-f 0.01] [-t 0.55] [-n 0] [--keep-perfect-matches] [--keep-main-matches] [--max-qcov-gap 0.4]
 //                 [-m 3] [-p frac] [-H qcov] [--level species|strain|assembly] [-T map.tsv[,more.tsv]]... [-X taxdump/] [-i list.txt]
 //                 [--recount recount.tsv[.gz]] [-r n] [-u n] [-U n] [-P prop] [-d stdev] [-D 0.05] [-R 0.05] [--no-amb-corr] [--norm-abund mean|min|max]
-//                 [--profile profile.tsv[.gz]] [-I 10] [--abund-pct-threshold 0.01] [-F 0]
+//                 [--profile profile.tsv[.gz]] [-I 10] [--abund-pct-threshold 0.01] [-F 0] [--binning out[.binning[.gz]]] [--sample-id S]
 //                 [a.tsv[.gz] ...]
 //
 // Semantics restated from the reference (the counting rule, the verdict and the presets are kmcp_amd/csrc/refstats_rule.hpp):
@@ -26,6 +26,9 @@
 //     per row of a reference stage 3 judged ok, and the distinct query names of one input at a time) and every
 //     pass applies the row cuts after the skip of the rows outside ITS whitelist, as profile.go:2039-2226 does.  -m 0 is refused: its
 //     final order rests on the score column, which this tool does not compute.
+//   * --binning FILE: the binning pass of `kmcp profile -B` (profile.go:2591-2784) after stage 4 — one line `query<TAB>TaxId` per read
+//     with a row of a reference the EM ended with (its whitelist after the last pass, before -F).  The rule, the pruned tree and what is
+//     done with unknown TaxIds are kmcp_amd/csrc/bin_rule.hpp, the file's name and format cli/binning_format.hpp.  Needs --profile, -T, -X.
 // The reference prints none of this (it goes on to stages 2-4); the output format is this tool's:
 //   # matched reads: N
 //   # unique reads: U
@@ -50,6 +53,8 @@
 #include "../kmcp_amd/csrc/refstats_rule.hpp"
 #include "../kmcp_amd/csrc/taxonomy.hpp"
 #include "../kmcp_amd/csrc/em_rule.hpp"
+#include "../kmcp_amd/csrc/bin_rule.hpp"
+#include "binning_format.hpp"
 #include "profile_format.hpp"
 #include "recount_format.hpp"
 #include "tsv_in.hpp"
@@ -100,7 +105,11 @@ void usage() {
       "                                    The rows of the references stage 3 keeps stay in memory for the passes: about 56 bytes per row.\n"
       "  -I, --abund-max-iters int         Maximum iteration of abundance estimation. (default 10)\n"
       "      --abund-pct-threshold float   If the percentage change of the predominant target is smaller than this threshold, stop the iteration. (default 0.01)\n"
-      "  -F, --filter-low-pct float        Filter out predictions with the smallest relative abundances summing up X%. Range: [0,100). (default 0)\n",
+      "  -F, --filter-low-pct float        Filter out predictions with the smallest relative abundances summing up X%. Range: [0,100). (default 0)\n"
+      "  -B, --binning string              Also save the binning result (one TaxId per read: that of its reference, or the lowest common\n"
+      "                                    ancestor of its references) in CAMI format; \".binning.gz\" is appended unless the name ends in\n"
+      "                                    \".binning\" or \".binning.gz\". Needs --profile, -T and -X. Stdin is not supported.\n"
+      "  -s, --sample-id string            Sample ID in the binning result.\n",
       stderr);
 }
 
@@ -162,7 +171,7 @@ bool parse_row(const char* p, size_t n, double min_qcov, double max_fpr, Fields*
 }  // namespace
 
 int main(int argc, char** argv) {
-  std::string out_file = "-", level = "species", taxdump, infile_list, cooccur_file, recount_file, norm_abund = "mean", profile_file;
+  std::string out_file = "-", level = "species", taxdump, infile_list, cooccur_file, recount_file, norm_abund = "mean", profile_file, binning_file, sample_id;
   long max_iters = 10;
   double pct_threshold = 0.01, filter_low_pct = 0;
   long flag_r = 50, flag_u = 20, flag_U = 5;
@@ -226,6 +235,8 @@ int main(int argc, char** argv) {
     else if (a == "--no-amb-corr") no_amb_corr = true;
     else if (a == "--norm-abund") norm_abund = need(i);
     else if (a == "--profile") profile_file = need(i);
+    else if (a == "-B" || a == "--binning" || a == "--binning-result") binning_file = need(i);
+    else if (a == "-s" || a == "--sample-id") sample_id = need(i);
     else if (a == "-I" || a == "--abund-max-iters") max_iters = integer("-I, --abund-max-iters", need(i));
     else if (a == "--abund-pct-threshold") pct_threshold = num("--abund-pct-threshold", need(i));
     else if (a == "-F" || a == "--filter-low-pct") filter_low_pct = num("-F, --filter-low-pct", need(i));
@@ -324,6 +335,18 @@ int main(int argc, char** argv) {
     if (same(out_file)) die("flag --profile: the file must not be the out file (-o)");
     if (!cooccur_file.empty() && same(cooccur_file)) die("flag --profile: the file must not be the --cooccur file");
     if (!recount_file.empty() && same(recount_file)) die("flag --profile: the file must not be the --recount file");
+  }
+  if (!binning_file.empty()) {  // before anything is read
+    if (profile_file.empty()) die("flag --binning: --profile is needed (the reads are binned over the references the EM ends with)");
+    if (map_files.empty() || taxdump.empty()) die("flag -T/--taxid-map and -X/--taxdump needed when -B/--binning-result given");
+    binning_file = binning_format::file_name(binning_file);
+    const auto same = [&](const std::string& other) { return tsv_in::clean_path(binning_file) == tsv_in::clean_path(other); };
+    for (const std::string& f : files) {
+      if (f == "-") die("flag --binning: stdin is not supported (the search results are read five times)");
+      if (same(f)) die("flag --binning: the file should not be one of the input file");
+    }
+    if (same(out_file) || same(profile_file) || (!cooccur_file.empty() && same(cooccur_file)) || (!recount_file.empty() && same(recount_file)))
+      die("flag --binning: the file must not be one of the other out files");
   }
   const bool stage3 = !recount_file.empty() || !profile_file.empty();
   th.min_chunks_fraction = min_frac;
@@ -635,6 +658,17 @@ int main(int argc, char** argv) {
     em_order = kmcpg::em_finish(em_classes, filter_low_pct, &em_res);
   }
 
+  // the binning pass (profile.go:2591-2784): the inputs once more, over the references the EM ended with — refused before a file is written
+  kmcpg::BinPlan bin_plan;
+  if (!binning_file.empty()) {
+    std::vector<std::string> whitelist;
+    for (size_t c = 0; c < em_classes.size(); c++)
+      if (c < em_res.est.size() && em_res.est[c]) whitelist.push_back(em_classes[c].name);
+    std::sort(whitelist.begin(), whitelist.end());  // (the refusal names the first in byte order, whatever numbered the references)
+    std::string missing;
+    if (!kmcpg::bin_plan_build(tax, tmap, whitelist, &bin_plan, &missing)) die("unknown taxid for %s, please check taxid mapping file(s)", missing.c_str());
+  }
+
   Out out(out_file, -1);
   char line[256];
   out.write(line, (size_t)snprintf(line, sizeof line, "# matched reads: %llu\n# unique reads: %llu\n", (unsigned long long)matched, (unsigned long long)unique));
@@ -673,6 +707,43 @@ int main(int argc, char** argv) {
     Out pf(profile_file, -1);
     profile_format::write(pf, em_classes, em_res, em_order);
     pf.close();
+  }
+
+  if (!binning_file.empty()) {
+    Out bf(binning_file, -1);
+    binning_format::write_header(bf, sample_id);
+    kmcpg::BinAcc acc;
+    acc.cut = cut;
+    for (const std::string& file : files) {
+      RawLines in(file);
+      std::string query;  // the name of the previous whitelisted row that passed -t / -f
+      bool any = false;
+      auto flush = [&] {
+        const uint32_t bin = any ? acc.bin(bin_plan) : kmcpg::BIN_NONE;
+        if (bin != kmcpg::BIN_NONE) binning_format::write_line(bf, query.data(), query.size(), bin);
+      };
+      const char* p = nullptr;
+      size_t n = 0;
+      while (in.next(&p, &n)) {
+        Fields fl;
+        double qcov = 0;
+        if (!parse_row(p, n, min_qcov, max_fpr, &fl, &qcov)) continue;
+        const char* fp;
+        const size_t fn = fl.get(6, &fp);
+        name.assign(fp, fn);
+        const uint32_t node = bin_plan.node_of(name);
+        if (node == kmcpg::BIN_NO_NODE) continue;  // skipped before anything else: it neither opens a query nor is its first row
+        if (!any || query.size() != fl.tab[0] || memcmp(query.data(), p, fl.tab[0]) != 0) {
+          flush();
+          query.assign(p, fl.tab[0]);
+          any = true;
+          acc.begin();
+        }
+        acc.row(node, qcov);
+      }
+      flush();
+    }
+    bf.close();
   }
 
   if (!cooccur_file.empty()) {

@@ -112,6 +112,11 @@ struct Options {
   // --ref-stats-only: the same files, and no search result — the batches go through kmcpg_submit_stats / kmcpg_wait_stats, no match leaves
   // the GPU but those of the reads the counting stages left to the host
   bool ref_stats_only = false;
+  // --binning FILE --binning-refs LIST --taxid-map ... --taxdump ... [--binning-sample-id S]: the binning file of `kmcp profile -B` and no
+  // search result — the batches go through kmcpg_submit_bins / kmcpg_wait_bins (K11 of the library, kmcpg_set_binning), four bytes per read
+  // leave the GPU; the file is what `kmcp-refstats -f 1 -t 0 ... --profile P --binning FILE` writes from this search's TSV when LIST = P
+  std::string binning, binning_refs, binning_sample_id;
+  const char* binning_flag = nullptr;  // the first --binning-* flag other than --binning that was given
   long long ref_stats_iters = 10;
   double ref_stats_pct = 0.01, ref_stats_filter = 0;
   const char* profile_flag = nullptr;       // the first of the three optional flags that was given
@@ -185,6 +190,14 @@ static void usage() {
       "                             --ref-stats-only: write the --ref-stats* files and NO search result — byte for byte the files of the\n"
       "                             same command without it, but no match leaves the GPU except those of the reads its counting kernels\n"
       "                             leave to the host, and no row is formatted.  Not with -o, --specific-level, --regions-bed, --also-db, -g.\n"
+      "           --binning file --binning-refs file --taxid-map file[,file...] --taxdump dir [--binning-sample-id string]\n"
+      "                             write the binning result of `kmcp profile -B` (CAMI format: one TaxId per read — that of its reference,\n"
+      "                             or the lowest common ancestor of its references) and NO search result: the reads are searched and\n"
+      "                             binned on the GPU, four bytes per read leave it.  --binning-refs lists the references to bin over, the\n"
+      "                             first column of every line that does not start with '#': a profile of --ref-stats-profile or\n"
+      "                             kmcp-refstats --profile as it is.  The file is what `kmcp-refstats -f 1 -t 0 ... --profile P --binning`\n"
+      "                             writes from the search result; \".binning.gz\" is appended unless the name ends in \".binning[.gz]\".\n"
+      "                             Not with -o, any --ref-stats* flag, or what --ref-stats-only refuses.\n"
       "           --parse-only (read the inputs and print records / bases / checksum per file; no database, no GPU)\n"
       "           --regions-bed file [--regions-min-overlap int (1)] [--regions-max-gap int (0)] [--regions-ignore-type]\n"
       "                             [--regions-name-species string] [--regions-name-assembly string]\n"
@@ -228,6 +241,7 @@ static Options parse_args(int argc, char** argv) {
       {"ref-stats", 0, 1}, {"ref-stats-mode", 0, 1}, {"ref-stats-min-hic-ureads-qcov", 0, 1}, {"ref-stats-min-chunks-fraction", 0, 1}, {"ref-stats-level", 0, 1}, {"ref-stats-cooccur", 0, 1}, {"ref-stats-cooccur-slots", 0, 1},
       {"ref-stats-recount", 0, 1}, {"ref-stats-no-amb-corr", 0, 0}, {"ref-stats-min-dreads-prop", 0, 1}, {"ref-stats-max-mismatch-err", 0, 1}, {"ref-stats-recount-log-mb", 0, 1},
       {"ref-stats-only", 0, 0}, {"ref-stats-profile", 0, 1}, {"ref-stats-abund-max-iters", 0, 1}, {"ref-stats-abund-pct-threshold", 0, 1}, {"ref-stats-filter-low-pct", 0, 1},
+      {"binning", 0, 1}, {"binning-refs", 0, 1}, {"binning-sample-id", 0, 1},
       {"regions-bed", 0, 1}, {"regions-min-overlap", 0, 1}, {"regions-max-gap", 0, 1}, {"regions-ignore-type", 0, 0},
       {"regions-name-species", 0, 1}, {"regions-name-assembly", 0, 1}};
   auto regions_flag = [&](const char* flag) {
@@ -294,6 +308,9 @@ static Options parse_args(int argc, char** argv) {
     else if (name == "ref-stats-recount-log-mb") { o.ref_stats_recount_log_mb = to_i(name, v); if (o.ref_stats_recount_log_mb < 0) o.ref_stats_recount_log_mb = 0; if (!o.recount_flag) o.recount_flag = "--ref-stats-recount-log-mb"; }
     else if (name == "ref-stats-profile") o.ref_stats_profile = v;
     else if (name == "ref-stats-only") o.ref_stats_only = true;
+    else if (name == "binning") o.binning = v;
+    else if (name == "binning-refs") { o.binning_refs = v; if (!o.binning_flag) o.binning_flag = "--binning-refs"; }
+    else if (name == "binning-sample-id") { o.binning_sample_id = v; if (!o.binning_flag) o.binning_flag = "--binning-sample-id"; }
     else if (name == "ref-stats-abund-max-iters") { o.ref_stats_iters = to_i(name, v); if (!o.profile_flag) o.profile_flag = "--ref-stats-abund-max-iters"; }
     else if (name == "ref-stats-abund-pct-threshold") { o.ref_stats_pct = to_f(name, v); if (!o.profile_flag) o.profile_flag = "--ref-stats-abund-pct-threshold"; }
     else if (name == "ref-stats-filter-low-pct") { o.ref_stats_filter = to_f(name, v); if (!o.profile_flag) o.profile_flag = "--ref-stats-filter-low-pct"; }
@@ -368,6 +385,8 @@ static Options parse_args(int argc, char** argv) {
 #include "../kmcp_amd/csrc/taxonomy.hpp"
 #include "../kmcp_amd/csrc/regions_rule.hpp"
 #include "../kmcp_amd/csrc/refstats_rule.hpp"
+#include "../kmcp_amd/csrc/bin_rule.hpp"
+#include "binning_format.hpp"
 #include "recount_format.hpp"
 #include "profile_format.hpp"
 #include "search_batch.hpp"
@@ -534,7 +553,23 @@ static int run_parse_only(const Options& o) {
 static int validate_flags(const Options& o, bool sliding) {
   // --specific-level: what would judge something else than a query's final matches, and the handles that do not hold them in one place,
   // are refused here, before a file or a GPU is touched (the words of kmcp utils filter where it has them, filter.go:93-114)
-  if (o.specific_level.empty() && o.ref_stats.empty() && (!o.taxid_maps.empty() || !o.taxdump.empty())) die("flags --taxid-map and --taxdump are only used with --specific-level");
+  if (o.specific_level.empty() && o.ref_stats.empty() && o.binning.empty() && (!o.taxid_maps.empty() || !o.taxdump.empty()))
+    die("flags --taxid-map and --taxdump are only used with --specific-level");
+  // --binning: no search result is written and no counting stage runs; what --ref-stats-only refuses is refused here, for its reasons
+  if (o.binning.empty() && o.binning_flag) die("flag %s is only used with --binning", o.binning_flag);
+  if (!o.binning.empty()) {
+    const char* stats = !o.ref_stats.empty() ? "--ref-stats" : o.ref_stats_flag ? o.ref_stats_flag : o.recount_flag ? o.recount_flag : !o.ref_stats_profile.empty() ? "--ref-stats-profile"
+                        : o.profile_flag ? o.profile_flag : o.ref_stats_only ? "--ref-stats-only" : nullptr;
+    if (stats) die("flag %s cannot be combined with --binning: the reads are binned over references a profile of an earlier run lists (--binning-refs)", stats);
+    const char* clash = o.out_file_given ? "-o/--out-file" : !o.specific_level.empty() ? "--specific-level" : !o.regions_bed.empty() ? "--regions-bed"
+                        : !o.also_dbs.empty() ? "--also-db" : o.whole_file ? "-g/--query-whole-file" : nullptr;
+    if (clash) die("flag %s cannot be combined with --binning: no search result is written, the reads are only binned", clash);
+    const char* bad = o.keep_unmatched ? "-K/--keep-unmatched" : o.try_se ? "--try-se" : o.top_scores != 0 ? "-n/--keep-top-scores"
+                      : sliding ? "--sliding-step/--sliding-window/--sliding-greedy" : o.gpus_given ? "--gpus/--gpu-ids" : o.gpu_passes >= 0 ? "--gpu-passes" : nullptr;
+    if (bad) die("flag %s cannot be combined with --binning", bad);
+    if (o.binning_refs.empty()) die("flag --binning needs --binning-refs: the list of the references to bin over (a profile of kmcp-refstats --profile or --ref-stats-profile as it is)");
+    if (o.taxid_maps.empty() || o.taxdump.empty()) die("TaxID mapping files (--taxid-map) and taxonomy dump files (--taxdump) are needed for --binning");
+  }
   if (!o.specific_level.empty()) {
     const bool species = o.specific_level == "species";
     if (!species && o.specific_level != "strain" && o.specific_level != "assembly")
@@ -790,12 +825,15 @@ struct Pipeline {
   const bool paired, sliding;
   bool regions() const { return !o.regions_bed.empty(); }
   bool stats_only() const { return o.ref_stats_only; }
+  bool bins_only() const { return !o.binning.empty(); }
   const kmcpg_window_spec wspec;
   // set by main after the database open and before the searchers start; the reader never looks at them
   kmcpg_db* db = nullptr;
   int32_t paged_passes = 0;  // > 1: a paged index, searched in this many passes per batch
   kmcpg_params params{};
   std::vector<std::string> target;  // target names after mapping, by column
+  kmcpg::BinPlan bin_plan;          // --binning: the pruned tree of the listed references ...
+  std::vector<uint32_t> bin_node;   // ... and the node of every column (kmcpg::BIN_NO_NODE: not listed)
 
   // ---- the queues and the gate
   Queue<std::unique_ptr<Batch>> q_in{24};  // reader -> searchers
@@ -814,11 +852,58 @@ struct Pipeline {
   // the writer loop alone (the main thread), read by print_summary and the trailer after it
   uint64_t total = 0, matched = 0;
   kmcpg_result_stats stats{};  // --ref-stats-only: the tickets' sums
+  kmcpg_result_bins bins{};    // --binning: the tickets' sums
   int fmt_threads = 0;
   double t_fmt = 0;                                       // formatting + writing, all of an iteration
   double t_fmt_busy = 0;                                  // summed over the formatter threads: time inside the parts
   double t_fmt_pool = 0, t_fmt_push = 0, t_fmt_wait = 0;  // rows being formatted / waiting for the flusher / waiting for a searched batch
 };
+
+// --binning: the listed references (--binning-refs: the first tab-separated column of every line that does not start with '#', so that a
+// profile can be passed as it is) and the plan over their TaxIds (kmcp_amd/csrc/bin_rule.hpp).  `target`: the database's printed target
+// names by column, from a metadata-only handle — a listed name the database does not have and a listed reference without a TaxId are
+// refused here, before the GPU is touched or a file is written
+static void plan_binning(const Options& o, Pipeline& p, const std::vector<std::string>& target, const kmcpg::Taxonomy& tax, const kmcpg::TaxidMap& map) {
+  std::vector<std::string> refs;
+  {
+    gzFile f = gzopen(o.binning_refs.c_str(), "rb");  // (reads plain files as they are)
+    if (!f) die("%s: %s", o.binning_refs.c_str(), strerror(errno));
+    std::string text;
+    char buf[1 << 16];
+    int n;
+    while ((n = gzread(f, buf, sizeof buf)) > 0) text.append(buf, (size_t)n);
+    if (n < 0) die("%s: read error", o.binning_refs.c_str());
+    gzclose(f);
+    std::set<std::string> seen;
+    for (size_t at = 0; at < text.size();) {
+      size_t end = text.find('\n', at);
+      if (end == std::string::npos) end = text.size();
+      std::string line = text.substr(at, end - at);
+      at = end + 1;
+      if (!line.empty() && line.back() == '\r') line.pop_back();
+      if (line.empty() || line[0] == '#') continue;
+      line.resize(std::min(line.size(), line.find('\t')));
+      if (seen.insert(line).second) refs.push_back(line);
+    }
+  }
+  std::sort(refs.begin(), refs.end());  // (the refusals name the first in byte order)
+  const std::set<std::string> have(target.begin(), target.end());
+  for (const std::string& r : refs)
+    if (!have.count(r)) die("flag --binning-refs: the database has no reference %s", r.c_str());
+  std::string missing;
+  if (!kmcpg::bin_plan_build(tax, map, refs, &p.bin_plan, &missing)) die("unknown taxid for %s, please check taxid mapping file(s)", missing.c_str());
+  if (p.bin_plan.unknown_taxids)
+    warn("%llu TaxId(s) of the listed references are deleted or not in nodes.dmp: a read that matches one of them and any other reference is binned at 0", (unsigned long long)p.bin_plan.unknown_taxids);
+  if (!o.quiet) info("  binning over %zu references, %zu nodes of the taxonomy", refs.size(), p.bin_plan.parent.size());
+}
+// ... and the library's stage, once the database is open
+static void set_binning(Pipeline& p) {
+  p.bin_node.resize(p.target.size());
+  for (size_t c = 0; c < p.target.size(); c++) p.bin_node[c] = p.bin_plan.node_of(p.target[c]);
+  if (kmcpg_set_binning(p.db, p.bin_node.data(), (uint32_t)p.bin_node.size(), p.bin_plan.parent.data(), p.bin_plan.last.data(), p.bin_plan.taxid.data(),
+                        (uint32_t)p.bin_plan.parent.size()) != 0)
+    die("%s", kmcpg_last_error());
+}
 
 // ---- reader thread
 
@@ -1443,8 +1528,31 @@ struct Searcher {
     kmcpg_result_pairs_free(&bb.res);
   }
 
+  // --binning, a batch the ticket route could not take for memory: the one-call form brings all its matches to the host (and halves the
+  // batch if it must), and the bins come from the rule itself (kmcp_amd/csrc/bin_rule.hpp) over the plan the library was given
+  void search_sync_bins(Batch& bb) {
+    static std::atomic<bool> said{false};
+    if (!said.exchange(true))
+      warn("--binning: a batch did not fit the binning route (%s); it is binned through the route that brings all its matches to the host", kmcpg_last_error());
+    search_sync(bb);
+    const kmcpg_result_pairs& r = bb.res;
+    bb.bres = kmcpg_result_bins{};
+    bb.bres.n_reads = r.n_reads;
+    bb.bins.assign(r.n_reads, kmcpg::BIN_NONE);
+    for (uint32_t i = 0; i < r.n_reads; i++) {
+      kmcpg::BinRange range;
+      for (uint64_t j = r.match_offs[i]; j < r.match_offs[i + 1]; j++) range.add(p.bin_node[r.pairs[j].col]);
+      bb.bins[i] = range.bin(p.bin_plan);
+      bb.bres.binned_reads += range.none() ? 0 : 1;
+    }
+    bb.bres.kept_pairs = r.n_reads ? r.match_offs[r.n_reads] : 0;
+    bb.bres.host_reads = r.n_reads, bb.bres.left_pairs = bb.bres.kept_pairs;  // (all of them came to the host)
+    bb.bres.bytes_d2h = bb.bres.kept_pairs * sizeof(kmcpg_pair) + bb.bres.n_reads * (sizeof(uint64_t) + 2 * sizeof(int32_t));
+    kmcpg_result_pairs_free(&bb.res);
+  }
+
   void publish(std::unique_ptr<Batch> bb) {
-    if (!p.o.quiet && !p.stats_only()) {  // order-independent checksum of the (query, column, mKmers) tuples: the same on 1, 2, 4, 8 GPUs
+    if (!p.o.quiet && !p.stats_only() && !p.bins_only()) {  // order-independent checksum of the (query, column, mKmers) tuples: the same on 1, 2, 4, 8 GPUs
       const kmcpg_result_pairs& r = bb->res;
       for (uint32_t i = 0; i < r.n_reads; i++)
         for (uint64_t j = r.match_offs[i]; j < r.match_offs[i + 1]; j++)
@@ -1459,9 +1567,14 @@ struct Searcher {
     std::unique_ptr<Batch> bb = std::move(fl.front().second);
     fl.pop_front();
     const auto t0 = Clock::now();
-    const int rc = p.stats_only() ? kmcpg_wait_stats(t, &bb->stats) : p.regions() ? kmcpg_wait_summaries(t, &bb->sres) : kmcpg_wait_pairs(t, &bb->res);
+    if (p.bins_only()) bb->bins.resize(bb->size());
+    const int rc = p.bins_only()    ? kmcpg_wait_bins(t, bb->bins.data(), &bb->bres)
+                   : p.stats_only() ? kmcpg_wait_stats(t, &bb->stats)
+                   : p.regions()    ? kmcpg_wait_summaries(t, &bb->sres)
+                                    : kmcpg_wait_pairs(t, &bb->res);
     // (a statistics-only batch may have been counted by the time its wait runs out of memory: searching it again would count it twice)
     if (rc != 0 && p.stats_only()) die("--ref-stats-only: %s", kmcpg_last_error());
+    else if (rc == KMCPG_ENOMEM && p.bins_only()) search_sync_bins(*bb);  // (binning a batch changes nothing on the handle: it may be searched again)
     else if (rc == KMCPG_ENOMEM && !p.regions()) search_sync(*bb);  // (kmcpg_wait consumed the ticket; the batch's buffers are still ours)
     else if (rc != 0) die("%s", kmcpg_last_error());
     my_gpu += seconds_since(t0);
@@ -1470,7 +1583,9 @@ struct Searcher {
 
   // the asynchronous form that takes the batch as the reader left it: the records' windows, packed codes, or text
   int submit(Batch& b, kmcpg_ticket** t) {
-    if (p.stats_only())  // (reads as text, single or paired: validate_flags refused the rest)
+    if (p.bins_only())  // (reads as text, single or paired: validate_flags refused the rest)
+      return kmcpg_submit_bins(p.db, b.seqs.data(), b.offs.data(), b.paired ? b.seqs2.data() : nullptr, b.paired ? b.offs2.data() : nullptr, (uint32_t)b.size(), &p.params, t);
+    if (p.stats_only())
       return kmcpg_submit_stats(p.db, b.seqs.data(), b.offs.data(), b.paired ? b.seqs2.data() : nullptr, b.paired ? b.offs2.data() : nullptr, (uint32_t)b.size(), &p.params, t);
     if (b.windows && p.regions()) return kmcpg_submit_windows_summary(p.db, b.seqs.data(), b.offs.data(), (uint32_t)(b.offs.size() - 1), &p.wspec, &p.params, t);
     if (b.windows) return kmcpg_submit_windows(p.db, b.seqs.data(), b.offs.data(), (uint32_t)(b.offs.size() - 1), &p.wspec, &p.params, t);
@@ -1504,13 +1619,14 @@ struct Searcher {
         }
         // The lanes are all the other searcher's.  The one place where windows and reads differ: a batch of reads goes to the one-call form
         // below; windows have none that takes them as they are (it would mean cutting their text), so they wait for a lane to come back.
-        // (a statistics-only batch waits as well: the one-call form would bring all its matches down)
-        if (!b->windows && !p.stats_only()) break;
+        // (a statistics-only or binning batch waits as well: the one-call form would bring all its matches down)
+        if (!b->windows && !p.stats_only() && !p.bins_only()) break;
         std::this_thread::sleep_for(std::chrono::microseconds(200));
       }
       if (rc == KMCPG_ENOMEM && p.regions()) die("%s", kmcpg_last_error());  // (summaries have no one-call form)
       if (rc == KMCPG_EBUSY || rc == KMCPG_ENOMEM) {  // no lane / a batch that must be halved: the one-call form
-        if (p.stats_only()) search_sync_stats(*b);
+        if (p.bins_only()) search_sync_bins(*b);
+        else if (p.stats_only()) search_sync_stats(*b);
         else search_sync(*b);
         my_gpu += seconds_since(t0);
         publish(std::move(b));
@@ -1741,6 +1857,33 @@ static void drain_stats(Pipeline& p) {
   }
 }
 
+// --binning: one line per binned read, the batches in input order; nothing else is formatted
+static void write_bins(Pipeline& p, tsv_out::Out& out) {
+  std::map<uint64_t, std::unique_ptr<Batch>> pending;
+  uint64_t next_seq = 0;
+  while (std::unique_ptr<Batch> b = next_in_order(p, pending, next_seq)) {
+    next_seq += b->n_seq;
+    const auto tf0 = Clock::now();
+    const size_t n = b->size();
+    for (size_t i = 0; i < n; i++) {
+      if (b->bins[i] == kmcpg::BIN_NONE) continue;
+      const std::string_view id = b->id(i);
+      binning_format::write_line(out, id.data(), id.size(), b->bins[i]);
+      p.matched++;
+    }
+    const kmcpg_result_bins& s = b->bres;
+    p.bins.n_reads += s.n_reads, p.bins.binned_reads += s.binned_reads, p.bins.kept_pairs += s.kept_pairs;
+    p.bins.host_reads += s.host_reads, p.bins.left_pairs += s.left_pairs, p.bins.bytes_d2h += s.bytes_d2h;
+    p.total += n;
+    recycle(*b);
+    p.t_fmt += seconds_since(tf0);
+    if (!p.o.quiet) {
+      double min = seconds_since(p.t_search) / 60.0;
+      fprintf(stderr, "processed queries: %llu, speed: %.3f million queries per minute\r", (unsigned long long)p.total, p.total / 1e6 / min);
+    }
+  }
+}
+
 // ---- the end of a run
 static void print_summary(const Pipeline& p) {
   fprintf(stderr, "\n");
@@ -1801,6 +1944,14 @@ int main(int argc, char** argv) {
   // q_in's capacity) are waiting.  Batch limits are the defaults until the open has finished; should the index turn out to be
   // paged (larger than the GPU's memory: a batch then costs passes - 1 uploads), the early batches are joined into large ones
   // before they are searched (Batch::append).
+  if (p.bins_only()) {  // the database's names from a metadata-only handle: what the list cannot give is refused before the GPU is touched
+    kmcpg_db* meta = nullptr;
+    kmcpg_opts mo{-1, 0, 1, 0};
+    kmcpg_info mi;
+    if (kmcpg_open(db_dirs[0].c_str(), &mo, &meta) != 0 || kmcpg_db_info(meta, &mi) != 0) die("%s", kmcpg_last_error());
+    plan_binning(o, p, resolve_targets(o, meta, mi, name_maps), *taxonomy, *taxid_map);
+    kmcpg_close(meta);
+  }
   if (o.whole_file && o.gpu_passes < 0) read_k_early(p, db_dirs[0]);
   Reader the_reader{p, files};
   std::thread reader(&Reader::run, &the_reader);
@@ -1834,11 +1985,17 @@ int main(int argc, char** argv) {
   if (!o.ref_stats_cooccur.empty()) cooccur_names = set_cooccur(o, p.db, p.target);
   std::vector<uint32_t> recount_classes;
   if (!o.ref_stats_recount.empty()) recount_classes = set_recount(o, p.db, p.target, taxonomy.get(), taxid_map.get());
+  if (p.bins_only()) set_binning(p);
 
   p.t_search = Clock::now();
   std::optional<Out> out_file;  // (--ref-stats-only: no search result, no file)
-  if (!p.stats_only()) out_file.emplace(p.regions() ? o.regions_bed : o.out_file);
-  if (!o.no_header && !p.regions() && !p.stats_only()) out_file->write("#query\tqLen\tqKmers\tFPR\thits\ttarget\tchunkIdx\tchunks\ttLen\tkSize\tmKmers\tqCov\ttCov\tjacc\tqueryIdx\n");
+  if (!p.stats_only() && !p.bins_only()) out_file.emplace(p.regions() ? o.regions_bed : o.out_file);
+  std::optional<tsv_out::Out> bin_file;  // --binning: the binning file instead
+  if (p.bins_only()) {
+    bin_file.emplace(binning_format::file_name(o.binning), -1);
+    binning_format::write_header(*bin_file, o.binning_sample_id);
+  }
+  if (!o.no_header && !p.regions() && !p.stats_only() && !p.bins_only()) out_file->write("#query\tqLen\tqKmers\tFPR\thits\ttarget\tchunkIdx\tchunks\ttLen\tkSize\tmKmers\tqCov\ttCov\tjacc\tqueryIdx\n");
   open_gate(p, dbi.k);
 
   const int n_search = p.paged_passes > 1 ? 1 : 2;  // (see Searcher)
@@ -1854,13 +2011,24 @@ int main(int argc, char** argv) {
   region_params.name_species = o.regions_name_species;
   region_params.name_assembly = o.regions_name_assembly;
   kmcpg::RegionMerger merger(region_params);
-  if (p.stats_only()) drain_stats(p);
+  if (p.bins_only()) write_bins(p, *bin_file);
+  else if (p.stats_only()) drain_stats(p);
   else if (p.regions()) write_regions(p, *out_file, merger);
   else write_results(p, *out_file);
   reader.join();
   for (auto& t : searchers) t.join();
 
-  if (p.stats_only()) {
+  if (p.bins_only()) {
+    bin_file->close();
+    if (!o.quiet) {
+      fprintf(stderr, "\n");
+      info("done searching (%.3f s in the GPU library, %.3f s waiting for the reader; no search result is written)", p.t_gpu, p.t_read_wait);
+      info("binning result of %llu reads saved to: %s", (unsigned long long)p.matched, binning_format::file_name(o.binning).c_str());
+    }
+    // (one line of its own, whatever -q says: the tests read it)
+    fprintf(stderr, "%llu reads searched, %llu binned; %llu reads (%llu pairs) left to the host, %llu bytes from the device\n", (unsigned long long)p.bins.n_reads,
+            (unsigned long long)p.bins.binned_reads, (unsigned long long)p.bins.host_reads, (unsigned long long)p.bins.left_pairs, (unsigned long long)p.bins.bytes_d2h);
+  } else if (p.stats_only()) {
     if (!o.quiet) {
       fprintf(stderr, "\n");
       info("done searching (%.3f s in the GPU library, %.3f s waiting for the reader; no search result is written)", p.t_gpu, p.t_read_wait);

@@ -47,6 +47,8 @@ struct Batch {
   std::vector<uint64_t> offs{0}, offs2{0};
   kmcpg_result_summaries sres{};  // --regions-bed: one summary per window instead (kmcpg_wait_summaries)
   kmcpg_result_stats stats{};  // --ref-stats-only: what the batch came to, nothing else (kmcpg_wait_stats)
+  std::vector<uint32_t> bins;   // --binning: one TaxId or KMCPG_BIN_NONE per query, and what the batch came to (kmcpg_wait_bins)
+  kmcpg_result_bins bres{};
   kmcpg_result_pairs res{};  // compact result: (column, mKmers) pairs; the formatter threads expand a query's pairs right before its rows
   bool paired = false;
   // -g queries (whole files) are packed where the reader first touches their bases: 2-bit codes + the runs of other bytes

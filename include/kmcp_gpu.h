@@ -728,6 +728,67 @@ int kmcpg_submit_stats(kmcpg_db* db, const uint8_t* seqs, const uint64_t* offs, 
 int kmcpg_wait_stats(kmcpg_ticket* ticket, kmcpg_result_stats* out);
 int kmcpg_last_stats(kmcpg_db* db, kmcpg_stats_ticket_stats* out, kmcpg_k4_launch* launches, uint32_t cap, uint32_t* n_launches);
 
+/* -- taxonomic binning (K11, k11_bin.hip): one TaxId per read — that of the one whitelisted reference it matches, or the lowest common
+ *    ancestor of the several (`kmcp profile -B`; the rule and the plan: kmcp_amd/csrc/bin_rule.hpp).
+ *    kmcpg_set_binning uploads copies of a plan: node_of_column[n_cols] = the pre-order number, in the plan's pruned tree, of the column's
+ *    target, or KMCPG_BIN_NO_NODE where the target is not whitelisted; parent / last / taxid [n_nodes] = the tree (node 0: the virtual
+ *    root, parent[0] = 0, last[0] = n_nodes - 1; parent[v] < v <= last[v] <= last[parent[v]] for every other node — KMCPG_EINVAL
+ *    otherwise, for a node_of_column that is neither a node nor KMCPG_BIN_NO_NODE, and for a taxid that is KMCPG_BIN_NONE or KMCPG_BIN_LEFT).  (NULL, 0, ...) switches the stage off.  It is
+ *    independent of the other stages and refuses the handles kmcpg_set_refstats refuses.
+ *    kmcpg_bin_device runs K11 alone on device pointers: K3's output (d_pairs, d_read_offs: n_reads + 1 words, at most pair_cap pairs),
+ *    d_qkmers and final_n as for kmcpg_specific_device (a read with pairs and more than final_n k-mers is LEFT: exactly the reads K4
+ *    leaves), the overflow guard of the counting stages (d_n_hits NULL: none; *d_n_hits > hit_cap: d_bins keeps what it held)
+ *    -> d_bins[n_reads]: the TaxId, KMCPG_BIN_NONE (no whitelisted match: no line) or KMCPG_BIN_LEFT.  Only enqueues on `stream`.
+ *    (Its arguments are kmcpg_refstats_device's with d_bins in the place of d_left, not kmcpg_specific_device's plus d_bins: K4's output
+ *    arguments — the compacted pairs, their offsets, the verdict bytes — have no counterpart here, and the overflow guard needs the
+ *    batch's hit counter.)
+ *    kmcpg_last_bins: the witness of the handle's last K11 launch (the call waits for the device to go idle); at profiling level >= 1
+ *    the HIP-event time and one record per kernel launched. */
+enum { KMCPG_K11_BIN = 70 };  /* kmcpg_k4_launch.kernel of K11's kernel */
+#define KMCPG_BIN_NO_NODE 0xffffffffu
+#define KMCPG_BIN_NONE 0xffffffffu
+#define KMCPG_BIN_LEFT 0xfffffffeu
+typedef struct {
+  uint64_t no_bin;        /* reads without a whitelisted match (KMCPG_BIN_NONE) */
+  uint64_t one;           /* reads whose whitelisted matches name one node of the plan */
+  uint64_t several;       /* ... several: the bin is their lowest common ancestor */
+  uint64_t left;          /* reads LEFT to the host (KMCPG_BIN_LEFT) */
+  uint64_t climb_steps;   /* parent steps of all climbs */
+  uint64_t bad_segments;  /* segments that did not lie inside pair_cap (treated as empty; must be 0) */
+  uint64_t skipped;       /* 1: the overflow guard skipped the launch */
+  uint32_t grid;          /* workgroups launched */
+  uint32_t in_lds;        /* 1: the plan's tables were in LDS */
+  double k11_ms;          /* HIP-event time of the kernel at profiling level >= 1; -1 otherwise */
+} kmcpg_bin_stats;
+int kmcpg_set_binning(kmcpg_db* db, const uint32_t* node_of_column, uint32_t n_cols, const uint32_t* parent, const uint32_t* last,
+                      const uint32_t* taxid, uint32_t n_nodes);
+int kmcpg_bin_device(kmcpg_db* db, const kmcpg_pair* d_pairs, const uint64_t* d_read_offs, uint64_t pair_cap, const int32_t* d_qkmers,
+                     uint32_t n_reads, int32_t final_n, const uint64_t* d_n_hits, uint64_t hit_cap, uint32_t* d_bins, void* stream);
+int kmcpg_last_bins(kmcpg_db* db, kmcpg_bin_stats* out, kmcpg_k4_launch* launches, uint32_t cap, uint32_t* n_launches);
+/*    kmcpg_submit_bins takes kmcpg_submit's arguments on a handle with the stage on (KMCPG_EINVAL with it off); the batch runs K1, K2, K3
+ *    and K11 — no other stage behind K3, whatever is on.  kmcpg_wait_bins writes one word per read to bins[n_reads]: the TaxId or
+ *    KMCPG_BIN_NONE, never KMCPG_BIN_LEFT.  With no LEFT read only the bins, the two hit counters, K3's last two words and the witness
+ *    words leave the GPU: bytes_d2h <= 4 n + 256.  With one, K10's compaction (kmcpg_left_compact_device, K11's LEFT byte as the stage's)
+ *    brings the LEFT reads' pairs together, and qkmers (4 bytes per read), the n + 1 offsets and 8 bytes per LEFT pair come down as well:
+ *    bytes_d2h <= 16 n + 264 + 8 left_pairs; the host half applies its own -f test to those pairs and then bin_rule.hpp.  A batch whose
+ *    hit buffer overflowed runs again — the attempt that overflowed wrote no bin (K11's and K10's guard) — and `reruns` says how often.  Refusals as for kmcpg_submit_stats: KMCPG_EINVAL with the species-specific stage on;
+ *    KMCPG_EUNSUPPORTED on database sets, on paged / multi-device / sharded handles, with KMCPG_DEVICE_FINALIZE=0 and for try_se,
+ *    top_n_scores != 0 and several k-mer sizes with k == 0.  The ticket is consumed by kmcpg_wait_bins ONLY: the other waits refuse it
+ *    (KMCPG_EINVAL, the ticket stays valid), and kmcpg_wait_bins refuses every other ticket.  After kmcpg_wait_bins, kmcpg_last_bins
+ *    reports that ticket's counters (`left`: the reads the device LEFT, all binned by the host half since). */
+typedef struct {
+  uint64_t n_reads;
+  uint64_t binned_reads;  /* reads with a TaxId in bins[] */
+  uint64_t kept_pairs;    /* K3's total */
+  uint64_t host_reads;    /* reads K11 LEFT: binned by the host half */
+  uint64_t left_pairs;    /* their pairs: all that came to the host of the batch's matches */
+  uint64_t bytes_d2h;     /* bytes that came from the device for the ticket, its last attempt's */
+  uint64_t reruns;        /* how often the batch ran again because its hit buffer overflowed: the attempt before wrote no bin */
+} kmcpg_result_bins;
+int kmcpg_submit_bins(kmcpg_db* db, const uint8_t* seqs, const uint64_t* offs, const uint8_t* seqs2, const uint64_t* offs2, uint32_t n_reads,
+                      const kmcpg_params* params, kmcpg_ticket** out);
+int kmcpg_wait_bins(kmcpg_ticket* ticket, uint32_t* bins, kmcpg_result_bins* out);
+
 /* -- benchmarking / full-size parity support (no counterpart in the reference) ------------------ */
 typedef struct {
   int32_t k;            /* 21 */

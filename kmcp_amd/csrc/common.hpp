@@ -270,6 +270,31 @@ struct K10Args {
   unsigned long long* stats;           // [K10_STATS], zero on entry
 };
 
+// K11 (k11_bin.hip): K3's segments -> one word per read, the TaxId of the read's bin (bin_rule.hpp): the lowest common ancestor, in the
+// pruned tree of the plan, of the whitelisted targets the read matches.
+constexpr uint32_t K11_NONE = 0xffffffffu, K11_LEFT = 0xfffffffeu;  // = KMCPG_BIN_NONE, KMCPG_BIN_LEFT (include/kmcp_gpu.h), BIN_* (bin_rule.hpp)
+constexpr uint32_t K11_LDS_NODES = 2048;  // the plan's three tables sit in LDS up to this many nodes (24 KiB per workgroup)
+// the witness: reads without a bin / with one target / with several / LEFT, climb steps, segments outside the buffer, launches the overflow
+// guard skipped
+enum { K11_NO_BIN = 0, K11_ONE, K11_SEVERAL, K11_LEFT_READS, K11_STEPS, K11_BAD, K11_SKIPPED, K11_STATS };
+struct K11Args {
+  const kmcpg_pair* pairs;             // K3's output
+  const uint64_t* offs;                // [n_reads + 1]
+  uint64_t pair_cap;                   // pairs there is room for behind `pairs`: a segment that ends behind it is treated as empty
+  const int32_t* nk;                   // NumKmers per read
+  uint32_t n_reads;
+  uint32_t n_cols;
+  int32_t final_n;                     // reads of more k-mers are LEFT (their pairs may still fall to -f on the host), as in K4
+  const uint32_t* node_of_column;      // [n_cols]: the pre-order number of the column's target, NO_CLASS = not whitelisted
+  const uint32_t *parent, *last, *taxid;  // [n_nodes] the plan's tables; node 0 is the virtual root
+  uint32_t n_nodes;
+  const unsigned long long* n_hits;    // device word or nullptr: the batch's hit counter ...
+  uint64_t hit_cap;                    // ... above this the batch will be run again: nothing is written now
+  uint32_t* bins;                      // out [n_reads]: a TaxId, K11_NONE or K11_LEFT
+  uint8_t* left;                       // out [n_reads] or nullptr: 1 where the bin is K11_LEFT, else 0 (the byte K10's compaction takes)
+  unsigned long long* stats;           // [K11_STATS], zero on entry
+};
+
 // K6 (k6_refstats.hip): K3's segments -> four counters per column, the counts of stage 1 of `kmcp profile` (refstats_rule.hpp); the reads
 // it cannot count exactly are LEFT to the host (a byte per read).
 constexpr uint32_t K6_CAP = 64;  // longest segment of several targets the device counts

@@ -854,6 +854,10 @@ extern "C" int kmcpg_close(kmcpg_db* db) {
   if (db->d_left_stats) (void)hipFree(db->d_left_stats);
   for (auto& ev : db->left_ev)
     if (ev) (void)hipEventDestroy(ev);
+  if (db->d_bin_tables) (void)hipFree(db->d_bin_tables);
+  if (db->d_bin_stats) (void)hipFree(db->d_bin_stats);
+  for (auto& ev : db->bin_ev)
+    if (ev) (void)hipEventDestroy(ev);
   kmcpg::release_fpr_bounds(db);
   kmcpg::async_release(db);
   if (db->k1_stream) (void)hipStreamDestroy(db->k1_stream);

@@ -342,6 +342,19 @@ struct kmcpg_db {
   // ... or, after kmcpg_wait_stats, what that ticket's batch came to
   bool left_from_ticket = false;
   kmcpg_stats_ticket_stats left_ticket{};
+  // K11, taxonomic binning (kmcpg_set_binning, kmcpg_bin_device; k11_bin.hip, binning.cpp): the plan's tables — node_of_column [n_cols],
+  // then parent, last, taxid [n_nodes] each, in ONE allocation — their host copies, the witness words and what the last launch noted
+  std::vector<uint32_t> h_bin_node, h_bin_parent, h_bin_last, h_bin_taxid;
+  uint32_t* d_bin_tables = nullptr;
+  unsigned long long* d_bin_stats = nullptr;  // [K11_STATS]
+  bool binning_on() const { return !h_bin_parent.empty(); }
+  unsigned bin_max_wgs = 0, bin_grid = 0;  // the chip's resident workgroups (KMCPG_BIN_WGS: fewer, for tests); the last launch's grid
+  bool bin_ran = false, bin_timed = false, bin_in_lds = false;
+  hipEvent_t bin_ev[2] = {};
+  std::vector<kmcpg_k4_launch> k11_log;
+  // ... or, after kmcpg_wait_bins, what that ticket's batch came to
+  bool bin_from_ticket = false;
+  kmcpg_bin_stats bin_ticket{};
   std::vector<kmcpg::FprBoundTable> fpr_bounds;  // -f bound tables (query.cpp fpr_bound): one per (max_fpr, size), never rewritten
   hipEvent_t ev[16] = {};   // ring of 4 calls x (start, COBS start, COBS done, k-mers done)
   uint64_t ev_calls = 0;    // profiled calls so far
@@ -581,6 +594,15 @@ int left_compact_reserve(kmcpg_db* db, uint32_t n_reads);
 int left_compact_enqueue(kmcpg_db* db, const kmcpg_pair* d_pairs, const uint64_t* d_read_offs, uint64_t pair_cap, uint32_t n_reads, const uint8_t* const d_left[N_COUNTING],
                          const uint64_t* d_n_hits, uint64_t hit_cap, uint8_t* d_mask, kmcpg_pair* d_left_pairs, uint64_t left_cap, uint64_t* d_left_offs,
                          unsigned long long* d_stats, hipStream_t st);
+// K11 behind K3 (binning.cpp): what kmcpg_bin_device does, without the public entry's argument checks.  d_left: nullptr, or a byte per
+// read, 1 where the bin is LEFT (what K10's compaction takes); d_stats = K11_STATS witness words of the caller's (a lane's), zeroed here, or
+// nullptr: the handle's.  bins_left_host (finalize.cpp): the host half — the LEFT reads of bins[] from their pairs, after the host's own
+// -f test, by bin_rule.hpp on the handle's copy of the plan; *host_reads counts them
+int bin_enqueue(kmcpg_db* db, const kmcpg_pair* d_pairs, const uint64_t* d_read_offs, uint64_t pair_cap, const int32_t* d_qkmers, uint32_t n_reads, int32_t final_n,
+                const uint64_t* d_n_hits, uint64_t hit_cap, uint32_t* d_bins, uint8_t* d_left, unsigned long long* d_stats, hipStream_t st);
+void bin_stats_from_words(const unsigned long long* words, kmcpg_bin_stats* out);  // the K11_STATS witness words -> the public form
+int bins_left_host(kmcpg_db* db, const kmcpg_pair* pairs, const uint64_t* read_offs, const int32_t* qkmers, uint32_t n_reads, const kmcpg_params& p, uint32_t* bins,
+                   uint64_t* host_reads);
 // bound_n: what the kmcpg_query_device call(s) that produced the list actually did — every query of up to bound_n k-mers had the -f bound
 // applied on the device, whichever kernel form served it (0: no bound table in that call).  query_device_after reports the value of its
 // call; lane.cpp keeps it with the batch (Lane::bound_n) and hands it to the finalizer, which takes a compact segment as final only for

@@ -33,6 +33,7 @@
 #include "specific_rule.hpp"
 #include "cooccur_rule.hpp"
 #include "refstats_rule.hpp"
+#include "bin_rule.hpp"
 #include "match_rule.hpp"
 #include "fpr.hpp"
 #include "kernels.hpp"
@@ -793,6 +794,39 @@ int left_reads_host(kmcpg_db* db, const kmcpg_pair* pairs, const uint64_t* read_
       if (db->is_set()) set_order_records(db, tmp.data(), tmp.size(), p.sort_by);
     }
     counting_hand_over(db, take, tmp.data(), tmp.size(), n, (take >> K8 & 1) ? qlen[r] : 0, sc);
+  }
+  return 0;
+}
+
+// ---- the host half of K11 (k11_bin.hip): the reads it LEFT — those above the device's -f bound.  Their pairs pass the host's own tests
+// (match_accept, as above), what is left names nodes of the handle's copy of the plan, and bin_rule.hpp's climb gives the bin.  Order does
+// not matter to a min and a max, and the GPU route has no row cuts
+int bins_left_host(kmcpg_db* db, const kmcpg_pair* pairs, const uint64_t* read_offs, const int32_t* qkmers, uint32_t n_reads, const kmcpg_params& p, uint32_t* bins,
+                   uint64_t* host_reads) {
+  *host_reads = 0;
+  if (!db->binning_on()) return kmcpg_fail(KMCPG_EINVAL, "the stage is off: call kmcpg_set_binning first");
+  const size_t n_cols = db->col_meta.size();
+  const uint64_t n_pairs = read_offs[n_reads];
+  FprRow row;
+  int row_n = -1;
+  const auto fpr_of = [&](int n2, int k) { return QueryFpr::value(*row, n2, k); };
+  for (uint32_t r = 0; r < n_reads; r++) {
+    if (bins[r] != BIN_LEFT) continue;
+    ++*host_reads;
+    const uint64_t s0 = read_offs[r], s1 = read_offs[r + 1];
+    if (s1 < s0 || s1 > n_pairs) return kmcpg_fail(KMCPG_EINVAL, "grouped hit list: offsets out of range");
+    const int n = qkmers[r];
+    if (n > 0 && n != row_n) {
+      row_n = n;
+      row = db->fpr->ensure_row(n);
+    }
+    BinRange range;
+    for (uint64_t i = s0; i < s1; i++) {
+      if (pairs[i].col >= n_cols) return kmcpg_fail(KMCPG_EINVAL, "grouped hit list: columns out of range");
+      kmcpg_match mm;
+      if (match_accept(pairs[i].col, (int)pairs[i].count, n, db->col_meta[pairs[i].col], p, fpr_of, &mm)) range.add(db->h_bin_node[pairs[i].col]);
+    }
+    bins[r] = range.bin(db->h_bin_parent.data(), db->h_bin_last.data(), db->h_bin_taxid.data());
   }
   return 0;
 }

@@ -23,7 +23,7 @@
 
 namespace kmcpg {
 
-int submit_impl(kmcpg_db* db, const HostBatch& b, const kmcpg_params& p, bool retry, bool block, kmcpg_ticket** out, const PackedIn* packed, bool summary, bool stats) {
+int submit_impl(kmcpg_db* db, const HostBatch& b, const kmcpg_params& p, bool retry, bool block, kmcpg_ticket** out, const PackedIn* packed, bool summary, bool stats, bool bins) {
   std::unique_ptr<kmcpg_ticket> t(new kmcpg_ticket());
   t->db = db;
   t->n = b.n;
@@ -31,6 +31,7 @@ int submit_impl(kmcpg_db* db, const HostBatch& b, const kmcpg_params& p, bool re
   t->p = p;
   t->summary = summary;
   t->stats = stats;
+  t->bins = bins;
   if (db->paged_passes > 0) {
     int rc = search_paged(db, b, p, t.get());
     if (rc) return rc;
@@ -60,7 +61,7 @@ int submit_impl(kmcpg_db* db, const HostBatch& b, const kmcpg_params& p, bool re
   auto one = [&](size_t i) {
     auto& pt = t->parts[i];
     rcs[i] = packed ? stage_packed(pt.lane, *packed, b) : stage(pt.lane, b, can_pack);
-    if (rcs[i] == 0) pt.lane->summary = summary, pt.lane->stats = stats;
+    if (rcs[i] == 0) pt.lane->summary = summary, pt.lane->stats = stats, pt.lane->bins = bins;
     if (rcs[i] == 0) rcs[i] = enqueue(pt.shard, pt.shard->async, pt.lane, p);
     if (rcs[i]) errs[i] = kmcpg_err_ref();
   };
@@ -484,6 +485,7 @@ extern "C" int kmcpg_wait(kmcpg_ticket* t, kmcpg_result* out) {
   }
   if (t->summary) return kmcpg_fail(KMCPG_EINVAL, "kmcpg_wait: a ticket of kmcpg_submit_windows_summary is consumed by kmcpg_wait_summaries (the ticket is still valid)");
   if (t->stats) return kmcpg_fail(KMCPG_EINVAL, "kmcpg_wait: a ticket of kmcpg_submit_stats is consumed by kmcpg_wait_stats (the ticket is still valid)");
+  if (t->bins) return kmcpg_fail(KMCPG_EINVAL, "kmcpg_wait: a ticket of kmcpg_submit_bins is consumed by kmcpg_wait_bins (the ticket is still valid)");
   return wait_impl(t, out, false);
 }
 
@@ -687,6 +689,7 @@ extern "C" int kmcpg_wait_pairs(kmcpg_ticket* t, kmcpg_result_pairs* out) {
   }
   if (t->summary) return kmcpg_fail(KMCPG_EINVAL, "kmcpg_wait_pairs: a ticket of kmcpg_submit_windows_summary is consumed by kmcpg_wait_summaries (the ticket is still valid)");
   if (t->stats) return kmcpg_fail(KMCPG_EINVAL, "kmcpg_wait_pairs: a ticket of kmcpg_submit_stats is consumed by kmcpg_wait_stats (the ticket is still valid)");
+  if (t->bins) return kmcpg_fail(KMCPG_EINVAL, "kmcpg_wait_pairs: a ticket of kmcpg_submit_bins is consumed by kmcpg_wait_bins (the ticket is still valid)");
   memset(out, 0, sizeof *out);
   const bool native = !may_retry(t->db, t->p, t->paired);
   kmcpg_result r{};
@@ -721,7 +724,7 @@ extern "C" int kmcpg_wait_stats(kmcpg_ticket* t, kmcpg_result_stats* out) {
     if (t) drop_ticket(t);
     return kmcpg_fail(KMCPG_EINVAL, "null argument");
   }
-  if (!t->stats) return kmcpg_fail(KMCPG_EINVAL, "kmcpg_wait_stats: the ticket is not one of kmcpg_submit_stats (it is still valid)");
+  if (!t->stats) return kmcpg_fail(KMCPG_EINVAL, "kmcpg_wait_stats: the ticket is not one of kmcpg_submit_stats (it is still valid)");  // (one of kmcpg_submit_bins is none)
   memset(out, 0, sizeof *out);
   kmcpg_db* db = t->db;
   int rc = 0;
@@ -744,6 +747,68 @@ extern "C" int kmcpg_wait_stats(kmcpg_ticket* t, kmcpg_result_stats* out) {
     db->left_ticket = st;
     db->left_from_ticket = true;
     db->left_ran = true;
+  }
+  drop_after(t, rc);
+  return rc;
+}
+
+// ---- binning search: the batch goes through K3 and K11 (lane.cpp), and nothing of its matches comes to the host but the pairs of the
+//      reads K11 LEFT
+extern "C" int kmcpg_submit_bins(kmcpg_db* db, const uint8_t* seqs, const uint64_t* offs, const uint8_t* seqs2, const uint64_t* offs2, uint32_t n_reads,
+                                 const kmcpg_params* params, kmcpg_ticket** out) {
+  const HostBatch b{seqs, offs, seqs2, offs2, n_reads};
+  if (!db || !out || (b.n && (!b.seqs || !b.offs))) return kmcpg_fail(KMCPG_EINVAL, "null argument");
+  *out = nullptr;
+  if ((b.seqs2 == nullptr) != (b.offs2 == nullptr)) return kmcpg_fail(KMCPG_EINVAL, "seqs2 and offs2 must be given together");
+  if (!db->binning_on()) return kmcpg_fail(KMCPG_EINVAL, "kmcpg_submit_bins: the stage is off: call kmcpg_set_binning first");
+  if (db->spec_on())
+    return kmcpg_fail(KMCPG_EINVAL, "kmcpg_submit_bins: the species-specific stage (kmcpg_set_specific) is on — it filters a result this ticket does not have; switch it off");
+  if (int rc = set_refuse_entry(db, "kmcpg_submit_bins")) return rc;
+  if (int rc = refuse_handle(db, "binning searches (kmcpg_submit_bins)", "a query's bin needs its matches from every block")) return rc;
+  kmcpg_params p;
+  if (int rc = submit_handle(db, params, &p)) return rc;
+  if (const char* what = final_matches_refused(db, p))
+    return kmcpg_fail(KMCPG_EUNSUPPORTED, "taxonomic bins (kmcpg_set_binning): %s is not supported — bin the results with kmcp-refstats --binning", what);
+  AsyncState* A = nullptr;
+  if (int rc = async_state(db, &A)) return rc;
+  if (!A->device_finalize || A->hits_stay_on_device)
+    return kmcpg_fail(KMCPG_EUNSUPPORTED, "kmcpg_submit_bins needs K3 on the device (KMCPG_DEVICE_FINALIZE=0 is set): use kmcpg_submit and kmcpg_wait");
+  return submit_impl(db, b, p, false, false, out, nullptr, false, false, true);
+}
+
+extern "C" int kmcpg_wait_bins(kmcpg_ticket* t, uint32_t* bins, kmcpg_result_bins* out) {
+  if (!t || !out || (t->n && !bins)) {
+    if (t) drop_ticket(t);
+    return kmcpg_fail(KMCPG_EINVAL, "null argument");
+  }
+  if (!t->bins) return kmcpg_fail(KMCPG_EINVAL, "kmcpg_wait_bins: the ticket is not one of kmcpg_submit_bins (it is still valid)");
+  memset(out, 0, sizeof *out);
+  kmcpg_db* db = t->db;
+  int rc = 0;
+  kmcpg_bin_stats st{};
+  st.k11_ms = -1;
+  if (t->n) {
+    auto& pt = t->parts[0];
+    Lane* L = pt.lane;
+    uint64_t n_hits = 0;
+    rc = collect(pt.shard, pt.shard->async, L, t->p, &n_hits, false);
+    if (rc == 0 && !L->bins_only()) rc = kmcpg_fail(KMCPG_EDEVICE, "internal: a binning batch did not go through K11");
+    if (rc == 0 && L->h_roffs.p[(size_t)t->n + 1] != 0)
+      rc = kmcpg_fail(KMCPG_EINVAL, "%llu hit(s) named a read or column that does not exist", (unsigned long long)L->h_roffs.p[(size_t)t->n + 1]);
+    if (rc == 0) {
+      st = L->bin_res;
+      memcpy(bins, L->h_bins.p, (size_t)t->n * sizeof(uint32_t));
+      out->n_reads = t->n;
+      out->kept_pairs = L->bin_kept_pairs, out->host_reads = st.left, out->left_pairs = L->bin_left_pairs, out->bytes_d2h = L->bin_bytes_d2h;
+      out->reruns = L->reruns;
+      for (uint32_t r = 0; r < t->n; r++) out->binned_reads += bins[r] != KMCPG_BIN_NONE;
+    }
+  }
+  if (rc == 0) {
+    std::lock_guard<std::mutex> g(db->mu);
+    db->bin_ticket = st;
+    db->bin_from_ticket = true;
+    db->bin_ran = true;
   }
   drop_after(t, rc);
   return rc;

@@ -276,6 +276,7 @@ extern "C" int kmcpg_wait_summaries(kmcpg_ticket* t, kmcpg_result_summaries* out
     return kmcpg_fail(KMCPG_EINVAL, "null argument");
   }
   if (t->stats) return kmcpg_fail(KMCPG_EINVAL, "kmcpg_wait_summaries: a ticket of kmcpg_submit_stats is consumed by kmcpg_wait_stats (the ticket is still valid)");
+  if (t->bins) return kmcpg_fail(KMCPG_EINVAL, "kmcpg_wait_summaries: a ticket of kmcpg_submit_bins is consumed by kmcpg_wait_bins (the ticket is still valid)");
   if (!t->summary) return kmcpg_fail(KMCPG_EINVAL, "kmcpg_wait_summaries: the ticket is not one of kmcpg_submit_windows_summary (it is still valid: kmcpg_wait / kmcpg_wait_pairs)");
   memset(out, 0, sizeof *out);
   kmcpg_db* db = t->db;

@@ -1,5 +1,5 @@
 // kernels.hpp — host-callable launchers of the HIP kernels in k1_kmers.hip (K1 entry; kernels in k1_reads.hip, k1_windows.hip, k1_seg.hip,
-// k1_win_once.hip), k1_dedup.hip, k2_cobs.hip, k3_finalize.hip (K3 and its scan), k4_specific.hip, k5_summary.hip, k6_refstats.hip, k7_cooccur.hip, k8_recount.hip, k9_em.hip, k10_left.hip (the
+// k1_win_once.hip), k1_dedup.hip, k2_cobs.hip, k3_finalize.hip (K3 and its scan), k4_specific.hip, k5_summary.hip, k6_refstats.hip, k7_cooccur.hip, k8_recount.hip, k9_em.hip, k10_left.hip, k11_bin.hip (the
 // stages behind K3; their shared walk is seg_walk.hpp), density.hip, windows.hip, build_scatter.hip, support.hip and sort_huge.hip.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -73,7 +73,7 @@ inline void k4_note(K4Log* log, int kernel, unsigned grid, unsigned block) {
   r.block = block;
   r.cls = kernel == KMCPG_K4_VERDICT || kernel == KMCPG_K4_COMPACT || kernel == KMCPG_K5_SUMMARY || kernel == KMCPG_K5_COMPACT || kernel == KMCPG_K6_REFSTATS || kernel == KMCPG_K7_COOCCUR ||
                   kernel == KMCPG_K8_LOG || kernel == KMCPG_K8_REPLAY || kernel == KMCPG_K9_EM || kernel == KMCPG_K10_MASK || kernel == KMCPG_K10_COMPACT ||
-                  kernel == KMCPG_K10_OFFS
+                  kernel == KMCPG_K10_OFFS || kernel == KMCPG_K11_BIN
               ? 3
               : 0;
   log->push_back(r);
@@ -99,6 +99,8 @@ unsigned launch_k9_em(const K9Args& a, unsigned max_wgs, hipStream_t st, K4Log* 
 // K10: the mask of the reads the counting stages LEFT, their segments compacted (k10_left.hip)
 void launch_k10(const K10Args& a, const kmcpg_pair* pairs, uint64_t* sums, uint64_t* offs_tmp, kmcpg_pair* left_pairs, uint64_t left_cap, uint64_t* left_offs,
                 hipStream_t st, K4Log* log);
+// K11: one TaxId per read, the LCA of its whitelisted targets (k11_bin.hip); returns the grid it launched (at most max_wgs workgroups)
+unsigned launch_k11(const K11Args& a, unsigned max_wgs, hipStream_t st, K4Log* log, bool* in_lds);
 void launch_max_nk(const int32_t* nk, uint32_t n_reads, unsigned long long* out, hipStream_t st);
 void launch_repack(const uint8_t* src, uint8_t* dst, uint64_t n_rows, uint32_t row_bytes, uint32_t stride, uint32_t byte_off, uint32_t ncols, hipStream_t st);
 void launch_gather_rows(const uint8_t* rows, uint32_t stride, uint32_t row_bytes, const uint64_t* idx, uint64_t first, uint64_t n, uint8_t* out,

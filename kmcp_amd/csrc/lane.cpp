@@ -168,7 +168,7 @@ bool pack_wanted(uint64_t total_bases, uint32_t n) {
 int lane_begin(Lane* L, const HostBatch& b) {
   L->up_reads = L->n = b.n;
   L->up_bases = L->tb1 = L->tb2 = 0;
-  L->packed = L->win = L->summary = L->stats = false;
+  L->packed = L->win = L->summary = L->stats = L->bins = false;
   L->n_exc = 0;
   L->ext_pack = nullptr;
   L->paired = b.seqs2 != nullptr;
@@ -300,9 +300,32 @@ int enqueue_query(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p, c
     L->counted = 0;  // (a lane keeps its fields from batch to batch: the summary path below returns before the counting stages' turn)
     // (a batch K5 summarises, and one searched for statistics only, needs K3's last two words only: the pairs it kept, and its count of bad hits)
     const bool stats_only = L->stats && counting_mask(db) != 0;
-    const size_t skip = L->summarized() || stats_only ? L->n : 0;
+    if (L->bins) L->spec = false;  // (kmcpg_submit_bins refuses a handle with K4 on)
+    const size_t skip = L->summarized() || stats_only || L->bins ? L->n : 0;
     HIPCHK(hipMemcpyAsync(L->h_roffs.p + skip, L->d_roffs.p + skip, ((size_t)L->n + 2 - skip) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     L->d_final = L->d_pairs.p;
+    if (L->bins) {
+      // K11 right behind K3, and nothing else: four bytes per read leave the GPU.  K11's LEFT byte goes through K10's compaction as a
+      // stage's byte would; the LEFT reads' pairs go into d_hits — dead once K3 has grouped it — and come down on demand (collect).  Every
+      // buffer first, as for the counting stages.  KMCPG_BIN_DEVICE=0: every read with matches goes to the host half
+      if (L->d_bins.ensure(L->n) || L->h_bins.ensure(L->n) || L->d_bleft.ensure(L->n) || L->d_bstats.ensure(K11_STATS) || L->h_bstats.ensure(K11_STATS) || L->d_mask.ensure(L->n) ||
+          L->d_loffs.ensure((size_t)L->n + 1) || L->d_lstats.ensure(K10_STATS) || L->h_lstats.ensure(K10_STATS))
+        return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
+      if (int rc2 = left_compact_reserve(db, L->n)) return rc2;
+      const char* e = getenv("KMCPG_BIN_DEVICE");
+      const int32_t final_n = e && atoi(e) == 0 ? -1 : std::min<int32_t>(L->bound_n, kFprBoundAlways);
+      rc = bin_enqueue(db, L->d_pairs.p, L->d_roffs.p, L->d_hits.cap, L->d_qk.p, L->n, final_n, L->d_cnt.p, L->d_hits.cap, L->d_bins.p, L->d_bleft.p, L->d_bstats.p, st);
+      if (rc) return rc;
+      const uint8_t* left[N_COUNTING] = {L->d_bleft.p, nullptr, nullptr};
+      kmcpg_pair* out = (kmcpg_pair*)L->d_hits.p;
+      rc = left_compact_enqueue(db, L->d_pairs.p, L->d_roffs.p, L->d_hits.cap, L->n, left, L->d_cnt.p, L->d_hits.cap, L->d_mask.p, out, L->d_hits.cap, L->d_loffs.p, L->d_lstats.p, st);
+      if (rc) return rc;
+      HIPCHK(hipMemcpyAsync(L->h_bins.p, L->d_bins.p, (size_t)L->n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+      HIPCHK(hipMemcpyAsync(L->h_bstats.p, L->d_bstats.p, K11_STATS * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+      HIPCHK(hipMemcpyAsync(L->h_lstats.p, L->d_lstats.p, K10_STATS * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+      L->d_final = out;
+      return 0;
+    }
     if (L->spec) {  // K4 right behind K3: only the surviving reads' matches leave the GPU
       if (L->d_soffs4.ensure((size_t)L->n + 1) || L->d_verd.ensure(L->n) || L->h_verd.ensure(L->n)) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
       // a segment is final on the device only where the -f bound was applied there (finalize.cpp: final_n); longer queries keep their
@@ -410,8 +433,8 @@ int enqueue(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p, bool ge
   }
   // K3 only where this handle holds the whole database: the lists of shards (several GPUs, passes of a paged handle) are merged first
   L->grouped = A->device_finalize && !A->hits_stay_on_device && db->opts.shard_count == 1;
-  // (a batch searched for statistics only brings no pairs down but those of the reads LEFT to the host: collect sizes h_pairs for them)
-  if (L->h_cnt.ensure(2) || L->h_qk.ensure(n) || L->h_ql.ensure(n) || (L->grouped ? (!L->stats && L->h_pairs.ensure(first)) : L->h_hits.ensure(first)))
+  // (a batch searched for statistics or for bins only brings no pairs down but those of the reads LEFT to the host: collect sizes h_pairs for them)
+  if (L->h_cnt.ensure(2) || L->h_qk.ensure(n) || L->h_ql.ensure(n) || (L->grouped ? (!L->stats && !L->bins && L->h_pairs.ensure(first)) : L->h_hits.ensure(first)))
     return kmcpg_fail(KMCPG_ENOMEM, "hipHostMalloc failed");
   // the reads go up on a stream of their own (150 MB per million reads: 4 ms of PCIe that would otherwise sit between the
   // kernels of consecutive batches); the lane's device buffers are idle, its previous batch was waited for
@@ -463,11 +486,13 @@ int enqueue(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p, bool ge
     rc = enqueue_query(db, A, L, p);
   }
   if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(L->h_qk.p, L->d_qk.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(L->h_ql.p, L->d_ql.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  if (!L->bins_only()) {  // (a batch searched for bins needs the k-mer counts only if K11 LEFT a read: collect asks for them; the lengths never)
+    HIPCHK(hipMemcpyAsync(L->h_qk.p, L->d_qk.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(L->h_ql.p, L->d_ql.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  }
   L->copied = A->hits_stay_on_device ? 0 : std::min<uint64_t>(first, L->d_hits.cap);
   L->eager_aside = false;
-  if (L->summarized() || L->stats_only()) L->copied = 0;  // no eager copy of pairs: what the host needs of them (the LEFT windows', the LEFT reads') it asks for by itself
+  if (L->summarized() || L->stats_only() || L->bins_only()) L->copied = 0;  // no eager copy of pairs: what the host needs of them (the LEFT windows', the LEFT reads') it asks for by itself
   if (L->copied && L->grouped && !generous_eager) {
     // a small copy (<= 32 pairs per read), in stream order before the lane's completion event (same-box A/B: on a stream of its own it
     // cost the pipelined submit / wait path 8 %)
@@ -553,6 +578,40 @@ int stats_collect(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p) {
   }
   return left_reads_host(db, L->h_pairs.p, L->h_loffs.p, L->h_qk.p, L->h_ql.p, n, p, mask, left);
 }
+
+// ... of a batch searched for bins only (Lane::bins_only): the bins and the two witnesses are here; if K11 LEFT a read, the k-mer counts,
+// K10's offsets and the pairs it compacted come down now, and the host half (finalize.cpp bins_left_host) writes those reads' bins over
+// the LEFT words.  Fills L->bin_res and the three totals beside it
+int bins_collect(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p) {
+  const uint32_t n = L->n;
+  const unsigned long long *w = L->h_bstats.p, *lw = L->h_lstats.p;
+  kmcpg_bin_stats& r = L->bin_res;
+  r = kmcpg_bin_stats{};
+  r.k11_ms = -1;
+  bin_stats_from_words(w, &r);
+  L->bin_kept_pairs = L->h_roffs.p[n];
+  L->bin_left_pairs = lw[K10_LEFT_PAIRS];
+  // the two hit counters, K3's last two words, the two witnesses and the bins
+  L->bin_bytes_d2h = 4 * sizeof(uint64_t) + (K11_STATS + K10_STATS) * sizeof(unsigned long long) + (uint64_t)n * sizeof(uint32_t);
+  if (r.skipped || lw[K10_SKIPPED] || lw[K10_LEFT] != r.left || L->bin_left_pairs > L->bin_kept_pairs || L->bin_left_pairs > L->d_hits.cap ||
+      r.no_bin + r.one + r.several + r.left != n)
+    return kmcpg_fail(KMCPG_EDEVICE, "internal: K11 binned %llu + %llu + %llu reads and left %llu of %u (K10: %llu reads, %llu pairs of %llu; skipped: %llu, %llu)",
+                      (unsigned long long)r.no_bin, (unsigned long long)r.one, (unsigned long long)r.several, (unsigned long long)r.left, n, lw[K10_LEFT], lw[K10_LEFT_PAIRS],
+                      (unsigned long long)L->bin_kept_pairs, (unsigned long long)r.skipped, lw[K10_SKIPPED]);
+  if (r.left == 0) return 0;
+  if (L->h_loffs.ensure((size_t)n + 1) || L->h_pairs.ensure(L->bin_left_pairs + 1)) return kmcpg_fail(KMCPG_ENOMEM, "hipHostMalloc failed");
+  HIPCHK(hipMemcpyAsync(L->h_qk.p, L->d_qk.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, A->copy_stream));
+  HIPCHK(hipMemcpyAsync(L->h_loffs.p, L->d_loffs.p, ((size_t)n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, A->copy_stream));
+  if (L->bin_left_pairs) HIPCHK(hipMemcpyAsync(L->h_pairs.p, L->d_final, L->bin_left_pairs * sizeof(kmcpg_pair), hipMemcpyDeviceToHost, A->copy_stream));
+  HIPCHK(hipStreamSynchronize(A->copy_stream));
+  L->bin_bytes_d2h += (uint64_t)n * sizeof(int32_t) + ((uint64_t)n + 1) * sizeof(uint64_t) + L->bin_left_pairs * sizeof(kmcpg_pair);
+  if (L->h_loffs.p[n] != L->bin_left_pairs)
+    return kmcpg_fail(KMCPG_EDEVICE, "internal: K10 compacted %llu pairs, counted %llu", (unsigned long long)L->h_loffs.p[n], (unsigned long long)L->bin_left_pairs);
+  uint64_t host_reads = 0;
+  if (int rc = bins_left_host(db, L->h_pairs.p, L->h_loffs.p, L->h_qk.p, n, p, L->h_bins.p, &host_reads)) return rc;
+  if (host_reads != r.left) return kmcpg_fail(KMCPG_EDEVICE, "internal: the host half binned %llu reads, K11 left %llu", (unsigned long long)host_reads, (unsigned long long)r.left);
+  return 0;
+}
 }  // namespace
 
 int collect(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p, uint64_t* n_hits, bool fetch) {
@@ -570,6 +629,7 @@ int collect(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p, uint64_
   } taint{db, L};
   HIPCHK(hipEventSynchronize(L->done));
   uint64_t cnt = L->h_cnt.p[0];
+  L->reruns = 0;
   for (int attempt = 0; cnt > L->d_hits.cap; attempt++) {  // the hit buffer was too small: rerun with room for every hit
     if (attempt == 2) return kmcpg_fail(KMCPG_ENOMEM, "hit buffer overflow");
     HIPCHK(hipStreamSynchronize(L->st));
@@ -577,6 +637,7 @@ int collect(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p, uint64_
     if (L->d_hits.ensure(cnt + cnt / 4)) return kmcpg_fail(KMCPG_ENOMEM, "hipMalloc failed");
     int rc = enqueue_query(db, A, L, p);
     if (rc) return rc;
+    L->reruns++;
     HIPCHK(hipStreamSynchronize(L->st));
     cnt = L->h_cnt.p[0];
     L->copied = 0;
@@ -611,6 +672,9 @@ int collect(kmcpg_db* db, AsyncState* A, Lane* L, const kmcpg_params& p, uint64_
   if (L->counted && L->grouped) {
     int rc = L->stats_only() ? stats_collect(db, A, L, p) : left_collect(db, A, L, p, fetch);
     if (rc) return rc;
+  }
+  if (L->bins_only()) {
+    if (int rc = bins_collect(db, A, L, p)) return rc;
   }
   // a batch large enough to say something about the data (one genome with 5 000 matches does not)
   if (L->n >= 1024) A->hits_hint.store(hits_hint_after(A->hits_hint.load(), cnt, L->n));

@@ -94,6 +94,19 @@ struct Lane {
   PinBuf<uint64_t> h_loffs;
   bool stats_only() const { return stats && grouped && counted != 0; }  // K10 ran: left_res is the result (after collect)
   kmcpg_stats_ticket_stats left_res{};
+  // K11 (binning batches, kmcpg_submit_bins): behind K3 one word per read, the bin, and a byte for the reads K11 LEFT, which K10's compaction
+  // takes as a stage's byte (d_mask, d_loffs, d_lstats, d_hits as above); the bins and the two witnesses come down with the batch, qkmers,
+  // the offsets and the LEFT pairs on demand (collect) — no counting stage runs, and of K3's offsets only the last two words come down
+  bool bins = false;  // the caller asked for bins only (set after lane_begin, before enqueue)
+  DevBuf<uint32_t> d_bins;
+  PinBuf<uint32_t> h_bins;
+  DevBuf<uint8_t> d_bleft;
+  DevBuf<unsigned long long> d_bstats;
+  PinBuf<unsigned long long> h_bstats;
+  bool bins_only() const { return bins && grouped; }  // K11 ran: bin_res is the result (after collect)
+  kmcpg_bin_stats bin_res{};
+  uint64_t bin_left_pairs = 0, bin_bytes_d2h = 0, bin_kept_pairs = 0;
+  uint32_t reruns = 0;  // how often collect() ran the batch again after a hit-buffer overflow (the witness of kmcpg_result_bins)
   bool spec = false;  // this batch went through K4: h_roffs / h_pairs hold ITS output, h_verd the verdicts
   // 2-bit packed upload (stage): the batch's bases as codes + the runs of foreign bytes instead of h_seqs; unpacked on the device
   PinBuf<uint8_t> h_pack;
@@ -137,6 +150,7 @@ struct Lane {
     for (auto& b : h_left) b.release();
     h_roffs3.release();
     d_mask.release(); h_mask.release(); d_lstats.release(); h_lstats.release(); h_loffs.release();
+    d_bins.release(); h_bins.release(); d_bleft.release(); d_bstats.release(); h_bstats.release();
     h_pack.release(); h_exc.release(); d_pack.release(); d_exc.release();
     h_wmeta.release(); d_soffs.release(); d_wmeta.release(); d_wsrc.release();
     if (done) (void)hipEventDestroy(done);
@@ -232,6 +246,8 @@ struct kmcpg_ticket {
   std::vector<kmcpg::SummaryPart> piece_sum;
   // kmcpg_submit_stats: the ticket is consumed by kmcpg_wait_stats only
   bool stats = false;
+  // kmcpg_submit_bins: the ticket is consumed by kmcpg_wait_bins only
+  bool bins = false;
 };
 
 namespace kmcpg {
@@ -282,7 +298,7 @@ void drop_ticket(kmcpg_ticket* t, bool failed = false);
 // the submit family works on a handle that holds the whole database and can reach a GPU; *p = the caller's params or the defaults
 int submit_handle(kmcpg_db* db, const kmcpg_params* params, kmcpg_params* p);
 int submit_impl(kmcpg_db* db, const HostBatch& b, const kmcpg_params& p, bool retry, bool block, kmcpg_ticket** out, const PackedIn* packed = nullptr,
-                bool summary = false, bool stats = false);
+                bool summary = false, bool stats = false, bool bins = false);
 // kmcpg_wait / kmcpg_wait_pairs: the ticket's result, as_pairs = in the compact form where the path it took collects that natively; gives the ticket back
 int wait_impl(kmcpg_ticket* t, kmcpg_result* out, bool as_pairs);
 // kmcpg_wait_summaries: the summaries of a ticket of kmcpg_submit_windows_summary (one batch or its pieces); gives the ticket back

@@ -1,5 +1,5 @@
 // seg_walk.hpp — the walk over K3's (column, count) segments that the stages behind K3 share: K4 (k4_specific.hip), K5 (k5_summary.hip),
-// K6 (k6_refstats.hip), K10 (k10_left.hip).  Device code, and nothing stage-specific: what a stage does with a segment's reduced classes is its own.
+// K6 (k6_refstats.hip), K10 (k10_left.hip), K11 (k11_bin.hip).  Device code, and nothing stage-specific: what a stage does with a segment's reduced classes is its own.
 //
 // One wave takes RPW = 16 consecutive reads (as k3_sort_wave): lanes 0..16 load the offsets with one coalesced load, and the LPR = 4 lanes
 // of lane group g work for read r0 + g.  A segment of up to GROUP_CAP = 64 pairs is reduced by its lane group (strided loads, two
@@ -114,24 +114,28 @@ struct MinMax {
   __device__ __forceinline__ bool one_species() const { return SPECIES && smin == smax && smin != 0; }  // (specific_rule.hpp: species 0 is none)
 };
 
-// What walk() hands every lane: the reduced classes of its group's segment (of nothing, where `judged` is false), and whether the lane
+// What walk() hands every lane: the reduced value of its group's segment (of nothing, where `judged` is false), and whether the lane
 // group reduced it (`small`) or the wave did (judged && !small)
-template <bool SPECIES>
-struct Walked {
-  MinMax<SPECIES> v;
+template <class V>
+struct WalkedAs {
+  V v;
   bool small;
 };
+template <bool SPECIES>
+using Walked = WalkedAs<MinMax<SPECIES>>;
 struct NoLongSegmentWork {
   template <class V>
   __device__ __forceinline__ void operator()(int, uint64_t, uint64_t, const V&) const {}
 };
-// The walk.  `own`: own_read()'s; `judged`: the group's segment is to be reduced (invariant 1: a function of the lane group).
-// on_long(q, t0, tm, reduced) is called wave-uniformly for every long segment — read r0 + q, pairs[t0 .. t0 + tm) — before its group
-// takes `reduced` over: what a stage does with the whole wave at hand.
-template <bool SPECIES, class OnLong = NoLongSegmentWork>
-__device__ __forceinline__ Walked<SPECIES> walk(const ClassTables& c, const kmcpg_pair* pairs, uint64_t pair_cap, uint64_t mine, uint32_t lane, const OwnRead& own,
-                                                 bool judged, OnLong on_long = OnLong()) {
-  Walked<SPECIES> out;
+// The walk over a reduced value V (MinMax above; K11's node range in k11_bin.hip) and the tables C it reads: V() is the value of no pair,
+// take_group / take_wave take a lane's share of a segment, fold_group / fold_wave bring the shares together with shuffles that EVERY lane
+// of the group / the wave runs (invariant 1).  `own`: own_read()'s; `judged`: the group's segment is to be reduced (invariant 1: a
+// function of the lane group).  on_long(q, t0, tm, reduced) is called wave-uniformly for every long segment — read r0 + q,
+// pairs[t0 .. t0 + tm) — before its group takes `reduced` over: what a stage does with the whole wave at hand.
+template <class V, class C, class OnLong = NoLongSegmentWork>
+__device__ __forceinline__ WalkedAs<V> walk_as(const C& c, const kmcpg_pair* pairs, uint64_t pair_cap, uint64_t mine, uint32_t lane, const OwnRead& own, bool judged,
+                                               OnLong on_long = OnLong()) {
+  WalkedAs<V> out;
   out.small = judged && own.seg.m <= GROUP_CAP;
   if (out.small) out.v.take_group(c, pairs + own.seg.s0, (uint32_t)own.seg.m, own.sub);
   out.v.fold_group();
@@ -139,13 +143,19 @@ __device__ __forceinline__ Walked<SPECIES> walk(const ClassTables& c, const kmcp
   while (longs) {  // wave-uniform
     const int q = pop_group(longs);
     const Segment t = segment(mine, q, pair_cap);
-    MinMax<SPECIES> w;
+    V w;
     w.take_wave(c, pairs + t.s0, t.m, lane);
     w.fold_wave();
     on_long(q, t.s0, t.m, w);
     if (own.g == q) out.v = w;
   }
   return out;
+}
+// ... over min / max of the classes: K4, K5, K6, K7, K8
+template <bool SPECIES, class OnLong = NoLongSegmentWork>
+__device__ __forceinline__ Walked<SPECIES> walk(const ClassTables& c, const kmcpg_pair* pairs, uint64_t pair_cap, uint64_t mine, uint32_t lane, const OwnRead& own,
+                                                 bool judged, OnLong on_long = OnLong()) {
+  return walk_as<MinMax<SPECIES>>(c, pairs, pair_cap, mine, lane, own, judged, on_long);
 }
 
 // Lane i holds pair i of a segment of tm <= 64 pairs and its class: is it the first of its class?  (wave-uniform loop; at most 63 shuffles)

@@ -33,6 +33,7 @@ EXPORTS = [
     "kmcpg_set_recount", "kmcpg_recount_log_device", "kmcpg_recount_run", "kmcpg_recount_read", "kmcpg_recount_reset", "kmcpg_last_recount",
     "kmcpg_em_pass", "kmcpg_em_read", "kmcpg_last_em", "kmcpg_count_left_reads",
     "kmcpg_left_compact_device", "kmcpg_submit_stats", "kmcpg_wait_stats", "kmcpg_last_stats",
+    "kmcpg_set_binning", "kmcpg_bin_device", "kmcpg_last_bins", "kmcpg_submit_bins", "kmcpg_wait_bins",
     "kmcpg_sketch_genomes_to", "kmcpg_builder_open", "kmcpg_builder_close", "kmcpg_builder_add_cols", "kmcpg_builder_plan",
     "kmcpg_builder_col_place", "kmcpg_builder_block_info", "kmcpg_builder_begin_round", "kmcpg_builder_scatter_device",
     "kmcpg_builder_end_round", "kmcpg_builder_finish", "kmcpg_builder_info",
@@ -265,6 +266,27 @@ class StatsTicketStats(C.Structure):
     """kmcpg_stats_ticket_stats: the witness of the last K10 launch, or of the last ticket of wait_stats"""
     _fields_ = [("n_reads", C.c_uint64), ("matched_reads", C.c_uint64), ("kept_pairs", C.c_uint64), ("left_reads", C.c_uint64),
                 ("left_pairs", C.c_uint64), ("bytes_d2h", C.c_uint64), ("bad_segments", C.c_uint64), ("skipped", C.c_uint64), ("k10_ms", C.c_double)]
+
+
+K11_BIN = 70  # KMCPG_K11_BIN: kmcpg_k4_launch.kernel of K11's kernel
+BIN_NO_NODE, BIN_NONE, BIN_LEFT = 0xffffffff, 0xffffffff, 0xfffffffe  # KMCPG_BIN_*
+
+
+class BinsResult(C.Structure):
+    """kmcpg_result_bins: what a binning ticket came to (plain values, nothing to free)"""
+    _fields_ = [("n_reads", C.c_uint64), ("binned_reads", C.c_uint64), ("kept_pairs", C.c_uint64), ("host_reads", C.c_uint64),
+                ("left_pairs", C.c_uint64), ("bytes_d2h", C.c_uint64), ("reruns", C.c_uint64)]
+
+
+class BinTicket(C.c_void_p):
+    """a ticket of submit_bins: the handle's pointer, and the reads it stands for (wait_bins sizes its output by it)"""
+    n_reads = 0
+
+
+class BinStats(C.Structure):
+    """kmcpg_bin_stats: the witness of the last K11 launch"""
+    _fields_ = [("no_bin", C.c_uint64), ("one", C.c_uint64), ("several", C.c_uint64), ("left", C.c_uint64), ("climb_steps", C.c_uint64),
+                ("bad_segments", C.c_uint64), ("skipped", C.c_uint64), ("grid", C.c_uint32), ("in_lds", C.c_uint32), ("k11_ms", C.c_double)]
 
 
 COL_STATS_DTYPE = np.dtype([("rows", "<u8"), ("firsts", "<u8"), ("ureads", "<u8"), ("hic_ureads", "<u8")])  # kmcpg_col_stats
@@ -549,6 +571,11 @@ def load():
     L.kmcpg_submit_stats.argtypes = [vp, vp, vp, vp, vp, C.c_uint32, C.POINTER(Params), C.POINTER(vp)]
     L.kmcpg_wait_stats.argtypes = [vp, C.POINTER(StatsResult)]
     L.kmcpg_last_stats.argtypes = [vp, C.POINTER(StatsTicketStats), C.POINTER(K4Launch), C.c_uint32, C.POINTER(C.c_uint32)]
+    L.kmcpg_set_binning.argtypes = [vp, vp, C.c_uint32, vp, vp, vp, C.c_uint32]
+    L.kmcpg_bin_device.argtypes = [vp, vp, vp, C.c_uint64, vp, C.c_uint32, C.c_int32, vp, C.c_uint64, vp, vp]
+    L.kmcpg_submit_bins.argtypes = [vp, vp, vp, vp, vp, C.c_uint32, C.POINTER(Params), C.POINTER(vp)]
+    L.kmcpg_wait_bins.argtypes = [vp, vp, C.POINTER(BinsResult)]
+    L.kmcpg_last_bins.argtypes = [vp, C.POINTER(BinStats), C.POINTER(K4Launch), C.c_uint32, C.POINTER(C.c_uint32)]
     L.kmcpg_sketch_genomes_to.argtypes = [vp, vp, vp, C.c_uint32, C.POINTER(SplitSpec), SKETCH_SINK, vp]
     u32p = C.POINTER(C.c_uint32)
     L.kmcpg_builder_open.argtypes = [C.POINTER(BuilderCfg), C.c_int32, C.POINTER(vp)]
@@ -1583,6 +1610,59 @@ class Database:
         _check(load().kmcpg_last_stats(self._h, C.byref(st), buf, n.value, C.byref(n)))
         self.last_k10_ms = float(st.k10_ms)  # HIP-event time of the stage's kernels (profiling level >= 1), else -1
         return {f: int(getattr(st, f)) for f, _ in StatsTicketStats._fields_ if f != "k10_ms"}, [buf[i] for i in range(n.value)]
+
+    # ---- taxonomic binning: K11 behind K3 ----------------------------------------------------------------------
+    def set_binning(self, node_of_column=None, parent=None, last=None, taxid=None):
+        """kmcpg_set_binning: node_of_column one uint32 per global column (BIN_NO_NODE: not whitelisted); parent, last, taxid one uint32
+        per node of the plan, numbered in pre-order with node 0 the virtual root; no argument = off."""
+        if node_of_column is None:
+            _check(load().kmcpg_set_binning(self._h, None, 0, None, None, None, 0))
+            return
+        c = np.ascontiguousarray(node_of_column, dtype=np.uint32)
+        t = [np.ascontiguousarray(x, dtype=np.uint32) for x in (parent, last, taxid)]
+        assert len(t[0]) == len(t[1]) == len(t[2])
+        _check(load().kmcpg_set_binning(self._h, c.ctypes.data, len(c), t[0].ctypes.data, t[1].ctypes.data, t[2].ctypes.data, len(t[0])))
+
+    def bin_device(self, d_pairs, d_read_offs, pair_cap, d_qkmers, n_reads, final_n, d_bins, d_n_hits=None, hit_cap=0, stream=None):
+        """kmcpg_bin_device on device pointers: K3's pairs and offsets -> one uint32 per read (a TaxId, BIN_NONE or BIN_LEFT)."""
+        _check(load().kmcpg_bin_device(self._h, d_pairs, d_read_offs, pair_cap, d_qkmers, n_reads, final_n, d_n_hits, hit_cap, d_bins, stream))
+
+    def submit_bins(self, seqs, offs, seqs2=None, offs2=None, params=None):
+        """kmcpg_submit_bins: submit's arguments on a handle with the binning stage on; the ticket is consumed by wait_bins only"""
+        p = params or default_params()
+        t = BinTicket()
+        n = len(offs) - 1
+        _check(load().kmcpg_submit_bins(self._h, seqs.ctypes.data, offs.ctypes.data, seqs2.ctypes.data if seqs2 is not None else None,
+                                        offs2.ctypes.data if offs2 is not None else None, n, C.byref(p), C.byref(t)))
+        t.n_reads = n
+        return t
+
+    def wait_bins(self, ticket):
+        """kmcpg_wait_bins: (uint32 [n]: a TaxId or BIN_NONE per read, dict of n_reads, binned_reads, kept_pairs, host_reads, left_pairs,
+        bytes_d2h, reruns).  A refused ticket stays valid and can be waited for again."""
+        n = ticket.n_reads if isinstance(ticket, BinTicket) else 0  # (a ticket of another submit is refused before a word is written)
+        bins = np.full(max(n, 1), BIN_LEFT, dtype=np.uint32)
+        r = BinsResult()
+        _check(load().kmcpg_wait_bins(ticket, bins.ctypes.data, C.byref(r)))
+        return bins[:n], {f: int(getattr(r, f)) for f, _ in BinsResult._fields_}
+
+    def search_bins(self, reads, reads2=None, params=None):
+        """`reads` (list of bytes) through submit_bins / wait_bins"""
+        seqs, offs = pack_reads(reads)
+        s2 = o2 = None
+        if reads2 is not None:
+            s2, o2 = pack_reads(reads2)
+        return self.wait_bins(self.submit_bins(seqs, offs, s2, o2, params))
+
+    def last_bins(self):
+        """kmcpg_last_bins: (dict of the counters, [K4Launch] of the last K11 launch — empty below profiling level 1)"""
+        st = BinStats()
+        n = C.c_uint32(0)
+        _check(load().kmcpg_last_bins(self._h, C.byref(st), None, 0, C.byref(n)))
+        buf = (K4Launch * max(1, n.value))()
+        _check(load().kmcpg_last_bins(self._h, C.byref(st), buf, n.value, C.byref(n)))
+        self.last_k11_ms = float(st.k11_ms)  # HIP-event time of the kernel (profiling level >= 1), else -1
+        return {f: int(getattr(st, f)) for f, _ in BinStats._fields_ if f != "k11_ms"}, [buf[i] for i in range(n.value)]
 
     # ---- bench / parity support -----------------------------------------------------------------------
     def read_row_range(self, block, first_row, out):
